@@ -2,24 +2,32 @@
 """Headline benchmark: denoise-steps/sec of the DDPM-UNet reverse loop.
 
     python bench.py --gpus N --steps K --warmup W            (BASELINE configs[1], the headline)
+    python bench.py --gpus N --steps K --warmup W --full     (the same, plus roofline, CPU baseline, `secondary`)
     python bench.py --mode train                              (configs[2]: training step, B = 128, own JSON line)
     python bench.py --dtype f16 --grid 24x72 --batch 32       (configs[4]: doubled grid, f16 matrix cores, own line)
 
 Workload of the default run (BASELINE.json configs[1]): config/ATC.yml sampling, batch 64 per GPU, T = 1000
 schedule, tensors [B,4,12,36,(5 past + 3 future)] -- synthetic inputs, random-init weights (torch-default init
 ranges from the repo PRNG).  A "step" is one pass of the hot path over the batch: 1 UNet forward + 1 sampler
-update (/root/reference/models/diffusion/ddpm.py:214-221).  The K timed steps are the first K visited timesteps
-of the 1000-step loop, run on the device behind ONE C-ABI call; the K-step region (barrier + device sync on both
-sides, max over ranks) is repeated `--repeats` times and the MEDIAN is reported.
+update (the reference's models/diffusion/ddpm.py:214-221).  The K timed steps are the first K visited timesteps
+of the 1000-step loop, run on the device behind ONE C-ABI call (K > 1000: consecutive calls of at most 1000 steps);
+the K-step region (barrier + device sync on both sides, max over ranks) is timed once, or `--repeats` times with
+the MEDIAN reported (default 5 under --full).
 
 N > 1: launched by torch.distributed.run, one rank per GPU; the batch of independent chains is sharded with
 crowdmod-ddpm-4d_amd/distributed.py (64 chains per GPU, weak scaling); the only collective is the gather of x_0
 at the end of every timed region (RCCL over xGMI).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel class = the 3x3x3 conv launches, timed with HIP
-events on their launch stream; algorithmic AND executed-FLOP fractions of the fp32 MFMA peak) and, at N = 1,
-`cpu_baseline` (this repo's torch-functional CPU restatement of the reference path -- the same ATen CPU kernels the
-reference dispatches to -- on the host cores, thread count chosen by a short sweep).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline.  With
+--full the line also carries `roofline` (dominant kernel class = the 3x3x3 conv launches, timed with HIP events on
+their launch stream in an extra profiled run; algorithmic AND executed-FLOP fractions of the fp32 MFMA peak), at
+N = 1 `cpu_baseline` (this repo's torch-functional CPU restatement of the reference path -- the same ATen CPU kernels
+the reference dispatches to -- on the host cores, thread count chosen by a short sweep) and `secondary` (the other
+BASELINE configs).
+
+--dump-outputs DIR writes what the last timed region returned to its caller -- the sampled tensor x after the K
+steps, gathered over the ranks -- as DIR/x.npy (float32; a fixed seeded sample of at most 64 MB if larger).  The
+inputs (weights, conditioning frames, device-drawn noise) are seeded, so the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -62,6 +70,21 @@ def self_launch(gpus: int) -> int:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.run(cmd, env=env).returncode
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6   # all dumped arrays together, under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float32.  An array over its share of DUMP_LIMIT_BYTES is replaced by a
+    fixed seeded sample of its flattened elements: the same positions in every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    per = DUMP_LIMIT_BYTES // len(arrays) // 4
+    for name, arr in arrays.items():
+        arr = np.asarray(arr, dtype=np.float32)
+        if arr.size > per:
+            arr = arr.reshape(-1)[np.sort(np.random.default_rng(0).choice(arr.size, per, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def csrc_sha16():
@@ -371,7 +394,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="timed K-step regions; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="timed K-step regions; the median is reported (default 1, "
+                    "5 under --full)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the conv-class "
+                    "roofline (an extra profiled run), the CPU baseline and the `secondary` object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed region's result as DIR/x.npy")
     ap.add_argument("--batch", type=int, default=None, help="chains per GPU (default 64; 128 windows in --mode train)")
     ap.add_argument("--channels", type=int, default=4)
     ap.add_argument("--mode", choices=("sample", "train"), default="sample")
@@ -387,6 +414,12 @@ def main():
                     "(bit-identical results); 1 = one launch per layer")
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` object (the other BASELINE configs, N = 1 only)")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.mode == "train":
+        ap.error("--dump-outputs applies to the sampling benchmark")
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.lanes is None:
         a.lanes = int(os.environ.get("CM_LANES", "2") or 2)
     os.environ["CM_LANES"] = str(max(1, a.lanes))   # read once by the library at the first loop call
@@ -442,8 +475,13 @@ def main():
     past = torch.from_numpy(prng.normal_per_sample(7, "bench/past", np.arange(lo, hi), per_p).reshape(shape_p)).to(dev)
 
     def run(nsteps):
-        x, _ = model._generate_ddpm(past, sampler, hi - lo, sample_id_base=lo, first_steps=nsteps)
-        return x
+        # one loop call visits at most `timesteps` steps: a longer K runs as consecutive calls
+        while True:
+            n = min(nsteps, sampler.timesteps)
+            x, _ = model._generate_ddpm(past, sampler, hi - lo, sample_id_base=lo, first_steps=n)
+            nsteps -= n
+            if nsteps <= 0:
+                return x
 
     def sync():
         if dist is not None:
@@ -458,7 +496,7 @@ def main():
         t0 = time.perf_counter()
         x = run(steps)
         if dist is not None:   # the trivial gather of the sharded result (RCCL over xGMI); gloo rehearsal stages through the host
-            cdist.gather_samples(x if backend == "nccl" else x.cpu(), gb, rank, world)
+            x = cdist.gather_samples(x if backend == "nccl" else x.cpu(), gb, rank, world)
         sync()
         el = time.perf_counter() - t0
         if dist is not None:
@@ -467,16 +505,18 @@ def main():
             el = float(tmax.item())
         times.append(el)
     elapsed = float(np.median(times))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"x": x.cpu().numpy()})
 
     # ---- roofline of the dominant kernel class: a profiled re-run of the same K steps ------
     roofline = None
-    if not a.no_profile and rank == 0:
+    if a.full and not a.no_profile and rank == 0:
         roofline = profile_roofline(model, run, steps, hi - lo, a.lanes)
     if dist is not None:
         dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_budget > 0 and a.dtype == "f32" and not a.grid and not a.config:
+    if a.full and rank == 0 and world == 1 and a.cpu_budget > 0 and a.dtype == "f32" and not a.grid and not a.config:
         cpu = cpu_baseline(res, Cn, B, a.cpu_budget)
 
     if rank == 0:
@@ -514,7 +554,7 @@ def main():
         if cpu:
             out["cpu_baseline"] = cpu
         # the other BASELINE configs, same process, fresh handles (default headline run at N = 1 only)
-        if world == 1 and not a.no_secondary and a.dtype == "f32" and not a.grid and not a.config and not a.batch and a.channels == 4:
+        if a.full and world == 1 and not a.no_secondary and a.dtype == "f32" and not a.grid and not a.config and not a.batch and a.channels == 4:
             model.denoiser._release(keep_training=False)
             out["secondary"] = measure_secondary(a)
         print(json.dumps(out))

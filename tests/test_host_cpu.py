@@ -528,6 +528,21 @@ def test_bench_self_launch_builds_a_torchrun_child_command(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: an array within the size limit is written whole as float32; a larger one becomes a
+    seeded sample of its elements that is the same in every run."""
+    import bench
+    x = np.arange(2 * 3 * 5, dtype=np.float64).reshape(2, 3, 5)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x})
+    got = np.load(tmp_path / "a" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x})
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.shape == (8,) and np.array_equal(b, c) and len(set(b.tolist())) == 8 and set(b.tolist()) <= set(x.ravel().tolist())
+
+
 def test_energy_metric_matches_the_reference_compute_energy():
     """models/guidance.py:10-42 restated in numpy (crowdmod-ddpm-4d_amd/metrics.py) against the reference's outputs
     (tests/golden/energy.npz, generated by importing the reference's module)."""
