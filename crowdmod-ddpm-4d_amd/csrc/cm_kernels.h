@@ -500,7 +500,7 @@ hipError_t launch_attn_block(const AttnBlockArgs &a, hipStream_t st);
 
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.
-struct StepRow { int t; float c_x, c_eps, c_noise, guid; int draw; int step; int pad; };
+struct StepRow { int t; float c_x, c_eps, c_noise, guid; int draw; int step; float mass; };   // mass: MassApplyArgs::c
 struct StepArgs {
   float *x;             // [B,C,H,W,F] reference layout, updated in place
   const float *eps_cl;  // channels-last UNet output [B][L][H][W][cs]
@@ -526,6 +526,22 @@ struct StepArgs {
   unsigned long long *zero_u64; long long zero_n;
 };
 hipError_t launch_sampler_step(const StepArgs &a, hipStream_t st);
+// mass_preservation guidance (cm_guidance.hip).  q = the reference's finite-difference quotient of compute_energy for
+// x [B][Cin][H][W][L] (Cin >= 3), written to q [B][Cout][H][W][L] (channels >= 3 are written as 0); one writer per element.
+hipError_t launch_mass_grad(const float *x, int Cin, float *q, int Cout, int B, int H, int W, int L, float delta_t,
+                            float delta_l, float eps, hipStream_t st);
+struct MassApplyArgs {
+  float *x;             // [B,C,H,W,F] reference layout: channels 0-2 updated in place, x -= c * q
+  const float *q;       // [B,3,H,W,F]
+  float *x8;            // UNet input [B][L][H][W][8]: future frames rewritten (as sampler_step_kernel does)
+  float *hist;          // optional history row of this step (rewritten after the sampler step's copy)
+  int B, C, H, W, P, F;
+  float c;              // 1 - alpha_t
+  // graph replay: c comes from tab[*kctr].mass and hist is the BASE pointer (row k + 1, sample offset boff)
+  const StepRow *tab; const int *kctr;
+  long long row_stride, boff;
+};
+hipError_t launch_mass_apply(const MassApplyArgs &a, hipStream_t st);
 hipError_t launch_q_sample(const float *x0, const long long *t, const float *eps, const float *sab, const float *s1m,
                            float *xt, int B, long long per, hipStream_t st);
 hipError_t launch_fill_t(long long *t, int B, long long value, hipStream_t st);

@@ -249,6 +249,7 @@ struct cm_model {
   size_t steptab_cap = 0;
   int *d_kctr = nullptr;        // device-side step counter read by the table-driven step kernels
   int *d_nonfinite = nullptr;   // result word of the sampler-output health check
+  float *mass_q = nullptr;      // mass_preservation guidance quotient [max_batch,3,H,W,F] (allocated on first use)
   float *stage_past = nullptr, *stage_fut = nullptr, *stage_out = nullptr;  // host-variant staging
   float *stage_noise = nullptr;
   size_t stage_noise_cap = 0;
@@ -2684,6 +2685,11 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
   const cm_unet_config &c = m->cfg;
   const size_t per = (size_t)m->per_sample();
   const std::vector<int> order = visit_order(s, opts);
+  // mass_preservation guidance runs in the DDPM loop only (ddpm.py:227-229; _generate_ddim and flow matching ignore it)
+  const bool mass = opts->guidance == CM_GUIDANCE_MASS_PRESERVATION && opts->sampler == CM_SAMPLER_DDPM;
+  if (mass && c.in_channels < 3) return fail("mass_preservation guidance needs >= 3 channels (r, u, v), model has %d", c.in_channels);
+  if (mass && !m->mass_q && dev_alloc(m, (void **)&m->mass_q, (size_t)c.max_batch * 3 * c.rows * c.cols * c.future_len * sizeof(float)))
+    return 1;
   if (prof_begin(m, st)) return 1;
   // x_T: injected or drawn on device (ddpm.py:211,242)
   if (d_xT) CM_HIP(hipMemcpyAsync(m->xstate, d_xT, B * per * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -2722,7 +2728,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
   for (size_t k = 0; k < order.size(); ++k) {
     const int t = order[k];
     cm::StepRow &r = rows[k];
-    r.t = t; r.step = t; r.pad = 0;
+    r.t = t; r.step = t; r.mass = 0.f;
     if (opts->sampler == CM_SAMPLER_FM_EULER) {
       r.c_x = 1.0f; r.c_eps = (float)(1.0 / (double)opts->fm_steps); r.c_noise = 0.f;  // xt + delta * u, flow_matching.py:219
       r.draw = 0; r.guid = 0.f;
@@ -2740,6 +2746,10 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       ddpm_coeffs(s, t, &r.c_x, &r.c_eps, &r.c_noise);
       r.draw = t > 0;                                              // ddpm.py:27
       r.guid = opts->guidance == CM_GUIDANCE_SPARSITY ? opts->lambda_guidance * sqrtf(s->tab[CM_TAB_BETA][t]) : 0.f;
+      if (mass) {                                                  // (1 - alpha_t) in fp32, alpha_t = 1 - beta_t (ddpm.py:38)
+        const float a = 1.0f - s->tab[CM_TAB_BETA][t];
+        r.mass = 1.0f - a;
+      }
     }
   }
   auto base_args = [&]() {
@@ -2747,6 +2757,19 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     a.C = c.in_channels; a.H = c.rows; a.W = c.cols; a.P = c.past_len; a.F = c.future_len;
     a.seed = opts->seed; a.cs = 8;
     return a;
+  };
+  // mass_preservation: q of the new x of samples [b0, b0 + Bn), then x -= c q (also into x8 and the history row)
+  const size_t per_q = (size_t)3 * c.rows * c.cols * c.future_len;
+  auto mass_step = [&](int b0, int Bn, float cmass, float *hist, const cm::StepRow *tab, long long boff, hipStream_t ls) -> int {
+    float *x = m->xstate + (size_t)b0 * per;
+    float *q = m->mass_q + (size_t)b0 * per_q;
+    CM_HIP(cm::launch_mass_grad(x, c.in_channels, q, 3, Bn, c.rows, c.cols, c.future_len, 1.0f, 1.0f, 0.1f, ls));   // ddpm.py:228
+    cm::MassApplyArgs ma{};
+    ma.x = x; ma.q = q; ma.x8 = m->x8 + (size_t)b0 * m->L() * c.rows * c.cols * 8; ma.hist = hist;
+    ma.B = Bn; ma.C = c.in_channels; ma.H = c.rows; ma.W = c.cols; ma.P = c.past_len; ma.F = c.future_len;
+    ma.c = cmass; ma.tab = tab; ma.kctr = m->d_kctr; ma.row_stride = (long long)B * per; ma.boff = boff;
+    CM_HIP(cm::launch_mass_apply(ma, ls));
+    return 0;
   };
   const bool graph = opts->use_graph && !m->profile && lanes == 1 && !stream && order.size() >= 3;
   if (graph) {
@@ -2772,6 +2795,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       if (m->astat_all) { al.zero_u64 = m->astat_all; al.zero_n = (long long)B * m->astat_C * 3; }
       CM_HIP(cm::launch_sampler_step(al, st));
       if (m->astat_all) { m->astat_clean[0].b0 = 0; m->astat_clean[0].B = B; }
+      if (mass && mass_step(0, B, 0.f, d_history, m->d_steptab, 0, st)) return 1;
       return 0;
     };
     if (enqueue_step()) return 1;
@@ -2814,6 +2838,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       }
       CM_HIP(cm::launch_sampler_step(al, ls));
       if (m->astat_all) { m->astat_clean[ln & 3].b0 = b0; m->astat_clean[ln & 3].B = Bn; }
+      if (mass && mass_step(b0, Bn, r.mass, al.hist, nullptr, 0, ls)) return 1;
     }
     return 0;
   };
@@ -3011,6 +3036,18 @@ int cm_frame_metrics(int32_t device, const float *d_pred, const float *d_gt, int
   hipFree(d_out);
   if (d_mm) hipFree(d_mm);
   if (e != hipSuccess) return fail("frame metrics failed: %s", hipGetErrorString(e));
+  return 0;
+}
+
+int cm_mass_preservation_grad(int32_t device, const float *d_x, int32_t B, int32_t Cc, int32_t H, int32_t W, int32_t L,
+                              float delta_t, float delta_l, float eps, float *d_grad, void *stream) {
+  if (!d_x || !d_grad) return fail("null argument");
+  if (B < 1 || H < 1 || W < 1 || L < 1) return fail("bad shape [%d,%d,%d,%d,%d]", B, Cc, H, W, L);
+  if (Cc < 3) return fail("mass_preservation gradient needs >= 3 channels (r, u, v: guidance.py:25-31), got %d", Cc);
+  if (delta_t == 0.f || delta_l == 0.f) return fail("delta_t and delta_l must be non-zero");
+  if (d_x == d_grad) return fail("d_grad must not alias d_x (the gradient is written out of place)");
+  DevGuard g(device);
+  CM_HIP(cm::launch_mass_grad(d_x, Cc, d_grad, Cc, B, H, W, L, delta_t, delta_l, eps, (hipStream_t)stream));
   return 0;
 }
 

@@ -101,9 +101,9 @@ class DDPM_model:
         r = self.res
         o = native.cm_sample_opts()
         o.sampler = sampler
-        o.guidance = native.GUIDANCE_SPARSITY if r.guidance == "Sparsity" else native.GUIDANCE_NONE  # case-sensitive, ddpm.py:223
-        if r.guidance == "mass_preservation":
-            raise NotImplementedError("mass_preservation guidance is out of scope (O(N^2) finite differences per step)")
+        # case-sensitive, ddpm.py:223,227; mass_preservation acts in the DDPM loop only (the library ignores it elsewhere)
+        o.guidance = {"Sparsity": native.GUIDANCE_SPARSITY,
+                      "mass_preservation": native.GUIDANCE_MASS_PRESERVATION}.get(r.guidance, native.GUIDANCE_NONE)
         o.lambda_guidance = float(r.lambda_guidance)
         o.ddim_sigma = float(r.sigma)
         o.ddim_divider = int(divider)

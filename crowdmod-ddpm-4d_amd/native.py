@@ -44,7 +44,7 @@ class cm_sample_opts(C.Structure):
 
 SAMPLER_DDPM, SAMPLER_DDIM, SAMPLER_FM_EULER = 0, 1, 2
 PRECISION_F32, PRECISION_F16, PRECISION_F32R, PRECISION_F32X = 0, 1, 2, 3
-GUIDANCE_NONE, GUIDANCE_SPARSITY = 0, 1
+GUIDANCE_NONE, GUIDANCE_SPARSITY, GUIDANCE_MASS_PRESERVATION = 0, 1, 2
 TABLES = ("beta", "alpha", "alpha_bar", "sqrt_alpha_bar", "one_by_sqrt_alpha", "sqrt_one_minus_alpha_bar")
 
 _lib: Optional[C.CDLL] = None
@@ -93,6 +93,8 @@ SIGNATURES = {
     "cm_model_exec_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
     "cm_model_issue_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cm_frame_metrics": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "cm_mass_preservation_grad": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_float, C.c_float, C.c_float, _P, _P]),
     "cm_debug_conv_flags": (C.c_int, [C.c_int32]),
     "cm_debug_conv_count": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "cm_debug_conv_info": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_int64]),

@@ -160,11 +160,16 @@ int cm_ddpm_step(const cm_schedule *s, const float *d_eps, float *d_x, int32_t t
 
 /* ---- whole reverse loop --------------------------------------------------- */
 enum { CM_SAMPLER_DDPM = 0, CM_SAMPLER_DDIM = 1, CM_SAMPLER_FM_EULER = 2 };
-enum { CM_GUIDANCE_NONE = 0, CM_GUIDANCE_SPARSITY = 1 };
+enum { CM_GUIDANCE_NONE = 0, CM_GUIDANCE_SPARSITY = 1, CM_GUIDANCE_MASS_PRESERVATION = 2 };
 
 typedef struct cm_sample_opts {
   int32_t sampler;        /* cfg.MODEL.DDPM.SAMPLER                              */
-  int32_t guidance;       /* cfg.MODEL.DDPM.GUIDANCE ("None" | "Sparsity")       */
+  int32_t guidance;       /* cfg.MODEL.DDPM.GUIDANCE: "None" | "Sparsity" | "mass_preservation" (CM_GUIDANCE_*).
+                             Sparsity (ddpm.py:223-226, 268-271): x[:,0] -= lambda_guidance * sqrt(beta_t) * sign(x[:,0])
+                             after every DDPM / DDIM step.  mass_preservation (ddpm.py:227-229): after every DDPM step
+                             x -= (1 - alpha_t) * cm_mass_preservation_grad(x, delta_t = 1, delta_l = 1, eps = 0.1), the
+                             history row holding the guided x; with CM_SAMPLER_DDIM / CM_SAMPLER_FM_EULER it is ignored,
+                             as in the reference.  Needs in_channels >= 3. */
   float lambda_guidance;  /* cfg.MODEL.DDPM.LAMBDA_GUIDANCE                      */
   float ddim_sigma;       /* cfg.MODEL.DDPM.SIGMA                                */
   int32_t ddim_divider;   /* cfg.MODEL.DDPM.DDIM_DIVIDER: taus = arange(0,T-1,d) */
@@ -237,6 +242,15 @@ int cm_model_issue_flops(const cm_model *m, int32_t B, double f32[8], double b16
  *   of the gt plane.  The log10 / max-over-repeats tail on [N,C,F] numbers stays on the host. */
 int cm_frame_metrics(int32_t device, const float *d_pred, const float *d_gt, int32_t N, int32_t C, int32_t H,
                      int32_t W, int32_t F, double *h_out, float *h_minmax);
+
+/* ---- mass_preservation guidance: preservationMassNumericalGradientOptimal (models/guidance.py:44-69) ----
+ * d_grad[i] = (E(x + eps e_i) - E(x)) / eps for every element i of d_x [B,C,H,W,L], E = compute_energy(x, delta_t,
+ * delta_l) (guidance.py:10-42) -- the reference's forward-difference quotient, evaluated in closed form (f is linear in
+ * every single element: at most four residual cells per element).  Channels >= 3 and elements
+ * no residual cell touches get exactly 0; H < 3, W < 3 or L < 2 give all zeros.  C < 3 is an error (the energy reads
+ * channels 0-2).  d_grad must not alias d_x.  Asynchronous on `stream` (NULL = the device's default stream). */
+int cm_mass_preservation_grad(int32_t device, const float *d_x, int32_t B, int32_t C, int32_t H, int32_t W, int32_t L,
+                              float delta_t, float delta_l, float eps, float *d_grad, void *stream);
 
 /* ---- tuning hooks (tools/tune_tiles.py): time one convolution of the plan with an explicit tile
  * geometry.  Diagnostics only -- the product path never calls them. */
