@@ -210,12 +210,18 @@ def test_training_forward_and_loss_vs_reference():
     loss, pred = m._train_step(fut, past, DDPM(timesteps=1000, scale=0.5), t=g["t"], noise=eps, drop_masks=masks)
     assert np.abs(pred - g["pred"]).max() <= TOL
     assert abs(loss - float(g["loss"])) <= 1e-5 * max(1.0, float(g["loss"]))
-    # masks drawn on the device: keep-probability and scaling are right, values are {0, 1/(1-p)}
+    # masks drawn on the device: keep-probability and scaling are right, values are {0, 1/(1-p)} -- the device draws
+    # exactly the restated masks (tests/philox_ref.py; their keep fraction is checked at B = 128 on the CPU)
+    import philox_ref
+    plan = spec.make_plan(ucfg)
+    row = philox_ref.dropout_masks(5, 0, 0, B, m.denoiser.dropout_layout()[1], 0.1)
+    assert np.all((row == 0) | (row == np.float32(1) / np.float32(0.9))) and 0 < int((row == 0).sum()) < row.size
     m.denoiser.train()
     p2 = m.denoiser.forward_train(fut, g["t"], past, seed=5)
     p3 = m.denoiser.forward_train(fut, g["t"], past, seed=5)
+    p4 = m.denoiser.forward_train(fut, g["t"], past, drop_masks=philox_ref.split_masks(row, plan))
     m.denoiser.eval()
-    assert np.array_equal(p2, p3) and not np.array_equal(p2, pred)
+    assert np.array_equal(p2, p3) and np.array_equal(p2, p4) and not np.array_equal(p2, pred)
 
 
 def _narrow_train_setup():
