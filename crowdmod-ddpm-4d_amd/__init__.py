@@ -16,12 +16,15 @@ from . import config  # noqa: F401,E402
 def __getattr__(name):
     # native-backed modules are imported lazily so that `import crowdmod_ddpm_4d_amd`
     # works on a box without the built library (e.g. for prng / spec / config only)
-    if name in ("native", "unet", "diffusion", "ddpm_model"):
+    if name in ("native", "unet", "dit", "diffusion", "ddpm_model"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name in ("UNet",):
         from .unet import UNet
         return UNet
+    if name == "DiT4D_V4":
+        from .dit import DiT4D_V4
+        return DiT4D_V4
     if name in ("DDPM", "ForwardSampler"):
         from . import diffusion
         return getattr(diffusion, name)

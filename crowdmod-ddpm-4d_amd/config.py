@@ -96,6 +96,22 @@ class Resolved:
     nsamples: int
     nsamples4plots: int
     train: Optional[AttrDict] = None
+    dit: Optional["DiTKeys"] = None   # arch DDPM-DiT: the MODEL.DDPM.DIT section
+
+
+@dataclass
+class DiTKeys:
+    """MODEL.DDPM.DIT as models/diffusion/ddpm.py:88-104 reads it."""
+    patch_size: int
+    t_patch_size: int
+    hidden_size: int
+    depth: int
+    num_heads: int
+    mlp_ratio: float
+    time_emb_mult: int
+    condition: str
+    dropout_rate: float
+    train: Optional[AttrDict]
 
 
 def _first(*vals, default=None):
@@ -121,6 +137,18 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
         return _first(gen.get(key), diff.get(key), model.get(key), default=default)
 
     train = _first(back.get("TRAIN"), gen.get("TRAIN"), cfg.get("TRAIN"))
+    dit = None
+    if arch == "DDPM-DiT":
+        # attribute access on the DIT node in the reference (ddpm.py:95-103): a missing key is an error naming it
+        def req(key):
+            if key not in back:
+                raise KeyError(f"MODEL.{gen_key}.{back_key}.{key} is missing (needed by arch {arch})")
+            return back[key]
+        dit = DiTKeys(int(req("PATCH_SIZE")), int(req("T_PATCH_SIZE")), int(req("HIDDEN_SIZE")), int(req("DEPTH")),
+                      int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")), str(req("CONDITION")),
+                      float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
+        if dit.condition != "Past":
+            raise NotImplementedError(f"DIT.CONDITION {dit.condition!r}: only 'Past' (the configuration every reference config uses)")
     mult = tuple(int(v) for v in bk("BASE_CH_MULT", (1, 2, 4)))
     attn = tuple(bool(v) for v in bk("APPLY_ATTENTION", (False, False, True, False)))
     return Resolved(
@@ -136,5 +164,5 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
         time_emb_mult=int(bk("TIME_EMB_MULT", 4)), condition=str(bk("CONDITION", "Past")),
         nsamples=int(_first(model.get("NSAMPLES"), diff.get("NSAMPLES"), default=1280)),
         nsamples4plots=int(_first(model.get("NSAMPLES4PLOTS"), diff.get("NSAMPLES4PLOTS"), default=20)),
-        train=train,
+        train=train, dit=dit,
     )

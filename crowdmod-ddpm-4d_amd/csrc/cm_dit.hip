@@ -1,0 +1,271 @@
+// DiT4D_V4 denoiser kernels (reference: models/backbones/DiT4D_V4.py).  The host plan lives in cm_dit_host.inc.
+//
+// Activations are token-major fp32 [B][T_p * N_s][D] (token order (t_p, h_p, w_p), DiT4D_V4.py:57-60); the residual
+// stream is updated in place by the gated epilogues.  Two kinds of kernel carry the whole forward:
+//   dit_gemm_kernel   Y = epilogue(prologue(A) W^T + b) on exact-fp32 matrix instructions (v_mfma_f32_32x32x2_f32),
+//                     W in the reference [out][in] layout.  Prologues: plain rows, LayerNorm (no affine, eps 1e-6,
+//                     biased variance) + modulate with the sample's row of the conditioning table, or the Conv3d
+//                     patch gather from the channels-last sampler tensor x8.  Epilogues: bias, SiLU, SiLU(SiLU(.))
+//                     (conditioning tables), exact-erf GELU, gated residual, patch embedding + both position
+//                     embeddings, and the unpatchify scatter of the final linear into eps_cl.  A row subset (the
+//                     temporal queries, the future slots of the final layer) maps logical GEMM rows to token rows.
+//   dit_attn_*        softmax(q k^T / 8) v per head (head dim 64) on the vector ALUs: spatial self-attention over the
+//                     N_s tokens of one (sample, slot), temporal cross-attention of the future slots of one (sample,
+//                     patch) over all T_p slots.
+// Determinism: every output element is written by one thread with a fixed summation order (k ascending in one fma
+// chain; fixed butterfly reductions), no atomics, and a sample only reads its own rows -- a chain's result does not
+// depend on the batch it runs in, the batch lane, or graph replay.
+#include "cm_kernels.h"
+
+#include <math.h>
+
+namespace cm {
+
+typedef float dit_f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+
+constexpr int GB = 64;    // rows and columns of a workgroup tile (2 x 2 waves of 32 x 32)
+constexpr int GK = 32;    // k chunk staged in LDS
+constexpr int GS = GK + 1;
+constexpr int TP_MAX = 8; // temporal slots the temporal-attention kernel holds in registers
+
+__device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ long long phys_row(const DitGemmArgs &a, long long r) {
+  return (r / a.grp) * (long long)a.grp_stride + a.grp_off + r % a.grp;
+}
+
+__device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+
+template <int PRO, int EPI>
+__global__ __launch_bounds__(256) void dit_gemm_kernel(const DitGemmArgs a) {
+  __shared__ float As[GB * GS], Ws[GB * GS];
+  __shared__ float s_mu[GB], s_rs[GB];
+  __shared__ const float *s_mod[GB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * GB;
+  const int n0 = blockIdx.y * GB;
+
+  if (PRO == DIT_PRO_LN) {
+    // row statistics of the tile's 64 token rows (K = D, the whole row): wave w owns rows 16w .. 16w + 15
+    for (int rr = wave * 16; rr < wave * 16 + 16; ++rr) {
+      const long long r = m0 + rr;
+      float mu = 0.f, rs = 0.f;
+      const float *mrow = nullptr;
+      if (r < a.M) {
+        const long long pr = phys_row(a, r);
+        const float *x = a.A + pr * a.lda;
+        float s = 0.f;
+        for (int k = lane; k < a.K; k += 64) s += x[k];
+        mu = wave_sum(s) / (float)a.K;
+        float q = 0.f;
+        for (int k = lane; k < a.K; k += 64) { const float d = x[k] - mu; q += d * d; }
+        rs = 1.0f / sqrtf(wave_sum(q) / (float)a.K + 1e-6f);
+        mrow = a.mod + a.tbuf[pr / a.tok] * (long long)a.ldmod;
+      }
+      if (lane == 0) { s_mu[rr] = mu; s_rs[rr] = rs; s_mod[rr] = mrow; }
+    }
+    __syncthreads();
+  }
+
+  dit_f32x16 acc;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int sr = tid >> 2, sk = (tid & 3) * 8;   // staging: one row, eight consecutive k per thread
+  const long long r = m0 + sr;
+  const bool rok = r < a.M;
+  const long long pr = rok ? phys_row(a, r) : 0;
+  const long long ar = a.a_compact ? r : pr;
+  const int n = n0 + sr;
+  for (int k0 = 0; k0 < a.K; k0 += GK) {
+    for (int e = 0; e < 8; ++e) {
+      const int k = k0 + sk + e;
+      float v = 0.f;
+      if (rok && k < a.K) {
+        if (PRO == DIT_PRO_PATCH) {
+          // Conv3d weight [D][C][pt][p][p] on x.permute(0,1,4,2,3) (DiT4D_V4.py:56-57): k = ((c*pt + it)*p + ih)*p + iw
+          const int p = a.p, pt = a.pt;
+          const int iw = k % p, ih = (k / p) % p, it = (k / (p * p)) % pt, c = k / (p * p * pt);
+          const long long b = pr / a.tok;
+          const int s = (int)(pr % a.tok), tp = s / a.Ns, hw = s % a.Ns;
+          const int hp = hw / a.wpn, wp = hw % a.wpn;
+          const int fr = tp * pt + it, y = hp * p + ih, x = wp * p + iw;
+          v = a.x8[((((b * a.L) + fr) * a.Hh + y) * a.Ww + x) * 8 + c];
+        } else if (PRO == DIT_PRO_LN) {
+          const float *mrow = s_mod[sr];
+          const float xn = (a.A[ar * a.lda + k] - s_mu[sr]) * s_rs[sr];
+          v = xn * (1.0f + mrow[a.off_scale + k]) + mrow[a.off_shift + k];   // modulate, DiT4D_V4.py:101-103
+        } else {
+          v = a.A[ar * a.lda + k];
+        }
+      }
+      As[sr * GS + sk + e] = v;
+      Ws[sr * GS + sk + e] = (n < a.N && k < a.K) ? a.W[(long long)n * a.K + k] : 0.f;
+    }
+    __syncthreads();
+    const float *ap = As + (wm * 32 + (lane & 31)) * GS + (lane >> 5);
+    const float *bp = Ws + (wn * 32 + (lane & 31)) * GS + (lane >> 5);
+#pragma unroll
+    for (int kk = 0; kk < GK; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[kk], bp[kk], acc, 0, 0, 0);
+    __syncthreads();
+  }
+
+  // C/D map: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+  const int col = n0 + wn * 32 + (lane & 31);
+  if (col >= a.N) return;
+  const float bias = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const long long rl = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+    if (rl >= a.M) continue;
+    const long long prow = phys_row(a, rl);
+    const float v = acc[i] + bias;
+    if (EPI == DIT_EPI_BIAS) {
+      a.Y[prow * a.ldy + col] = v;
+    } else if (EPI == DIT_EPI_SILU) {
+      a.Y[prow * a.ldy + col] = silu(v);
+    } else if (EPI == DIT_EPI_SILU2) {
+      a.Y[prow * a.ldy + col] = silu(silu(v));
+    } else if (EPI == DIT_EPI_GELU) {
+      a.Y[prow * a.ldy + col] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    } else if (EPI == DIT_EPI_GATE) {
+      const float *mrow = a.mod + a.tbuf[prow / a.tok] * (long long)a.ldmod;
+      float *y = a.Y + prow * a.ldy + col;
+      *y = *y + mrow[a.off_gate + col] * v;
+    } else if (EPI == DIT_EPI_PATCH) {
+      const int s = (int)(prow % a.tok), tp = s / a.Ns, hw = s % a.Ns;
+      a.Y[prow * a.ldy + col] = v + a.spos[hw * a.N + col] + a.tpos[tp * a.N + col];
+    } else {   // DIT_EPI_UNPATCH: feature ((it*C + c)*p + ih)*p + iw -> frame tp*pt + it, row hp*p + ih, col wp*p + iw
+      const int p = a.p, pt = a.pt;
+      const int iw = col % p, ih = (col / p) % p, c = (col / (p * p)) % a.Cout, it = col / (p * p * a.Cout);
+      const long long b = prow / a.tok;
+      const int s = (int)(prow % a.tok), tp = s / a.Ns, hw = s % a.Ns;
+      const int hp = hw / a.wpn, wp = hw % a.wpn;
+      const int fr = tp * pt + it, y = hp * p + ih, x = wp * p + iw;
+      a.Y[((((b * a.L) + fr) * a.Hh + y) * a.Ww + x) * 8 + c] = v;
+    }
+  }
+}
+
+// Spatial self-attention: one 64-thread workgroup per (sample, slot, head); thread i = query token i (N_s <= 64).
+// K / V of the head in LDS, scores of each query in its own LDS row, softmax and P V in fp32.
+__global__ __launch_bounds__(64) void dit_attn_spatial_kernel(const DitAttnArgs a) {
+  __shared__ float Ks[64 * 65], Vs[64 * 65], Ps[64 * 65];
+  const int i = threadIdx.x;
+  const int h = blockIdx.x % a.heads;
+  const long long g = blockIdx.x / a.heads;                 // (sample, slot)
+  const long long base = g * a.Ns;                          // first token row of the group
+  const int E3 = 3 * a.E;
+  for (int j = 0; j < a.Ns; ++j) {
+    const float *row = a.qkv + (base + j) * E3 + h * 64;
+    Ks[j * 65 + i] = row[a.E + i];
+    Vs[j * 65 + i] = row[2 * a.E + i];
+  }
+  __syncthreads();
+  if (i >= a.Ns) return;
+  float q[64];
+  const float *qr = a.qkv + (base + i) * E3 + h * 64;
+#pragma unroll
+  for (int d = 0; d < 64; ++d) q[d] = qr[d] * 0.125f;     // 1/sqrt(64), exact
+  float mx = -INFINITY;
+  for (int j = 0; j < a.Ns; ++j) {
+    float s = 0.f;
+#pragma unroll
+    for (int d = 0; d < 64; ++d) s = fmaf(q[d], Ks[j * 65 + d], s);
+    Ps[i * 65 + j] = s;
+    mx = fmaxf(mx, s);
+  }
+  float den = 0.f;
+  for (int j = 0; j < a.Ns; ++j) { const float e = expf(Ps[i * 65 + j] - mx); Ps[i * 65 + j] = e; den += e; }
+  const float inv = 1.0f / den;
+  float *o = a.out + (base + i) * a.E + h * 64;
+  for (int d0 = 0; d0 < 64; d0 += 16) {
+    float acc[16];
+#pragma unroll
+    for (int d = 0; d < 16; ++d) acc[d] = 0.f;
+    for (int j = 0; j < a.Ns; ++j) {
+      const float pj = Ps[i * 65 + j];
+#pragma unroll
+      for (int d = 0; d < 16; ++d) acc[d] = fmaf(pj, Vs[j * 65 + d0 + d], acc[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < 16; ++d) o[d0 + d] = acc[d] * inv;
+  }
+}
+
+// Temporal cross-attention: one wave per (sample, patch, head), lane = head channel.  Keys / values: the T_p slots of
+// the patch; queries: slots qs .. T_p-1 (DiT4D_V4.py:182-188).  Output rows are compact: [B][(T_p - qs) * N_s][E].
+__global__ __launch_bounds__(256) void dit_attn_temporal_kernel(const DitAttnArgs a) {
+  const int d = threadIdx.x & 63;
+  const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const long long nw = (long long)a.B * a.Ns * a.heads;
+  if (w >= nw) return;
+  const int h = (int)(w % a.heads);
+  const long long bp = w / a.heads;
+  const int patch = (int)(bp % a.Ns);
+  const long long b = bp / a.Ns;
+  const int tok = a.Tp * a.Ns, nq = a.Tp - a.qs, E3 = 3 * a.E;
+  const float *base = a.qkv + (b * tok + patch) * E3 + h * 64 + d;
+  float k[TP_MAX], v[TP_MAX];
+#pragma unroll
+  for (int j = 0; j < TP_MAX; ++j) {
+    k[j] = j < a.Tp ? base[(long long)j * a.Ns * E3 + a.E] : 0.f;
+    v[j] = j < a.Tp ? base[(long long)j * a.Ns * E3 + 2 * a.E] : 0.f;
+  }
+  for (int qi = 0; qi < nq; ++qi) {
+    const float q = base[(long long)(a.qs + qi) * a.Ns * E3] * 0.125f;
+    float s[TP_MAX], mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < TP_MAX; ++j) {
+      s[j] = wave_sum(q * k[j]);
+      if (j < a.Tp) mx = fmaxf(mx, s[j]);
+    }
+    float den = 0.f, o = 0.f;
+#pragma unroll
+    for (int j = 0; j < TP_MAX; ++j)
+      if (j < a.Tp) {
+        const float e = expf(s[j] - mx);
+        den += e;
+        o = fmaf(e, v[j], o);
+      }
+    a.out[((b * nq + qi) * a.Ns + patch) * a.E + h * 64 + d] = o / den;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  dim3 grid((unsigned)((a.M + GB - 1) / GB), (unsigned)((a.N + GB - 1) / GB));
+#define CM_DIT_G(P, E) \
+  if (a.pro == P && a.epi == E) { hipLaunchKernelGGL((dit_gemm_kernel<P, E>), grid, dim3(256), 0, st, a); return hipGetLastError(); }
+  CM_DIT_G(DIT_PRO_NONE, DIT_EPI_BIAS)
+  CM_DIT_G(DIT_PRO_NONE, DIT_EPI_SILU)
+  CM_DIT_G(DIT_PRO_NONE, DIT_EPI_SILU2)
+  CM_DIT_G(DIT_PRO_NONE, DIT_EPI_GATE)
+  CM_DIT_G(DIT_PRO_LN, DIT_EPI_BIAS)
+  CM_DIT_G(DIT_PRO_LN, DIT_EPI_GELU)
+  CM_DIT_G(DIT_PRO_LN, DIT_EPI_UNPATCH)
+  CM_DIT_G(DIT_PRO_PATCH, DIT_EPI_PATCH)
+#undef CM_DIT_G
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_dit_attn_spatial(const DitAttnArgs &a, hipStream_t st) {
+  if (a.Ns < 1 || a.Ns > 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dit_attn_spatial_kernel, dim3((unsigned)((long long)a.B * a.Tp * a.heads)), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st) {
+  if (a.Tp < 1 || a.Tp > TP_MAX || a.qs >= a.Tp) return hipErrorInvalidValue;
+  const long long nw = (long long)a.B * a.Ns * a.heads;
+  hipLaunchKernelGGL(dit_attn_temporal_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace cm

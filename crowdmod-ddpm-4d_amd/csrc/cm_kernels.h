@@ -498,6 +498,35 @@ bool attn_block_ok(int S, int E, int heads, int groups);
 size_t attn_block_lds_bytes(int S, int E, int heads);
 hipError_t launch_attn_block(const AttnBlockArgs &a, hipStream_t st);
 
+// DiT4D_V4 denoiser (cm_dit.hip): one token GEMM with fused prologue / epilogue, and the two attention kernels.
+enum { DIT_PRO_NONE = 0, DIT_PRO_LN = 1, DIT_PRO_PATCH = 2 };
+enum { DIT_EPI_BIAS = 0, DIT_EPI_SILU = 1, DIT_EPI_SILU2 = 2, DIT_EPI_GELU = 3, DIT_EPI_GATE = 4, DIT_EPI_PATCH = 5,
+       DIT_EPI_UNPATCH = 6 };
+struct DitGemmArgs {
+  int pro, epi;
+  const float *A; int lda;        // A rows (PRO_NONE / PRO_LN; PRO_LN needs K = the whole row)
+  const float *W, *bias;          // W [N][K] (reference layout), bias [N] or null
+  float *Y; int ldy;              // output rows; EPI_GATE: the residual stream, updated in place; EPI_UNPATCH: eps_cl
+  long long M; int N, K;
+  int grp, grp_stride, grp_off;   // logical row r -> token row (r / grp) * grp_stride + grp_off + r % grp
+  int a_compact;                  // A is read at the logical row (otherwise at the token row)
+  int tok;                        // tokens per sample (sample of a token row = row / tok)
+  const long long *tbuf;          // timestep per sample
+  const float *mod; int ldmod;    // conditioning table [1000][ldmod]
+  int off_shift, off_scale, off_gate;
+  const float *x8;                // PRO_PATCH: sampler tensor [B][L][H][W][8]
+  const float *spos, *tpos;       // EPI_PATCH: spatial [N_s][D] and temporal [T_p][D] position embeddings
+  int L, Hh, Ww, p, pt, Ns, wpn, Cout;
+};
+struct DitAttnArgs {
+  const float *qkv;               // [B][T_p * N_s][3E] (q | k | v)
+  float *out;                     // spatial: [B][T_p * N_s][E]; temporal: [B][(T_p - qs) * N_s][E]
+  int B, Tp, Ns, qs, E, heads;    // head dim E / heads = 64
+};
+hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st);
+hipError_t launch_dit_attn_spatial(const DitAttnArgs &a, hipStream_t st);
+hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st);
+
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.
 struct StepRow { int t; float c_x, c_eps, c_noise, guid; int draw; int step; float mass; };   // mass: MassApplyArgs::c

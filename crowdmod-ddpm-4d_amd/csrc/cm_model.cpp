@@ -195,9 +195,11 @@ struct cm_schedule {
 };
 
 struct cm_train_state;
+struct cm_dit_plan;   // cm_dit_host.inc: the DiT4D_V4 backbone (null on a UNet handle)
 void cm_free_train_state(cm_train_state *t);  // cm_train_host.inc (host-side struct only; device buffers live in allocs)
 struct cm_model {
-  cm_unet_config cfg{};
+  cm_unet_config cfg{};   // DiT handle: the sampler geometry (channels, grid, frames, max_batch, device) only
+  cm_dit_plan *dit = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};  // extra lanes of the batch interleave
@@ -2296,6 +2298,16 @@ std::vector<int> visit_order(const cm_schedule *s, const cm_sample_opts *o) {
 
 }  // namespace
 
+#include "cm_dit_host.inc"
+
+namespace {
+// entry points of the UNet plan that a DiT handle does not have
+int refuse_dit(const char *what) {
+  return fail("%s: not available on a DDPM-DiT (DiT4D_V4) handle, only on the UNet backbone", what);
+}
+}  // namespace
+#define CM_NOT_DIT(m, what) do { if ((m) && (m)->dit) return refuse_dit(what); } while (0)
+
 // ================================================================================
 // C ABI
 // ================================================================================
@@ -2380,6 +2392,7 @@ int cm_model_create(const cm_unet_config *cfg, cm_model **out) {
 
 int cm_model_destroy(cm_model *m) {
   if (!m) return 0;
+  delete m->dit;
   if (m->device < 0) { delete m; return 0; }
   DevGuard g(m->device);
   hipDeviceSynchronize();
@@ -2438,6 +2451,7 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
 int cm_model_set_precision(cm_model *m, int32_t precision) {
   if (!m) return fail("null model handle");
   if (m->finalized) return fail("precision must be chosen before cm_model_finalize");
+  if (m->dit && precision != CM_PRECISION_F32) return refuse_dit("a precision other than CM_PRECISION_F32");
   if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16 && precision != CM_PRECISION_F32R && precision != CM_PRECISION_F32X)
     return fail("unknown precision %d", precision);
   m->precision = precision;
@@ -2450,6 +2464,7 @@ int cm_model_finalize(cm_model *m) {
   if (m->device < 0) return fail("host-only handle (device < 0) cannot be finalized: there is no CPU path");
   for (auto &p : m->params)
     if (!p.set) return fail("missing key in state_dict: %s", p.name.c_str());
+  if (m->dit) return dit_finalize(m);
   DevGuard g(m->device);
   const cm_unet_config &c = m->cfg;
   const size_t B = (size_t)c.max_batch;
@@ -2485,7 +2500,7 @@ int cm_unet_forward(cm_model *m, const float *d_future, const int64_t *d_t, cons
   if (prof_begin(m, st)) return 1;
   CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
   CM_HIP(cm::launch_assemble_input(d_past, d_future, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
-  if (run_ops(m, B, st)) return 1;
+  if (denoise(m, B, st, 0, 0)) return 1;
   CM_HIP(cm::launch_extract_output(m->eps_cl, 8, d_out, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st));
   return prof_collect(m, st);
 }
@@ -2517,6 +2532,7 @@ int cm_unet_forward_host(cm_model *m, const float *h_future, const int64_t *h_t,
 }
 
 int cm_model_dropout_width(const cm_model *m, int32_t *width) {
+  CM_NOT_DIT(m, "cm_model_dropout_width");
   if (!m || !width) return fail("null argument");
   if (!m->finalized) return fail("model not finalized");
   *width = m->nproj;
@@ -2526,6 +2542,7 @@ int cm_model_dropout_width(const cm_model *m, int32_t *width) {
 int cm_unet_forward_train(cm_model *m, const float *d_future, const int64_t *d_t, const float *d_past,
                           const float *d_dropmask, float p, uint64_t seed, int64_t sample_id_base, float *d_out,
                           int32_t B, void *stream) {
+  CM_NOT_DIT(m, "cm_unet_forward_train");
   if (check_ready(m, B)) return 1;
   if (!d_future || !d_t || !d_past || !d_out) return fail("null tensor argument");
   if (!(p >= 0.f && p < 1.f)) return fail("dropout rate %g outside [0,1)", p);
@@ -2547,6 +2564,7 @@ int cm_unet_forward_train(cm_model *m, const float *d_future, const int64_t *d_t
 }
 
 int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t n, float *h_loss, void *stream) {
+  CM_NOT_DIT(m, "cm_mse_loss");
   if (!m || !d_pred || !d_target || !h_loss || n < 1) return fail("bad argument");
   if (!m->finalized) return fail("model not finalized");
   DevGuard g(m->device);
@@ -2558,6 +2576,7 @@ int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t
 }
 
 int cm_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity, int64_t shape[5]) {
+  CM_NOT_DIT(m, "cm_debug_activation");
   if (!m || !name || !h_out) return fail("null argument");
   if (!m->finalized) return fail("model not finalized");
   auto it = m->act_by_name.find(name);
@@ -2786,7 +2805,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     CM_HIP(hipStreamSynchronize(st));                            // `rows` is host memory of this call
     auto enqueue_step = [&]() -> int {
       CM_HIP(cm::launch_step_begin(m->tbuf, B, m->d_steptab, m->d_kctr, st));
-      if (run_ops(m, B, st, 0, 0)) return 1;
+      if (denoise(m, B, st, 0, 0)) return 1;
       cm::StepArgs al = base_args();
       al.B = B; al.x = m->xstate; al.eps_cl = m->eps_cl; al.x8 = m->x8;
       al.sample_id_base = opts->sample_id_base;
@@ -2823,7 +2842,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       const cm::StepRow &r = rows[k];
       al.step = r.step; al.c_x = r.c_x; al.c_eps = r.c_eps; al.c_noise = r.c_noise; al.draw = r.draw; al.guid = r.guid;
       if (k == 0) CM_HIP(cm::launch_fill_t(m->tbuf + b0, Bn, t, ls));
-      if (run_ops(m, Bn, ls, b0, ln)) return 1;
+      if (denoise(m, Bn, ls, b0, ln)) return 1;
       al.B = Bn;
       if (k + 1 < order.size()) { al.t_next = m->tbuf + b0; al.t_next_v = order[k + 1]; }
       al.x = m->xstate + (size_t)b0 * per;
@@ -2958,18 +2977,21 @@ int cm_sample_loop_host(cm_model *m, const cm_schedule *s, const float *h_past, 
 }
 
 int cm_profile_enable(cm_model *m, int32_t on) {
+  CM_NOT_DIT(m, "cm_profile_enable");
   if (!m) return fail("null model handle");
   m->profile = on != 0;
   return 0;
 }
 
 int cm_profile_read(cm_model *m, float ms[8], int64_t launches[8]) {
+  CM_NOT_DIT(m, "cm_profile_read");
   if (!m || !ms || !launches) return fail("null argument");
   for (int i = 0; i < 8; ++i) { ms[i] = m->prof_ms[i]; launches[i] = m->prof_n[i]; }
   return 0;
 }
 
 int cm_profile_read_union(cm_model *m, float ms[8]) {
+  CM_NOT_DIT(m, "cm_profile_read_union");
   if (!m || !ms) return fail("null argument");
   for (int i = 0; i < 8; ++i) ms[i] = m->prof_union_ms[i];
   return 0;
@@ -2977,6 +2999,7 @@ int cm_profile_read_union(cm_model *m, float ms[8]) {
 
 int cm_model_cost(const cm_model *m, int32_t B, double *flops, double *bytes) {
   if (!m || !m->finalized) return fail("model not finalized");
+  if (m->dit) return dit_cost(m, B, flops, bytes);
   double f = 0, by = 0;
   for (const Op &op : m->ops) {
     if (op.kind == OP_CONV) {
@@ -2996,6 +3019,7 @@ int cm_model_cost(const cm_model *m, int32_t B, double *flops, double *bytes) {
 }
 
 int cm_profile_report(cm_model *m, char *buf, int64_t capacity) {
+  CM_NOT_DIT(m, "cm_profile_report");
   if (!m || !buf || capacity < 1) return fail("null argument");
   std::string out;
   char line[512];
@@ -3058,6 +3082,7 @@ int cm_debug_conv_flags(int32_t flags) {
 }
 
 int cm_debug_conv_count(const cm_model *m, int32_t *count) {
+  CM_NOT_DIT(m, "cm_debug_conv_count");
   if (!m || !m->finalized || !count) return fail("model not finalized");
   *count = (int32_t)m->ops.size();
   return 0;
@@ -3065,6 +3090,7 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count) {
 
 // One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags" or "other <label>".
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
+  CM_NOT_DIT(m, "cm_debug_conv_info");
   if (!m || !m->finalized || !buf || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
@@ -3083,6 +3109,7 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
 // same layer on fp32 matrix instructions (the split fragments withheld); mode 2: the h2 form where the plan has one (the caller
 // keeps its operands inside the bound the plan guarantees, tests/test_gpu_h2.py).
 int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B) {
+  CM_NOT_DIT(m, "cm_debug_conv_io");
   if (check_ready(m, B)) return 1;
   if (!h_in0 || !h_out || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   Op &op = m->ops[index];
@@ -3123,6 +3150,7 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
 // geometry (MB; bz,by,bx) -- 0 keeps the op's own.  The activations are whatever the last forward left.
 int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32_t by, int32_t bx, int32_t B,
                        int32_t iters, float *us) {
+  CM_NOT_DIT(m, "cm_debug_time_conv");
   if (check_ready(m, B)) return 1;
   if (!us || index < 0 || index >= (int)m->ops.size() || iters < 1) return fail("bad argument");
   Op &op = m->ops[index];
@@ -3188,6 +3216,7 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
 // a six-term layer (fp32 products from exact three-way bf16 splits) issues six v_mfma_f32_32x32x16_bf16 products per
 // fp32-equivalent product, an f16-plan layer one; `flops` then keeps the part issued as fp32 matrix instructions.
 static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], double *b16) {
+  CM_NOT_DIT(m, "the exec / issue FLOP split");
   if (!m || !m->finalized || !flops) return fail("model not finalized");
   for (int i = 0; i < 8; ++i) flops[i] = 0;
   if (b16) for (int i = 0; i < 8; ++i) b16[i] = 0;
@@ -3260,6 +3289,7 @@ int cm_model_issue_flops(const cm_model *m, int32_t B, double f32[8], double b16
 }
 
 int cm_model_class_flops(const cm_model *m, int32_t B, double flops[8]) {
+  CM_NOT_DIT(m, "cm_model_class_flops");
   if (!m || !m->finalized || !flops) return fail("model not finalized");
   for (int i = 0; i < 8; ++i) flops[i] = 0;
   for (const Op &op : m->ops) {

@@ -929,6 +929,7 @@ int apply_adam(cm_model *m, hipStream_t st) {
 extern "C" {
 
 int cm_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay, float dropout_rate) {
+  CM_NOT_DIT(m, "cm_train_init");
   if (!m || !m->finalized) return fail("model not finalized");
   if (m->precision != CM_PRECISION_F32 && m->precision != CM_PRECISION_F32X)
     return fail("training runs on default-plan fp32 handles: the f16 operand copies of a reduced-precision handle are not re-packed after an "
@@ -1000,6 +1001,7 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
 int cm_train_step(cm_model *m, const cm_schedule *s, const float *d_future, const float *d_past, const int64_t *d_t,
                   const float *d_eps, const float *d_dropmask, uint64_t seed, float *h_loss, int32_t B,
                   int32_t apply_update, void *stream) {
+  CM_NOT_DIT(m, "cm_train_step");
   if (check_ready(m, B)) return 1;
   if (!m->train) return fail("cm_train_init has not been called");
   if (!s || !d_future || !d_past || !d_t || !h_loss) return fail("null argument");
@@ -1020,6 +1022,7 @@ int cm_train_step(cm_model *m, const cm_schedule *s, const float *d_future, cons
 
 int cm_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const int64_t *d_t, const float *d_target,
                      const float *d_dropmask, uint64_t seed, float *h_loss, int32_t B, int32_t apply_update, void *stream) {
+  CM_NOT_DIT(m, "cm_train_step_xt");
   if (check_ready(m, B)) return 1;
   if (!m->train) return fail("cm_train_init has not been called");
   if (!d_xt || !d_past || !d_t || !d_target || !h_loss) return fail("null argument");

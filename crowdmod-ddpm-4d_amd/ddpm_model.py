@@ -49,7 +49,7 @@ class ReduceLROnPlateau:
 
 
 class DDPM_model:
-    _ARCHS = ("DDPM-UNet",)
+    _ARCHS = ("DDPM-UNet", "DDPM-DiT")
 
     def __init__(self, cfg, arch, mprops_count, output_dir=None, from_fixed_past=False, *, device: int = 0,
                  seed: int = 42):
@@ -89,6 +89,14 @@ class DDPM_model:
         if self.arch not in self._ARCHS:
             raise ValueError(f"Unknown Architecture {self.arch}")
         r = self.res
+        if self.arch == "DDPM-DiT":
+            from .dit import DiT4D_V4
+            d = r.dit
+            return DiT4D_V4(input_channels=self.mprops_count, output_channels=self.mprops_count, grid_rows=r.rows,
+                            grid_cols=r.cols, past_len=r.past_len, future_len=r.future_len, t_patch_size=d.t_patch_size,
+                            patch_size=d.patch_size, hidden_size=d.hidden_size, depth=d.depth, num_heads=d.num_heads,
+                            mlp_ratio=d.mlp_ratio, dropout_rate=d.dropout_rate, time_multiple=d.time_emb_mult,
+                            condition=d.condition, device=self.device, max_batch=max(1, r.batch_size), seed=self.seed)
         return UNet(input_channels=self.mprops_count, output_channels=self.mprops_count,
                     num_res_blocks=r.num_res_blocks, base_channels=r.base_ch,
                     base_channels_multiples=r.base_ch_mult, apply_attention=r.apply_attention,
@@ -196,6 +204,7 @@ class DDPM_model:
         The backward pass and the Adam update of ddpm.py:142-144 run inside `_train_one_epoch` (one native
         cm_train_step per batch); this method is the stand-alone loss evaluation with injectable t / noise /
         masks that the parity tests use."""
+        self._refuse_training()
         future = np.ascontiguousarray(future, dtype=np.float32)
         B = future.shape[0]
         if t is None:
@@ -210,6 +219,10 @@ class DDPM_model:
         return self.denoiser.mse_loss(pred, eps), pred
 
     # -- training (ddpm.py:123-202) ---------------------------------------------------
+    def _refuse_training(self):
+        if self.arch != "DDPM-UNet":
+            raise NotImplementedError(f"training {self.arch} is not implemented on this path (sampling only)")
+
     def _solver(self):
         tr = self.res.train or {}
         sol = tr.get("SOLVER", {}) if hasattr(tr, "get") else {}
@@ -240,6 +253,7 @@ class DDPM_model:
         noise, train-mode forward, MSE, backward, Adam -- one native call per batch.  `grad_sync`, when
         given, is called between backward and update (data-parallel gradient averaging).
         Returns the mean batch loss (MeanMetric)."""
+        self._refuse_training()
         # one stream of timesteps per (seed, epoch, rank): replicas must not train on identical draws
         rng = rng or np.random.default_rng([self.seed + epoch, self.dp_rank] if self.dp_world > 1 else self.seed + epoch)
         total, count = 0.0, 0
@@ -289,6 +303,7 @@ class DDPM_model:
         distributed.mean_over_ranks) averages the epoch loss, so that the scheduler, the NaN stop and the
         checkpoint decisions are identical on every rank (a rank that stopped alone would leave the others
         blocked in the gradient all-reduce)."""
+        self._refuse_training()
         import logging
         forward_sampler = DDPM(timesteps=max(2, self.res.timesteps), scale=self.res.scale, device=self.device)
         if baseline_ckpt is not None:

@@ -36,8 +36,8 @@ def main(argv=None):
     ap.add_argument('--device', type=int, default=0)
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
-    if args.arch != "DDPM-UNet":
-        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT"):
+        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet and DDPM-DiT on this path")
     from crowdmod_ddpm_4d_amd.ddpm_model import DDPM_model
     from generate_samples import model_fullname, windows
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)

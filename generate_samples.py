@@ -62,8 +62,8 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
-    if args.arch not in ("DDPM-UNet", "FM-UNet"):
-        raise SystemExit(f"{args.arch}: only the UNet-backbone generators (DDPM-UNet, FM-UNet) are implemented on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-UNet"):
+        raise SystemExit(f"{args.arch}: only DDPM-UNet, DDPM-DiT and FM-UNet are implemented on this path")
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
     res = cfgmod.resolve(cfg, args.arch)
     mprops = 3  # generate_samples.py:76 of the reference

@@ -54,6 +54,28 @@ typedef struct cm_unet_config {
                                              names, shapes, set / get) that can never be finalized      */
 } cm_unet_config;
 
+/* Hyper-parameters of reference DiT4D_V4.__init__ (models/backbones/DiT4D_V4.py:235-254) plus the tensor geometry, as
+ * DDPM_model builds it for arch "DDPM-DiT" (models/diffusion/ddpm.py:88-104).  A DiT handle is the same opaque cm_model,
+ * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 only)
+ * / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it; every
+ * other handle entry point (training, dropout width, debug and conv hooks, profiling, FLOP splits) returns non-zero. */
+typedef struct cm_dit_config {
+  int32_t in_channels;                    /* mprops_count                                        */
+  int32_t out_channels;
+  int32_t rows, cols;                     /* MACROPROPS.ROWS / COLS (multiples of patch_size)    */
+  int32_t past_len, future_len;           /* DATASET.PAST_LEN / FUTURE_LEN                       */
+  int32_t patch_size;                     /* PATCH_SIZE                                          */
+  int32_t t_patch_size;                   /* T_PATCH_SIZE (divides past_len + future_len)        */
+  int32_t hidden_size;                    /* HIDDEN_SIZE = num_heads * 64                        */
+  int32_t depth;                          /* DEPTH                                               */
+  int32_t num_heads;                      /* NUM_HEADS                                           */
+  int32_t mlp_hidden;                     /* int(HIDDEN_SIZE * MLP_RATIO), a multiple of 64      */
+  int32_t time_multiple;                  /* TIME_EMB_MULT                                       */
+  int32_t t_max;                          /* T_max (constructor default 32)                      */
+  int32_t max_batch;                      /* workspace is sized for this batch                   */
+  int32_t device;                         /* HIP device ordinal; < 0: host-only handle            */
+} cm_dit_config;
+
 /* ---- errors / info ------------------------------------------------------ */
 const char *cm_last_error(void);
 int cm_abi_version(void);
@@ -70,6 +92,11 @@ int cm_device_synchronize(int device);
 /* ---- denoiser: replaces UNet(...) / .load_state_dict / .state_dict ------ */
 /* unet.py:11-122 (ctor). */
 int cm_model_create(const cm_unet_config *cfg, cm_model **out);
+/* DiT4D_V4.__init__ (DiT4D_V4.py:235-315): 15 + 14 * depth state_dict tensors in the reference's order.  Refused with a
+ * status: a grid not divisible by patch_size, past_len + future_len not divisible by t_patch_size, more temporal slots
+ * than temporal_pos_embed has (t_max / t_patch_size), hidden_size not divisible by num_heads, a head dim other than 64,
+ * mlp_hidden not a multiple of 64, more than 64 spatial patches or 8 temporal slots. */
+int cm_model_create_dit(const cm_dit_config *cfg, cm_model **out);
 int cm_model_destroy(cm_model *m);
 /* state_dict() enumeration: names and shapes are the reference's (169 tensors
  * for config/ATC.yml; conv weights [Co,Ci,kH,kW,kL]). */
