@@ -244,7 +244,7 @@ bool conv_fin_pick(int Y, int X, int *by, int *bx) {
 
 bool conv_fin_ok(const ConvArgs &a) {
   return a.ntaps == 27 && a.td == 3 && a.stride == 1 && !a.par && !a.ups && a.C0 == 32 && a.C1 == 0 && a.Co >= 1 && a.Co <= 4 && !a.temb &&
-         !a.resid && !a.stat_part && !a.astat && !a.pm && a.ks <= 1 && a.out_cs >= a.Co && a.Zs == a.Zo && a.Ys == a.Yo && a.Xs == a.Xo && a.by > 0 &&
+         !a.resid && !a.stat_part && !a.pm && a.ks <= 1 && a.out_cs >= a.Co && a.Zs == a.Zo && a.Ys == a.Yo && a.Xs == a.Xo && a.by > 0 &&
          a.bx > 0 && a.Yo % a.by == 0 && a.Xo % a.bx == 0 && (a.by + 2) * (a.bx + 2) <= FIN_ROWS && a.by * a.bx <= 64 && !(a.h16 & ~1);
 }
 

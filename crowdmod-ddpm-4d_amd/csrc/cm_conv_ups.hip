@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, OCC) void conv_ups_kernel(const ConvArgs a, co
         for (int e = 0; e < 16; ++e)
           if (nok && orow[e] >= 0) outb[(size_t)orow[e] * a.out_cs + nn] = rs[e];
       }
-      if (a.stat_part || a.astat) {
+      if (a.stat_part) {
         float s1 = 0.f, cnt = 0.f;
 #pragma unroll
         for (int e = 0; e < 16; ++e)
@@ -298,16 +298,12 @@ __global__ __launch_bounds__(256, OCC) void conv_ups_kernel(const ConvArgs a, co
           if (orow[e] >= 0) { const float dd = rs[e] - mean; q2 += dd * dd; }
         q2 += __shfl_xor(q2, 32);
         const int slot = ((p * 2 + pz) * 4 + wave) * MBW + j;
-        if (a.astat) {
-          if (hh == 0 && nok && cnt > 0.f) cm_stat_atomic(a.astat + ((size_t)b * a.astat_C + nn) * 3, s1, mean, q2);
-        } else {
-          if (hh == 0 && nok) {
-            float *sp2 = a.stat_part + (((size_t)b * ns + slot) * a.stat_C + nn) * 2;
-            sp2[0] = mean;
-            sp2[1] = q2;
-          }
-          if (lane == 0 && nn == 0) a.stat_cnt[(size_t)b * ns + slot] = cnt;
+        if (hh == 0 && nok) {
+          float *sp2 = a.stat_part + (((size_t)b * ns + slot) * a.stat_C + nn) * 2;
+          sp2[0] = mean;
+          sp2[1] = q2;
         }
+        if (lane == 0 && nn == 0) a.stat_cnt[(size_t)b * ns + slot] = cnt;
       }
     }
   }

@@ -84,7 +84,7 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs &a, const f32x16 &v
 #pragma unroll
   for (int reg = 0; reg < 16; ++reg)
     if (nok && offs[reg] >= 0) a.out[(size_t)offs[reg] * a.out_cs + n] = rs[reg];
-  if (a.stat_part || a.astat) {
+  if (a.stat_part) {
     float s1 = 0.f, cnt = 0.f;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg)
@@ -97,16 +97,12 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs &a, const f32x16 &v
     for (int reg = 0; reg < 16; ++reg)
       if (offs[reg] >= 0) { const float dd = rs[reg] - mean; q += dd * dd; }
     q += __shfl_xor(q, 32);
-    if (a.astat) {
-      if (hh == 0 && nok && b0 < a.B && cnt > 0.f) cm_stat_atomic(a.astat + ((size_t)b0 * a.astat_C + n) * 3, s1, mean, q);
-    } else {
-      if (hh == 0 && nok && b0 < a.B) {
-        float *sp2 = a.stat_part + (((size_t)b0 * a.stat_ns + slot) * a.stat_C + n) * 2;
-        sp2[0] = mean;
-        sp2[1] = q;
-      }
-      if (lane == 0 && n == 0 && b0 < a.B) a.stat_cnt[(size_t)b0 * a.stat_ns + slot] = cnt;
+    if (hh == 0 && nok && b0 < a.B) {
+      float *sp2 = a.stat_part + (((size_t)b0 * a.stat_ns + slot) * a.stat_C + n) * 2;
+      sp2[0] = mean;
+      sp2[1] = q;
     }
+    if (lane == 0 && n == 0 && b0 < a.B) a.stat_cnt[(size_t)b0 * a.stat_ns + slot] = cnt;
   }
 }
 
@@ -571,7 +567,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
   int *outoff = reinterpret_cast<int *>(lds);       // [4 sub-blocks (a, b)][32 rows] in-sample output voxel index or -1
   float *U = lds + 128;
   float *R = U + UX;
-  float *GNL = R + RVC * RS_;                       // accumulator statistics (a.gs0): scale / shift rows [2][C0 + C1] of the current sample
+  float *GNL = R + RVC * RS_;                       // own GroupNorm (a.gp0): scale / shift rows [2][C0 + C1] of the current sample
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv8 = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -692,18 +688,16 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
   const int n2a = SKIP ? a.s2C0 >> 5 : 0, n2 = SKIP ? (a.s2C0 + a.s2C1) >> 5 : 0;
   const int slot = p * 4 + wave;
 
-  const bool own_gn = a.gs0 != nullptr || a.gp0 != nullptr;  // the GroupNorm of the input is finalised in this workgroup
+  const bool own_gn = a.gp0 != nullptr;                      // the GroupNorm of the input is finalised in this workgroup
   const bool norm = a.gn != nullptr || own_gn;               // GroupNorm (+ SiLU) on load
   for (int b = g0; b < a.B; b += G) {
     const bool more_b = b + G < a.B;
     const float tv_pre = a.temb ? a.temb[(size_t)a.tidx[b] * a.temb_stride + nc_epi] : 0.f;
     if (own_gn) {
       // the GroupNorm of this sample's input finalised HERE (no gn_finalize launch) from the producers' slot partials (few slots:
-      // half / quarter resolution) or accumulator rows: the halo loads of the first chunk are already in flight, the rows are
-      // read from LDS in step A
+      // half / quarter resolution): the halo loads of the first chunk are already in flight, the rows are read from LDS in step A
       __syncthreads();                            // (the previous sample's last step A has read its rows, its epilogue the exchange buffer)
-      if (a.gp0) cm_gn_rows_from_slots(a, b, (int)Vs, GNL, U, tid, NT);                     // (U is free here: scratch)
-      else cm_gn_rows_from_sums(a, b, (int)Vs, GNL, reinterpret_cast<double *>(U), tid, NT);
+      cm_gn_rows_from_slots(a, b, (int)Vs, GNL, U, tid, NT);                                 // (U is free here: scratch)
       __syncthreads();
     }
     f32x16 acc[4];
@@ -985,7 +979,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
           if (nok && orow[reg] >= 0)
             *reinterpret_cast<float *>(reinterpret_cast<char *>(outb) + (__umul24((unsigned)orow[reg], ocs4) + n4)) = rs[reg];
       }
-      if (a.stat_part || a.astat) {
+      if (a.stat_part) {
         float s1 = 0.f, cnt = 0.f;
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
@@ -998,16 +992,12 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
         for (int reg = 0; reg < 16; ++reg)
           if (orow[reg] >= 0) { const float dd = rs[reg] - mean; q += dd * dd; }
         q += __shfl_xor(q, 32);
-        if (a.astat) {
-          if (hh == 0 && nok && cnt > 0.f) cm_stat_atomic(a.astat + ((size_t)b * a.astat_C + n) * 3, s1, mean, q);
-        } else {
-          if (hh == 0 && nok) {
-            float *sp2 = a.stat_part + (((size_t)b * a.stat_ns + slot) * a.stat_C + n) * 2;
-            sp2[0] = mean;
-            sp2[1] = q;
-          }
-          if (lane == 0 && n == 0) a.stat_cnt[(size_t)b * a.stat_ns + slot] = cnt;
+        if (hh == 0 && nok) {
+          float *sp2 = a.stat_part + (((size_t)b * a.stat_ns + slot) * a.stat_C + n) * 2;
+          sp2[0] = mean;
+          sp2[1] = q;
         }
+        if (lane == 0 && n == 0) a.stat_cnt[(size_t)b * a.stat_ns + slot] = cnt;
       }
     }
   }
@@ -1199,6 +1189,25 @@ bool conv_wino_b6_ok(int bz, int by, int bx, int Co, int Zo) {
   return nbw == 1 && by == 4 && bx == 4 && Zo == 8 && 2 * conv_wino_p_lds(bz, by, bx, false, 1, true) <= 160 * 1024 && !cm::diag_env("CM_NO_WINO_B6_FULL");
 }
 
+// LDS of conv_wino_p_kernel for one launch: with own_gn (a.gp0) the 2 (C0 + C1) scale / shift rows of the input's GroupNorm as well
+static size_t wino_p_lds_launch(const ConvArgs &a, bool f16, int nbw, bool b6, bool own_gn) {
+  return conv_wino_p_lds(a.bz, a.by, a.bx, f16, nbw, b6) + (own_gn ? (size_t)2 * (a.C0 + a.C1) * sizeof(float) : 0);
+}
+
+// Persistent two-step form: workgroup = (tile position, sample lane), loops over its samples.
+// Measured (round 3, ATC B = 64): on the one-round launches of the two-tile form (one workgroup per sample and tile) the
+// leaner prologue / epilogue is worth 1-2 %; on the full-resolution 8x2x2 tile (3.4 rounds) the persistent loop is no
+// faster per tile than the hardware's own workgroup scheduling -- the kernel is issue-bound, not latency-bound: SQ counters
+// show the SIMD 83 % busy (58 % matrix, 24 % other vector instructions) while two workgroups are resident -- and its static
+// sample lanes balance worse (85 vs 79 us).  CM_WINO_P=1 under CM_DIAG forces it everywhere for A/B runs.
+bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn) {
+  static const bool no_p = cm::diag_env("CM_NO_WINO_P") != nullptr, all_p = cm::diag_env("CM_WINO_P") != nullptr;
+  const int nbw = conv_wino_nbw_run(a, f16);
+  const bool b6 = a.f16 == 2 || a.f16 == 3 || a.f16 == 4;
+  return !no_p && conv_wino_two_step(a.bz, a.by, a.bx, f16, nbw) && (nbw == 2 || all_p || b6) &&
+         wino_p_lds_launch(a, f16, nbw, b6, own_gn) <= 160 * 1024;
+}
+
 hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   ConvArgs a = a_in;
   a.dbg = conv_dbg_flags();
@@ -1207,7 +1216,6 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   const bool b6 = a.f16 == 2 || a.f16 == 3 || a.f16 == 4;   // 3: the relaxed plan's three-term form on the same fragments;
   const bool t3 = a.f16 == 3, h2 = a.f16 == 4;               // 4: h2 fragments (f16 hi / mid of w * 2^k), three f16 cross terms
   if (b6 && (f16 || !conv_wino_b6_ok(a.bz, a.by, a.bx, a.Co, a.Zo))) return hipErrorInvalidValue;
-  static const bool no_p = cm::diag_env("CM_NO_WINO_P") != nullptr;
 #define CM_WINO_ATTR(KERNEL)                                                                        \
     static bool attr_set[64] = {false};                                                             \
     int dev = 0;                                                                                    \
@@ -1217,15 +1225,9 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
       if (e != hipSuccess) return e;                                                                \
       attr_set[dev & 63] = true;                                                                    \
     }
-  // ---- persistent two-step form: workgroup = (tile position, sample lane), loops over its samples -----------------
-  // Measured (round 3, ATC B = 64): on the one-round launches of the two-tile form (one workgroup per sample and tile) the
-  // leaner prologue / epilogue is worth 1-2 %; on the full-resolution 8x2x2 tile (3.4 rounds) the persistent loop is no
-  // faster per tile than the hardware's own workgroup scheduling -- the kernel is issue-bound, not latency-bound: SQ counters
-  // show the SIMD 83 % busy (58 % matrix, 24 % other vector instructions) while two workgroups are resident -- and its static
-  // sample lanes balance worse (85 vs 79 us).  CM_WINO_P=1 under CM_DIAG forces it everywhere for A/B runs.
-  static const bool all_p = cm::diag_env("CM_WINO_P") != nullptr;
-  if (conv_wino_two_step(a.bz, a.by, a.bx, f16, nbw) && !no_p && (nbw == 2 || all_p || b6)) {
-    const size_t ldsp = conv_wino_p_lds(a.bz, a.by, a.bx, f16, nbw, b6) + ((a.gs0 || a.gp0) ? (size_t)2 * (a.C0 + a.C1) * sizeof(float) : 0);
+  // ---- persistent two-step form (conv_wino_p_taken) -----------------------------------------------------------------
+  if (conv_wino_p_taken(a, f16, a.gp0 != nullptr)) {
+    const size_t ldsp = wino_p_lds_launch(a, f16, nbw, b6, a.gp0 != nullptr);
     const int ntp = a.ntz * a.nty * a.ntx, nz = (a.Co + 31) / 32 / nbw;
     const int per_cu = (nbw == 1 && 2 * ldsp <= 160 * 1024) ? 2 : 1;
     const int slots = wino_cu_count() * per_cu;
@@ -1264,7 +1266,7 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
 #define CM_WINO_PGO61(Z, PY_, PX_, THREADS) CM_WINO_PGO6N(Z, PY_, PX_, 1, THREADS)
 #define CM_WINO_PGO6(Z, PY_, PX_, THREADS) CM_WINO_PGO6N(Z, PY_, PX_, 2, THREADS)
 #define X(z, py, px)                                                                                \
-    if (a.bz == z && a.by == 2 * py && a.bx == 2 * px && ldsp <= 160 * 1024) {                      \
+    if (a.bz == z && a.by == 2 * py && a.bx == 2 * px) {                                            \
       if constexpr (z != 8) {                                                                       \
         if (nbw == 2 && b6) CM_WINO_PGO6(z, py, px, 512)                                            \
         if (nbw == 2 && f16) CM_WINO_PGO(z, py, px, true, 2, 512)                                   \
@@ -1280,6 +1282,7 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
 #undef X
   }
   if (b6) return hipErrorInvalidValue;            // (only the table-driven kernel has the six-term form)
+  if (a.gp0) return hipErrorInvalidValue;         // (... and the GroupNorm finalised from slot partials)
   const dim3 grid((unsigned)(a.B * a.ntz * a.nty * a.ntx), (unsigned)((a.Co + 31) / 32 / nbw));
   const size_t lds = conv_wino_lds(a.bz, a.by, a.bx, f16, nbw);
 #define CM_WINO_GO(KERNEL, THREADS)                                                                 \

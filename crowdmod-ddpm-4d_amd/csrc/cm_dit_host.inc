@@ -266,7 +266,6 @@ extern "C" int cm_model_create_dit(const cm_dit_config *cfg, cm_model **out) {
       CM_HIP(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
     }
     CM_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-    CM_HIP(hipEventCreateWithFlags(&m->ev_half, hipEventDisableTiming));
   }
   *out = m.release();
   return 0;

@@ -133,59 +133,20 @@ struct ConvArgs {
   // Default plan, "h2" layers (a.f16 == 4): the weight fragments hold f16 hi / mid terms of w * 2^k (cm_split2_f16; k chosen per
   // layer at pack time so that the mid terms are normal numbers); the kernel multiplies its accumulators by h2_oscale = 2^-k.
   float h2_oscale;
-  // Round 4 -- GroupNorm statistics WITHOUT the gn_finalize launch (inference plan).  Producer side: instead of slot partials,
-  // every 32-row block ADDS its per-channel sums to astat[b][astat_C][3] (64-bit fixed point: sum x * 2^16 as two's complement,
-  // floor(sum x^2 / 2^32), (sum x^2 mod 2^32) * 2^20): integer adds are exact and order-independent, so the totals are
-  // bit-identical however the launch is tiled, sharded or scheduled -- cm_stat_atomic.  Consumer side: the workgroup finalises
-  // the GroupNorm of its input itself from the accumulators of its (one or two) source tensors -- cm_gn_rows_from_sums.
-  unsigned long long *astat;             // output accumulator rows of sample 0 of this launch, or null (then stat_part as before)
-  int astat_C;                           //   accumulator channels per sample (row stride in channels)
-  const unsigned long long *gs0, *gs1;   // consumer: accumulators of src0 / src1, [B][gs_C][3] from sample 0 of this launch (null: a.gn rows)
-  int gs_C;
-  const float *gs_gamma, *gs_beta;       //   affine of this layer's GroupNorm over the C0 + C1 input channels
+  // Unused: the 40 bytes that the removed accumulator-statistics fields took.  Register allocation in conv_wino_p_kernel follows
+  // the argument offsets: with the fields below moved up by 40 bytes, its launches of the default plan measured 1.5-4 % slower
+  // (same instructions, other scalar spills), so the offsets stay as they were.
+  alignas(8) unsigned char layout_pad[40];
+  // Round 4 -- GroupNorm of the input finalised by the consumer workgroup itself from the producers' SLOT partials, when they
+  // are few (half / quarter resolution: <= 32 slots per sample): part [B][gns][C][2] (mean, M2), cnt [B][gns], from sample 0
+  // of this launch, as gn_finalize reads them (conv_qr2 has done this since round 3).
+  const float *gs_gamma, *gs_beta;       // affine of this layer's GroupNorm over the C0 + C1 input channels
   int gs_groups;
   float gs_eps;
-  // Round 4 -- the same consumer-side finalisation from the producers' SLOT partials, when they are few (half / quarter
-  // resolution: <= 32 slots per sample): part [B][gns][C][2] (mean, M2), cnt [B][gns], from sample 0 of this launch, as
-  // gn_finalize reads them (conv_qr2 has done this since round 3).  Shares gs_gamma / gs_beta / gs_groups / gs_eps.
   const float *gp0, *gc0, *gp1, *gc1;
   int gns0, gns1;
 };
 #ifdef __HIPCC__
-// ---- statistics accumulators (ConvArgs::astat) ----------------------------------------------------------------------------
-constexpr unsigned long long CM_STAT_POISON = 1ull << 63;      // a non-finite or out-of-range contribution was added
-// One 32-row block's contribution for one channel: s1 = sum of its rows, mean = s1 / cnt, m2 = sum (x - mean)^2 (all fp32, as
-// the slot format holds them).  sum x^2 = m2 + s1 * mean is formed in fp64, so the fixed-point words lose nothing the fp32
-// partials had.  Range: |sum x| < 2^46 and sum x^2 < 2^94 per sample and channel; beyond that (or NaN / Inf) the poison bit is set
-// and the consumer's statistics come out NaN, as non-finite slot partials did.
-__device__ __forceinline__ void cm_stat_atomic(unsigned long long *acc, float s1, float mean, float m2) {
-  const double q = (double)m2 + (double)s1 * (double)mean;
-  const double sx = (double)s1 * 65536.0;
-  if (!(fabs(sx) < 4.0e18) || !(q < 1.9e28)) {                 // (also catches NaN)
-    __hip_atomic_fetch_or(acc + 1, CM_STAT_POISON, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  const double qh = floor(q * (1.0 / 4294967296.0));
-  const unsigned long long QH = (unsigned long long)qh;
-  const unsigned long long QL = (unsigned long long)((q - qh * 4294967296.0) * 1048576.0 + 0.5);
-  const long long SX = __double2ll_rn(sx);
-  __hip_atomic_fetch_add(acc, (unsigned long long)SX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_fetch_add(acc + 1, QH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_fetch_add(acc + 2, QL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// (sum x, sum x^2) of one channel from its accumulator words; NaN when poisoned
-__device__ __forceinline__ void cm_stat_read(const unsigned long long *acc, double *sx, double *sq) {
-  const unsigned long long w0 = acc[0], w1 = acc[1], w2 = acc[2];
-  if (w1 & CM_STAT_POISON) { *sx = __builtin_nan(""); *sq = __builtin_nan(""); return; }
-  *sx = (double)(long long)w0 * (1.0 / 65536.0);
-  *sq = (double)w1 * 4294967296.0 + (double)w2 * (1.0 / 1048576.0);
-}
-// Consumer prologue: scale / shift rows of sample `b` for the C0 + C1 input channels into rows[2 (C0 + C1)] (LDS or global):
-// rows[c] = gamma[c] * rstd(group of c), rows[Ctot + c] = beta[c] - mean * rows[c]   (nn.GroupNorm, layers.py:30,41: biased
-// variance, eps inside the root).  Called by ALL `nth` threads of the workgroup (it contains one barrier): pass 1 -- thread c
-// reads its channel's three words (ONE round trip for the whole workgroup; a loop over the group's channels per thread paid one
-// per channel, 6 us per workgroup) into `scratch` [Ctot][2] doubles in LDS; pass 2 -- every channel sums its group's entries
-// (4 ... 24 LDS reads) and finishes in registers.  V = voxels per sample.  The caller synchronises before it reads `rows`.
 // Chan et al. pairwise combination of (n, mean, M2) triples (cm_misc.hip: chan_combine; same arithmetic)
 __device__ __forceinline__ void cm_chan_combine(float &n, float &mean, float &m2, float nb, float meanb, float m2b) {
   if (nb == 0.f) return;
@@ -269,32 +230,6 @@ __device__ __forceinline__ float cm_h2_sample_scale(const float *__restrict__ gp
   if (!(m > 0.f) || e == 255u) se = 127;                       // all-zero / non-finite statistics: no scaling
   return __uint_as_float((unsigned)se << 23);
 }
-__device__ __forceinline__ void cm_gn_rows_from_sums(const ConvArgs &a, int b, int V, float *rows, double *scratch, int tid, int nth) {
-  const int Ctot = a.C0 + a.C1, cg = Ctot / a.gs_groups;
-  for (int c = tid; c < Ctot; c += nth) {
-    const unsigned long long *p = c < a.C0 ? a.gs0 + ((size_t)b * a.gs_C + c) * 3 : a.gs1 + ((size_t)b * a.gs_C + (c - a.C0)) * 3;
-    const unsigned long long w0 = p[0], w1 = p[1], w2 = p[2];
-    const bool bad = (w1 & CM_STAT_POISON) != 0ull;
-    const double sx = (double)(long long)w0 * (1.0 / 65536.0);
-    const double sq = (double)w1 * 4294967296.0 + (double)w2 * (1.0 / 1048576.0);
-    scratch[2 * c] = bad ? __builtin_nan("") : sx;
-    scratch[2 * c + 1] = bad ? __builtin_nan("") : sq;
-  }
-  __syncthreads();
-  const double inv_n = 1.0 / ((double)cg * (double)V);
-  for (int c = tid; c < Ctot; c += nth) {
-    const int g0 = (c / cg) * cg;
-    double sx = 0.0, sq = 0.0;
-    for (int k = g0; k < g0 + cg; ++k) { sx += scratch[2 * k]; sq += scratch[2 * k + 1]; }
-    const double mean = sx * inv_n;
-    double var = sq * inv_n - mean * mean;
-    var = var < 0.0 ? 0.0 : var;                   // (NaN stays NaN)
-    const float rstd = 1.0f / sqrtf((float)var + a.gs_eps);
-    const float sc = a.gs_gamma[c] * rstd;
-    rows[c] = sc;
-    rows[Ctot + c] = a.gs_beta[c] - (float)mean * sc;
-  }
-}
 #endif
 
 bool conv_zsplit_variant(const ConvArgs &a, int MB, int NB);
@@ -348,6 +283,10 @@ size_t conv_wino_lds(int bz, int by, int bx, bool f16, int nbw);
 int conv_wino_nbw(int bz, int Co);
 int conv_wino_nbw_run(const ConvArgs &a, bool f16);   // ... of one launch (a.B, a.ntz / nty / ntx set): see cm_conv_wino.hip
 bool conv_wino_two_step(int bz, int by, int bx, bool f16, int nbw);
+// does launch_conv_wino run this launch (a.f16, wfrag and the geometry set) on conv_wino_p_kernel?  That kernel alone finalises
+// the input's GroupNorm from slot partials (a.gp0), so the caller asks here before it passes them (own_gn = true) instead of
+// a.gn rows; the launcher branches on the same call and refuses a.gp0 on any other kernel.
+bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn);
 // f16: a.wfrag holds the f16 packing (3 groups per chunk and wave, 8 halves per lane): fp32 accumulate, f16 operands
 hipError_t launch_conv_wino(const ConvArgs &a, bool f16, hipStream_t st);
 // six-term bf16 form (a.f16 = 2, wfrag = pack_wino_b6 fragments): two-tile table-driven kernel only
@@ -412,22 +351,6 @@ bool conv_f16d_ok(const ConvArgs &a, int mbw);
 int conv_f16d_slots(const ConvArgs &a, int mbw);
 hipError_t launch_conv_f16d(const ConvArgs &a, int mbw, hipStream_t st);
 
-// Direct 3x3x3 stride-1 conv in fp32 arithmetic from six bf16 cross terms (cm_conv_b6d.hip; fp32 plan, full-resolution layers):
-// a.bz/by/bx = output box (divides the grid), nw = waves per workgroup (2 / 4), mbw = 32-row blocks per wave;
-// a.wfrag: [Co/(32 NB)][Ci/16][27][NB][3 terms][64 lanes][8 bf16] (pack_b6d), a.s2w: [Co/(32 NB)][Cs/16][NB][3][64][8], NB =
-// conv_b6d_nb(Co); statistics slots per sample: conv_b6d_slots.
-bool conv_b6d_pick(int Z, int Y, int X, int *bz, int *by, int *bx, int *nw, int *mbw, int stride = 1, int Zs = 0, int Ys = 0, int Xs = 0);
-bool conv_b6d_ok(const ConvArgs &a, int nw, int mbw);
-int conv_b6d_slots(const ConvArgs &a, int nw, int mbw);
-int conv_b6d_nb(int Co);
-hipError_t launch_conv_b6d(const ConvArgs &a, int nw, int mbw, hipStream_t st);
-// host-side geometry tables of one (grid, tile) pair (cm_conv_b6d.hip; also driven by the sanitizer self-test)
-void conv_b6d_tables(int Z, int Y, int X, int bz, int by, int bx, int nw, int mbw, std::vector<int> &tS, std::vector<int> &tM,
-                     int *NSP, int *HVP, int *PY, int *PZ, int *ntp, int *conflicts, int stride = 1, int Zs = 0, int Ys = 0, int Xs = 0);
-int conv_b6d_nld(int stride);   // staging items per thread the kernel instance of this stride holds
-// split fragments from the layer's fp32 weights in the REFERENCE layout [Co][Ci][kH][kW][kL] (or [Co][Ci], taps = 1), e.g. after an optimizer step
-hipError_t launch_b6d_repack(const float *w, float *w6, int Co, int Ci, int taps, int NB, hipStream_t st);
-
 // The UNet's last conv (32 -> C <= 4 channels) on the matrix core with the 27 taps packed into the columns (cm_conv_fin.hip):
 // a.by / a.bx = in-plane tile of conv_fin_pick; wfin = launch_fin_pack fragments (three bf16 terms, or one f16 term with f16 = true)
 bool conv_fin_pick(int Y, int X, int *by, int *bx);
@@ -439,10 +362,6 @@ constexpr size_t CM_FIN_W_FLOATS = 4 * 2 * 3 * 64 * 4;   // fragment floats (six
 // ---- small kernels --------------------------------------------------------
 // Per-(sample, slice, channel) mean and M2 of a channels-last tensor.
 //   part [B][nslice][C][2]
-// Fall-backs of the accumulator scheme (round 4): gn rows [B][2][C0 + C1] from the accumulators (a consumer kernel that cannot
-// finalise them itself), and accumulators from slot partials (a producer kernel that cannot add to them itself)
-hipError_t launch_gn_from_sums(const ConvArgs &a, int V, float *gn_rows, hipStream_t st);
-hipError_t launch_slots_to_sums(const float *part, const float *cnt, int nslots, int C, int B, unsigned long long *astat, int astat_C, hipStream_t st);
 hipError_t launch_chan_stats(const float *x, int B, int V, int C, int nslice, float *part, float *cnt, hipStream_t st);
 // Combine partial statistics (per slot: mean, M2 in part[b][slot][C][2], row count in
 // cnt[b][slot]) of (up to) two concatenated tensors into GroupNorm scale/shift rows:
@@ -551,8 +470,6 @@ struct StepArgs {
   long long boff;        // b0 * per
   // plain loop: this step also writes the NEXT step's time index into the UNet's t buffer (saves a launch per step)
   long long *t_next; long long t_next_v;
-  // round 4: this step's denoiser has consumed the GroupNorm accumulators (ConvArgs::astat); clear this lane's rows for the next step
-  unsigned long long *zero_u64; long long zero_n;
 };
 hipError_t launch_sampler_step(const StepArgs &a, hipStream_t st);
 // mass_preservation guidance (cm_guidance.hip).  q = the reference's finite-difference quotient of compute_energy for

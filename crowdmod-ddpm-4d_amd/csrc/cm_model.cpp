@@ -73,8 +73,6 @@ struct Act {
   int nslice = 1;         // slots when the stand-alone statistics kernel fills them
   int nslots = 0;         // slots of the last producer (fused conv epilogue or stats kernel)
   bool h16 = false;       // reduced-precision plan: the tensor is stored as _Float16 (same layout and strides; plan_h16)
-  int aoff = -1;          // >= 0: GroupNorm statistics of this tensor go to the accumulator rows (cm_model::astat_all, channel offset aoff)
-                          //   in the inference plan -- producers add exact fixed-point sums, consumers finalise, no gn_finalize launch
   int V() const { return Z * Y * X; }
 };
 
@@ -127,8 +125,6 @@ struct Op {
   bool h2_off = false;      // refresh_h2: this layer's GroupNorm affine no longer satisfies the static bound -> six-term form
   bool dbg_h2 = false;      // cm_debug_conv_io mode 2: raw sources, but the h2 form where the plan has one (the caller bounds its operands)
   bool dbg_raw = false;     // cm_debug_conv_io: the whole-sample quarter-resolution kernel without its GroupNorm (raw sources)
-  bool b6d = false;         // fp32 plan: direct six-term kernel (cm_conv_b6d.hip) instead of the six-term Winograd one (inference forward)
-  int b6d_bz = 0, b6d_by = 0, b6d_bx = 0, b6d_nw = 0, b6d_mbw = 0;
   // default plan, layers whose input is GroupNorm + SiLU output (bounded): f16 two-way splits, three cross terms ("h2", cm_kernels.h:
   // cm_split2_f16) instead of bf16 three-way splits, six cross terms -- same accuracy, half the matrix instructions.  Fragments of
   // w * 2^k; h2_oscale = 2^-k.  Inference-only handles (a handle that trains keeps the six-term form: its repack kernels do not
@@ -136,9 +132,7 @@ struct Op {
   float *d_wfin_h2 = nullptr, *d_wwino_h2 = nullptr, *d_wqr_h2 = nullptr;
   float *d_wups_h2 = nullptr;   // upsample conv (raw source): h2 with a per-sample scale from the source tensor's slot statistics
   float h2_oscale = 1.f;
-  bool b6s2 = false;        // fp32 plan: the stride-2 DownSample conv on the same kernel (tile fields above)
-  float *d_wb6d = nullptr, *d_wb6d_skip = nullptr;
-  bool qr = false;          // whole-sample kernel of the lowest resolution (cm_conv_qr.hip), inference plan
+  bool qr = false;         // whole-sample kernel of the lowest resolution (cm_conv_qr.hip), inference plan
   float *d_wqr = nullptr, *d_wqr_skip = nullptr;
   float *d_wqr_b6 = nullptr;    // exact bf16 x 3 split of d_wqr for the six-term form of conv_qr2 (pack_qr_b6)
   bool train_qr = false;        // the training forward may take conv_qr2 as well (set by train_setup once the geometry is checked)
@@ -147,7 +141,6 @@ struct Op {
   bool from_slots = false;  // OP_GNFIN (inference plan): its only consumer is a six-term Winograd conv that finalises the statistics from the
                             //   producers' slot partials itself when they are few (run_conv decides per launch; set by plan_slot_consumers)
   bool fin_skipped[4] = {false, false, false, false};   // per batch lane: this step's launch of the op was skipped on that promise
-  bool atomic = false;      // OP_GNFIN (inference plan): its source tensors keep accumulator statistics and its consumers finalise them -- no launch
   bool first_k = false;     // the UNet's first conv on its dedicated kernel (cm_conv_io.hip)
   int first_cin = 4;        //   input channels it contracts per tap: 4 (C <= 4) or 8
   float *d_wfirst = nullptr;
@@ -203,8 +196,7 @@ struct cm_model {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};  // extra lanes of the batch interleave
-  hipEvent_t ev_join[4] = {nullptr, nullptr, nullptr, nullptr}, ev_fork = nullptr, ev_half = nullptr;
-  int mid_at = -1;          // run_ops records ev_half after this op (once): the second lane starts half a step late
+  hipEvent_t ev_join[4] = {nullptr, nullptr, nullptr, nullptr}, ev_fork = nullptr;
   std::vector<Param> params;
   std::map<std::string, int> pindex;
   std::vector<BlockDesc> enc, bott, dec;
@@ -241,9 +233,6 @@ struct cm_model {
   long long *train_iota = nullptr;
   bool use_train_temb = false;
   float *mse_partial = nullptr, *mse_loss = nullptr;
-  unsigned long long *astat_all = nullptr;  // accumulator statistics [max_batch][astat_C][3] (ConvArgs::astat), sample-major
-  int astat_C = 0;              //   channels of all accumulator tensors together
-  struct { int b0 = -1, B = 0; } astat_clean[4];   // per batch lane: the sample range whose rows are known to be zero (the last sampler step cleared them)
   float *ks_scratch = nullptr;  // raw partial outputs of K-split convs [S][B][V][Co]
   size_t ks_scratch_floats = 0;
   float *xstate = nullptr;      // sampler state [B,C,H,W,F]
@@ -865,29 +854,6 @@ std::vector<float> pack_f16d(const float *w, int Co, int Ci, int taps, int NB) {
   return packed;
 }
 
-// bf16 x 3 fragments of the direct six-term kernel (cm_conv_b6d.hip): [Co/(32 NB)][Ci/16][taps][NB][term hi / mid / lo][lane][8 bf16]
-// with co = 32 NB nt + 32 nb + lane % 32, ci = 16 c + 8 (lane / 32) + j; `w` is [Co][Ci][taps] (taps = 27 internal order, or 1).
-// The device re-derives them from the reference-layout master weights after an optimizer step (b6d_repack_kernel).
-std::vector<float> pack_b6d(const float *w, int Co, int Ci, int taps, int NB) {
-  const int ntn = Co / (32 * NB), nc = Ci / 16;
-  std::vector<uint16_t> out((size_t)ntn * nc * taps * NB * 3 * 64 * 8, 0);
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int c = 0; c < nc; ++c)
-      for (int t = 0; t < taps; ++t)
-        for (int nb = 0; nb < NB; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-              const int co = nt * 32 * NB + nb * 32 + (lane & 31), ci = 16 * c + 8 * (lane >> 5) + j;
-              uint16_t t3[3];
-              bf16_split3(w[((size_t)co * Ci + ci) * taps + t], t3);
-              for (int tm = 0; tm < 3; ++tm)
-                out[(((((((size_t)nt * nc + c) * taps + t) * NB + nb) * 3 + tm) * 64) + lane) * 8 + j] = t3[tm];
-            }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
 // Weights of the whole-sample quarter-resolution kernel (cm_conv_qr.hip): [Co/32][g = k8*9 + dy*3 + dx][dz][lane][jj]
 // with co = 32 nt + lane % 32, ci = 8 k8 + 4 (lane / 32) + jj; `wi` in the internal tap order [Co][Ci][(dz*3 + dy)*3 + dx].
 std::vector<float> pack_qr(const std::vector<float> &wi, int Co, int Ci) {
@@ -1001,19 +967,6 @@ static float h2_pack_ups(const float *w_ref, int Co, int Ci_ref, std::vector<flo
   return ws;
 }
 
-// Which Winograd-eligible layers take the direct six-term kernel instead.  Round 4, same-box A/B on the full-resolution layers
-// (B = 64, ATC): 82 / 84 / 208 / 109 / 142 / 99 us against the six-term Winograd kernel's 55 / 62 / 144 / 76 / 98 / 67 (step 1.563
-// vs 1.381 ms) -- its phases add up (skeleton 23 + matrix 50 + epilogue 10 us on the 32 -> 32 layer), see DESIGN section 6 --
-// so NONE by default; CM_B6D=full (Co = 32, >= 8 planes) / all under CM_DIAG=1 select it for A/B runs and the parity tests.
-bool b6d_wanted(int Co, int Z, int Y, int X) {
-  (void)Y; (void)X;
-  if (const char *e = cm::diag_env("CM_B6D")) {
-    if (!strcmp(e, "all")) return true;
-    if (!strcmp(e, "full")) return Co == 32 && Z >= 8;
-  }
-  return false;
-}
-
 int add_conv(cm_model *m, const ConvSpec &s) {
   Op op;
   op.kind = OP_CONV;
@@ -1049,12 +1002,8 @@ int add_conv(cm_model *m, const ConvSpec &s) {
     op.wino = s.ntaps == 27 && s.stride == 1 && !s.ups && a.C0 % 16 == 0 && a.C1 % 16 == 0 && s.Co % 32 == 0 && s.Co == s.out->C &&
               s.ci_valid < 0 && s.out->V() > 64 && cm::conv_wino_pick(s.out->Z, s.out->Y, s.out->X, &wz, &wy, &wx) && !cm::diag_env("CM_NO_WINO");
   }
-  // tiny-spatial layers are overhead-bound, not throughput-bound: fewer, fatter workgroups
-  // (all 128 output channels per workgroup, K split over workgroups) amortise the per-workgroup
-  // fixed costs over 4x the matrix work
-  // (NB = 4 "fat" tiles -- all 128 output channels per workgroup -- spill ~80 VGPRs on the register-ring path and
-  // measured no better than two NB = 2 workgroups: opt-in only)
-  if (s.ntaps == 27 && s.out->V() <= 64 && s.Co % 128 == 0 && cm::diag_env("CM_FAT_TILES")) op.NB = 4;
+  // tiny-spatial layers keep NB = 2: NB = 4 tiles (all 128 output channels per workgroup) spill ~80 VGPRs on the register-ring
+  // path and measured no better than two NB = 2 workgroups
   if (s.ntaps == 27 && s.out->V() <= 64 && cm::diag_env("CM_QR_NB")) op.NB = atoi(cm::diag_env("CM_QR_NB"));
   if (op.wino) op.NB = 1;
   if (s.ntaps == 27 && s.out->V() > 64 && !op.wino) {
@@ -1182,31 +1131,6 @@ int add_conv(cm_model *m, const ConvSpec &s) {
       if (upload(m, pack_f16d(wi.data(), s.Co, Ci_ref, 27, s.Co % 64 == 0 ? 2 : 1), &op.d_w16d)) return 1;
       op.f16d = true;
     }
-    // fp32 plan, full-resolution layers (Co = 32: one output tile, so the Winograd form has no second tile to share its U image with):
-    // the direct six-term kernel -- the split paid once per staged element instead of once per frequency component, 1.5 instead of
-    // 8 vector instructions per matrix instruction (cm_conv_b6d.hip)
-    if (m->precision != CM_PRECISION_F16 && Ci_ref == Ci_pad && a.C0 % 16 == 0 && a.C1 % 16 == 0 && b6d_wanted(s.Co, s.out->Z, s.out->Y, s.out->X) &&
-        cm::conv_b6d_pick(s.out->Z, s.out->Y, s.out->X, &op.b6d_bz, &op.b6d_by, &op.b6d_bx, &op.b6d_nw, &op.b6d_mbw)) {
-      if (upload(m, pack_b6d(wi.data(), s.Co, Ci_ref, 27, cm::conv_b6d_nb(s.Co)), &op.d_wb6d)) return 1;
-      op.b6d = true;
-    }
-  }
-  // fp32 plan: the DownSample conv (3x3x3, stride 2, raw input: layers.py:91-97) on the direct six-term kernel -- one staging pass
-  // and the split per staged element, no K split / second pass at quarter resolution.  OPT-IN (CM_DIAG=1 CM_B6S2=1): measured
-  // SLOWER than the generic kernel on the ATC grid (32.2 vs 31.5 us at half resolution, 46.7 vs 18.7 + 7.0 us at quarter
-  // resolution; step 1.402 vs 1.380 ms): with one row block per wave the kernel waits on its weight fragments (3 taps of
-  // read-ahead = 576 matrix cycles, less than the L2 latency under load) and an 8-voxel halo per output voxel is staged per chunk
-  if (s.ntaps == 27 && s.stride == 2 && !s.ups && !parity && !s.gn && !s.temb && !s.resid && !s.skip0 && m->precision != CM_PRECISION_F16 &&
-      Ci_ref == Ci_pad && a.C0 % 16 == 0 && a.C1 % 16 == 0 && s.Co % 32 == 0 && s.Co == s.out->C && cm::diag_env("CM_B6S2") &&
-      cm::conv_b6d_pick(s.out->Z, s.out->Y, s.out->X, &op.b6d_bz, &op.b6d_by, &op.b6d_bx, &op.b6d_nw, &op.b6d_mbw, 2, s.s0->Z, s.s0->Y, s.s0->X)) {
-    if (const char *t = cm::diag_env("CM_B6S2_TILE")) {      // "bz,by,bx,nw": A/B of tile shapes
-      int z = 0, y = 0, x = 0, w = 0;
-      if (sscanf(t, "%d,%d,%d,%d", &z, &y, &x, &w) == 4 && s.out->Z % z == 0 && s.out->Y % y == 0 && s.out->X % x == 0 && z * y * x <= 32 * w) {
-        op.b6d_bz = z; op.b6d_by = y; op.b6d_bx = x; op.b6d_nw = w; op.b6d_mbw = 1;
-      }
-    }
-    if (upload(m, pack_b6d(wi.data(), s.Co, Ci_ref, 27, cm::conv_b6d_nb(s.Co)), &op.d_wb6d)) return 1;
-    op.b6s2 = true;
   }
   // the UNet's first conv (C <= 8 data channels -> base): dedicated kernel, whole weight set in registers
   if (s.s0 == m->x8_act && s.ntaps == 27 && s.stride == 1 && !s.ups && !s.gn && !s.temb && !s.resid && !s.s1 &&
@@ -1296,15 +1220,6 @@ int add_conv(cm_model *m, const ConvSpec &s) {
       if (upload(m, pack_f16d(w2.host.data(), s.Co, Cs, 1, s.Co % 64 == 0 ? 2 : 1), &op.d_w16d_skip)) return 1;
     } else {
       op.f16d = false;
-    }
-  }
-  if (op.b6d && op.d_s2w) {
-    const Param &w2 = P(m, s.skip_w);
-    const int Cs = (int)w2.shape[1];
-    if (Cs % 16 == 0 && s.skip0->C % 16 == 0 && (!s.skip1 || s.skip1->C % 16 == 0)) {
-      if (upload(m, pack_b6d(w2.host.data(), s.Co, Cs, 1, cm::conv_b6d_nb(s.Co)), &op.d_wb6d_skip)) return 1;
-    } else {
-      op.b6d = false;
     }
   }
   // Lowest resolution (two z planes, <= 64 voxels per plane): whole-sample kernel with the GroupNorm finalisation of its
@@ -1589,73 +1504,14 @@ int plan_slot_consumers(cm_model *m) {
   const int nops = (int)m->ops.size();
   for (int i = 0; i < nops; ++i) {
     Op &g = m->ops[i];
-    if (g.kind != OP_GNFIN || g.qr_consumer || g.in_attn_block || g.atomic) continue;
+    if (g.kind != OP_GNFIN || g.qr_consumer || g.in_attn_block) continue;
     int ncons = 0, cons = -1;
     for (int j = 0; j < nops; ++j)
       if (m->ops[j].kind == OP_CONV && m->ops[j].gn_op == i) { ++ncons; cons = j; }
     if (ncons != 1) continue;
     const Op &c = m->ops[cons];
-    g.from_slots = c.wino && !c.qr && c.ks <= 1 && !c.f16d && !c.b6d && !c.skip_if_fused && (c.d_wwino_b6 || c.d_wwino16);
+    g.from_slots = c.wino && !c.qr && c.ks <= 1 && !c.f16d && !c.skip_if_fused && (c.d_wwino_b6 || c.d_wwino16);
   }
-  return 0;
-}
-
-// Which GroupNorm finalisations of the INFERENCE plan can go without their launch (round 4): the source tensors' producers add
-// exact fixed-point sums to accumulator rows (cm_stat_atomic), the consuming conv finalises them in its prologue (six-term Winograd
-// kernel) or through a fall-back launch that costs what gn_finalize cost.  Eligible: fp32 plan; every source tensor produced by an
-// ordinary conv launch (no K split, not the whole-sample quarter-resolution kernel -- those feed slot partials to consumers that
-// merge slots); no consumer that merges slots itself (conv_qr).  A tensor takes accumulators only if ALL GroupNorms over it do.
-// MEASURED SLOWER than the gn_finalize launches it removes (round 4, same-box: 1.456 vs 1.413 ms per step; removing the 13 launches
-// outright would be worth 88 us): per full-resolution layer the 663 k 8-byte atomic adds -- 108 per accumulator word -- cost 14-17 us
-// (conv_first 26 -> 40 us, the stage-once upsample conv 86 -> 118) and the consumer prologue ~3 us, against the 6.4 us launch.
-// Opt-in only: CM_DIAG=1 CM_ASTAT=1 (kept with its parity test as the record of the experiment).
-int plan_astat(cm_model *m) {
-  if (m->precision == CM_PRECISION_F16 || !cm::diag_env("CM_ASTAT")) return 0;
-  const int nops = (int)m->ops.size();
-  std::map<const Act *, int> producer;
-  for (int i = 0; i < nops; ++i)
-    if (m->ops[i].kind == OP_CONV && m->ops[i].stat_act) producer[m->ops[i].stat_act] = i;
-  std::vector<char> cand((size_t)nops, 0);
-  auto act_ok = [&](const Act *a) {
-    auto it = producer.find(a);
-    if (it == producer.end()) return false;
-    const Op &po = m->ops[it->second];
-    return po.ks <= 1 && !po.qr && !po.skip_if_fused && a->part != nullptr;
-  };
-  for (int i = 0; i < nops; ++i) {
-    Op &g = m->ops[i];
-    if (g.kind != OP_GNFIN || g.qr_consumer || g.in_attn_block) continue;
-    bool ok = act_ok(g.g0) && (!g.g1 || act_ok(g.g1));
-    int ncons = 0;
-    for (int j = 0; j < nops && ok; ++j)
-      if (m->ops[j].kind == OP_CONV && m->ops[j].gn_op == i) { ++ncons; if (m->ops[j].qr) ok = false; }
-    cand[(size_t)i] = ok && ncons > 0;
-  }
-  for (bool changed = true; changed;) {            // a tensor keeps accumulators only if every GroupNorm over it is a candidate
-    changed = false;
-    for (int i = 0; i < nops; ++i) {
-      if (!cand[(size_t)i]) continue;
-      const Op &g = m->ops[i];
-      for (int j = 0; j < nops; ++j) {
-        const Op &h = m->ops[j];
-        if (h.kind != OP_GNFIN || cand[(size_t)j]) continue;
-        if (h.g0 == g.g0 || h.g0 == g.g1 || (h.g1 && (h.g1 == g.g0 || h.g1 == g.g1))) { cand[(size_t)i] = 0; changed = true; break; }
-      }
-    }
-  }
-  int totC = 0;
-  for (int i = 0; i < nops; ++i) {
-    if (!cand[(size_t)i]) continue;
-    Op &g = m->ops[i];
-    g.atomic = true;
-    for (const Act *a : {g.g0, g.g1})
-      if (a && a->aoff < 0) { const_cast<Act *>(a)->aoff = totC; totC += a->C; }
-  }
-  if (!totC) return 0;
-  m->astat_C = totC;
-  const size_t bytes = (size_t)m->cfg.max_batch * totC * 3 * sizeof(unsigned long long);
-  if (dev_alloc(m, (void **)&m->astat_all, bytes)) return 1;
-  CM_HIP(hipMemset(m->astat_all, 0, bytes));
   return 0;
 }
 
@@ -1839,27 +1695,20 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
     ca.stat_part = op.stat_act->part + (size_t)b0 * ns * ca.stat_C * 2;
     ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns;
   }
-  // ---- which kernel will run (needed up front: only some kernels speak the accumulator statistics of round 4) -------------------
+  // ---- which kernel will run ----------------------------------------------------------------------------------------------
   static const bool no_train_b6 = cm::diag_env("CM_NO_TRAIN_B6") != nullptr;
   // relaxed fp32 plan (cm_model_set_precision): the six-term kernels issue only their three leading cross terms (inference forward)
   const bool relaxed = m->precision == CM_PRECISION_F32R && !m->train_fwd;
   // default plan: the f16 two-way-split form on layers with bounded input (inference-only handles, see Op::d_wfin_h2)
   const bool h2_live = m->precision == CM_PRECISION_F32 && !m->train_fwd && !m->h2_stale && !op.h2_off;
-  cm::ConvArgs s2a = ca;
-  s2a.bz = op.b6d_bz; s2a.by = op.b6d_by; s2a.bx = op.b6d_bx;
-  // (the training forward as well: exact splits, fp32 accumulate; its fragments follow every optimizer step)
-  const bool take_b6s2 = op.b6s2 && !(m->train_fwd && no_train_b6) && m->precision != CM_PRECISION_F16 && !ca.h16 && !ca.pm &&
-                         cm::conv_b6d_ok(s2a, op.b6d_nw, op.b6d_mbw);
-  const int ks = take_b6s2 ? 1 : op.ks;            // (the direct stride-2 kernel replaces the K split)
-  const bool take_ups = ks <= 1 && op.ups && (op.d_wups16 || !(op.d_wfrag16 && !m->train_fwd));
-  const bool take_f16d = ks <= 1 && !take_ups && op.wino && op.f16d && !m->train_fwd;
-  const bool take_b6d = take_b6s2 || (ks <= 1 && !take_ups && !take_f16d && op.wino && op.b6d && !m->train_fwd && m->precision != CM_PRECISION_F16);
-  const bool take_wino = ks <= 1 && !take_ups && !take_f16d && !take_b6d && op.wino;
+  const bool take_ups = op.ks <= 1 && op.ups && (op.d_wups16 || !(op.d_wfrag16 && !m->train_fwd));
+  const bool take_f16d = op.ks <= 1 && !take_ups && op.wino && op.f16d && !m->train_fwd;
+  const bool take_wino = op.ks <= 1 && !take_ups && !take_f16d && op.wino;
   // The slot count of the output tensor is written ONCE per launch with the count of the kernel that runs: the batch lanes
   // enqueue from two host threads, and the other lane's gn_finalize reads it -- a generic count first and the upsample /
-  // direct kernel's own count afterwards left a window in which that reader saw the wrong number of slots (a rare wrong
+  // f16 kernel's own count afterwards left a window in which that reader saw the wrong number of slots (a rare wrong
   // statistic: the one-off failure of the two-lane bit-identity test in round 4).  All lanes write the same value.
-  if (op.stat_act && ks <= 1 && !take_ups && !take_f16d && !take_b6d) op.stat_act->nslots = ns;
+  if (op.stat_act && op.ks <= 1 && !take_ups && !take_f16d) op.stat_act->nslots = ns;
   const bool wino_f16 = take_wino && op.d_wwino16 && !m->train_fwd;     // reduced-precision plan: f16 operands in the inference forward
   // two-tile layers / the full-resolution tile, fp32 plan: six-term bf16 products (the training forward as well: exact splits, fp32
   // accumulate; its fragments follow every optimizer step)
@@ -1867,31 +1716,21 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
                        cm::conv_wino_b6_ok(ca.bz, ca.by, ca.bx, ca.Co, ca.Zo);
   if (ca.h16) {
     // only these kernels read / write f16 tensors; anything else here would misread them silently
-    const bool ok16 = take_f16d || (take_ups && op.d_wups16 && !(ca.h16 & ~5)) || (op.first_k && !(ca.h16 & ~4) && ks <= 1 && !take_ups && !op.wino) ||
-                      (op.small_n && !(ca.h16 & ~3) && ks <= 1 && !take_ups && !op.wino && !op.first_k);
+    const bool ok16 = take_f16d || (take_ups && op.d_wups16 && !(ca.h16 & ~5)) || (op.first_k && !(ca.h16 & ~4) && op.ks <= 1 && !take_ups && !op.wino) ||
+                      (op.small_n && !(ca.h16 & ~3) && op.ks <= 1 && !take_ups && !op.wino && !op.first_k);
     if (!ok16) return fail("conv %s: f16 tensors (mask %d) reach a kernel without f16 tensor support", op.label.c_str(), ca.h16);
   }
-  // consumer side: the GroupNorm of the input comes from the producers' accumulator rows -- finalised inside the six-term
-  // Winograd kernel, or by a fall-back launch that writes the rows gn_finalize would have written
-  if (!m->train_fwd && m->astat_all && op.gn_op >= 0 && m->ops[op.gn_op].atomic && ca.gn) {
-    const Op &g = m->ops[op.gn_op];
-    ca.gs0 = m->astat_all + ((size_t)b0 * m->astat_C + g.g0->aoff) * 3;
-    ca.gs1 = g.g1 ? m->astat_all + ((size_t)b0 * m->astat_C + g.g1->aoff) * 3 : nullptr;
-    ca.gs_C = m->astat_C; ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS;
-    if (wino_b6) {
-      ca.gn = nullptr;
-    } else {
-      CM_HIP(cm::launch_gn_from_sums(ca, (int)Vs, const_cast<float *>(ca.gn), st));
-      ca.gs0 = ca.gs1 = nullptr;
-    }
+  if (take_wino) {
+    ca.wfrag = wino_f16 ? op.d_wwino16 : op.d_wwino;
+    if (wino_b6) { ca.wfrag = op.d_wwino_b6; ca.f16 = relaxed ? 3 : 2; }
+    if (wino_b6 && h2_live && op.d_wwino_h2 && (!op.dbg_raw || op.dbg_h2)) { ca.wfrag = op.d_wwino_h2; ca.f16 = 4; ca.h2_oscale = op.h2_oscale; }
   }
-  // ... or from their slot partials when run_ops skipped the gn_finalize launch on that promise (few slots)
+  // The GroupNorm of the input from the producers' slot partials when run_ops skipped the gn_finalize launch on that promise (few
+  // slots).  Only conv_wino_p_kernel finalises them itself; conv_wino_p_taken is the launcher's own test for that kernel.
   if (!m->train_fwd && op.gn_op >= 0 && m->ops[op.gn_op].fin_skipped[slab & 3] && ca.gn) {
     const Op &g = m->ops[op.gn_op];
     const Act *g0 = g.g0, *g1 = g.g1;
-    const int nbw = cm::conv_wino_nbw_run(ca, wino_f16);
-    const bool p_kernel = take_wino && cm::conv_wino_two_step(ca.bz, ca.by, ca.bx, wino_f16, nbw) && (nbw == 2 || wino_b6);
-    if (p_kernel) {
+    if (take_wino && cm::conv_wino_p_taken(ca, wino_f16, true)) {
       ca.gp0 = g0->part + (size_t)b0 * g0->nslots * g0->C * 2; ca.gc0 = g0->cnt + (size_t)b0 * g0->nslots; ca.gns0 = g0->nslots;
       if (g1) { ca.gp1 = g1->part + (size_t)b0 * g1->nslots * g1->C * 2; ca.gc1 = g1->cnt + (size_t)b0 * g1->nslots; ca.gns1 = g1->nslots; }
       ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS;
@@ -1905,17 +1744,7 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
                                     g.gn_out + (size_t)b0 * 2 * Ct, nullptr, B, st));
     }
   }
-  // producer side: this launch adds its output's statistics to the accumulator rows instead of writing slot partials
-  const bool use_astat = !m->train_fwd && m->astat_all && op.stat_act && op.stat_act->aoff >= 0;
-  auto to_astat = [&]() {
-    if (!use_astat) return;
-    ca.astat = m->astat_all + ((size_t)b0 * m->astat_C + op.stat_act->aoff) * 3;
-    ca.astat_C = m->astat_C;
-    ca.stat_part = nullptr; ca.stat_cnt = nullptr;
-    m->astat_clean[slab & 3].B = 0;
-  };
-  if (use_astat && ks > 1) return fail("conv %s: a K-split layer cannot feed accumulator statistics", op.label.c_str());
-  if (ks > 1) {
+  if (op.ks > 1) {
     cm::ConvArgs ka = ca;
     const int V = op.out_act->V();
     float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
@@ -1938,7 +1767,7 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
     // reduced-precision plan's inference forward)
     if (op.d_wups16 && !m->train_fwd) { ca.wfrag = op.d_wups16; ca.wpar_stride = op.wups16_stride; ca.f16 = 1; }
     else if (op.d_wups_b6 && !(m->train_fwd && cm::diag_env("CM_NO_TRAIN_B6"))) { ca.wfrag = op.d_wups_b6; ca.wpar_stride = op.wups_b6_stride; ca.f16 = relaxed ? 3 : 2; }   // six-term bf16 products (training forward too); relaxed plan: three
-    if (ca.f16 == 2 && h2_live && op.d_wups_h2 && op.in0 && op.in0->part && op.in0->nslots > 0 && !m->astat_all && (!op.dbg_raw || op.dbg_h2)) {
+    if (ca.f16 == 2 && h2_live && op.d_wups_h2 && op.in0 && op.in0->part && op.in0->nslots > 0 && (!op.dbg_raw || op.dbg_h2)) {
       // default plan, inference-only handle: h2 with the sample's block exponent from the source tensor's slot statistics
       const Act *si = op.in0;
       ca.wfrag = op.d_wups_h2; ca.f16 = 4; ca.h2_oscale = op.h2_oscale;
@@ -1954,7 +1783,6 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
       ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * nsu;
       op.stat_act->nslots = nsu;
     }
-    to_astat();
     CM_HIP(cm::launch_conv_ups(ca, op.ups_mbw, op.ups_planes, op.NB, st));
   } else if (take_f16d) {
     // reduced-precision plan: direct f16 kernel with its own tile geometry / statistics slots
@@ -1970,34 +1798,9 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
       op.stat_act->nslots = ns16;
     }
     CM_HIP(cm::launch_conv_f16d(ca, op.f16d_mbw, st));
-    if (use_astat) {                               // (this kernel writes slot partials only: convert them)
-      m->astat_clean[slab & 3].B = 0;
-      CM_HIP(cm::launch_slots_to_sums(ca.stat_part, ca.stat_cnt, ca.stat_ns, ca.stat_C, B,
-                                      m->astat_all + ((size_t)b0 * m->astat_C + op.stat_act->aoff) * 3, m->astat_C, st));
-    }
-  } else if (take_b6d) {
-    // fp32 plan, inference forward: direct six-term kernel with its own tile geometry / statistics slots
-    ca.bz = op.b6d_bz; ca.by = op.b6d_by; ca.bx = op.b6d_bx;
-    ca.wfrag = op.d_wb6d;
-    if (ca.s2w) ca.s2w = op.d_wb6d_skip;
-    if (op.stat_act) {
-      const int ns6 = cm::conv_b6d_slots(ca, op.b6d_nw, op.b6d_mbw);
-      if (ns6 > MAX_SLOTS) return fail("statistics slots %d exceed %d", ns6, MAX_SLOTS);
-      ca.stat_ns = ns6;
-      ca.stat_part = op.stat_act->part + (size_t)b0 * ns6 * ca.stat_C * 2;
-      ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns6;
-      op.stat_act->nslots = ns6;
-    }
-    to_astat();
-    CM_HIP(cm::launch_conv_b6d(ca, op.b6d_nw, op.b6d_mbw, st));
   } else if (take_wino) {
-    ca.wfrag = wino_f16 ? op.d_wwino16 : op.d_wwino;
-    if (wino_b6) { ca.wfrag = op.d_wwino_b6; ca.f16 = relaxed ? 3 : 2; }
-    if (wino_b6 && h2_live && op.d_wwino_h2 && (!op.dbg_raw || op.dbg_h2)) { ca.wfrag = op.d_wwino_h2; ca.f16 = 4; ca.h2_oscale = op.h2_oscale; }
-    to_astat();
     CM_HIP(cm::launch_conv_wino(ca, wino_f16, st));
   } else if (op.first_k) {
-    to_astat();
     CM_HIP(cm::launch_conv_first(ca, op.first_cin, op.d_wfirst, st));
   } else if (op.small_n) {
     bool done = false;
@@ -2022,7 +1825,6 @@ int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
     if (op.d_wfrag16 && !m->train_fwd && cm::conv_par_f16_variant(op.MB, op.NB, ca.bz, ca.by, ca.bx)) {
       ca.wfrag = op.d_wfrag16; ca.wpar_stride = op.wpar_stride16; ca.f16 = 1;   // f16 operands, fp32 accumulate
     }
-    to_astat();
     CM_HIP(cm::launch_conv(ca, op.MB, op.NB, st));
   }
   return 0;
@@ -2058,14 +1860,6 @@ int run_combine(cm_model *m, cm::CombineArgs &cb, hipStream_t st) {
 // Every sample-indexed pointer is offset by b0, so two disjoint sub-batches can run
 // concurrently on two streams (`slab` selects the stream's K-split scratch region).
 int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
-  if (m->astat_all && !m->train_fwd) {
-    // accumulator statistics: this forward ADDS to the rows of its samples -- they must be zero.  The sampling loop's step
-    // kernel clears them for the next step (no launch); any other caller pays one memset here.
-    auto &cl = m->astat_clean[slab & 3];
-    if (!(cl.b0 <= b0 && b0 + B <= cl.b0 + cl.B))
-      CM_HIP(hipMemsetAsync(m->astat_all + (size_t)b0 * m->astat_C * 3, 0, (size_t)B * m->astat_C * 3 * sizeof(unsigned long long), st));
-    cl.B = 0;                                     // dirty from here on
-  }
   for (size_t oi = 0; oi < m->ops.size(); ++oi) {
     Op &op = m->ops[oi];
     // the fused attention block runs in the inference plan, its four generic ops in the training forward
@@ -2106,18 +1900,15 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
       }
       case OP_GNFIN: {
         if (op.qr_consumer && !m->train_fwd) break;   // its consumer finalises the statistics itself (cm_conv_qr.hip)
-        if (op.atomic && !m->train_fwd) break;        // accumulator statistics: finalised by the consuming conv (run_conv)
         op.fin_skipped[slab & 3] = false;
         // (<= 16 slots: measured -0.7 % on the ATC step, -1.6 % on the 24x72 f16 plan; HERMES-CR-120's half resolution has 24 slots
         //  per tensor and up to 192 channels -- there the merge in 256 workgroups cost more than the launch, +0.5 %)
-        static const int few_sc = cm::diag_env("CM_FEW_SC") ? atoi(cm::diag_env("CM_FEW_SC")) : 0;   // (slots x channels bound, experiments)
-        const auto few = [](const Act *t) { return t->nslots <= 16 || t->nslots * t->C <= few_sc; };
+        const auto few = [](const Act *t) { return t->nslots <= 16; };
         if (op.from_slots && !m->train_fwd && few(op.g0) && (!op.g1 || few(op.g1)) &&
             (!op.g1 || op.g1->V() == op.g0->V())) {
           op.fin_skipped[slab & 3] = true;            // few slots: the consuming Winograd conv merges them in its prologue (run_conv)
           break;
         }
-        { static const bool skip = cm::diag_env("CM_SKIP_GNFIN") != nullptr; if (skip) break; }   // timing bound only (stale rows)
         if (op.g1 && op.g1->V() != op.g0->V()) return fail("concat sources disagree on voxel count");
         const Act *g0 = op.g0, *g1 = op.g1;
         const int Ct = g0->C + (g1 ? g1->C : 0);
@@ -2163,10 +1954,6 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
     if (m->profile) {
       CM_HIP(hipEventRecord(e1, st));
       m->prof_events[slab & 3].push_back({(int)oi, {e0, e1}});
-    }
-    if (m->mid_at >= 0 && (int)oi >= m->mid_at) {
-      CM_HIP(hipEventRecord(m->ev_half, st));
-      m->mid_at = -1;
     }
     if (tl_fin_done) oi = fin_at;   // (the ops in between are the ones this mode skips anyway)
     tl_fin_next = nullptr; tl_fin_done = false;
@@ -2385,7 +2172,6 @@ int cm_model_create(const cm_unet_config *cfg, cm_model **out) {
     CM_HIP(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
   }
   CM_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-  CM_HIP(hipEventCreateWithFlags(&m->ev_half, hipEventDisableTiming));
   *out = m.release();
   return 0;
 }
@@ -2403,7 +2189,6 @@ int cm_model_destroy(cm_model *m) {
     if (m->ev_join[i]) hipEventDestroy(m->ev_join[i]);
   }
   if (m->ev_fork) hipEventDestroy(m->ev_fork);
-  if (m->ev_half) hipEventDestroy(m->ev_half);
   if (m->prof_base) hipEventDestroy(m->prof_base);
   if (m->train) cm_free_train_state(m->train);
   delete m;
@@ -2472,7 +2257,6 @@ int cm_model_finalize(cm_model *m) {
   CM_HIP(hipMemset(m->tbuf, 0, B * sizeof(long long)));
   if (build_ops(m)) return 1;
   if (plan_h16(m)) return 1;
-  if (plan_astat(m)) return 1;
   if (plan_slot_consumers(m)) return 1;
   if (build_time_table(m)) return 1;
   const size_t per = (size_t)m->per_sample();
@@ -2811,9 +2595,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       al.sample_id_base = opts->sample_id_base;
       al.tab = m->d_steptab; al.kctr = m->d_kctr; al.row_stride = (long long)B * per; al.boff = 0;
       al.hist = d_history; al.noise = d_noise;
-      if (m->astat_all) { al.zero_u64 = m->astat_all; al.zero_n = (long long)B * m->astat_C * 3; }
       CM_HIP(cm::launch_sampler_step(al, st));
-      if (m->astat_all) { m->astat_clean[0].b0 = 0; m->astat_clean[0].B = B; }
       if (mass && mass_step(0, B, 0.f, d_history, m->d_steptab, 0, st)) return 1;
       return 0;
     };
@@ -2851,12 +2633,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       al.sample_id_base = opts->sample_id_base + b0;
       al.hist = d_history ? d_history + (k + 1) * B * per + (size_t)b0 * per : nullptr;
       al.noise = (d_noise && al.draw) ? d_noise + k * B * per + (size_t)b0 * per : nullptr;
-      if (m->astat_all) {                          // the step kernel clears this lane's accumulator rows for the next forward
-        al.zero_u64 = m->astat_all + (size_t)b0 * m->astat_C * 3;
-        al.zero_n = (long long)Bn * m->astat_C * 3;
-      }
       CM_HIP(cm::launch_sampler_step(al, ls));
-      if (m->astat_all) { m->astat_clean[ln & 3].b0 = b0; m->astat_clean[ln & 3].B = Bn; }
       if (mass && mass_step(b0, Bn, r.mass, al.hist, nullptr, 0, ls)) return 1;
     }
     return 0;
@@ -2867,16 +2644,8 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     // Step 0 of every lane from the calling thread (lazy tile set-up and function attributes happen there, once);
     // the remaining steps of lane ln > 0 are enqueued by a host thread of its own, so that the lanes' launch
     // streams fill independently (one thread alternating between the streams is launch-bandwidth bound).
-    // Lane offset: lane 1 starts after lane 0 has passed a given op of its first step, so that afterwards one lane's
-    // full-resolution (issue-bound) section runs beside the other's quarter-resolution (latency-bound) section instead of both
-    // lanes marching through the same section together.  CM_LANE_OFFSET = fraction of the op list (0 = start together).
-    static const double lane_off = [] { const char *e = cm::diag_env("CM_LANE_OFFSET"); return e ? atof(e) : 0.0; }();   // (measured: 0.25 ... 0.75 all within noise of 0 -- 1.398 ... 1.414 vs 1.404 / 1.406 ms; off by default)
-    for (int ln = 0; ln < lanes; ++ln) {
-      if (ln == 0 && lanes == 2 && lane_off > 0.0 && lane_off < 1.0 && order.size() >= 2) m->mid_at = (int)(lane_off * (double)m->ops.size());
-      if (ln == 1 && lanes == 2 && lane_off > 0.0 && lane_off < 1.0 && order.size() >= 2) CM_HIP(hipStreamWaitEvent(sts[1], m->ev_half, 0));
+    for (int ln = 0; ln < lanes; ++ln)
       if (lane_steps(ln, 0, 1)) return 1;
-      m->mid_at = -1;
-    }
     // (nothing may throw across the C ABI: a worker's exception becomes its lane's error; a lane whose thread cannot be
     //  created is enqueued from the calling thread instead)
     std::vector<int> rcs((size_t)lanes, 0);
@@ -3125,9 +2894,8 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   tmp.ca.gn = nullptr; tmp.ca.silu = 0; tmp.ca.temb = nullptr; tmp.temb_off = -1; tmp.ca.resid = nullptr; tmp.resid_act = nullptr;
   tmp.d_s2w = nullptr; tmp.d_wqr_skip = nullptr; tmp.skip_if_fused = false; tmp.dbg_raw = true; tmp.pm_off = -1;
   if (!tmp.qr) tmp.gn_op = -1;
-  if (tmp.stat_act && tmp.stat_act->aoff >= 0) tmp.stat_act = nullptr;      // (no additions to the accumulator rows of the plan)
   tmp.dbg_h2 = mode == 2;
-  if (mode == 1) { tmp.d_wwino_b6 = nullptr; tmp.d_wqr_b6 = nullptr; tmp.d_wups_b6 = nullptr; tmp.b6d = false; tmp.b6s2 = false; }
+  if (mode == 1) { tmp.d_wwino_b6 = nullptr; tmp.d_wqr_b6 = nullptr; tmp.d_wups_b6 = nullptr; }
   const int ns_keep = op.stat_act ? op.stat_act->nslots : 0;
   const int ns_in_keep = op.in0->nslots;
   if (mode == 2 && op.ups && op.in0->part) {
@@ -3238,10 +3006,6 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
       // 64-row x 128-column x 32-deep GEMM per (plane, in-plane tile): rows beyond the halo box and columns beyond 27 x Co are padding
       f = (double)(a.Yo / op.fin_by) * (a.Xo / op.fin_bx) * a.Zo * 64.0 * 128.0 * 32.0 * 2;
       mult16 = (p16 && op.d_wfin16) ? 1.0 : ((h2l && op.d_wfin_h2) || rel) ? 3.0 : 6.0;
-    } else if ((op.b6d || op.b6s2) && !p16) {
-      const double tiles = (double)(a.Zo / op.b6d_bz) * (a.Yo / op.b6d_by) * (a.Xo / op.b6d_bx);
-      f = tiles * 32.0 * op.b6d_nw * op.b6d_mbw * a.Co * (Ci * 27.0 + (op.d_wb6d_skip ? op.skip0->C + (op.skip1 ? op.skip1->C : 0) : 0)) * 2;
-      mult16 = 6.0;
     } else if (op.qr) {
       {
         // the launcher's own predicate (conv_qr2_b6_ok: 8 groups, channel bound, LDS fit), not a copy of one of its clauses
@@ -3267,7 +3031,7 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
       const double pairs = 2.0 * op.ups_mbw - ((op.ups_planes && op.ups_tz == a.Zs) ? 1.0 : 0.0);
       f = tiles * 8.0 * 32.0 * pairs * 4.0 * a.Co * Ci * 2;
       if (p16 && op.d_wups16) mult16 = 1.0;
-      else if (!p16 && op.d_wups_b6) mult16 = (rel || (h2l && op.d_wups_h2 && !m->astat_all)) ? 3.0 : 6.0;
+      else if (!p16 && op.d_wups_b6) mult16 = (rel || (h2l && op.d_wups_h2)) ? 3.0 : 6.0;
     } else if (a.par) {
       if (p16 && op.d_wfrag16) mult16 = 1.0;
       f = op.flops_per_sample * 8.0 / 27.0;

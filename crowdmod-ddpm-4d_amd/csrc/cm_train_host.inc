@@ -269,12 +269,6 @@ int repack_all(cm_model *m, hipStream_t st) {
     if (op.d_wwino_b6) CM_HIP(cm::launch_wino_b6_repack(op.d_wwino, op.d_wwino_b6, op.wwino_floats, st));
     if (op.d_wqr_b6) CM_HIP(cm::launch_qr_b6_repack(op.d_wqr, op.d_wqr_b6, op.wqr_floats, op.ca.C0 + op.ca.C1, st));
     if (op.d_wfin) CM_HIP(cm::launch_fin_pack(T->pbuf + T->poff[op.wname], op.d_wfin, op.ca.Co, 0, st));   // the last conv's column-packed fragments
-    if (op.d_wb6d) {      // direct six-term fragments of the inference forward: straight from the master weights
-      const int nb6 = cm::conv_b6d_nb(op.ca.Co);
-      CM_HIP(cm::launch_b6d_repack(T->pbuf + T->poff[op.wname], op.d_wb6d, op.ca.Co, op.ca.C0 + op.ca.C1, 27, nb6, st));
-      if (op.d_wb6d_skip)
-        CM_HIP(cm::launch_b6d_repack(T->pbuf + T->poff[op.skip_w], op.d_wb6d_skip, op.ca.Co, op.skip0->C + (op.skip1 ? op.skip1->C : 0), 1, nb6, st));
-    }
   }
   for (auto &D : T->dg) {
     if (D.wwino_b6) CM_HIP(cm::launch_wino_b6_repack(D.wwino, D.wwino_b6, D.wwino_floats, st));
