@@ -25,6 +25,7 @@
 #include "cm_kernels.h"
 
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -541,9 +542,23 @@ __global__ __launch_bounds__(256 * NBW, OCC) void conv_wino_kernel(const ConvArg
 #ifndef CM_WINO_ABL
 #define CM_WINO_ABL 0        // compile-time ablations of the six-term chunk loop (experiments only; results are wrong)
 #endif
-template <int BZ, int PY, int PX, bool F16, int NBW, bool SKIP, int B6 = 0>   // B6: 0 off, 1 six bf16 cross terms, 2 three (relaxed plan), 3 three f16 cross terms (h2)
+// FM (launch form, a set of WINO_FORM_* bits decided on the host by conv_wino_form; 0 = the generic kernel): what is uniform over
+// a launch and known when it is made, as compile-time facts -- the generic body keeps a sample loop, training and slot-GroupNorm
+// paths alive that a sampling launch never takes, and pays for them in scalar registers spilled to vector lanes.
+//   ONE    G >= B: the workgroup handles sample blockIdx.x only (no sample loop, no next-sample prefetch)
+//   PLAIN  GroupNorm + SiLU on load, no Dropout3d multiplier (a.pm); the GroupNorm rows come from a.gn, or with
+//   OWNGN  are finalised in the prologue from the producers' slot partials (a.gp0)
+//   WHOLE  8 x 2 x 2 tile on a grid that it divides, Co a multiple of 32: every wave owns all 32 rows x 32 channels, row -> voxel
+//          is linear in the tile origin -- no output-offset table, no row masks, per-lane base + uniform strides for the stores,
+//          the residual loads and the skip conv's rows
+// Same arithmetic in the same order in every form: results are bit-identical to FM = 0 (tests/test_gpu_wino_forms.py).
+template <int BZ, int PY, int PX, bool F16, int NBW, bool SKIP, int B6 = 0, int FM = 0>   // B6: 0 off, 1 six bf16 cross terms, 2 three (relaxed plan), 3 three f16 cross terms (h2)
 __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArgs a, const int *__restrict__ tabA,
                                                                   const int *__restrict__ tabO, int G) {
+  constexpr bool ONE = (FM & WINO_FORM_ONE) != 0, PLAIN = (FM & WINO_FORM_PLAIN) != 0, OWNGN = (FM & WINO_FORM_OWNGN) != 0;
+  constexpr bool WHOLE = (FM & WINO_FORM_WHOLE) != 0;
+  static_assert(!WHOLE || (BZ == 8 && PY == 2 && PX == 2 && NBW == 1), "the whole-tile form is the full-resolution tile's");
+  static_assert(!OWNGN || PLAIN, "own GroupNorm is a variant of the plain activation form");
   constexpr int NT = 256 * NBW;
   constexpr int NP = PY * PX, ROWS = BZ * NP;
   static_assert(ROWS <= 32 && ROWS > 16, "one (partly filled) 32-row accumulator block per frequency component");
@@ -575,12 +590,16 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
   const int r = lane & 31, hh = lane >> 5;
   const int g0 = blockIdx.x, p = blockIdx.y;
   const int nt = blockIdx.z * NBW + nbw;
-  if (g0 >= a.B) return;
-  const int nc_epi = nt * 32 + r < a.Co ? nt * 32 + r : 0;
+  if (!ONE && g0 >= a.B) return;
+  const int nc_epi = (WHOLE || nt * 32 + r < a.Co) ? nt * 32 + r : 0;
   const float bias_pre = a.bias[nc_epi];
 
   // ---- tile geometry from the tables (cm_conv_wino.hip: wino_tables) --------------------------------------------
-  if (tid < 128) outoff[tid] = tabO[p * 128 + tid];
+  if constexpr (!WHOLE) {
+    if (tid < 128) outoff[tid] = tabO[p * 128 + tid];
+  }
+  // WHOLE: in-sample output voxel of the tile's first row, sub-block (0, 0) -- the tile origin; every other row is linear in it
+  const int o0 = WHOLE ? tabO[p * 128] : 0;
   int asoff[RK];
   unsigned aok = 0;
 #pragma unroll
@@ -664,34 +683,37 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       asm volatile("" : "+v"(vo));               // keep ONE copy of the offsets live (no hoisted per-source products)
       ald[k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (__umul24(vo, cb) + aq16));
     }
-    if (a.gn) {
+    if (PLAIN ? !OWNGN : a.gn != nullptr) {
       const float *gp = a.gn + (size_t)b * 2 * Ctot + (s0 ? ch * CS : a.C0 + (ch - n0) * CS);              // wave-uniform
       scn = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp) + aq16);
       shn = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp + Ctot) + aq16);
     }
   };
   issue(g0, 0);
-  __syncthreads();                               // outoff visible
+  if constexpr (!WHOLE) __syncthreads();         // outoff visible
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   // this lane's output rows of the epilogue: reg -> row (reg & 3) + 8 (reg >> 2) + 4 hh of sub-block `wave` (re-read per tile:
   // four 16-byte broadcast reads are cheaper than 16 registers held across the matrix phase)
   const i32x4 *const op4 = reinterpret_cast<const i32x4 *>(outoff + wave * 32 + 4 * hh);
   bool allv = true;
+  if constexpr (!WHOLE) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const i32x4 v4 = op4[2 * q];
-    allv = allv && v4[0] >= 0 && v4[1] >= 0 && v4[2] >= 0 && v4[3] >= 0;
+    for (int q = 0; q < 4; ++q) {
+      const i32x4 v4 = op4[2 * q];
+      allv = allv && v4[0] >= 0 && v4[1] >= 0 && v4[2] >= 0 && v4[3] >= 0;
+    }
   }
-  const bool wave_all = __all(allv) && nt * 32 + 31 < a.Co;       // the wave owns all 32 rows x 32 channels: mask-free path
+  const bool wave_all = WHOLE || (__all(allv) && nt * 32 + 31 < a.Co);       // the wave owns all 32 rows x 32 channels: mask-free path
   const int n = nt * 32 + r;
-  const bool nok = n < a.Co;
+  const bool nok = WHOLE || n < a.Co;
   const int n2a = SKIP ? a.s2C0 >> 5 : 0, n2 = SKIP ? (a.s2C0 + a.s2C1) >> 5 : 0;
   const int slot = p * 4 + wave;
 
-  const bool own_gn = a.gp0 != nullptr;                      // the GroupNorm of the input is finalised in this workgroup
-  const bool norm = a.gn != nullptr || own_gn;               // GroupNorm (+ SiLU) on load
-  for (int b = g0; b < a.B; b += G) {
-    const bool more_b = b + G < a.B;
+  const bool own_gn = PLAIN ? OWNGN : a.gp0 != nullptr;      // the GroupNorm of the input is finalised in this workgroup
+  const bool norm = PLAIN || a.gn != nullptr || own_gn;      // GroupNorm (+ SiLU) on load
+  int b = g0;                                                // (g0 < a.B: the loop body runs at least once; ONE: exactly once)
+  do {
+    const bool more_b = !ONE && b + G < a.B;
     const float tv_pre = a.temb ? a.temb[(size_t)a.tidx[b] * a.temb_stride + nc_epi] : 0.f;
     if (own_gn) {
       // the GroupNorm of this sample's input finalised HERE (no gn_finalize launch) from the producers' slot partials (few slots:
@@ -716,8 +738,10 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       }
       f32x4 pm1 = {1.f, 1.f, 1.f, 1.f};
       if (!((CM_WINO_ABL & 32) && ch > 0)) {
-      if (a.pm) pm1 = *reinterpret_cast<const f32x4 *>(a.pm + (size_t)b * a.pm_stride + (ch < n0 ? ch * CS : a.C0 + (ch - n0) * CS) + 4 * aq);
-      if (norm && a.silu && !a.pm) {
+      if constexpr (!PLAIN) {
+        if (a.pm) pm1 = *reinterpret_cast<const f32x4 *>(a.pm + (size_t)b * a.pm_stride + (ch < n0 ? ch * CS : a.C0 + (ch - n0) * CS) + 4 * aq);
+      }
+      if (PLAIN || (norm && a.silu && !a.pm)) {
 #pragma unroll
         for (int k = 0; k < RK; ++k) {
           const int v = (tid >> 2) + (NT / 4) * k + RV0;
@@ -900,8 +924,12 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
     f32x4 ska[4], skw[4];
     int svox = 0;
     if constexpr (SKIP) {
-      const int o = outoff[wave * 32 + r];
-      svox = (o >= 0 ? o : 0) + (int)(b * Vo);
+      if constexpr (WHOLE) {                     // row r = 4 z + 2 py + px of sub-block (wave >> 1, wave & 1)
+        svox = o0 + ((r >> 2) * a.Yo + 2 * ((r >> 1) & 1) + (wave >> 1)) * a.Xo + 2 * (r & 1) + (wave & 1) + (int)(b * Vo);
+      } else {
+        const int o = outoff[wave * 32 + r];
+        svox = (o >= 0 ? o : 0) + (int)(b * Vo);
+      }
       // h2 (24 registers lighter than the six-term form): the skip conv's first operand chunk travels under the output transform
       if constexpr (SKIP_EARLY) wino_skip_load1(a, nt, n2a, n2, 0, svox, lane, ska, skw);
     }
@@ -944,7 +972,55 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       }
     }
     // bias, time-embedding row, residual, channels-last store, GroupNorm statistics (slot format of gn_finalize)
-    {
+    if constexpr (WHOLE) {
+      // this lane's rows: reg -> row (reg & 3) + 8 (reg >> 2) + 4 hh = 4 z + 2 py + px with z = 2 (reg >> 2) + hh, py = (reg >> 1) & 1,
+      // px = reg & 1, so voxel(reg) = [origin + (hh Yo + oa) Xo + ob] + [(reg >> 2) 2 Yo Xo + ((reg >> 1) & 1) 2 Xo + (reg & 1) 2]: one
+      // per-lane byte offset, sixteen launch-uniform strides (scalar base + vector offset addressing; nothing per row on the vector pipe)
+      float *const outb = a.out + (size_t)b * Vo * a.out_cs;
+      const unsigned ocs4 = (unsigned)a.out_cs * 4u, n4 = (unsigned)n * 4u;
+      const unsigned vl = (unsigned)(o0 + (hh * a.Yo + oa) * a.Xo + ob);
+      auto rowv = [&](int reg) -> unsigned { return (unsigned)(((reg >> 2) * 2 * a.Yo + ((reg >> 1) & 1) * 2) * a.Xo + (reg & 1) * 2); };
+      float rs[16];
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) rs[reg] = v[reg] + bias_pre;
+      if (a.temb) {
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) rs[reg] += tv_pre;
+      }
+      if (a.resid) {
+        const char *const resb = reinterpret_cast<const char *>(a.resid + (size_t)b * Vo * a.res_cs);
+        const unsigned rcs4 = (unsigned)a.res_cs * 4u;
+        const unsigned lr = __umul24(vl, rcs4) + n4;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) rs[reg] += *reinterpret_cast<const float *>(resb + (size_t)(rowv(reg) * rcs4) + lr);
+      }
+      {
+        char *const ob8 = reinterpret_cast<char *>(outb);
+        const unsigned lo = __umul24(vl, ocs4) + n4;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) *reinterpret_cast<float *>(ob8 + (size_t)(rowv(reg) * ocs4) + lo) = rs[reg];
+      }
+      if (a.stat_part) {
+        float s1 = 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) s1 += rs[reg];
+        s1 += __shfl_xor(s1, 32);
+        const float cnt = 32.f;                     // 16 rows in each half of the wave
+        const float mean = s1 / cnt;
+        float q = 0.f;
+#pragma unroll
+        // (explicit fma chain in row order, the masked loop's own rounding sequence: left to contraction, the mask-free sum
+        //  was compiled as fma(d0, d0, d1 * d1) -- the other association of its first two terms -- and differed in the last bit)
+        for (int reg = 0; reg < 16; ++reg) { const float dd = rs[reg] - mean; q = __builtin_fmaf(dd, dd, q); }
+        q += __shfl_xor(q, 32);
+        if (hh == 0) {
+          float *sp2 = a.stat_part + (((size_t)b * a.stat_ns + slot) * a.stat_C + n) * 2;
+          sp2[0] = mean;
+          sp2[1] = q;
+        }
+        if (lane == 0 && n == 0) a.stat_cnt[(size_t)b * a.stat_ns + slot] = cnt;
+      }
+    } else {
       float *const outb = a.out + (size_t)b * Vo * a.out_cs;
       const unsigned ocs4 = (unsigned)a.out_cs * 4u, n4 = (unsigned)(nok ? n : 0) * 4u;
       int orow[16];
@@ -1000,7 +1076,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
         if (lane == 0 && n == 0) a.stat_cnt[(size_t)b * a.stat_ns + slot] = cnt;
       }
     }
-  }
+  } while (!ONE && (b += G) < a.B);
 }
 
 // Geometry tables of the persistent kernel for one (grid, tile) pair, `nth` = threads per workgroup:
@@ -1208,6 +1284,34 @@ bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn) {
          wino_p_lds_launch(a, f16, nbw, b6, own_gn) <= 160 * 1024;
 }
 
+// The launch form (FM of conv_wino_p_kernel) of one launch with G sample lanes; 0 = generic.  Only forms that a BASELINE config
+// launches are instantiated -- all on the h2 arithmetic (a.f16 == 4) of the default plan's sampling path:
+//   ONE | PLAIN | WHOLE   8 x 2 x 2 tile, plain and fused-skip   full resolution of ATC 12 x 36, CR-120 28 x 24 and 24 x 72 (rows from a.gn)
+//   ONE | PLAIN           two-tile kernels 2 x 3 x 5 and 2 x 7 x 2, plain and fused-skip   half resolution, GroupNorm rows from a.gn
+//   ONE | PLAIN | OWNGN   the same with the GroupNorm finalised from slot partials (a.gp0)
+// Everything else runs the generic kernel: training launches (a.pm, or a conv without GroupNorm + SiLU on load), more samples than
+// sample lanes (B > G), a full-resolution grid the tile does not divide, the six-term / relaxed / f16 / fp32 operand forms, and every
+// diagnostic run (a.dbg != 0: the CM_CONV_DBG / cm_debug_conv_flags switches; bit 1 << 20 selects nothing else and is the
+// documented way to force the generic kernel for an A/B or a bit-identity check).
+int conv_wino_form(const ConvArgs &a, int G) {
+  if (a.dbg != 0 || a.f16 != 4) return 0;
+  if (G < a.B || a.pm || !a.silu) return 0;
+  const bool own = a.gp0 != nullptr;
+  if (own == (a.gn != nullptr)) return 0;           // GroupNorm rows from exactly one place
+  if (a.bz == 8) {
+    const bool whole = a.by == 4 && a.bx == 4 && a.Yo % 4 == 0 && a.Xo % 4 == 0 && a.Zo % 8 == 0 && a.Co % 32 == 0;
+    if (own || !whole || conv_wino_nbw(a.bz, a.Co) != 1) return 0;
+    return WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE;
+  }
+  if (conv_wino_nbw(a.bz, a.Co) != 2) return 0;
+  return WINO_FORM_ONE | WINO_FORM_PLAIN | (own ? WINO_FORM_OWNGN : 0);
+}
+
+static std::atomic<long long> wino_form_launches[16];
+void conv_wino_form_counts(long long counts[16], bool reset) {
+  for (int i = 0; i < 16; ++i) counts[i] = reset ? wino_form_launches[i].exchange(0) : wino_form_launches[i].load();
+}
+
 hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   ConvArgs a = a_in;
   a.dbg = conv_dbg_flags();
@@ -1239,6 +1343,8 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
     hipError_t et = wino_tabs_get(a, 256 * nbw, &tb);
     if (et != hipSuccess) return et;
     const dim3 gridp((unsigned)G, (unsigned)ntp, (unsigned)nz);
+    const int fm = nbw == conv_wino_nbw(a.bz, a.Co) ? conv_wino_form(a, G) : 0;
+    wino_form_launches[fm & 15].fetch_add(1, std::memory_order_relaxed);
 #define CM_WINO_PGO1(KERNEL, THREADS)                                                               \
   {                                                                                                 \
     CM_WINO_ATTR(KERNEL)                                                                            \
@@ -1250,6 +1356,11 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
     if (a.s2w) CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, F, NB, true>), THREADS)                \
     CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, F, NB, false>), THREADS)                          \
   }
+#define CM_WINO_PGOFM(Z, PY_, PX_, NB, THREADS, FM_)                                                \
+    if (h2 && fm == (FM_)) {                                                                        \
+      if (a.s2w) CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, true, 3, (FM_)>), THREADS) \
+      CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, false, 3, (FM_)>), THREADS)          \
+    }
 #define CM_WINO_PGO6N(Z, PY_, PX_, NB, THREADS)                                                     \
   {                                                                                                 \
     if (h2) {                                                                                       \
@@ -1268,13 +1379,20 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
 #define X(z, py, px)                                                                                \
     if (a.bz == z && a.by == 2 * py && a.bx == 2 * px) {                                            \
       if constexpr (z != 8) {                                                                       \
-        if (nbw == 2 && b6) CM_WINO_PGO6(z, py, px, 512)                                            \
+        if (nbw == 2 && b6) {                                                                       \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN)                         \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN)       \
+          CM_WINO_PGO6(z, py, px, 512)                                                              \
+        }                                                                                           \
         if (nbw == 2 && f16) CM_WINO_PGO(z, py, px, true, 2, 512)                                   \
         if (nbw == 2) CM_WINO_PGO(z, py, px, false, 2, 512)                                         \
       }                                                                                             \
       if (f16) CM_WINO_PGO(z, py, px, true, 1, 256)                                                 \
       if constexpr (z == 8 && py == 2 && px == 2) {                                                 \
-        if (b6) CM_WINO_PGO61(z, py, px, 256)                                                       \
+        if (b6) {                                                                                   \
+          CM_WINO_PGOFM(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE)       \
+          CM_WINO_PGO61(z, py, px, 256)                                                             \
+        }                                                                                           \
         CM_WINO_PGO(z, py, px, false, 1, 256)                                                       \
       }                                                                                             \
     }

@@ -302,6 +302,43 @@ void test_round3_packers() {
   EXPECT(!cm::conv_qr_ok(q));
 }
 
+// conv_wino_form: the specialised launch forms of conv_wino_p_kernel are taken only for what they were compiled for; everything else
+// -- a training launch (Dropout3d multiplier), more samples than sample lanes, a grid the full-resolution tile does not divide,
+// diagnostic flags, another operand form -- gets the generic kernel (form 0)
+void test_wino_form_dispatch() {
+  const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+  cm::ConvArgs full{};
+  full.f16 = 4; full.silu = 1; full.gn = dummy; full.B = 64;
+  full.C0 = 32; full.Co = 32; full.Zo = full.Zs = 8; full.Yo = full.Ys = 12; full.Xo = full.Xs = 36;
+  full.bz = 8; full.by = 4; full.bx = 4; full.ntz = 1; full.nty = 3; full.ntx = 9;
+  const int whole = cm::WINO_FORM_ONE | cm::WINO_FORM_PLAIN | cm::WINO_FORM_WHOLE;
+  EXPECT(cm::conv_wino_form(full, 64) == whole);
+  for (const int yx : {28 * 1000 + 24, 24 * 1000 + 72}) {            // CR-120 and the 2x grid divide by the tile as well
+    cm::ConvArgs a = full;
+    a.Yo = a.Ys = yx / 1000; a.Xo = a.Xs = yx % 1000; a.nty = a.Yo / 4; a.ntx = a.Xo / 4;
+    EXPECT(cm::conv_wino_form(a, 64) == whole);
+  }
+  { cm::ConvArgs a = full; a.pm = dummy; EXPECT(cm::conv_wino_form(a, 64) == 0); }                 // training launch
+  { cm::ConvArgs a = full; a.B = 96; EXPECT(cm::conv_wino_form(a, 64) == 0); }                     // B above the grid's sample lanes
+  { cm::ConvArgs a = full; a.Yo = a.Ys = 10; a.Xo = a.Xs = 14; a.nty = 3; a.ntx = 4; EXPECT(cm::conv_wino_form(a, 64) == 0); }   // shifted last tiles
+  { cm::ConvArgs a = full; a.dbg = 4096; EXPECT(cm::conv_wino_form(a, 64) == 0); }                 // diagnostic flags
+  { cm::ConvArgs a = full; a.dbg = 1 << 20; EXPECT(cm::conv_wino_form(a, 64) == 0); }              // the documented force-generic bit
+  { cm::ConvArgs a = full; a.f16 = 2; EXPECT(cm::conv_wino_form(a, 64) == 0); }                    // six-term form
+  { cm::ConvArgs a = full; a.gn = nullptr; a.silu = 0; EXPECT(cm::conv_wino_form(a, 64) == 0); }   // raw source (no GroupNorm + SiLU)
+  { cm::ConvArgs a = full; a.gp0 = dummy; EXPECT(cm::conv_wino_form(a, 64) == 0); }                // rows from two places
+  { cm::ConvArgs a = full; a.Co = 48; EXPECT(cm::conv_wino_form(a, 64) == 0); }                    // partly filled channel tile
+  cm::ConvArgs half{};
+  half.f16 = 4; half.silu = 1; half.gn = dummy; half.B = 32;
+  half.C0 = 64; half.Co = 64; half.Zo = half.Zs = 4; half.Yo = half.Ys = 6; half.Xo = half.Xs = 18;
+  half.bz = 2; half.by = 6; half.bx = 10; half.ntz = 2; half.nty = 1; half.ntx = 2;
+  EXPECT(cm::conv_wino_form(half, 32) == (cm::WINO_FORM_ONE | cm::WINO_FORM_PLAIN));
+  { cm::ConvArgs a = half; a.gn = nullptr; a.gp0 = dummy; EXPECT(cm::conv_wino_form(a, 32) == (cm::WINO_FORM_ONE | cm::WINO_FORM_PLAIN | cm::WINO_FORM_OWNGN)); }
+  { cm::ConvArgs a = half; a.B = 64; EXPECT(cm::conv_wino_form(a, 32) == 0); }
+  { cm::ConvArgs a = half; a.pm = dummy; EXPECT(cm::conv_wino_form(a, 32) == 0); }
+  { cm::ConvArgs a = half; a.dbg = 512; EXPECT(cm::conv_wino_form(a, 32) == 0); }
+  { cm::ConvArgs a = half; a.Co = 32; EXPECT(cm::conv_wino_form(a, 32) == 0); }                    // one-tile workgroups: no h2 form at all
+}
+
 void test_misc_errors() {
   EXPECT(cm_abi_version() == CM_ABI_VERSION);
   EXPECT(cm_device_count(nullptr) != 0);
@@ -326,6 +363,7 @@ int main() {
   test_packers();
   test_tile_planner();
   test_round3_packers();
+  test_wino_form_dispatch();
   test_misc_errors();
   printf("selftest ok: %d checks\n", g_checks);
   return 0;

@@ -2857,17 +2857,18 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count) {
   return 0;
 }
 
-// One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags" or "other <label>".
+// One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags out_C C0 C1 wino" or "other <label>".
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
   CM_NOT_DIT(m, "cm_debug_conv_info");
   if (!m || !m->finalized || !buf || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
   const cm::ConvArgs &a = op.ca;
-  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", op.label.c_str(), a.ntaps, a.stride, a.par,
+  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", op.label.c_str(), a.ntaps, a.stride, a.par,
            a.C0 + a.C1, a.Co, a.Zo, a.Yo, a.Xo, op.NB, op.MB, a.bz, a.by, a.bx, op.ks,
            (op.small_n ? 1 : 0) | (op.first_k ? 2 : 0) | (op.stat_act ? 4 : 0) | (op.skip_if_fused ? 8 : 0) | (a.CK == 32 ? 16 : 0),
-           op.out_act ? op.out_act->C : a.Co);       // (last field: channel stride of the output tensor, cm_debug_conv_io's h_out)
+           op.out_act ? op.out_act->C : a.Co,        // (channel stride of the output tensor, cm_debug_conv_io's h_out)
+           a.C0, a.C1, op.wino ? 1 : 0);             // (channels of the two sources; does the Winograd launcher take the op)
   return 0;
 }
 
@@ -2876,7 +2877,10 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
 // [B][Zs][Ys][Xs][C0 / C1] (h_in1 null when the op has one source); h_out: host [B][Zo][Yo][Xo][channel stride of the output
 // tensor].  mode 0: the six-term bf16 form where the plan has one (raw operands are unbounded: never the h2 form); mode 1: the
 // same layer on fp32 matrix instructions (the split fragments withheld); mode 2: the h2 form where the plan has one (the caller
-// keeps its operands inside the bound the plan guarantees, tests/test_gpu_h2.py).
+// keeps its operands inside the bound the plan guarantees, tests/test_gpu_h2.py); mode 3: the op exactly as the sampling forward
+// launches it -- GroupNorm + SiLU on load, time-embedding row, residual, fused skip conv, h2 where the plan has it -- on the caller's
+// sources; the GroupNorm rows / slot partials, the time rows, the residual and the skip conv's source are what the last forward
+// left (tests/test_gpu_wino_forms.py compares two kernels for the SAME launch with it; cm_debug_conv_stats reads the slots it wrote).
 int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B) {
   CM_NOT_DIT(m, "cm_debug_conv_io");
   if (check_ready(m, B)) return 1;
@@ -2890,10 +2894,14 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   const size_t Vs = (size_t)op.in0->V(), Vo = (size_t)op.out_act->V();
   CM_HIP(hipMemcpy(op.in0->d, h_in0, (size_t)B * Vs * op.in0->C * sizeof(float), hipMemcpyHostToDevice));
   if (op.in1) CM_HIP(hipMemcpy(op.in1->d, h_in1, (size_t)B * Vs * op.in1->C * sizeof(float), hipMemcpyHostToDevice));
+  if (mode < 0 || mode > 3) return fail("mode %d", mode);
   Op tmp = op;
-  tmp.ca.gn = nullptr; tmp.ca.silu = 0; tmp.ca.temb = nullptr; tmp.temb_off = -1; tmp.ca.resid = nullptr; tmp.resid_act = nullptr;
-  tmp.d_s2w = nullptr; tmp.d_wqr_skip = nullptr; tmp.skip_if_fused = false; tmp.dbg_raw = true; tmp.pm_off = -1;
-  if (!tmp.qr) tmp.gn_op = -1;
+  if (mode != 3) {
+    tmp.ca.gn = nullptr; tmp.ca.silu = 0; tmp.ca.temb = nullptr; tmp.temb_off = -1; tmp.ca.resid = nullptr; tmp.resid_act = nullptr;
+    tmp.d_s2w = nullptr; tmp.d_wqr_skip = nullptr; tmp.dbg_raw = true; tmp.pm_off = -1;
+    if (!tmp.qr) tmp.gn_op = -1;
+  }
+  tmp.skip_if_fused = false;
   tmp.dbg_h2 = mode == 2;
   if (mode == 1) { tmp.d_wwino_b6 = nullptr; tmp.d_wqr_b6 = nullptr; tmp.d_wups_b6 = nullptr; }
   const int ns_keep = op.stat_act ? op.stat_act->nslots : 0;
@@ -2911,6 +2919,33 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   if (rc) return 1;
   if (e != hipSuccess) return fail("debug conv launch failed: %s", hipGetErrorString(e));
   CM_HIP(hipMemcpy(h_out, op.out_act->d, (size_t)B * Vo * op.out_act->C * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Launches of the table-driven Winograd kernel per launch form (cm::conv_wino_form; index 0 = the generic kernel) since the last reset.
+int cm_debug_wino_form_counts(int64_t counts[16], int32_t reset) {
+  if (!counts) return fail("bad argument");
+  long long c[16];
+  cm::conv_wino_form_counts(c, reset != 0);
+  for (int i = 0; i < 16; ++i) counts[i] = (int64_t)c[i];
+  return 0;
+}
+
+// The statistics slots the last launch of conv op `index` wrote for its output tensor: h_part [B][nslots][C][2] (mean, M2), h_cnt
+// [B][nslots] rows behind each slot.  h_part / h_cnt may be null: only *nslots / *C are returned (size the buffers, call again).
+int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, float *h_cnt, int32_t *nslots, int32_t *C) {
+  CM_NOT_DIT(m, "cm_debug_conv_stats");
+  if (check_ready(m, B)) return 1;
+  if (!nslots || !C || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
+  const Op &op = m->ops[index];
+  if (op.kind != OP_CONV || !op.stat_act || !op.stat_act->part) return fail("op %d writes no statistics", index);
+  const Act *t = op.stat_act;
+  *nslots = t->nslots;
+  *C = t->C;
+  DevGuard g(m->device);
+  CM_HIP(hipStreamSynchronize(m->stream));
+  if (h_part) CM_HIP(hipMemcpy(h_part, t->part, (size_t)B * t->nslots * t->C * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_cnt) CM_HIP(hipMemcpy(h_cnt, t->cnt, (size_t)B * t->nslots * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -291,8 +291,19 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
  * field of cm_debug_conv_info];
  * mode 0 = the six-term bf16 form where the plan has one (raw operands are unbounded: never the h2 form), 1 = the same layer on
  * fp32 matrix instructions (split fragments withheld), 2 = the h2 form (f16 two-way splits) where the plan has one: the caller
- * keeps |x| inside the bound the plan guarantees for that layer (8000; tests/test_gpu_h2.py). */
+ * keeps |x| inside the bound the plan guarantees for that layer (8000; tests/test_gpu_h2.py), 3 = the op exactly as the sampling
+ * forward launches it (GroupNorm + SiLU on load, time row, residual, fused skip conv) on the caller's sources; everything else it
+ * reads is what the last forward left.  With cm_debug_conv_flags(1 << 20) -- a bit no kernel reads; any non-zero value marks a
+ * diagnostic run -- the Winograd launcher takes its generic kernel instead of a specialised launch form: the two must agree
+ * bit for bit (tests/test_gpu_wino_forms.py). */
 int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B);
+/* Statistics slots the last launch of conv op `index` wrote: h_part [B][*nslots][*C][2], h_cnt [B][*nslots]; with null buffers
+ * only the two sizes are returned. */
+int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, float *h_cnt, int32_t *nslots, int32_t *C);
+/* Launches of the table-driven Winograd kernel per launch form since the last reset (process-wide): counts[0] = the generic kernel,
+ * counts[f] = the instantiation compiled for form f (bits: 1 one sample per workgroup, 2 plain GroupNorm + SiLU load, 4 GroupNorm
+ * finalised from slot partials, 8 whole full-resolution tiles). */
+int cm_debug_wino_form_counts(int64_t counts[16], int32_t reset);
 int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32_t by, int32_t bx,
                        int32_t B, int32_t iters, float *us);
 
