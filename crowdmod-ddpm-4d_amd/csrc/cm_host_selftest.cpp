@@ -339,6 +339,164 @@ void test_wino_form_dispatch() {
   { cm::ConvArgs a = half; a.Co = 32; EXPECT(cm::conv_wino_form(a, 32) == 0); }                    // one-tile workgroups: no h2 form at all
 }
 
+// conv_route: the one place that decides which kernel family and operand form a conv runs on.  Hand-built ops, one per layer class
+// of the plan, carrying the fragment sets add_conv packs for each precision plan (dummy non-null pointers: the route only asks
+// whether a set exists), crossed with precision x training forward x stale h2 x h2_off x debug steering.  Every combination is
+// asserted against the table below (the kernel call tables under profiles/) AND against the invariants.
+enum RouteClass { RC_WINO_FULL, RC_WINO_FULL_SKIP, RC_WINO_HALF, RC_WINO_HALF_SKIP, RC_QUARTER, RC_QUARTER_NO_TRAIN_QR, RC_KSPLIT, RC_STRIDE2,
+                  RC_UPS_STATS, RC_UPS_NO_STATS, RC_FIRST, RC_LAST, RC_1X1, RC_1X1_STATS, RC_SKIP_ABSORBED, RC_COUNT };
+
+Op route_class_op(int rc, int precision) {
+  static float frag[4];
+  static Act src, skip, out;
+  const bool p32 = precision == CM_PRECISION_F32, p16 = precision == CM_PRECISION_F16;
+  src.part = frag; src.nslots = 8; skip.C = 64; out.C = 64;
+  Op op;
+  op.kind = OP_CONV; op.cls = K_CONV3;
+  op.in0 = &src; op.out_act = &out;
+  cm::ConvArgs &a = op.ca;
+  a.ntaps = 27; a.td = 3; a.stride = 1; a.CK = 32; a.bs = a.bz = a.by = a.bx = 1; a.ntz = a.nty = a.ntx = 1;
+  auto grid = [&](int Z, int Y, int X, int Ci, int Co) { a.Zs = a.Zo = Z; a.Ys = a.Yo = Y; a.Xs = a.Xo = X; a.C0 = Ci; a.Co = Co; a.out_cs = Co; };
+  const bool skipc = rc == RC_WINO_FULL_SKIP || rc == RC_WINO_HALF_SKIP;
+  switch (rc) {
+    case RC_WINO_FULL: case RC_WINO_FULL_SKIP: case RC_WINO_HALF: case RC_WINO_HALF_SKIP: {
+      const bool full = rc == RC_WINO_FULL || rc == RC_WINO_FULL_SKIP;
+      if (full) grid(8, 12, 36, skipc ? 96 : 32, 32); else grid(4, 6, 18, skipc ? 192 : 64, 64);
+      a.gn = frag; a.silu = 1; op.gn_op = 0; op.stat_act = &out; op.NB = 1;
+      op.wino = true; op.d_wwino = frag;
+      EXPECT(resolve_conv(nullptr, op) == 0 && op.wino && op.MB == 4);        // (a Winograd op that fits its tile touches no device)
+      if (!p16) { EXPECT(cm::conv_wino_b6_ok(a.bz, a.by, a.bx, a.Co, a.Zo)); op.d_wwino_b6 = frag; }
+      if (p32) op.d_wwino_h2 = frag;
+      if (p16) { op.d_wwino16 = frag; op.f16d = true; op.d_w16d = frag; }     // (Z >= 4 on both grids: the direct f16 kernel)
+      if (skipc) { op.d_s2w = op.d_bias_fused = frag; op.skip0 = &skip; op.pm_off = 0; if (p16) op.d_w16d_skip = frag; }
+      break;
+    }
+    case RC_QUARTER: case RC_QUARTER_NO_TRAIN_QR:
+      grid(2, 3, 9, 128, 128);
+      a.gn = frag; a.silu = 1; op.gn_op = 0; op.stat_act = &out; op.NB = 2;
+      op.ks = 4; op.d_zero_bias = frag;                                       // (the K-split set-up stays for the training forward)
+      op.qr = true; op.d_wqr = frag;
+      if (!p16) { op.d_wqr_b6 = frag; op.train_qr = rc == RC_QUARTER; }
+      if (p32) op.d_wqr_h2 = frag;
+      break;
+    case RC_KSPLIT:    // stride-2 conv into the quarter resolution: statistics, no GroupNorm on load -> no whole-sample kernel
+      grid(2, 3, 9, 64, 128); a.Zs = 4; a.Ys = 6; a.Xs = 18; a.stride = 2; op.stat_act = &out; op.NB = 2; op.ks = 2; op.d_zero_bias = frag;
+      break;
+    case RC_STRIDE2:
+      grid(4, 6, 18, 32, 64); a.Zs = 8; a.Ys = 12; a.Xs = 36; a.stride = 2; op.stat_act = &out; op.NB = 2;
+      break;
+    case RC_UPS_STATS: case RC_UPS_NO_STATS:
+      grid(8, 12, 36, 64, 64); a.Zs = 4; a.Ys = 6; a.Xs = 18; a.par = 1; a.ntaps = 8; a.td = 2; op.stat_act = &out; op.NB = 2;
+      op.ups = true;
+      if (!p16) op.d_wups_b6 = frag;
+      if (p32) op.d_wups_h2 = frag;
+      if (p16) { op.d_wups16 = frag; op.d_wfrag16 = frag; }
+      break;
+    case RC_FIRST:
+      grid(8, 12, 36, 8, 32); a.CK = 8; op.stat_act = &out; op.first_k = true; op.d_wfirst = frag;
+      break;
+    case RC_LAST:
+      grid(8, 12, 36, 32, 4); a.out_cs = 8; a.gn = frag; a.silu = 1; op.gn_op = 0;
+      op.small_n = true; op.d_wsmall = frag;
+      EXPECT(cm::conv_fin_pick(a.Yo, a.Xo, &op.fin_by, &op.fin_bx));
+      op.fin = true; op.d_wfin = op.d_wfin_src = frag;
+      if (p32) op.d_wfin_h2 = frag;
+      if (p16) op.d_wfin16 = frag;
+      break;
+    case RC_1X1: case RC_1X1_STATS: case RC_SKIP_ABSORBED:
+      grid(2, 3, 9, 128, 384); a.ntaps = 1; a.td = 1; a.CK = 128; op.cls = K_CONV1; op.NB = 2;
+      if (rc == RC_1X1_STATS) op.stat_act = &out;
+      else if (p16) op.d_w1x1_16 = frag;
+      op.skip_if_fused = rc == RC_SKIP_ABSORBED;
+      break;
+  }
+  return op;
+}
+
+void test_conv_route() {
+  struct Want { ConvKernel kernel; ConvForm form; };
+  // [class][plan]: inference forward of the F32 (default), F32X, F32R and F16 plans -- the F32X column is the default plan with
+  // every H2 replaced by B6 (include/crowdmod_hip.h), the F32R one with B3 -- and [class][4 / 5]: the training forward of a
+  // 32-bit plan (all three alike: six-term fragments, no h2, no relaxed form) and of the f16 plan (never an f16 operand).
+  const ConvKernel QR = CONV_QR, KS = CONV_KSPLIT, UPS = CONV_UPS, F16D = CONV_F16D, WINO = CONV_WINO, FIRST = CONV_FIRST, FIN = CONV_FIN,
+                   X11 = CONV_1X1_F16, GEN = CONV_GENERIC, NONE = CONV_NONE;
+  const ConvForm FP32 = FORM_FP32, F16 = FORM_F16, B6 = FORM_B6, B3 = FORM_B3, H2 = FORM_H2;
+  const Want want[RC_COUNT][6] = {
+      /* WINO_FULL         */ {{WINO, H2}, {WINO, B6}, {WINO, B3}, {F16D, F16}, {WINO, B6}, {WINO, FP32}},
+      /* WINO_FULL_SKIP    */ {{WINO, H2}, {WINO, B6}, {WINO, B3}, {F16D, F16}, {WINO, B6}, {WINO, FP32}},
+      /* WINO_HALF         */ {{WINO, H2}, {WINO, B6}, {WINO, B3}, {F16D, F16}, {WINO, B6}, {WINO, FP32}},
+      /* WINO_HALF_SKIP    */ {{WINO, H2}, {WINO, B6}, {WINO, B3}, {F16D, F16}, {WINO, B6}, {WINO, FP32}},
+      /* QUARTER           */ {{QR, H2}, {QR, B6}, {QR, B3}, {QR, FP32}, {QR, B6}, {KS, FP32}},
+      /* QUARTER_NO_TRAIN  */ {{QR, H2}, {QR, B6}, {QR, B3}, {QR, FP32}, {KS, FP32}, {KS, FP32}},
+      /* KSPLIT            */ {{KS, FP32}, {KS, FP32}, {KS, FP32}, {KS, FP32}, {KS, FP32}, {KS, FP32}},
+      /* STRIDE2           */ {{GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}},
+      /* UPS_STATS         */ {{UPS, H2}, {UPS, B6}, {UPS, B3}, {UPS, F16}, {UPS, B6}, {UPS, FP32}},
+      /* UPS_NO_STATS      */ {{UPS, B6}, {UPS, B6}, {UPS, B3}, {UPS, F16}, {UPS, B6}, {UPS, FP32}},
+      /* FIRST             */ {{FIRST, FP32}, {FIRST, FP32}, {FIRST, FP32}, {FIRST, FP32}, {FIRST, FP32}, {FIRST, FP32}},
+      /* LAST              */ {{FIN, H2}, {FIN, B6}, {FIN, B3}, {FIN, F16}, {FIN, B6}, {FIN, B6}},
+      /* 1X1               */ {{GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {X11, F16}, {GEN, FP32}, {GEN, FP32}},
+      /* 1X1_STATS         */ {{GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}, {GEN, FP32}},
+      /* SKIP_ABSORBED     */ {{NONE, FP32}, {NONE, FP32}, {NONE, FP32}, {NONE, FP32}, {GEN, FP32}, {GEN, FP32}},
+  };
+  const int plans[4] = {CM_PRECISION_F32, CM_PRECISION_F32X, CM_PRECISION_F32R, CM_PRECISION_F16};
+  int walked = 0;
+  for (int rc = 0; rc < RC_COUNT; ++rc)
+    for (int pi = 0; pi < 4; ++pi)
+      for (int train = 0; train < 2; ++train)
+        for (int stale = 0; stale < 2; ++stale)
+          for (int off = 0; off < 2; ++off)
+            for (int dbg = 0; dbg < 3; ++dbg) {   // plain, dbg_raw, dbg_raw + dbg_h2
+              Op op = route_class_op(rc, plans[pi]);
+              op.h2_off = off; op.dbg_raw = dbg >= 1; op.dbg_h2 = dbg == 2;
+              const bool src_stats = rc != RC_UPS_NO_STATS;
+              const ConvRoute r = conv_route(op, plans[pi], train, stale, src_stats);
+              ++walked;
+              // the table: h2 where the default plan has it and nothing withdraws it, else what F32X runs
+              const bool h2_live = !stale && !off && dbg != 1;
+              const Want w = train ? want[rc][pi == 3 ? 5 : 4] : want[rc][(pi == 0 && !h2_live) ? 1 : pi];
+              EXPECT(r.kernel == w.kernel && r.form == w.form);
+              // the invariants
+              if (r.form == FORM_H2) EXPECT(plans[pi] == CM_PRECISION_F32 && !train && !stale && !off && (!op.dbg_raw || op.dbg_h2) &&
+                                            (op.d_wwino_h2 || op.d_wqr_h2 || op.d_wfin_h2 || (op.d_wups_h2 && src_stats)));
+              if (train) EXPECT(r.form != FORM_F16 && r.form != FORM_B3 && r.kernel != CONV_F16D && r.kernel != CONV_1X1_F16 && r.kernel != CONV_NONE);
+              if (train && r.kernel == CONV_QR) EXPECT(op.train_qr && op.d_wqr_b6);
+              if (op.ks > 1) EXPECT(r.kernel == CONV_QR || r.kernel == CONV_KSPLIT);
+              // the kernel FAMILY depends on the plan and on training / inference only: what plan_slot_consumers and plan_h16 decide
+              // at finalize still holds when h2 goes stale, a bound is withdrawn or a debug hook steers the form
+              EXPECT(r.kernel == conv_route(op, plans[pi], train, false).kernel);
+              // f16 tensors: plan_h16 and the launch-time check ask route_takes_h16; it accepts what ConvArgs::h16 documents, no more
+              for (int mask = 1; mask < 64; ++mask) {
+                const bool takes = r.kernel == CONV_F16D || (r.kernel == CONV_UPS && r.form == FORM_F16 && !(mask & ~(1 | 4))) ||
+                                   (r.kernel == CONV_FIRST && mask == 4) || ((r.kernel == CONV_FIN || r.kernel == CONV_SMALLN) && !(mask & ~(1 | 2)));
+                EXPECT(route_takes_h16(r, mask) == takes);
+              }
+            }
+  // the last conv off its matrix-core kernel: a Dropout3d multiplier (no such layer exists; the launcher refuses it) or a second source
+  {
+    Op op = route_class_op(RC_LAST, CM_PRECISION_F32);
+    op.pm_off = 0;
+    EXPECT(conv_route(op, CM_PRECISION_F32, true, false).kernel == CONV_SMALLN && conv_route(op, CM_PRECISION_F32, false, false).kernel == CONV_FIN);
+    op.ca.C1 = 32;
+    EXPECT(conv_route(op, CM_PRECISION_F32, false, false).kernel == CONV_SMALLN);
+    walked += 3;
+  }
+  // a parity conv the stage-once kernel does not take: f16 fragments only where the generic launcher has an f16 instantiation
+  {
+    Op op = route_class_op(RC_UPS_STATS, CM_PRECISION_F16);
+    op.d_wups16 = nullptr;
+    op.MB = 5; op.NB = 1; op.ca.bz = 4; op.ca.by = 6; op.ca.bx = 6;
+    ConvRoute r = conv_route(op, CM_PRECISION_F16, false, false);
+    EXPECT(r.kernel == CONV_GENERIC && r.form == FORM_F16);
+    op.ca.bx = 5;
+    r = conv_route(op, CM_PRECISION_F16, false, false);
+    EXPECT(r.kernel == CONV_GENERIC && r.form == FORM_FP32);
+    r = conv_route(op, CM_PRECISION_F16, true, false);
+    EXPECT(r.kernel == CONV_UPS && r.form == FORM_FP32);
+    walked += 3;
+  }
+  printf("test_conv_route: %d combinations walked\n", walked);
+}
+
 void test_misc_errors() {
   EXPECT(cm_abi_version() == CM_ABI_VERSION);
   EXPECT(cm_device_count(nullptr) != 0);
@@ -364,6 +522,7 @@ int main() {
   test_tile_planner();
   test_round3_packers();
   test_wino_form_dispatch();
+  test_conv_route();
   test_misc_errors();
   printf("selftest ok: %d checks\n", g_checks);
   return 0;

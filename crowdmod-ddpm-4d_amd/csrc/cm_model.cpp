@@ -89,8 +89,7 @@ struct Op {
   int cls;
   // conv
   cm::ConvArgs ca{};
-  int MB = 1, NB = 1;
-  int tuned_B = -1;
+  int MB = 1, NB = 1;         // tile geometry (ca.bs .. ca.ntx, MB) and tables: resolve_conv, at finalize
   int *d_hvtab = nullptr, *d_mtab = nullptr;  // device copies of the box coordinate tables
   Act *stat_act = nullptr;  // output tensor whose GroupNorm statistics this conv produces in its epilogue
   int pm_off = -1;          // >= 0: conv_2 of a ResnetBlock; offset of its Dropout3d mask row slice (training forward)
@@ -105,7 +104,8 @@ struct Op {
   std::string skip_w, skip_b;
   float *d_s2w = nullptr, *d_bias_fused = nullptr;
   bool skip_if_fused = false;  // this op is the stand-alone skip conv that a later op absorbs
-  bool wino = false;        // Winograd F(2x2,3x3) kernel (cm_conv_wino.hip): full-resolution stride-1 3x3x3 layers
+  bool wino = false;        // Winograd F(2x2,3x3) kernel (cm_conv_wino.hip): full- and half-resolution stride-1 3x3x3 layers.  add_conv
+                            //   sets it from the layer shape; resolve_conv withdraws it when the tile does not fit; final after finalize
   float *d_wwino = nullptr;
   float *d_wwino16 = nullptr;   // the same weights as f16 operands (reduced-precision plan, cm_model_set_precision)
   float *d_wwino_b6 = nullptr;  // fp32 plan, inference forward, two-tile layers: exact bf16 x 3 split of d_wwino (pack_wino_b6)
@@ -138,10 +138,11 @@ struct Op {
   bool train_qr = false;        // the training forward may take conv_qr2 as well (set by train_setup once the geometry is checked)
   long long wqr_floats = 0;
   bool qr_consumer = false; // OP_GNFIN whose only consumer is a qr conv: that kernel finalises the statistics itself
-  bool from_slots = false;  // OP_GNFIN (inference plan): its only consumer is a six-term Winograd conv that finalises the statistics from the
-                            //   producers' slot partials itself when they are few (run_conv decides per launch; set by plan_slot_consumers)
+  bool from_slots = false;  // OP_GNFIN (inference plan): its only consumer's inference route is the Winograd kernel on split or f16 fragments,
+                            //   which finalises the statistics from the producers' slot partials itself when they are few (plan_slot_consumers
+                            //   asks conv_route; run_ops / run_conv decide per launch)
   bool fin_skipped[4] = {false, false, false, false};   // per batch lane: this step's launch of the op was skipped on that promise
-  bool first_k = false;     // the UNet's first conv on its dedicated kernel (cm_conv_io.hip)
+  bool first_k = false;     // the UNet's first conv on its dedicated kernel (cm_conv_io.hip); resolve_conv withdraws it when no tile fits
   int first_cin = 4;        //   input channels it contracts per tap: 4 (C <= 4) or 8
   float *d_wfirst = nullptr;
   bool small_n = false;     // <= 8 output channels: vector-ALU kernel (cm_conv_small.hip)
@@ -156,7 +157,7 @@ struct Op {
   std::string label;
   double prof_ms = 0;
   int64_t prof_n = 0;
-  int prof_B = 0;           // batch of the last launch (profile report)
+  mutable int prof_B = 0;   // batch of the last launch (profile report): the one field a launch writes
   // stats
   const Act *act = nullptr;
   // gn finalize
@@ -775,7 +776,6 @@ void pick_tile(Op &op, int B) {
         (!op.small_n || !(t->MB & (t->MB - 1)))) {
       op.MB = t->MB;
       a.ntz = (a.Zo / osdt + a.bz - 1) / a.bz; a.nty = (a.Yo / osdt + a.by - 1) / a.by; a.ntx = (a.Xo / osdt + a.bx - 1) / a.bx;
-      op.tuned_B = B;
       return;
     }
   }
@@ -813,7 +813,6 @@ void pick_tile(Op &op, int B) {
   a.bs = bbs; a.bz = bbz; a.by = bby; a.bx = bbx;
   op.MB = bMB;
   a.ntz = (Zo + bbz - 1) / bbz; a.nty = (Yo + bby - 1) / bby; a.ntx = (Xo + bbx - 1) / bbx;
-  op.tuned_B = B;
 }
 
 struct ConvSpec {
@@ -1463,33 +1462,151 @@ int build_ops(cm_model *m) {
   return 0;
 }
 
-// Time-embedding tables for all 1000 rows (embeddings.py:24-30 + layers.py:35,62).
+// Finish the plan of one conv (cm_model_finalize, after build_ops): the tile geometry of the kernel family add_conv prepared, with
+// the fall-backs a grid may force.  Feasibility is known only with the geometry: a grid the Winograd tiles do not fit, or a first
+// conv with more columns than the full-X tile holds, goes to the direct kernel (its fragments `wfrag` are packed for every conv;
+// NB was fixed before packing), which gets its tile from pick_tile and its coordinate tables on the device.  Nothing here depends
+// on a launch: the tile is chosen for TUNE_BATCH, the Winograd and first-conv pickers see only the grid.
+int resolve_conv(cm_model *m, Op &op) {
+  if (op.wino) {
+    cm::ConvArgs a = op.ca;
+    a.bs = 1;
+    op.wino = cm::conv_wino_pick(a.Zo, a.Yo, a.Xo, &a.bz, &a.by, &a.bx);
+    if (op.wino) {
+      a.ntz = a.Zo / a.bz; a.nty = (a.Yo + a.by - 1) / a.by; a.ntx = (a.Xo + a.bx - 1) / a.bx;
+      op.wino = cm::conv_wino_ok(a);
+    }
+    if (op.wino) {
+      op.ca = a;
+      op.MB = 4;                     // statistics slots per tile: the four (a, b) output sub-blocks
+      return 0;
+    }
+  }
+  if (op.first_k) {
+    const cm::ConvArgs keep = op.ca;
+    pick_tile_first(op);
+    if (cm::conv_first_ok(op.ca, op.first_cin)) return 0;
+    op.ca = keep;
+    op.first_k = false;
+  }
+  pick_tile(op, TUNE_BATCH);
+  std::vector<int> hv((size_t)cm::conv_halo_voxels(op.ca)), mt((size_t)32 * op.MB);
+  if (hv.size() > 16384) return fail("halo box too large");
+  cm::conv_build_tables(op.ca, op.MB, hv.data(), mt.data());
+  if (dev_alloc(m, (void **)&op.d_hvtab, 16384 * sizeof(int))) return 1;
+  if (dev_alloc(m, (void **)&op.d_mtab, 256 * sizeof(int))) return 1;
+  CM_HIP(hipMemcpyAsync(op.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+  CM_HIP(hipMemcpyAsync(op.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+  CM_HIP(hipStreamSynchronize(m->stream));
+  op.ca.hvtab = op.d_hvtab;
+  op.ca.mtab = op.d_mtab;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------
+// which kernel a conv runs on, and on which operands
+// ------------------------------------------------------------------------------
+// add_conv decides what CAN run (the fragment sets it packs), resolve_conv fixes the geometry, conv_route decides what DOES run in
+// a given context; the launchers then pick their own template instantiation.  Everything that needs to know the kernel or the
+// operand form of a conv -- the launch, the FLOP accounting, the f16-tensor plan, the slot-consumer plan, the debug hooks -- asks here.
+enum ConvKernel { CONV_NONE, CONV_QR, CONV_KSPLIT, CONV_UPS, CONV_F16D, CONV_WINO, CONV_FIRST, CONV_FIN, CONV_SMALLN, CONV_1X1_F16, CONV_GENERIC };
+const char *const kConvKernelName[] = {"none", "qr", "ksplit", "ups", "f16d", "wino", "first", "fin", "smalln", "1x1_f16", "generic"};
+// (= ConvArgs::f16 where a kernel takes it)  fp32 matrix instructions; f16 operands; six bf16 cross terms of exact three-way splits;
+// their three leading terms (relaxed plan); three f16 cross terms of two-way splits ("h2", bounded operands)
+enum ConvForm { FORM_FP32 = 0, FORM_F16 = 1, FORM_B6 = 2, FORM_B3 = 3, FORM_H2 = 4 };
+struct ConvRoute { ConvKernel kernel; ConvForm form; };
+
+// Bit mask of the op's tensors that are stored as _Float16 (ConvArgs::h16; plan_h16): half the bytes per element.  The training
+// forward never sees them (training refuses f16 handles); with the skip conv fused in, its sources take the residual's place.
+int h16_mask(const Op &op, bool train_fwd) {
+  auto is16 = [&](const Act *t) { return t && t->h16 && !train_fwd; };
+  const int io = (is16(op.in0) ? 1 : 0) | (is16(op.in1) ? 2 : 0) | (is16(op.out_act) ? 4 : 0);
+  if (op.d_s2w && !train_fwd) return io | (is16(op.skip0) ? 16 : 0) | (is16(op.skip1) ? 32 : 0);
+  return io | (is16(op.resid_act) ? 8 : 0);
+}
+
+// Pure function of the resolved op and the context: no device pointer is dereferenced (fragment pointers count as present /
+// absent), no stream, no model.  `ups_src_stats` is the one input that is launch state: the upsample conv takes h2 only when its
+// source tensor carries slot statistics NOW (written by the producer's launch); callers without a launch assume it does.
+ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale, bool ups_src_stats = true) {
+  static const bool no_train_qr = cm::diag_env("CM_NO_TRAIN_QR") != nullptr, no_train_b6 = cm::diag_env("CM_NO_TRAIN_B6") != nullptr;
+  const bool infer = !train_fwd;
+  // the six-term fragments serve the training forward as well (exact splits, fp32 accumulate; they follow every optimizer step);
+  // relaxed fp32 plan: only their three leading cross terms, in the inference forward
+  const bool six_ok = infer || !no_train_b6;
+  const ConvForm six = (precision == CM_PRECISION_F32R && infer) ? FORM_B3 : FORM_B6;
+  // default plan, layers with bounded input, inference-only fragments (Op::d_wfin_h2); raw debug operands are unbounded unless the caller says otherwise
+  const bool h2 = precision == CM_PRECISION_F32 && infer && !h2_stale && !op.h2_off && (!op.dbg_raw || op.dbg_h2);
+  auto form = [&](const float *w16, const float *w6, const float *wh2) {   // f16 fragments exist under the reduced-precision plan only
+    return (w16 && infer) ? FORM_F16 : !w6 ? FORM_FP32 : (h2 && wh2) ? FORM_H2 : six;
+  };
+  const cm::ConvArgs &g = op.ca;
+  if (op.skip_if_fused && infer) return {CONV_NONE, FORM_FP32};      // absorbed by the block's conv_2 (inference plan)
+  // (training forward: the same whole-sample kernel in its six-term form -- it finalises the GroupNorm of its input from the
+  //  producers' partials like the inference plan does; the gn_finalize op still runs there for the backward's mean / rstd rows)
+  if (op.qr && (infer || (op.d_wqr_b6 && op.train_qr && !no_train_qr))) {
+    cm::QrArgs q{};                  // the launcher's own predicate for its split forms (8 groups, channel bound, LDS fit)
+    q.C0 = g.C0; q.C1 = g.C1; q.Co = g.Co; q.Y = g.Yo; q.X = g.Xo; q.groups = GN_GROUPS; q.raw = 1; q.wq6 = op.d_wqr_b6;
+    return {CONV_QR, form(nullptr, cm::conv_qr2_b6_ok(q) ? op.d_wqr_b6 : nullptr, op.d_wqr_h2)};
+  }
+  if (op.ks > 1) return {CONV_KSPLIT, FORM_FP32};
+  if (op.ups && (op.d_wups16 || !(op.d_wfrag16 && infer)))
+    return {CONV_UPS, form(op.d_wups16, six_ok ? op.d_wups_b6 : nullptr, ups_src_stats ? op.d_wups_h2 : nullptr)};
+  if (op.wino && op.f16d && infer) return {CONV_F16D, FORM_F16};
+  if (op.wino)
+    return {CONV_WINO, form(op.d_wwino16, (op.d_wwino_b6 && six_ok && cm::conv_wino_b6_ok(g.bz, g.by, g.bx, g.Co, g.Zo)) ? op.d_wwino_b6 : nullptr, op.d_wwino_h2)};
+  if (op.first_k) return {CONV_FIRST, FORM_FP32};
+  // The remaining launchers' predicates also read what run_conv fills in per launch, as null / non-null only; each is a fact of the
+  // op and the context: statistics <=> stat_act, Dropout3d multipliers <=> training forward of a conv_2, fused skip conv <=> inference.
+  static float set;
+  cm::ConvArgs a = g;
+  a.stat_part = op.stat_act ? &set : nullptr;
+  a.pm = (train_fwd && op.pm_off >= 0) ? &set : nullptr;
+  a.s2w = infer ? op.d_s2w : nullptr;
+  a.h16 = h16_mask(op, train_fwd);
+  if (op.small_n) {
+    a.by = op.fin_by; a.bx = op.fin_bx;
+    if (op.fin && cm::conv_fin_ok(a)) return {CONV_FIN, form(op.d_wfin16, op.d_wfin, op.d_wfin_h2)};
+    return {CONV_SMALLN, FORM_FP32};
+  }
+  if (op.d_w1x1_16 && infer && cm::conv1x1_f16_ok(a, op.NB)) return {CONV_1X1_F16, FORM_F16};
+  return {CONV_GENERIC, form(cm::conv_par_f16_variant(op.MB, op.NB, g.bz, g.by, g.bx) ? op.d_wfrag16 : nullptr, nullptr, nullptr)};
+}
+
+// Which routes read / write tensors stored as _Float16, by the launch's tensor mask (h16_mask): the direct f16 conv (source, residual,
+// fused skip source, output), the f16 stage-once upsample conv (source, output), the first conv (output), the last conv (sources).
+// plan_h16 flags a tensor only when every kernel around it passes; run_conv refuses a launch that does not.
+bool route_takes_h16(ConvRoute r, int mask) {
+  switch (r.kernel) {
+    case CONV_F16D: return true;
+    case CONV_UPS: return r.form == FORM_F16 && !(mask & ~5);
+    case CONV_FIRST: return !(mask & ~4);
+    case CONV_FIN: case CONV_SMALLN: return !(mask & ~3);
+    default: return false;
+  }
+}
+
 // f16 ACTIVATIONS (round 4; reduced-precision plan = BASELINE configs[4]; the reference's autocast stores every conv output as
 // fp16, ddpm.py:116-120): a tensor is stored as _Float16 when the kernel that produces it can write f16 and every kernel that reads
-// it can read f16 -- the direct f16 conv (source, residual, fused skip source, output), the first conv (output), the f16 stage-once
-// upsample conv (source, output) and the last conv (source).  That covers the full- and half-resolution tensors of a grid with >= 4
+// it can read f16 (route_takes_h16).  That covers the full- and half-resolution tensors of a grid with >= 4
 // planes at half resolution except the inputs of the two stride-2 convs; quarter-resolution tensors (2 % of the bytes) stay fp32.
 // GroupNorm statistics come from the fp32 accumulators of the producer; a kernel that cannot honour a flagged tensor fails loudly
 // (run_conv) instead of misreading it.  CM_NO_H16 under CM_DIAG=1 keeps fp32 storage (A/B runs).
 int plan_h16(cm_model *m) {
   if (m->precision != CM_PRECISION_F16 || cm::diag_env("CM_NO_H16")) return 0;
-  auto writes16 = [](const Op &o) { return o.kind == OP_CONV && o.ks <= 1 && ((o.wino && o.f16d) || o.first_k || (o.ups && o.d_wups16)); };
+  auto takes = [&](const Op &o, int role) { return route_takes_h16(conv_route(o, m->precision, false, false), role); };
   for (auto &ap : m->acts) {
     Act *a = ap.get();
     bool ok = false;
     for (const Op &o : m->ops)
-      if (o.kind == OP_CONV && o.out_act == a && !o.skip_if_fused) ok = writes16(o);
-    if (!ok) continue;
+      if (o.kind == OP_CONV && o.out_act == a && !o.skip_if_fused) ok = takes(o, 4);
     for (const Op &o : m->ops) {
       if (!ok) break;
       if (o.kind == OP_ATTNBLK && o.ab_x == a) ok = false;
       if (o.kind == OP_ATTN && (o.qkv == a->d || o.aout == a->d)) ok = false;
-      if (o.kind != OP_CONV) continue;
-      const bool f16d = o.wino && o.f16d && o.ks <= 1;
-      if (o.skip_if_fused) continue;                            // the stand-alone skip conv: absorbed by the block's conv_2 at inference
-      if (o.in0 == a || o.in1 == a) ok = ok && (f16d || (o.in0 == a && !o.in1 && o.ups && o.d_wups16 && o.ks <= 1) || (o.small_n && o.ks <= 1));
-      if (o.resid_act == a) ok = ok && f16d;
-      if (o.skip0 == a || o.skip1 == a) ok = ok && f16d && o.d_w16d_skip;
+      if (o.kind != OP_CONV || o.skip_if_fused) continue;       // (the stand-alone skip conv: absorbed by the block's conv_2 at inference)
+      const int role = (o.in0 == a ? 1 : 0) | (o.in1 == a ? 2 : 0) | (o.resid_act == a ? 8 : 0) | (o.skip0 == a ? 16 : 0) | (o.skip1 == a ? 32 : 0);
+      if (role) ok = takes(o, role);
     }
     a->h16 = ok;
   }
@@ -1509,12 +1626,13 @@ int plan_slot_consumers(cm_model *m) {
     for (int j = 0; j < nops; ++j)
       if (m->ops[j].kind == OP_CONV && m->ops[j].gn_op == i) { ++ncons; cons = j; }
     if (ncons != 1) continue;
-    const Op &c = m->ops[cons];
-    g.from_slots = c.wino && !c.qr && c.ks <= 1 && !c.f16d && !c.skip_if_fused && (c.d_wwino_b6 || c.d_wwino16);
+    const ConvRoute r = conv_route(m->ops[cons], m->precision, false, false);
+    g.from_slots = r.kernel == CONV_WINO && r.form != FORM_FP32;
   }
   return 0;
 }
 
+// Time-embedding tables for all 1000 rows (embeddings.py:24-30 + layers.py:35,62).
 int build_time_table(cm_model *m) {
   const cm_unet_config &c = m->cfg;
   const int te = c.base_channels, tx = c.base_channels * c.time_multiple;
@@ -1556,8 +1674,19 @@ static thread_local const Op *tl_fin_next = nullptr;   // GroupNorm finalisation
 static thread_local int tl_fin_b0 = 0;
 static thread_local bool tl_fin_done = false;
 
+// the stand-alone GroupNorm finalisation `g` (an OP_GNFIN) for the `B` samples from `b0`; `mr`: its mean / rstd rows (training), or null
+int run_gnfin(const Op &g, float *mr, int B, hipStream_t st, int b0) {
+  const Act *g0 = g.g0, *g1 = g.g1;
+  const int Ct = g0->C + (g1 ? g1->C : 0);
+  CM_HIP(cm::launch_gn_finalize(g0->part + (size_t)b0 * g0->nslots * g0->C * 2, g0->cnt + (size_t)b0 * g0->nslots, g0->nslots, g0->C,
+                                g1 ? g1->part + (size_t)b0 * g1->nslots * g1->C * 2 : nullptr, g1 ? g1->cnt + (size_t)b0 * g1->nslots : nullptr,
+                                g1 ? g1->nslots : 0, g1 ? g1->C : 0, g0->V(), g.gamma, g.beta, GN_GROUPS, GN_EPS,
+                                g.gn_out + (size_t)b0 * 2 * Ct, mr ? mr + (size_t)b0 * 2 * Ct : nullptr, B, st));
+  return 0;
+}
+
 // the whole-sample kernel of the lowest resolution (inference plan): the GroupNorm statistics of its sources come raw
-int run_conv_qr(cm_model *m, Op &op, int B, hipStream_t st, int b0) {
+int run_conv_qr(cm_model *m, const Op &op, ConvForm form, int B, hipStream_t st, int b0) {
   const Op &gop = m->ops[op.gn_op];
   const Act *g0 = gop.g0, *g1 = gop.g1;
   const cm::ConvArgs &ca = op.ca;
@@ -1572,11 +1701,9 @@ int run_conv_qr(cm_model *m, Op &op, int B, hipStream_t st, int b0) {
   if (op.dbg_raw) { q.gamma = q.beta = nullptr; q.raw = 1; q.silu = 0; }
   q.wq = op.d_wqr; q.bias = ca.bias;
   q.wq6 = op.d_wqr_b6;
-  q.three = (m->precision == CM_PRECISION_F32R && !m->train_fwd) ? 1 : 0;
+  q.three = form == FORM_B3 ? 1 : 0;
   // default plan, inference-only handle: the f16 two-way-split form (bounded input: GroupNorm + SiLU inside the kernel)
-  if (m->precision == CM_PRECISION_F32 && !m->train_fwd && !m->h2_stale && !op.h2_off && op.d_wqr_h2 && (!op.dbg_raw || op.dbg_h2)) {
-    q.wq6 = op.d_wqr_h2; q.three = 2; q.h2_oscale = op.h2_oscale;
-  }
+  if (form == FORM_H2) { q.wq6 = op.d_wqr_h2; q.three = 2; q.h2_oscale = op.h2_oscale; }
   q.temb = ca.temb; q.temb_stride = ca.temb_stride; q.tidx = ca.tidx + b0;
   q.resid = ca.resid ? ca.resid + (size_t)b0 * V * ca.res_cs : nullptr; q.res_cs = ca.res_cs;
   if (m->train_fwd) {
@@ -1603,229 +1730,147 @@ int run_conv_qr(cm_model *m, Op &op, int B, hipStream_t st, int b0) {
   return 0;
 }
 
-int run_conv(cm_model *m, Op &op, int B, hipStream_t st, int b0, int slab) {
-  if (op.skip_if_fused && !m->train_fwd) return 0;  // absorbed by the block's conv_2 (inference plan)
-  // (training forward: the same whole-sample kernel in its six-term form -- it finalises the GroupNorm of its input from the
-  //  producers' partials like the inference plan does; the gn_finalize op still runs there for the backward's mean / rstd rows)
-  static const bool no_train_qr = cm::diag_env("CM_NO_TRAIN_QR") != nullptr;
-  if (op.qr && (!m->train_fwd || (op.d_wqr_b6 && op.train_qr && !no_train_qr))) return run_conv_qr(m, op, B, st, b0);
-  if (op.tuned_B < 0 && op.wino) {
-    // feasibility is known only with the launch geometry: a grid the Winograd tiles do not fit falls back to the
-    // direct kernel (its fragments `wfrag` are packed for every conv; NB = 1 was fixed before packing)
-    cm::ConvArgs a = op.ca;
-    a.bs = 1;
-    bool ok = cm::conv_wino_pick(a.Zo, a.Yo, a.Xo, &a.bz, &a.by, &a.bx);
-    if (ok) {
-      a.ntz = a.Zo / a.bz; a.nty = (a.Yo + a.by - 1) / a.by; a.ntx = (a.Xo + a.bx - 1) / a.bx;
-      ok = cm::conv_wino_ok(a);
-    }
-    if (ok) {
-      op.ca = a;
-      op.MB = 4;                     // statistics slots per tile: the four (a, b) output sub-blocks
-      op.tuned_B = B;
-    } else {
-      op.wino = false;
-    }
-  }
-  if (op.tuned_B < 0 && op.first_k) {
-    const cm::ConvArgs keep = op.ca;
-    pick_tile_first(op);
-    if (cm::conv_first_ok(op.ca, op.first_cin)) {
-      op.tuned_B = B;
-    } else {
-      op.ca = keep;                  // e.g. more columns than the full-X tile holds: the direct kernel takes it
-      op.first_k = false;
-    }
-  }
-  if (op.tuned_B < 0) {
-    pick_tile(op, TUNE_BATCH);
-    op.tuned_B = B;
-    std::vector<int> hv((size_t)cm::conv_halo_voxels(op.ca)), mt((size_t)32 * op.MB);
-    cm::conv_build_tables(op.ca, op.MB, hv.data(), mt.data());
-    if (!op.d_hvtab) {
-      if (dev_alloc(m, (void **)&op.d_hvtab, 16384 * sizeof(int))) return 1;
-      if (dev_alloc(m, (void **)&op.d_mtab, 256 * sizeof(int))) return 1;
-    }
-    if (hv.size() > 16384) return fail("halo box too large");
-    CM_HIP(hipMemcpyAsync(op.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    CM_HIP(hipMemcpyAsync(op.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    CM_HIP(hipStreamSynchronize(st));
-    op.ca.hvtab = op.d_hvtab;
-    op.ca.mtab = op.d_mtab;
-  }
+int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab) {
+  const ConvRoute route = conv_route(op, m->precision, m->train_fwd, m->h2_stale, op.in0 && op.in0->part && op.in0->nslots > 0);
+  if (route.kernel == CONV_NONE) return 0;
+  if (route.kernel == CONV_QR) return run_conv_qr(m, op, route.form, B, st, b0);
   cm::ConvArgs ca = op.ca;
   ca.B = B;
   op.prof_B = B;
   ca.nts = (B + ca.bs - 1) / ca.bs;
   const size_t Vs = (size_t)ca.Zs * ca.Ys * ca.Xs, Vo = (size_t)ca.Zo * ca.Yo * ca.Xo;
   // f16 tensors of the reduced-precision plan (plan_h16): half the bytes per element, so half the float offset; the mask tells the
-  // kernel which of its tensors they are (the training forward never sees them: training refuses f16 handles)
-  auto is16 = [&](const Act *t) { return t && t->h16 && !m->train_fwd; };
-  auto adv = [&](const float *p, size_t elems, bool h) { return p + (h ? elems / 2 : elems); };
-  ca.h16 = (is16(op.in0) ? 1 : 0) | (is16(op.in1) ? 2 : 0) | (is16(op.out_act) ? 4 : 0) | (is16(op.resid_act) ? 8 : 0);
-  ca.src0 = adv(ca.src0, (size_t)b0 * Vs * ca.C0, is16(op.in0));
-  if (ca.src1) ca.src1 = adv(ca.src1, (size_t)b0 * Vs * ca.C1, is16(op.in1));
+  // kernel which of its tensors they are
+  ca.h16 = h16_mask(op, m->train_fwd);
+  auto adv = [&](const float *p, size_t elems, int bit) { return p + ((ca.h16 & bit) ? elems / 2 : elems); };
+  ca.src0 = adv(ca.src0, (size_t)b0 * Vs * ca.C0, 1);
+  if (ca.src1) ca.src1 = adv(ca.src1, (size_t)b0 * Vs * ca.C1, 2);
   if (ca.gn) ca.gn += (size_t)b0 * 2 * (ca.C0 + ca.C1);
   ca.tidx += b0;
-  if (m->train_fwd && op.pm_off >= 0) {
-    ca.pm = m->dropmask + (size_t)b0 * m->nproj + op.pm_off;
-    ca.pm_stride = m->nproj;
-  }
-  if (m->use_train_temb && op.temb_off >= 0) {
-    ca.temb = m->train_temb + op.temb_off;
-    ca.tidx = m->train_iota + b0;
-  }
-  if (ca.resid) ca.resid = adv(ca.resid, (size_t)b0 * Vo * ca.res_cs, is16(op.resid_act));
+  if (m->train_fwd && op.pm_off >= 0) { ca.pm = m->dropmask + (size_t)b0 * m->nproj + op.pm_off; ca.pm_stride = m->nproj; }
+  if (m->use_train_temb && op.temb_off >= 0) { ca.temb = m->train_temb + op.temb_off; ca.tidx = m->train_iota + b0; }
+  if (ca.resid) ca.resid = adv(ca.resid, (size_t)b0 * Vo * ca.res_cs, 8);
   if (op.d_s2w && !m->train_fwd) {
     if (!op.wino && 32 * op.MB > cm::conv_halo_voxels(ca)) return fail("fused skip conv: tile rows exceed the staged box");
     ca.s2w = op.d_s2w;
-    ca.s2src0 = adv(op.skip0->d, (size_t)b0 * Vo * op.skip0->C, is16(op.skip0)); ca.s2C0 = op.skip0->C;
-    ca.s2src1 = op.skip1 ? adv(op.skip1->d, (size_t)b0 * Vo * op.skip1->C, is16(op.skip1)) : nullptr; ca.s2C1 = op.skip1 ? op.skip1->C : 0;
-    ca.h16 = (ca.h16 & ~8) | (is16(op.skip0) ? 16 : 0) | (is16(op.skip1) ? 32 : 0);
+    ca.s2src0 = adv(op.skip0->d, (size_t)b0 * Vo * op.skip0->C, 16); ca.s2C0 = op.skip0->C;
+    ca.s2src1 = op.skip1 ? adv(op.skip1->d, (size_t)b0 * Vo * op.skip1->C, 32) : nullptr; ca.s2C1 = op.skip1 ? op.skip1->C : 0;
     ca.resid = nullptr;
     ca.bias = op.d_bias_fused;
   }
-  ca.out = const_cast<float *>(adv(ca.out, (size_t)b0 * Vo * ca.out_cs, is16(op.out_act)));
-  int ns = 0;
-  if (op.stat_act) {
-    ns = ca.ntz * ca.nty * ca.ntx * op.MB * (ca.par ? 8 : 1);
+  ca.out = const_cast<float *>(adv(ca.out, (size_t)b0 * Vo * ca.out_cs, 4));
+  // only some kernels read / write f16 tensors; anything else here would misread them silently
+  if (ca.h16 && !route_takes_h16(route, ca.h16))
+    return fail("conv %s: f16 tensors (mask %d) reach a kernel without f16 tensor support", op.label.c_str(), ca.h16);
+  // Statistics slots of the output tensor.  Its slot count is written ONCE per launch, in the arm of the kernel that runs, with
+  // that kernel's count: the batch lanes enqueue from two host threads, and the other lane's gn_finalize reads it -- a generic
+  // count first and the upsample / f16 kernel's own count afterwards left a window in which that reader saw the wrong number of
+  // slots (a rare wrong statistic: the one-off failure of the two-lane bit-identity test in round 4).  All lanes write the same value.
+  auto stat_slots = [&](int ns) -> int {
+    if (!op.stat_act) return 0;
     if (ns > MAX_SLOTS) return fail("statistics slots %d exceed %d", ns, MAX_SLOTS);
     ca.stat_C = op.stat_act->C;
     ca.stat_ns = ns;
     ca.stat_part = op.stat_act->part + (size_t)b0 * ns * ca.stat_C * 2;
     ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns;
-  }
-  // ---- which kernel will run ----------------------------------------------------------------------------------------------
-  static const bool no_train_b6 = cm::diag_env("CM_NO_TRAIN_B6") != nullptr;
-  // relaxed fp32 plan (cm_model_set_precision): the six-term kernels issue only their three leading cross terms (inference forward)
-  const bool relaxed = m->precision == CM_PRECISION_F32R && !m->train_fwd;
-  // default plan: the f16 two-way-split form on layers with bounded input (inference-only handles, see Op::d_wfin_h2)
-  const bool h2_live = m->precision == CM_PRECISION_F32 && !m->train_fwd && !m->h2_stale && !op.h2_off;
-  const bool take_ups = op.ks <= 1 && op.ups && (op.d_wups16 || !(op.d_wfrag16 && !m->train_fwd));
-  const bool take_f16d = op.ks <= 1 && !take_ups && op.wino && op.f16d && !m->train_fwd;
-  const bool take_wino = op.ks <= 1 && !take_ups && !take_f16d && op.wino;
-  // The slot count of the output tensor is written ONCE per launch with the count of the kernel that runs: the batch lanes
-  // enqueue from two host threads, and the other lane's gn_finalize reads it -- a generic count first and the upsample /
-  // f16 kernel's own count afterwards left a window in which that reader saw the wrong number of slots (a rare wrong
-  // statistic: the one-off failure of the two-lane bit-identity test in round 4).  All lanes write the same value.
-  if (op.stat_act && op.ks <= 1 && !take_ups && !take_f16d) op.stat_act->nslots = ns;
-  const bool wino_f16 = take_wino && op.d_wwino16 && !m->train_fwd;     // reduced-precision plan: f16 operands in the inference forward
-  // two-tile layers / the full-resolution tile, fp32 plan: six-term bf16 products (the training forward as well: exact splits, fp32
-  // accumulate; its fragments follow every optimizer step)
-  const bool wino_b6 = take_wino && !wino_f16 && op.d_wwino_b6 && !(m->train_fwd && (no_train_b6 || m->precision == CM_PRECISION_F16)) &&
-                       cm::conv_wino_b6_ok(ca.bz, ca.by, ca.bx, ca.Co, ca.Zo);
-  if (ca.h16) {
-    // only these kernels read / write f16 tensors; anything else here would misread them silently
-    const bool ok16 = take_f16d || (take_ups && op.d_wups16 && !(ca.h16 & ~5)) || (op.first_k && !(ca.h16 & ~4) && op.ks <= 1 && !take_ups && !op.wino) ||
-                      (op.small_n && !(ca.h16 & ~3) && op.ks <= 1 && !take_ups && !op.wino && !op.first_k);
-    if (!ok16) return fail("conv %s: f16 tensors (mask %d) reach a kernel without f16 tensor support", op.label.c_str(), ca.h16);
-  }
-  if (take_wino) {
-    ca.wfrag = wino_f16 ? op.d_wwino16 : op.d_wwino;
-    if (wino_b6) { ca.wfrag = op.d_wwino_b6; ca.f16 = relaxed ? 3 : 2; }
-    if (wino_b6 && h2_live && op.d_wwino_h2 && (!op.dbg_raw || op.dbg_h2)) { ca.wfrag = op.d_wwino_h2; ca.f16 = 4; ca.h2_oscale = op.h2_oscale; }
-  }
-  // The GroupNorm of the input from the producers' slot partials when run_ops skipped the gn_finalize launch on that promise (few
-  // slots).  Only conv_wino_p_kernel finalises them itself; conv_wino_p_taken is the launcher's own test for that kernel.
-  if (!m->train_fwd && op.gn_op >= 0 && m->ops[op.gn_op].fin_skipped[slab & 3] && ca.gn) {
-    const Op &g = m->ops[op.gn_op];
-    const Act *g0 = g.g0, *g1 = g.g1;
-    if (take_wino && cm::conv_wino_p_taken(ca, wino_f16, true)) {
-      ca.gp0 = g0->part + (size_t)b0 * g0->nslots * g0->C * 2; ca.gc0 = g0->cnt + (size_t)b0 * g0->nslots; ca.gns0 = g0->nslots;
-      if (g1) { ca.gp1 = g1->part + (size_t)b0 * g1->nslots * g1->C * 2; ca.gc1 = g1->cnt + (size_t)b0 * g1->nslots; ca.gns1 = g1->nslots; }
-      ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS;
-      ca.gn = nullptr;
-    } else {
-      // (a kernel that cannot: the launch that was skipped, now)
-      const int Ct = g0->C + (g1 ? g1->C : 0);
-      CM_HIP(cm::launch_gn_finalize(g0->part + (size_t)b0 * g0->nslots * g0->C * 2, g0->cnt + (size_t)b0 * g0->nslots, g0->nslots, g0->C,
-                                    g1 ? g1->part + (size_t)b0 * g1->nslots * g1->C * 2 : nullptr, g1 ? g1->cnt + (size_t)b0 * g1->nslots : nullptr,
-                                    g1 ? g1->nslots : 0, g1 ? g1->C : 0, g0->V(), g.gamma, g.beta, GN_GROUPS, GN_EPS,
-                                    g.gn_out + (size_t)b0 * 2 * Ct, nullptr, B, st));
+    return 0;
+  };
+  const int ns_tile = ca.ntz * ca.nty * ca.ntx * op.MB * (ca.par ? 8 : 1);   // of the resolved tile (every kernel but the upsample / direct f16 / K-split ones)
+  if (stat_slots(ns_tile)) return 1;
+  switch (route.kernel) {
+    case CONV_NONE: case CONV_QR: break;   // (taken above)
+    case CONV_KSPLIT: {
+      cm::ConvArgs ka = ca;
+      const int V = op.out_act->V();
+      float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
+      ka.temb = nullptr; ka.resid = nullptr; ka.stat_part = nullptr; ka.bias = op.d_zero_bias;
+      ka.out = scratch; ka.out_cs = ka.Co;
+      ka.ks = op.ks; ka.kpart = (long long)B * V * ka.Co;
+      CM_HIP(cm::launch_conv(ka, op.MB, op.NB, st));
+      cm::CombineArgs cb{};
+      cb.part = scratch; cb.S = op.ks; cb.stride = ka.kpart;
+      cb.bias = ca.bias; cb.temb = ca.temb; cb.temb_stride = ca.temb_stride; cb.tidx = ca.tidx;
+      cb.resid = ca.resid; cb.res_cs = ca.res_cs;
+      cb.out = ca.out; cb.C = ka.Co; cb.V = V; cb.B = B;
+      cb.nslots = (V + 31) / 32;
+      cb.stat_part = op.stat_act->part + (size_t)b0 * cb.nslots * cb.C * 2;
+      cb.stat_cnt = op.stat_act->cnt + (size_t)b0 * cb.nslots;
+      op.stat_act->nslots = cb.nslots;
+      return run_combine(m, cb, st);
     }
-  }
-  if (op.ks > 1) {
-    cm::ConvArgs ka = ca;
-    const int V = op.out_act->V();
-    float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
-    ka.temb = nullptr; ka.resid = nullptr; ka.stat_part = nullptr; ka.bias = op.d_zero_bias;
-    ka.out = scratch; ka.out_cs = ka.Co;
-    ka.ks = op.ks; ka.kpart = (long long)B * V * ka.Co;
-    CM_HIP(cm::launch_conv(ka, op.MB, op.NB, st));
-    cm::CombineArgs cb{};
-    cb.part = scratch; cb.S = op.ks; cb.stride = ka.kpart;
-    cb.bias = ca.bias; cb.temb = ca.temb; cb.temb_stride = ca.temb_stride; cb.tidx = ca.tidx;
-    cb.resid = ca.resid; cb.res_cs = ca.res_cs;
-    cb.out = ca.out; cb.C = ka.Co; cb.V = V; cb.B = B;
-    cb.nslots = (V + 31) / 32;
-    cb.stat_part = op.stat_act->part + (size_t)b0 * cb.nslots * cb.C * 2;
-    cb.stat_cnt = op.stat_act->cnt + (size_t)b0 * cb.nslots;
-    op.stat_act->nslots = cb.nslots;
-    if (run_combine(m, cb, st)) return 1;
-  } else if (take_ups) {
-    // upsample conv: stage-once parity kernel with its own source tile / statistics slots (f16 operands under the
-    // reduced-precision plan's inference forward)
-    if (op.d_wups16 && !m->train_fwd) { ca.wfrag = op.d_wups16; ca.wpar_stride = op.wups16_stride; ca.f16 = 1; }
-    else if (op.d_wups_b6 && !(m->train_fwd && cm::diag_env("CM_NO_TRAIN_B6"))) { ca.wfrag = op.d_wups_b6; ca.wpar_stride = op.wups_b6_stride; ca.f16 = relaxed ? 3 : 2; }   // six-term bf16 products (training forward too); relaxed plan: three
-    if (ca.f16 == 2 && h2_live && op.d_wups_h2 && op.in0 && op.in0->part && op.in0->nslots > 0 && (!op.dbg_raw || op.dbg_h2)) {
-      // default plan, inference-only handle: h2 with the sample's block exponent from the source tensor's slot statistics
-      const Act *si = op.in0;
-      ca.wfrag = op.d_wups_h2; ca.f16 = 4; ca.h2_oscale = op.h2_oscale;
-      ca.gp0 = si->part + (size_t)b0 * si->nslots * si->C * 2; ca.gc0 = si->cnt + (size_t)b0 * si->nslots; ca.gns0 = si->nslots;
-    }
-    ca.bz = op.ups_tz; ca.by = op.ups_ty; ca.bx = op.ups_tx;
-    ca.ntz = ca.Zs / ca.bz; ca.nty = ca.Ys / ca.by; ca.ntx = ca.Xs / ca.bx;
-    if (op.stat_act) {
-      const int nsu = cm::conv_ups_slots(ca, op.ups_mbw);
-      if (nsu > MAX_SLOTS) return fail("statistics slots %d exceed %d", nsu, MAX_SLOTS);
-      ca.stat_ns = nsu;
-      ca.stat_part = op.stat_act->part + (size_t)b0 * nsu * ca.stat_C * 2;
-      ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * nsu;
-      op.stat_act->nslots = nsu;
-    }
-    CM_HIP(cm::launch_conv_ups(ca, op.ups_mbw, op.ups_planes, op.NB, st));
-  } else if (take_f16d) {
-    // reduced-precision plan: direct f16 kernel with its own tile geometry / statistics slots
-    ca.bz = op.f16d_bz; ca.by = op.f16d_by; ca.bx = op.f16d_bx;
-    ca.wfrag = op.d_w16d;
-    if (ca.s2w) ca.s2w = op.d_w16d_skip;
-    if (op.stat_act) {
-      const int ns16 = cm::conv_f16d_slots(ca, op.f16d_mbw);
-      if (ns16 > MAX_SLOTS) return fail("statistics slots %d exceed %d", ns16, MAX_SLOTS);
-      ca.stat_ns = ns16;
-      ca.stat_part = op.stat_act->part + (size_t)b0 * ns16 * ca.stat_C * 2;
-      ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns16;
-      op.stat_act->nslots = ns16;
-    }
-    CM_HIP(cm::launch_conv_f16d(ca, op.f16d_mbw, st));
-  } else if (take_wino) {
-    CM_HIP(cm::launch_conv_wino(ca, wino_f16, st));
-  } else if (op.first_k) {
-    CM_HIP(cm::launch_conv_first(ca, op.first_cin, op.d_wfirst, st));
-  } else if (op.small_n) {
-    bool done = false;
-    if (op.fin) {
-      cm::ConvArgs fa = ca;
-      fa.by = op.fin_by; fa.bx = op.fin_bx;
-      const bool f16 = op.d_wfin16 && !m->train_fwd;
-      const bool h2 = !f16 && h2_live && op.d_wfin_h2 && (!op.dbg_raw || op.dbg_h2);
-      fa.h2_oscale = op.h2_oscale;
-      if (cm::conv_fin_ok(fa)) {
-        CM_HIP(cm::launch_conv_fin(fa, f16 ? op.d_wfin16 : (h2 ? op.d_wfin_h2 : op.d_wfin), f16 ? 1 : (h2 ? 3 : (relaxed ? 2 : 0)), st));
-        done = true;
+    case CONV_UPS:
+      // upsample conv: stage-once parity kernel with its own source tile / statistics slots
+      if (route.form == FORM_F16) { ca.wfrag = op.d_wups16; ca.wpar_stride = op.wups16_stride; }
+      else if (route.form != FORM_FP32) { ca.wfrag = op.d_wups_b6; ca.wpar_stride = op.wups_b6_stride; }
+      ca.f16 = route.form;
+      if (route.form == FORM_H2) {
+        // default plan, inference-only handle: h2 with the sample's block exponent from the source tensor's slot statistics
+        const Act *si = op.in0;
+        ca.wfrag = op.d_wups_h2; ca.h2_oscale = op.h2_oscale;
+        ca.gp0 = si->part + (size_t)b0 * si->nslots * si->C * 2; ca.gc0 = si->cnt + (size_t)b0 * si->nslots; ca.gns0 = si->nslots;
       }
+      ca.bz = op.ups_tz; ca.by = op.ups_ty; ca.bx = op.ups_tx;
+      ca.ntz = ca.Zs / ca.bz; ca.nty = ca.Ys / ca.by; ca.ntx = ca.Xs / ca.bx;
+      if (stat_slots(cm::conv_ups_slots(ca, op.ups_mbw))) return 1;
+      if (op.stat_act) op.stat_act->nslots = ca.stat_ns;
+      CM_HIP(cm::launch_conv_ups(ca, op.ups_mbw, op.ups_planes, op.NB, st));
+      break;
+    case CONV_F16D:
+      // reduced-precision plan: direct f16 kernel with its own tile geometry / statistics slots
+      ca.bz = op.f16d_bz; ca.by = op.f16d_by; ca.bx = op.f16d_bx;
+      ca.wfrag = op.d_w16d;
+      if (ca.s2w) ca.s2w = op.d_w16d_skip;
+      if (stat_slots(cm::conv_f16d_slots(ca, op.f16d_mbw))) return 1;
+      if (op.stat_act) op.stat_act->nslots = ca.stat_ns;
+      CM_HIP(cm::launch_conv_f16d(ca, op.f16d_mbw, st));
+      break;
+    case CONV_WINO: {
+      const bool f16 = route.form == FORM_F16;
+      ca.wfrag = f16 ? op.d_wwino16 : route.form == FORM_H2 ? op.d_wwino_h2 : route.form == FORM_FP32 ? op.d_wwino : op.d_wwino_b6;
+      if (!f16) ca.f16 = route.form;
+      if (route.form == FORM_H2) ca.h2_oscale = op.h2_oscale;
+      // The GroupNorm of the input from the producers' slot partials when run_ops skipped the gn_finalize launch on the promise that
+      // this route merges them (few slots; plan_slot_consumers: the kernel family of a route depends on nothing a launch can change).
+      // Only conv_wino_p_kernel does; conv_wino_p_taken is the launcher's own test for it -- otherwise the skipped launch happens now.
+      if (ca.gn && op.gn_op >= 0 && m->ops[op.gn_op].fin_skipped[slab & 3] && !m->train_fwd) {
+        const Op &g = m->ops[op.gn_op];
+        const Act *g0 = g.g0, *g1 = g.g1;
+        if (cm::conv_wino_p_taken(ca, f16, true)) {
+          ca.gp0 = g0->part + (size_t)b0 * g0->nslots * g0->C * 2; ca.gc0 = g0->cnt + (size_t)b0 * g0->nslots; ca.gns0 = g0->nslots;
+          if (g1) { ca.gp1 = g1->part + (size_t)b0 * g1->nslots * g1->C * 2; ca.gc1 = g1->cnt + (size_t)b0 * g1->nslots; ca.gns1 = g1->nslots; }
+          ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS;
+          ca.gn = nullptr;
+        } else if (run_gnfin(g, nullptr, B, st, b0)) {
+          return 1;
+        }
+      }
+      if (op.stat_act) op.stat_act->nslots = ns_tile;
+      CM_HIP(cm::launch_conv_wino(ca, f16, st));
+      break;
     }
-    if (!done) CM_HIP(cm::launch_conv_smalln(ca, op.MB, op.d_wsmall, st));
-  } else {
-    if (op.d_w1x1_16 && !m->train_fwd && cm::conv1x1_f16_ok(ca, op.NB)) {
+    case CONV_FIRST:
+      if (op.stat_act) op.stat_act->nslots = ns_tile;
+      CM_HIP(cm::launch_conv_first(ca, op.first_cin, op.d_wfirst, st));
+      break;
+    case CONV_FIN: {
+      const ConvForm f = route.form;      // (launch_conv_fin's modes: 0 six bf16 terms, 1 f16, 2 three bf16 terms, 3 h2)
+      ca.by = op.fin_by; ca.bx = op.fin_bx;
+      ca.h2_oscale = op.h2_oscale;
+      CM_HIP(cm::launch_conv_fin(ca, f == FORM_F16 ? op.d_wfin16 : f == FORM_H2 ? op.d_wfin_h2 : op.d_wfin, f == FORM_F16 ? 1 : f == FORM_H2 ? 3 : f == FORM_B3 ? 2 : 0, st));
+      break;
+    }
+    case CONV_SMALLN:
+      CM_HIP(cm::launch_conv_smalln(ca, op.MB, op.d_wsmall, st));
+      break;
+    case CONV_1X1_F16:
       ca.wfrag = op.d_w1x1_16;
       CM_HIP(cm::launch_conv1x1_f16(ca, op.NB, st));
-      return 0;
-    }
-    if (op.d_wfrag16 && !m->train_fwd && cm::conv_par_f16_variant(op.MB, op.NB, ca.bz, ca.by, ca.bx)) {
-      ca.wfrag = op.d_wfrag16; ca.wpar_stride = op.wpar_stride16; ca.f16 = 1;   // f16 operands, fp32 accumulate
-    }
-    CM_HIP(cm::launch_conv(ca, op.MB, op.NB, st));
+      break;
+    case CONV_GENERIC:
+      if (route.form == FORM_F16) { ca.wfrag = op.d_wfrag16; ca.wpar_stride = op.wpar_stride16; ca.f16 = 1; }   // f16 operands, fp32 accumulate
+      if (op.stat_act) op.stat_act->nslots = ns_tile;
+      CM_HIP(cm::launch_conv(ca, op.MB, op.NB, st));
+      break;
   }
   return 0;
 }
@@ -1910,13 +1955,7 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
           break;
         }
         if (op.g1 && op.g1->V() != op.g0->V()) return fail("concat sources disagree on voxel count");
-        const Act *g0 = op.g0, *g1 = op.g1;
-        const int Ct = g0->C + (g1 ? g1->C : 0);
-        CM_HIP(cm::launch_gn_finalize(g0->part + (size_t)b0 * g0->nslots * g0->C * 2, g0->cnt + (size_t)b0 * g0->nslots,
-                                      g0->nslots, g0->C, g1 ? g1->part + (size_t)b0 * g1->nslots * g1->C * 2 : nullptr,
-                                      g1 ? g1->cnt + (size_t)b0 * g1->nslots : nullptr, g1 ? g1->nslots : 0,
-                                      g1 ? g1->C : 0, g0->V(), op.gamma, op.beta, GN_GROUPS, GN_EPS,
-                                      op.gn_out + (size_t)b0 * 2 * Ct, op.gn_mr ? op.gn_mr + (size_t)b0 * 2 * Ct : nullptr, B, st));
+        if (run_gnfin(op, op.gn_mr, B, st, b0)) return 1;
         break;
       }
       case OP_ATTN:
@@ -2256,6 +2295,8 @@ int cm_model_finalize(cm_model *m) {
   if (dev_alloc(m, (void **)&m->tbuf, B * sizeof(long long))) return 1;
   CM_HIP(hipMemset(m->tbuf, 0, B * sizeof(long long)));
   if (build_ops(m)) return 1;
+  for (Op &op : m->ops)
+    if (op.kind == OP_CONV && resolve_conv(m, op)) return 1;
   if (plan_h16(m)) return 1;
   if (plan_slot_consumers(m)) return 1;
   if (build_time_table(m)) return 1;
@@ -2577,8 +2618,8 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
   const bool graph = opts->use_graph && !m->profile && lanes == 1 && !stream && order.size() >= 3;
   if (graph) {
     // hipGraph replay: one captured step (the kernels read their per-step scalars from a device table indexed by a
-    // device counter), launched once per remaining step.  Step 0 runs eagerly: it performs the lazy tile set-up
-    // and per-kernel attribute calls that may not happen inside a capture.
+    // device counter), launched once per remaining step.  Step 0 runs eagerly: the launchers set their kernels' function
+    // attributes on first use, which may not happen inside a capture (the plan itself is complete since finalize).
     if (m->steptab_cap < rows.size()) {
       if (dev_alloc(m, (void **)&m->d_steptab, rows.size() * sizeof(cm::StepRow))) return 1;
       m->steptab_cap = rows.size();
@@ -2641,7 +2682,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
   if (!graph && lanes == 1) {
     if (lane_steps(0, 0, order.size())) return 1;
   } else if (!graph) {
-    // Step 0 of every lane from the calling thread (lazy tile set-up and function attributes happen there, once);
+    // Step 0 of every lane from the calling thread (the launchers' first-use function attributes are set there, once);
     // the remaining steps of lane ln > 0 are enqueued by a host thread of its own, so that the lanes' launch
     // streams fill independently (one thread alternating between the streams is launch-bandwidth bound).
     for (int ln = 0; ln < lanes; ++ln)
@@ -2857,18 +2898,21 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count) {
   return 0;
 }
 
-// One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags out_C C0 C1 wino" or "other <label>".
+// One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags out_C C0 C1 wino kernel form" or "other <label>";
+// kernel (a name of kConvKernelName) and form (a ConvForm number) are the op's inference route (conv_route).
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
   CM_NOT_DIT(m, "cm_debug_conv_info");
   if (!m || !m->finalized || !buf || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
   const cm::ConvArgs &a = op.ca;
-  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d", op.label.c_str(), a.ntaps, a.stride, a.par,
+  const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);
+  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s %d", op.label.c_str(), a.ntaps, a.stride, a.par,
            a.C0 + a.C1, a.Co, a.Zo, a.Yo, a.Xo, op.NB, op.MB, a.bz, a.by, a.bx, op.ks,
            (op.small_n ? 1 : 0) | (op.first_k ? 2 : 0) | (op.stat_act ? 4 : 0) | (op.skip_if_fused ? 8 : 0) | (a.CK == 32 ? 16 : 0),
            op.out_act ? op.out_act->C : a.Co,        // (channel stride of the output tensor, cm_debug_conv_io's h_out)
-           a.C0, a.C1, op.wino ? 1 : 0);             // (channels of the two sources; does the Winograd launcher take the op)
+           a.C0, a.C1, op.wino ? 1 : 0,              // (channels of the two sources; does the Winograd launcher take the op)
+           kConvKernelName[r.kernel], (int)r.form);
   return 0;
 }
 
@@ -2887,7 +2931,6 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   if (!h_in0 || !h_out || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   Op &op = m->ops[index];
   if (op.kind != OP_CONV || !op.in0 || !op.out_act) return fail("op %d is not a convolution", index);
-  if (op.tuned_B < 0 && !op.qr) return fail("run a forward first");
   if ((op.in1 != nullptr) != (h_in1 != nullptr)) return fail("op %d has %d source tensors", index, op.in1 ? 2 : 1);
   DevGuard g(m->device);
   hipStream_t st = m->stream;
@@ -2958,7 +3001,6 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
   if (!us || index < 0 || index >= (int)m->ops.size() || iters < 1) return fail("bad argument");
   Op &op = m->ops[index];
   if (op.kind != OP_CONV || ((op.first_k || op.wino) && MB > 0)) return fail("op %d is not a tunable convolution", index);
-  if (op.tuned_B < 0) return fail("run a forward first");
   DevGuard g(m->device);
   hipStream_t st = m->stream;
   const Op saved = op;
@@ -2985,8 +3027,7 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
     }
   }
   if (!rc) {
-    const bool was_skip = op.skip_if_fused;
-    op.skip_if_fused = false;
+    op.skip_if_fused = false;          // (`saved` restores it)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipEventCreate(&e0); hipEventCreate(&e1);
     for (int i = 0; i < 2 && !rc; ++i) rc = run_conv(m, op, B, st, 0, 0);
@@ -2998,7 +3039,6 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
     float ms = 0.f;
     if (!rc) { hipEventElapsedTime(&ms, e0, e1); *us = ms * 1e3f / (float)iters; }
     hipEventDestroy(e0); hipEventDestroy(e1);
-    op.skip_if_fused = was_skip;
   }
   // restore the op's own geometry and tables
   const bool changed = MB > 0;
@@ -3023,56 +3063,45 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
   if (!m || !m->finalized || !flops) return fail("model not finalized");
   for (int i = 0; i < 8; ++i) flops[i] = 0;
   if (b16) for (int i = 0; i < 8; ++i) b16[i] = 0;
-  const bool p16 = m->precision == CM_PRECISION_F16;
   for (const Op &op : m->ops) {
     if (op.kind == OP_ATTN) { flops[op.cls] += 4.0 * op.S * (double)op.S * op.E * B; continue; }
-    if (op.kind != OP_CONV || op.skip_if_fused) continue;
-    double mult16 = 0.0;     // 0: fp32 matrix instructions; 1: f16 operands; 6: six-term bf16 products; 3: h2 / relaxed (three cross terms)
-    const bool h2l = m->precision == CM_PRECISION_F32 && !m->h2_stale && !op.h2_off;   // (as run_conv)
-    const bool rel = m->precision == CM_PRECISION_F32R;
+    if (op.kind != OP_CONV) continue;
+    // the inference route (the upsample convs' source statistics assumed present)
+    const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);
+    // 0: fp32 matrix instructions; 1: f16 operands; 6: six-term bf16 products; 3: h2 / relaxed (three cross terms)
+    double mult16 = r.form == FORM_F16 ? 1.0 : r.form == FORM_B6 ? 6.0 : r.form == FORM_FP32 ? 0.0 : 3.0;
     const cm::ConvArgs &a = op.ca;
-    const double Ci = a.C0 + a.C1;
+    const double Ci = a.C0 + a.C1, Cskip = op.skip0 ? op.skip0->C + (op.skip1 ? op.skip1->C : 0) : 0;   // (fused 1x1x1 skip conv)
     double f = op.flops_per_sample;
-    if (op.f16d && m->precision == CM_PRECISION_F16) {
-      const double tiles = (double)(a.Zo / op.f16d_bz) * (a.Yo / op.f16d_by) * (a.Xo / op.f16d_bx);
-      f = tiles * 128.0 * op.f16d_mbw * a.Co * (Ci * 27.0 + (op.d_w16d_skip ? op.skip0->C + (op.skip1 ? op.skip1->C : 0) : 0)) * 2;
-      mult16 = 1.0;
-    } else if (op.fin) {
-      // 64-row x 128-column x 32-deep GEMM per (plane, in-plane tile): rows beyond the halo box and columns beyond 27 x Co are padding
-      f = (double)(a.Yo / op.fin_by) * (a.Xo / op.fin_bx) * a.Zo * 64.0 * 128.0 * 32.0 * 2;
-      mult16 = (p16 && op.d_wfin16) ? 1.0 : ((h2l && op.d_wfin_h2) || rel) ? 3.0 : 6.0;
-    } else if (op.qr) {
-      {
-        // the launcher's own predicate (conv_qr2_b6_ok: 8 groups, channel bound, LDS fit), not a copy of one of its clauses
-        cm::QrArgs q{};
-        q.C0 = a.C0; q.C1 = a.C1; q.Co = a.Co; q.Y = a.Yo; q.X = a.Xo; q.groups = GN_GROUPS; q.raw = 1; q.wq6 = op.d_wqr_b6;
-        if (op.d_wqr_skip) { q.s2w = op.d_wqr_skip; q.s2C0 = op.skip0->C; q.s2C1 = op.skip1 ? op.skip1->C : 0; }
-        if (op.d_wqr_b6 && cm::conv_qr2_b6_ok(q)) mult16 = ((h2l && op.d_wqr_h2) || rel) ? 3.0 : 6.0;
+    switch (r.kernel) {
+      case CONV_NONE: continue;
+      case CONV_F16D:
+        f = (double)(a.Zo / op.f16d_bz) * (a.Yo / op.f16d_by) * (a.Xo / op.f16d_bx) * 128.0 * op.f16d_mbw * a.Co * (Ci * 27.0 + Cskip) * 2;
+        break;
+      case CONV_FIN:
+        // 64-row x 128-column x 32-deep GEMM per (plane, in-plane tile): rows beyond the halo box and columns beyond 27 x Co are padding
+        f = (double)(a.Yo / op.fin_by) * (a.Xo / op.fin_bx) * a.Zo * 64.0 * 128.0 * 32.0 * 2;
+        break;
+      case CONV_QR:
+        // whole 32-row blocks, one or two per plane
+        f = 2.0 * (a.Yo * a.Xo > 32 ? 2 : 1) * 32 * a.Co * (Ci * 18.0 + Cskip) * 2;
+        break;
+      case CONV_WINO:   // per tile and 32-channel block (the fused skip conv stays fp32: counted with the layer, a few % of it)
+        f = (double)a.ntz * a.nty * a.ntx * ((a.Co + 31) / 32) * (16.0 * 32 * 32 * Ci * 3 * 2 + 4.0 * 32 * 32 * Cskip * 2);
+        break;
+      case CONV_UPS: {
+        // whole 32-row blocks per (tile, class); planes tiles that span Z skip one of 2 MBW (row block, z tap) pairs
+        const double tiles = (double)(a.Zs / op.ups_tz) * (a.Ys / op.ups_ty) * (a.Xs / op.ups_tx);
+        const double pairs = 2.0 * op.ups_mbw - ((op.ups_planes && op.ups_tz == a.Zs) ? 1.0 : 0.0);
+        f = tiles * 8.0 * 32.0 * pairs * 4.0 * a.Co * Ci * 2;
+        break;
       }
-      const double rows = 2.0 * (a.Yo * a.Xo > 32 ? 2 : 1) * 32;        // whole 32-row blocks, one or two per plane
-      f = rows * a.Co * (Ci * 18.0 + (op.d_wqr_skip ? op.skip0->C + (op.skip1 ? op.skip1->C : 0) : 0)) * 2;
-    } else if (op.wino) {
-      int bz = 0, by = 0, bx = 0;
-      if (cm::conv_wino_pick(a.Zo, a.Yo, a.Xo, &bz, &by, &bx)) {
-        const double tiles = (double)(a.Zo / bz) * ((a.Yo + by - 1) / by) * ((a.Xo + bx - 1) / bx);
-        f = tiles * ((a.Co + 31) / 32) * 16.0 * 32 * 32 * Ci * 3 * 2;
-        if (op.d_s2w) f += tiles * ((a.Co + 31) / 32) * 4.0 * 32 * 32 * (op.skip0->C + (op.skip1 ? op.skip1->C : 0)) * 2;
-        if (p16 && op.d_wwino16) mult16 = 1.0;
-        else if (!p16 && op.d_wwino_b6 && cm::conv_wino_b6_ok(bz, by, bx, a.Co, a.Zo)) mult16 = ((h2l && op.d_wwino_h2) || rel) ? 3.0 : 6.0;   // (the fused 1x1 skip conv stays fp32: counted with the layer, a few % of it)
-      }
-    } else if (a.par && op.ups && (op.d_wups16 || !(op.d_wfrag16 && m->precision == CM_PRECISION_F16))) {
-      // whole 32-row blocks per (tile, class); planes tiles that span Z skip one of 2 MBW (row block, z tap) pairs
-      const double tiles = (double)(a.Zs / op.ups_tz) * (a.Ys / op.ups_ty) * (a.Xs / op.ups_tx);
-      const double pairs = 2.0 * op.ups_mbw - ((op.ups_planes && op.ups_tz == a.Zs) ? 1.0 : 0.0);
-      f = tiles * 8.0 * 32.0 * pairs * 4.0 * a.Co * Ci * 2;
-      if (p16 && op.d_wups16) mult16 = 1.0;
-      else if (!p16 && op.d_wups_b6) mult16 = (rel || (h2l && op.d_wups_h2)) ? 3.0 : 6.0;
-    } else if (a.par) {
-      if (p16 && op.d_wfrag16) mult16 = 1.0;
-      f = op.flops_per_sample * 8.0 / 27.0;
-      if (cm::conv_zsplit_variant(a, op.MB, op.NB)) f *= 6.0 / 8.0;    // two-plane source: 6 of 8 (row block, z tap) pairs
-    } else if (cm::conv_zsplit_variant(a, op.MB, op.NB)) {
-      f *= 18.0 / 27.0;                                                // two-plane grid: the padding-plane tap is never issued
+      case CONV_1X1_F16: mult16 = 0.0;   // (a 1x1x1 layer's f16 products have always been counted with the fp32 issue; kept)
+      // fallthrough
+      default:
+        if (a.par) f = f * 8.0 / 27.0;
+        // two-plane source: 6 of 8 (row block, z tap) pairs; two-plane grid: the padding-plane tap is never issued
+        if (cm::conv_zsplit_variant(a, op.MB, op.NB)) f *= a.par ? 6.0 / 8.0 : 18.0 / 27.0;
     }
     if (b16 && mult16 > 0.0) b16[op.cls] += mult16 * f * B;
     else flops[op.cls] += f * B;

@@ -44,7 +44,7 @@ def tune_one(grid, channels, nb64, nb128, B, iters):
         if f[0] != "conv":
             continue
         label = f[1]
-        ntaps, stride, par, Ci, Co, Zo, Yo, Xo, NB, MB0, bz0, by0, bx0, ks, flags = (int(v) for v in f[2:])
+        ntaps, stride, par, Ci, Co, Zo, Yo, Xo, NB, MB0, bz0, by0, bx0, ks, flags = (int(v) for v in f[2:17])
         if ntaps not in (27, 8) or (flags & 8):
             continue
         osd = 2 if par else 1
