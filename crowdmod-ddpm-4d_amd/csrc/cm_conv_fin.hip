@@ -19,6 +19,10 @@
 //     the order dz = 0, 1, 2 from three consecutive planes, so the summation order is fixed; the thread that adds dz = 2
 //     finishes the voxel (bias, store) and clears the slot.
 // Zero padding: out-of-grid halo voxels are zero rows (P = 0); the padding planes z = -1 and Z are never staged.
+// Sampling loop: a step reads only the future frames of the output, so the launch takes an output plane range (ConvArgs::zo_first /
+// zo_end; the plane loop then runs over input planes zo_first - 1 .. zo_end, and a kept output still meets its taps in the order
+// dz = 0, 1, 2), and the workgroup applies the reverse-process update to what it has finished (template argument FUSE) instead of
+// storing eps_hat for a sampler_step_kernel launch to read back.
 // F16 (reduced-precision plan): one v_mfma_f32_32x32x16_f16 per (row block, k step) on f16 operands; the source tensor may be
 // stored as f16 (ConvArgs::h16 bit 0).
 #include "cm_kernels.h"
@@ -41,8 +45,11 @@ constexpr int FIN_ROWS = 64;                     // halo voxels of a plane tile 
 constexpr int FIN_PCOLS = 132;                   // P row stride in floats (128 columns + 4: 16-byte gathers of a row group stay apart)
 
 // wfin: [nb 4][k step 2][term NTM][lane 64] 16 B, column n = 32 nb + lane % 32 = 4 t + co, k = 16 ks + 8 (lane / 32) + j
-template <int MODE>                                // 0: six bf16 cross terms, 1: f16 operands, 2: three bf16 cross terms (relaxed plan), 3: three f16 cross terms (h2)
-__global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, const float *__restrict__ wfin, int ntx) {
+// FUSE (the sampling loop, planes [a.zo_first, a.zo_end) = the step's future frames): the finished outputs are not stored; the
+// reverse-process update (cm_sampler_update) is applied to them.  1: they wait in LDS ([frame][voxel][4]) until the plane loop has
+// ended, then one thread per (channel, voxel, frame) element, frame fastest as in x; 2: by the thread that finishes the voxel.
+template <int MODE, int FUSE>                      // 0: six bf16 cross terms, 1: f16 operands, 2: three bf16 cross terms (relaxed plan), 3: three f16 cross terms (h2)
+__global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, const float *__restrict__ wfin, int ntx, const StepArgs sa_in) {
   constexpr bool F16 = MODE == 1, H2 = MODE == 3;
   constexpr int U0 = MODE >= 2 ? 3 : 0, NTW = MODE >= 2 ? 2 : 3;
   constexpr int NTM = F16 ? 1 : 3;
@@ -51,6 +58,9 @@ __global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, cons
   float *A = lds;                                // [2 k steps][2 hh][FIN_ROWS][RW]
   float *P = A + 4 * FIN_ROWS * RW;              // [FIN_ROWS][FIN_PCOLS]   (A: two k steps x two k halves)
   float *OACC = P + FIN_ROWS * FIN_PCOLS;        // [3][BY * BX (<= 64)][4] running sums of three output planes
+  float *EPSB = OACC + 3 * 64 * 4;               // FUSE == 1: [zo_end - zo_first][64][4] finished outputs (eps_hat)
+  StepArgs sa = sa_in;
+  if constexpr (FUSE != 0) cm_step_resolve(sa);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, hh = lane >> 5;
@@ -146,12 +156,15 @@ __global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, cons
   for (int i = tid; i < 3 * 64 * 4; i += 256) OACC[i] = 0.f;
 
   const int Z = a.Zs;
+  const int zf = a.zo_first, ze = a.zo_end > 0 ? a.zo_end : a.Zo;   // output planes of this launch
+  int zs, zl;                                     // its input planes
+  conv_fin_zloop(zf, ze, Z, &zs, &zl);
   constexpr int TA[6] = {0, 2, 1, 0, 1, 0}, TB[6] = {2, 0, 1, 1, 0, 0};
-  issue(0);
+  issue(zs);
   stage();
-  if (Z > 1) issue(1);
-  __syncthreads();                                // A of plane 0 complete, the running sums cleared
-  for (int z = 0; z < Z; ++z) {
+  if (zs + 1 < zl) issue(zs + 1);
+  __syncthreads();                                // A of the first plane complete, the running sums cleared
+  for (int z = zs; z < zl; ++z) {
     // ---- P^T = W^T x A^T for this wave's 32 columns, both row blocks: the WEIGHTS are the row operand, so that a lane ends up
     //      with 4 taps x 4 output channels of ITS voxel -- four 16-byte stores per block instead of sixteen 4-byte ones ---------
     f32x16 acc[2];
@@ -191,15 +204,15 @@ __global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, cons
       }
     __syncthreads();                              // P complete; every wave has read A
     // ---- the next plane's image (A is free) beside this plane's gathers (P) -------------------------------------------------
-    if (z + 1 < Z) {
+    if (z + 1 < zl) {
       stage();
-      if (z + 2 < Z) issue(z + 2);
+      if (z + 2 < zl) issue(z + 2);
     }
     // gather: input plane z feeds output plane zo = z + 1 - dz through z tap dz; the taps of one output arrive from three
     // consecutive planes in the order dz = 0, 1, 2, each added by one thread: a fixed summation order
     if (gath) {
       const int zo = z + 1 - dzg;
-      if (zo >= 0 && zo < a.Zo) {
+      if (zo >= zf && zo < ze) {
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t9 = 0; t9 < 9; ++t9) {
@@ -212,11 +225,20 @@ __global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, cons
         // the thread that adds it finishes the voxel (bias, store) and clears the slot for output plane zo + 3
         const bool last = dzg == 2 || (dzg == 1 && z == Z - 1);
         if (last) {
-          if (oin) {
-            float *o = a.out + ((size_t)((b * a.Zo + zo) * a.Yo + oy) * a.Xo + ox) * a.out_cs;
+          if constexpr (FUSE == 1) {
+            *reinterpret_cast<f32x4 *>(EPSB + (size_t)((zo - zf) * 64 + gu) * 4) = v + bias4;
+          } else if (oin) {
+            if constexpr (FUSE == 2) {
+              const size_t cl = ((size_t)(b * a.Zo + zo) * a.Yo + oy) * a.Xo + ox;
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (c < a.Co) o[c] = v[c] + bias4[c];
+              for (int c = 0; c < 4; ++c)
+                if (c < a.Co) cm_sampler_update(sa, b, ((long long)(c * sa.H + oy) * sa.W + ox) * sa.F + (zo - zf), c, cl, v[c] + bias4[c]);
+            } else {
+              float *o = a.out + ((size_t)((b * a.Zo + zo) * a.Yo + oy) * a.Xo + ox) * a.out_cs;
+#pragma unroll
+              for (int c = 0; c < 4; ++c)
+                if (c < a.Co) o[c] = v[c] + bias4[c];
+            }
           }
           v = f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -224,6 +246,24 @@ __global__ __launch_bounds__(256, 2) void conv_fin_kernel(const ConvArgs a, cons
       }
     }
     __syncthreads();                              // A of plane z + 1 complete; the gathers have read P; slot updates visible
+  }
+  if constexpr (FUSE != 0) {
+    // the next step's time index (the UNet of this step has consumed the buffer: every kernel that reads it ran before this one)
+    if (blockIdx.x == 0 && sa.t_next)
+      for (int i = tid; i < a.B; i += 256) sa.t_next[i] = sa.t_next_v;
+  }
+  if constexpr (FUSE == 1) {
+    const int nz = ze - zf, total = a.Co * NV * nz;
+    for (int idx = tid; idx < total; idx += 256) {
+      const int f = idx % nz;
+      int qv = idx / nz;
+      const int ux = qv % BX; qv /= BX;
+      const int uy = qv % BY;
+      const int c = qv / BY;
+      const int hy = y0 + uy, wx = x0 + ux;
+      const size_t cl = ((size_t)(b * a.Zo + zf + f) * a.Yo + hy) * a.Xo + wx;
+      cm_sampler_update(sa, b, ((long long)(c * sa.H + hy) * sa.W + wx) * sa.F + f, c, cl, EPSB[(size_t)(f * 64 + uy * BX + ux) * 4 + c]);
+    }
   }
 }
 
@@ -248,34 +288,51 @@ bool conv_fin_ok(const ConvArgs &a) {
          a.bx > 0 && a.Yo % a.by == 0 && a.Xo % a.bx == 0 && (a.by + 2) * (a.bx + 2) <= FIN_ROWS && a.by * a.bx <= 64 && !(a.h16 & ~1);
 }
 
-size_t conv_fin_lds(bool f16) {
-  return ((size_t)2 * 2 * FIN_ROWS * (f16 ? 4 : 12) + (size_t)FIN_ROWS * FIN_PCOLS + 3 * 64 * 4) * sizeof(float);
+size_t conv_fin_lds(bool f16, int fused_planes = 0) {
+  return ((size_t)2 * 2 * FIN_ROWS * (f16 ? 4 : 12) + (size_t)FIN_ROWS * FIN_PCOLS + 3 * 64 * 4 + (size_t)fused_planes * 64 * 4) * sizeof(float);
+}
+
+// the fused update addresses x, x8 and the history row by the conv's own coordinates: the two must describe the same tensors
+bool conv_fin_fuse_ok(const ConvArgs &a, const StepArgs &s) {
+  const int nz = a.zo_end - a.zo_first;
+  return conv_fin_ok(a) && s.x && a.zo_first == s.P && nz == s.F && nz >= 1 && nz <= 8 && a.Zo == s.P + s.F && a.Yo == s.H && a.Xo == s.W &&
+         a.Co == s.C && a.B == s.B && s.cs == a.out_cs;
+}
+
+template <int FUSE>
+static const void *conv_fin_fn(int mode) {
+  return mode == 1 ? reinterpret_cast<const void *>(conv_fin_kernel<1, FUSE>)
+       : mode == 2 ? reinterpret_cast<const void *>(conv_fin_kernel<2, FUSE>)
+       : mode == 3 ? reinterpret_cast<const void *>(conv_fin_kernel<3, FUSE>) : reinterpret_cast<const void *>(conv_fin_kernel<0, FUSE>);
 }
 
 // mode 0: six-term products (fragments of launch_fin_pack(f16 = false)), 1: f16 operands, 2: three of the six terms on the mode-0 fragments
-hipError_t launch_conv_fin(const ConvArgs &a_in, const float *wfin, int mode, hipStream_t st) {
+// a.zo_first / a.zo_end, step, variant: the sampling loop's forms (cm_kernels.h)
+hipError_t launch_conv_fin(const ConvArgs &a_in, const float *wfin, int mode, hipStream_t st, const StepArgs *step, int variant) {
   ConvArgs a = a_in;
   a.dbg = conv_dbg_flags();
   if (!conv_fin_ok(a) || mode < 0 || mode > 3) return hipErrorInvalidValue;
+  if (a.zo_end == 0 && a.zo_first == 0) a.zo_end = a.Zo;
+  if (a.zo_first < 0 || a.zo_end <= a.zo_first || a.zo_end > a.Zo) return hipErrorInvalidValue;
+  const int fuse = step ? (variant == 2 ? 2 : 1) : 0;
+  if (fuse && !conv_fin_fuse_ok(a, *step)) return hipErrorInvalidValue;
   const int nty = a.Yo / a.by, ntx = a.Xo / a.bx;
   a.nty = nty;
   const dim3 grid((unsigned)(a.B * nty * ntx));
-  const size_t lds = conv_fin_lds(mode == 1);
-  static bool attr_set[64][4] = {{false}};
+  const size_t lds = conv_fin_lds(mode == 1, fuse == 1 ? a.zo_end - a.zo_first : 0);
+  static bool attr_set[64][4][3] = {{{false}}};
   int dev = 0;
   (void)hipGetDevice(&dev);
-  const void *fn = mode == 1 ? reinterpret_cast<const void *>(conv_fin_kernel<1>)
-                 : mode == 2 ? reinterpret_cast<const void *>(conv_fin_kernel<2>)
-                 : mode == 3 ? reinterpret_cast<const void *>(conv_fin_kernel<3>) : reinterpret_cast<const void *>(conv_fin_kernel<0>);
-  if (!attr_set[dev & 63][mode]) {
+  const void *fn = fuse == 1 ? conv_fin_fn<1>(mode) : fuse == 2 ? conv_fin_fn<2>(mode) : conv_fin_fn<0>(mode);
+  if (!attr_set[dev & 63][mode][fuse]) {
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
-    attr_set[dev & 63][mode] = true;
+    attr_set[dev & 63][mode][fuse] = true;
   }
-  if (mode == 1) hipLaunchKernelGGL(conv_fin_kernel<1>, grid, dim3(256), lds, st, a, wfin, ntx);
-  else if (mode == 2) hipLaunchKernelGGL(conv_fin_kernel<2>, grid, dim3(256), lds, st, a, wfin, ntx);
-  else if (mode == 3) hipLaunchKernelGGL(conv_fin_kernel<3>, grid, dim3(256), lds, st, a, wfin, ntx);
-  else hipLaunchKernelGGL(conv_fin_kernel<0>, grid, dim3(256), lds, st, a, wfin, ntx);
+  const StepArgs sa = step ? *step : StepArgs{};
+  void *params[] = {(void *)&a, (void *)&wfin, (void *)&ntx, (void *)&sa};
+  hipError_t e = hipLaunchKernel(fn, grid, dim3(256), params, lds, st);
+  if (e != hipSuccess) return e;
   return hipGetLastError();
 }
 

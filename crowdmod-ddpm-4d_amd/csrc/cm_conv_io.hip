@@ -16,7 +16,10 @@
 //   * MFMA (tap t, step p) contracts k = {channel (CIN/2)*hh + p : hh = 0, 1}; the weights are packed on the
 //     host in exactly that order, one register per step;
 //   * epilogue: bias, channels-last store (128 B per voxel row), GroupNorm statistics of the output per
-//     32-row block in the slot format gn_finalize reads (same arithmetic as the generic conv epilogue).
+//     32-row block in the slot format gn_finalize reads (same arithmetic as the generic conv epilogue);
+//   * no GroupNorm, time row or residual in front of it: output plane z depends on input planes z - 1 .. z + 1 alone, so in the
+//     sampling loop the z tiles below the last past frame are the same in every step and are launched once per loop call
+//     (ConvArgs::tz_first).
 #include "cm_kernels.h"
 
 namespace cm {
@@ -35,9 +38,12 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvArgs a, const
   const int r = lane & 31, hh = lane >> 5;
   int tile = blockIdx.x;
   if (!(gridDim.x & 7) && !(a.dbg & 4096)) tile = (tile & 7) * (int)(gridDim.x >> 3) + (tile >> 3);  // XCD-aware order (cm_conv.hip)
+  // (a.tz_first > 0: the sampling loop's later steps, which launch only the z tiles that see a future frame; outputs and slots are
+  //  addressed by the true tz, so the tiles left out keep what the whole launch of the loop's first step wrote)
+  const int ntz_run = a.ntz - a.tz_first;
   const int ty = tile % a.nty; tile /= a.nty;
-  const int tz = tile % a.ntz;
-  const int b = tile / a.ntz;
+  const int tz = a.tz_first + tile % ntz_run;
+  const int b = tile / ntz_run;
   const int nt = blockIdx.y;
   const int X = a.Xo, bz = a.bz, by = a.by;
   const int z0 = tz * bz, y0 = ty * by;
@@ -182,9 +188,9 @@ bool conv_first_ok(const ConvArgs &a, int cin) {
 hipError_t launch_conv_first(const ConvArgs &a_in, int cin, const float *wpk, hipStream_t st) {
   ConvArgs a = a_in;
   a.dbg = conv_dbg_flags();
-  if (!conv_first_ok(a, cin)) return hipErrorInvalidValue;
+  if (!conv_first_ok(a, cin) || a.tz_first < 0 || a.tz_first >= a.ntz) return hipErrorInvalidValue;
   const int nblk = conv_first_blocks(a);
-  const dim3 grid((unsigned)(a.B * a.ntz * a.nty), (unsigned)((a.Co + 31) / 32));
+  const dim3 grid((unsigned)(a.B * (a.ntz - a.tz_first) * a.nty), (unsigned)((a.Co + 31) / 32));
   const size_t lds = conv_first_lds(a, cin);
   if (cin == 4) hipLaunchKernelGGL(conv_first_kernel<4>, grid, dim3(256), lds, st, a, wpk, nblk);
   else hipLaunchKernelGGL(conv_first_kernel<8>, grid, dim3(256), lds, st, a, wpk, nblk);

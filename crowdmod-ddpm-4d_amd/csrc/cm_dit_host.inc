@@ -213,8 +213,9 @@ int dit_cost(const cm_model *m, int B, double *flops, double *bytes) {
   return 0;
 }
 
-int denoise(cm_model *m, int B, hipStream_t st, int b0, int slab) {
-  return m->dit ? dit_forward(m, B, st, b0) : run_ops(m, B, st, b0, slab);
+// `le`: what a cm_sample_loop step leaves out at the ends of the UNet (LoopEnds; null: the whole forward)
+int denoise(cm_model *m, int B, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
+  return m->dit ? dit_forward(m, B, st, b0) : run_ops(m, B, st, b0, slab, le);
 }
 
 }  // namespace

@@ -497,6 +497,91 @@ void test_conv_route() {
   printf("test_conv_route: %d combinations walked\n", walked);
 }
 
+// The sampling loop's launch ranges of the UNet's two end convs (loop_ends_plan, conv_first_const_ztiles, conv_fin_zloop)
+void test_loop_ends() {
+  // first conv: pick_tile_first's tile on the three benchmark grids and the odd ones; with P = 5 every bz divides P - 1 = 4
+  struct G { int Y, X, bz, by; };
+  const G grids[] = {{12, 36, 4, 3}, {28, 24, 4, 4}, {24, 72, 2, 3}, {13, 37, 1, 13}, {11, 35, 1, 11}};
+  for (const G &g : grids) {
+    Op op = route_class_op(RC_FIRST, CM_PRECISION_F32);
+    op.ca.Zo = op.ca.Zs = 8; op.ca.Yo = op.ca.Ys = g.Y; op.ca.Xo = op.ca.Xs = g.X;
+    pick_tile_first(op);
+    EXPECT(op.ca.bz == g.bz && op.ca.by == g.by && op.ca.ntz == 8 / g.bz);
+    const int t = cm::conv_first_const_ztiles(op.ca.bz, op.ca.ntz, 5);
+    EXPECT(t == 4 / g.bz && 2 * t == op.ca.ntz);              // exactly half of the z tiles are constant
+    for (int tz = 0; tz < op.ca.ntz; ++tz) EXPECT((tz < t) == (tz * g.bz + g.bz <= 4));   // launched <=> the tile reaches plane P - 1 or above
+  }
+  // P / F combinations: the skipped tiles never reach the last past frame's output plane; no constant tile => the full launch
+  for (int P = 1; P <= 9; ++P)
+    for (int F = 1; F <= 4; ++F)
+      for (int bz = 1; bz <= P + F; ++bz) {
+        if ((P + F) % bz) continue;
+        const int ntz = (P + F) / bz, t = cm::conv_first_const_ztiles(bz, ntz, P);
+        EXPECT(t >= 0 && t < ntz && t * bz <= P - 1);
+        EXPECT(((P - 1) % bz == 0 && P > 1) ? t == (P - 1) / bz : t == 0);
+      }
+  EXPECT(cm::conv_first_const_ztiles(4, 2, 1) == 0 && cm::conv_first_const_ztiles(1, 2, 1) == 0 && cm::conv_first_const_ztiles(3, 3, 5) == 0);
+  // last conv: input planes of an output plane range; every kept output still meets its taps in the order dz = 0, 1, 2
+  for (int P = 1; P <= 6; ++P)
+    for (int F = 1; F <= 4; ++F) {
+      const int Z = P + F;
+      int zs, zl;
+      cm::conv_fin_zloop(P, Z, Z, &zs, &zl);
+      EXPECT(zs == P - 1 && zl == Z);
+      cm::conv_fin_zloop(0, Z, Z, &zs, &zl);
+      EXPECT(zs == 0 && zl == Z);                              // the whole range: the loop of a stand-alone forward
+      cm::conv_fin_zloop(0, 1, Z, &zs, &zl);
+      EXPECT(zs == 0 && zl == 2);
+    }
+  // the plan: both ends on their kernels, each switch alone, a last conv off the matrix-core kernel, other frame counts
+  {
+    static float x8, eps;
+    std::vector<Op> ops;
+    ops.push_back(route_class_op(RC_FIRST, CM_PRECISION_F32));
+    ops.push_back(route_class_op(RC_WINO_FULL, CM_PRECISION_F32));
+    ops.push_back(route_class_op(RC_LAST, CM_PRECISION_F32));
+    ops[0].ca.src0 = &x8; pick_tile_first(ops[0]);
+    ops[2].ca.out = &eps;
+    LoopEnds le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 1 && le.zo_first == 5 && le.zo_end == 8 && le.fuse == 1);
+    le = loop_ends_plan(ops, &x8, &eps, 15, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.fuse == 2);
+    le = loop_ends_plan(ops, &x8, &eps, 0, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 0 && le.zo_end == 0 && le.fuse == 0);
+    le = loop_ends_plan(ops, &x8, &eps, 1, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 0 && le.zo_first == 5 && le.zo_end == 8 && le.fuse == 0);
+    le = loop_ends_plan(ops, &x8, &eps, 4, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 1 && le.zo_end == 0 && le.fuse == 0);
+    le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 1, 7, 4, 4);     // P = 1: no constant tile
+    EXPECT(le.tz_first == 0 && le.zo_first == 1 && le.zo_end == 8 && le.fuse == 1);
+    le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 7, 1, 4, 4);     // F = 1; bz = 4 does not divide 6
+    EXPECT(le.tz_first == 0 && le.zo_first == 7 && le.zo_end == 8 && le.fuse == 1);
+    le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 5, 3, 3, 4);     // channel counts differ: the separate sampler launch
+    EXPECT(le.zo_end == 8 && le.fuse == 0);
+    ops[2].ca.C1 = 32;                                                                // last conv on conv_smalln: all planes, separate launch
+    le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 1 && le.zo_end == 0 && le.fuse == 0);
+    ops[0].first_k = false;                                                           // first conv on the generic kernel
+    le = loop_ends_plan(ops, &x8, &eps, 7, CM_PRECISION_F32, false, 5, 3, 4, 4);
+    EXPECT(le.tz_first == 0);
+  }
+  // the fused update's launch predicate: the conv and the step must describe the same tensors
+  {
+    Op op = route_class_op(RC_LAST, CM_PRECISION_F32);
+    cm::ConvArgs a = op.ca;
+    a.by = op.fin_by; a.bx = op.fin_bx; a.B = 2; a.zo_first = 5; a.zo_end = 8;
+    static float x;
+    cm::StepArgs st{};
+    st.x = &x; st.B = 2; st.C = 4; st.H = 12; st.W = 36; st.P = 5; st.F = 3; st.cs = 8;
+    EXPECT(cm::conv_fin_fuse_ok(a, st));
+    st.F = 2; EXPECT(!cm::conv_fin_fuse_ok(a, st)); st.F = 3;
+    st.C = 3; EXPECT(!cm::conv_fin_fuse_ok(a, st)); st.C = 4;
+    a.zo_first = 4; EXPECT(!cm::conv_fin_fuse_ok(a, st)); a.zo_first = 5;
+    st.B = 1; EXPECT(!cm::conv_fin_fuse_ok(a, st));
+  }
+  printf("test_loop_ends ok\n");
+}
+
 void test_misc_errors() {
   EXPECT(cm_abi_version() == CM_ABI_VERSION);
   EXPECT(cm_device_count(nullptr) != 0);
@@ -523,6 +608,7 @@ int main() {
   test_round3_packers();
   test_wino_form_dispatch();
   test_conv_route();
+  test_loop_ends();
   test_misc_errors();
   printf("selftest ok: %d checks\n", g_checks);
   return 0;

@@ -135,8 +135,12 @@ struct ConvArgs {
   float h2_oscale;
   // Unused: the 40 bytes that the removed accumulator-statistics fields took.  Register allocation in conv_wino_p_kernel follows
   // the argument offsets: with the fields below moved up by 40 bytes, its launches of the default plan measured 1.5-4 % slower
-  // (same instructions, other scalar spills), so the offsets stay as they were.
-  alignas(8) unsigned char layout_pad[40];
+  // (same instructions, other scalar spills), so the offsets stay as they were.  The sampling loop's launch ranges of the UNet's two
+  // end convs live in the first 12 of them (zero = the whole tensor, so a zero-initialised ConvArgs means what it always did):
+  alignas(8) int zo_first;   // conv_fin: output planes [zo_first, zo_end) only; zo_end == 0: all Zo planes
+  int zo_end;
+  int tz_first;              // conv_first: z tiles [tz_first, ntz) only (their outputs and statistics slots; the others keep what an earlier launch wrote)
+  unsigned char layout_pad[28];
   // Round 4 -- GroupNorm of the input finalised by the consumer workgroup itself from the producers' SLOT partials, when they
   // are few (half / quarter resolution: <= 32 slots per sample): part [B][gns][C][2] (mean, M2), cnt [B][gns], from sample 0
   // of this launch, as gn_finalize reads them (conv_qr2 has done this since round 3).
@@ -362,7 +366,21 @@ hipError_t launch_conv_f16d(const ConvArgs &a, int mbw, hipStream_t st);
 // a.by / a.bx = in-plane tile of conv_fin_pick; wfin = launch_fin_pack fragments (three bf16 terms, or one f16 term with f16 = true)
 bool conv_fin_pick(int Y, int X, int *by, int *bx);
 bool conv_fin_ok(const ConvArgs &a);
-hipError_t launch_conv_fin(const ConvArgs &a, const float *wfin, int mode /*0 six bf16 terms, 1 f16, 2 three bf16 terms, 3 three f16 terms (h2)*/, hipStream_t st);
+// a.zo_first / a.zo_end: output plane range (the plane loop then starts at input plane zo_first - 1).  `step` != null: the workgroup
+// applies the reverse-process update (cm_sampler_update) to the outputs it has finished instead of storing them -- planes
+// [zo_first, zo_end) must be the step's future frames [P, P + F); variant 1: one thread per (voxel, channel, frame) through LDS,
+// 2: by the thread that finishes the voxel (kept for measurements).  conv_fin_fuse_ok: whether that launch is possible.
+struct StepArgs;
+bool conv_fin_fuse_ok(const ConvArgs &a, const StepArgs &s);
+hipError_t launch_conv_fin(const ConvArgs &a, const float *wfin, int mode /*0 six bf16 terms, 1 f16, 2 three bf16 terms, 3 three f16 terms (h2)*/, hipStream_t st,
+                           const StepArgs *step = nullptr, int variant = 1);
+// conv_first z tiles whose outputs depend on past frames only (z0 + bz <= P - 1), counted from tile 0; taken only when the tile
+// height divides P - 1, so that the constant planes are whole tiles of the resolved slot structure (0: every step launches all tiles)
+inline int conv_first_const_ztiles(int bz, int ntz, int P) {
+  if (bz < 1 || P < 2 || (P - 1) % bz) return 0;
+  const int n = (P - 1) / bz;
+  return n < ntz ? n : 0;
+}
 hipError_t launch_fin_pack(const float *w_ref /*[Co][32][3][3][3] reference layout, device*/, float *wfin, int Co, int mode /*0 three bf16 terms, 1 one f16 term, 2 f16 hi / mid of w * wscale*/, hipStream_t st, float wscale = 1.f);
 constexpr size_t CM_FIN_W_FLOATS = 4 * 2 * 3 * 64 * 4;   // fragment floats (six-term form; the f16 form uses a third)
 
@@ -479,6 +497,74 @@ struct StepArgs {
   long long *t_next; long long t_next_v;
 };
 hipError_t launch_sampler_step(const StepArgs &a, hipStream_t st);
+#ifdef __HIPCC__
+// Device RNG: Philox4x32-10 keyed by the seed, counter = (element quad, global sample id, step, stream).  Independent of batch
+// sharding: sample i of the job draws the same numbers on 1 GPU and on 8.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned out[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned long long p0 = 0xD2511F53ull * c0;
+    const unsigned long long p1 = 0xCD9E8D57ull * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
+    const unsigned n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    const unsigned n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ float philox_normal(unsigned long long seed, long long sample, int step, long long elem) {
+  unsigned r[4];
+  philox4x32_10((unsigned)(elem >> 1), (unsigned)sample, (unsigned)step, (unsigned)((sample >> 32) ^ 0x5eed),
+                (unsigned)seed, (unsigned)(seed >> 32), r);
+  // Box-Muller on one pair; element parity picks cos / sin branch
+  const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float rad = sqrtf(-2.0f * __logf(u1));
+  const float ang = 6.283185307179586f * u2;
+  return (elem & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
+}
+
+// The reverse-process update, ONE definition for sampler_step_kernel and for the tail of the UNet's last conv (conv_fin_kernel,
+// which applies it to the values it has just finished).  cm_step_resolve: graph replay takes the step's scalars and rows from
+// the device table.  cm_sampler_update: element e = ((c H + h) W + w) F + f of sample b, whose eps_hat is `eps` and whose voxel in
+// the channels-last UNet input is `cl`; writes x, the future frame of x8 and the history row.
+__device__ __forceinline__ void cm_step_resolve(StepArgs &a) {
+  if (a.tab) {
+    const int k = *a.kctr;
+    const StepRow r = a.tab[k];
+    a.c_x = r.c_x; a.c_eps = r.c_eps; a.c_noise = r.c_noise; a.guid = r.guid; a.draw = r.draw; a.step = r.step;
+    if (a.noise) a.noise += (long long)k * a.row_stride + a.boff;
+    if (a.hist) a.hist += (long long)(k + 1) * a.row_stride + a.boff;
+  }
+}
+__device__ __forceinline__ void cm_sampler_update(const StepArgs &a, long long b, long long e, int c, size_t cl, float eps) {
+  const long long i = b * ((long long)a.C * a.H * a.W * a.F) + e;
+  float z = 0.f;
+  if (a.draw) z = a.noise ? a.noise[i] : philox_normal(a.seed, a.sample_id_base + b, a.step, e);
+  // x' = c_x x + c_eps eps + c_noise z, the contraction written out: (c_noise z) + fma(c_x, x, c_eps eps), both products rounded.
+  // Left to -ffp-contract the compiler chose exactly this in the stand-alone kernel, and is free to choose otherwise elsewhere.
+  float xn;
+  {
+#pragma clang fp contract(off)
+    const float pe = a.c_eps * eps, pz = a.c_noise * z;
+    xn = pz + __builtin_fmaf(a.c_x, a.x[i], pe);
+    if (a.guid != 0.f && c == 0) xn = xn - a.guid * (xn > 0.f ? 1.f : (xn < 0.f ? -1.f : 0.f));   // (the product is exact)
+  }
+  a.x[i] = xn;
+  if (a.x8) a.x8[cl * 8 + c] = xn;
+  if (a.hist) a.hist[i] = xn;
+}
+#endif
+// Output planes [zf, ze) of a 3-tap conv along z on a Z-plane tensor read input planes [*zs, *zl) (zero padding outside the grid)
+__host__ __device__ inline void conv_fin_zloop(int zf, int ze, int Z, int *zs, int *zl) {
+  *zs = zf > 0 ? zf - 1 : 0;
+  *zl = ze < Z ? ze + 1 : Z;
+}
 // mass_preservation guidance (cm_guidance.hip).  q = the reference's finite-difference quotient of compute_energy for
 // x [B][Cin][H][W][L] (Cin >= 3), written to q [B][Cout][H][W][L] (channels >= 3 are written as 0); one writer per element.
 hipError_t launch_mass_grad(const float *x, int Cin, float *q, int Cout, int B, int H, int W, int L, float delta_t,

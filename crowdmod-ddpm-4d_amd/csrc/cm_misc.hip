@@ -860,40 +860,7 @@ hipError_t launch_attn_core_f16(const float *qkv, float *out, int B, int S, int 
   return hipGetLastError();
 }
 
-// --------------------------------------------------------------------------------
-// Device RNG: Philox4x32-10 keyed by the seed, counter = (element quad, global
-// sample id, step, stream).  Independent of batch sharding: sample i of the job
-// draws the same numbers on 1 GPU and on 8.
-// --------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned out[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned long long p0 = 0xD2511F53ull * c0;
-    const unsigned long long p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ float philox_normal(unsigned long long seed, long long sample, int step, long long elem) {
-  unsigned r[4];
-  philox4x32_10((unsigned)(elem >> 1), (unsigned)sample, (unsigned)step, (unsigned)((sample >> 32) ^ 0x5eed),
-                (unsigned)seed, (unsigned)(seed >> 32), r);
-  // Box-Muller on one pair; element parity picks cos / sin branch
-  const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float rad = sqrtf(-2.0f * __logf(u1));
-  const float ang = 6.283185307179586f * u2;
-  return (elem & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
-}
-
+// (Device RNG: philox4x32_10 / philox_normal live in cm_kernels.h, shared with the last conv's fused sampler update.)
 __global__ __launch_bounds__(256) void randn_kernel(float *__restrict__ x, long long per, long long total,
                                                     unsigned long long seed, long long sample_id_base, int step) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -922,13 +889,7 @@ hipError_t launch_randn(float *x, int B, long long per, unsigned long long seed,
 // UNet input so the next step needs no re-assembly.
 // --------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sampler_step_kernel(StepArgs a) {
-  if (a.tab) {
-    const int k = *a.kctr;
-    const StepRow r = a.tab[k];
-    a.c_x = r.c_x; a.c_eps = r.c_eps; a.c_noise = r.c_noise; a.guid = r.guid; a.draw = r.draw; a.step = r.step;
-    if (a.noise) a.noise += (long long)k * a.row_stride + a.boff;
-    if (a.hist) a.hist += (long long)(k + 1) * a.row_stride + a.boff;
-  }
+  cm_step_resolve(a);
   const long long per = (long long)a.C * a.H * a.W * a.F;
   const long long total = per * a.B;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -942,15 +903,8 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(StepArgs a) {
   const int c = (int)(q / a.H);
   const int L = a.P + a.F;
   const size_t cl = ((((size_t)b * L + (a.P + f)) * a.H + hh) * a.W + w);
-  const float eps = a.eps_cl[cl * a.cs + c];
-  float z = 0.f;
-  if (a.draw) z = a.noise ? a.noise[i] : philox_normal(a.seed, a.sample_id_base + b, a.step, e);
-  // evaluation order mirrors the reference expression tree where it matters for rounding
-  float xn = a.c_x * a.x[i] + a.c_eps * eps + a.c_noise * z;
-  if (a.guid != 0.f && c == 0) xn -= a.guid * (xn > 0.f ? 1.f : (xn < 0.f ? -1.f : 0.f));
-  a.x[i] = xn;
-  if (a.x8) a.x8[cl * 8 + c] = xn;
-  if (a.hist) a.hist[i] = xn;
+  // (the element's arithmetic and stores: cm_sampler_update, cm_kernels.h -- shared with conv_fin_kernel's tail)
+  cm_sampler_update(a, b, e, c, cl, a.eps_cl[cl * a.cs + c]);
 }
 
 hipError_t launch_sampler_step(const StepArgs &a, hipStream_t st) {

@@ -241,6 +241,12 @@ struct cm_model {
   size_t steptab_cap = 0;
   int *d_kctr = nullptr;        // device-side step counter read by the table-driven step kernels
   int *d_nonfinite = nullptr;   // result word of the sampler-output health check
+  // What cm_sample_loop may leave out at the two ends of the UNet (loop_ends_plan): 1 the last conv computes the future planes only,
+  // 2 it applies the sampler update in its tail (no sampler_step_kernel launch), 4 steps after the first launch only the first conv's
+  // z tiles that see a future frame, 8 (measurements) the update runs on the thread that finishes a voxel.  0 = whole convs and a
+  // separate sampler launch (cm_debug_loop_ends: tests compare the two sequences bit for bit in one process; CM_LOOP_ENDS under
+  // CM_DIAG=1 sets a new handle's mask for A/B runs).
+  int loop_ends = cm::diag_env("CM_LOOP_ENDS") ? (atoi(cm::diag_env("CM_LOOP_ENDS")) & 15) : 7;
   float *mass_q = nullptr;      // mass_preservation guidance quotient [max_batch,3,H,W,F] (allocated on first use)
   float *stage_past = nullptr, *stage_fut = nullptr, *stage_out = nullptr;  // host-variant staging
   float *stage_noise = nullptr;
@@ -1586,6 +1592,38 @@ bool route_takes_h16(ConvRoute r, int mask) {
   }
 }
 
+// The two ends of the UNet inside cm_sample_loop.  The z axis is the frame axis: P past frames, then F noisy ones; a loop step reads
+// only the output's future planes, and rewrites only the input's.  Decided here, once per loop call, from the routes of the two convs:
+//   * tz_first: the first conv (CONV_FIRST: no GroupNorm, time row or residual in front of it) launches z tiles [tz_first, ntz) in
+//     every step but the call's first -- the tiles below compute from past frames alone, and their outputs and statistics slots stay
+//     where step 0 left them (every activation has its own allocation).  Only when the resolved tile height divides P - 1.
+//   * zo_first / zo_end: the last conv (CONV_FIN) computes output planes [P, P + F) only.
+//   * fuse: it also applies the reverse-process update to them (variant 1 or 2 of launch_conv_fin); the loop then launches no
+//     sampler_step_kernel and eps_cl is not written.  Mass-preservation guidance still runs afterwards, on the new x.
+// A DiT handle, a last conv on conv_smalln (other channel counts, odd grids) or a first conv on the generic kernel keep the whole
+// launch and the separate sampler kernel.  Nothing here outlives the loop call.
+struct LoopEnds {
+  int tz_first = 0;
+  int zo_first = 0, zo_end = 0;
+  int fuse = 0;
+  const cm::StepArgs *step = nullptr;   // per step and lane: the update's arguments (fuse != 0)
+};
+LoopEnds loop_ends_plan(const std::vector<Op> &ops, const float *x8, const float *eps_cl, int mask, int precision, bool h2_stale, int P, int F,
+                        int Cin, int Cout) {
+  LoopEnds le;
+  for (const Op &op : ops) {
+    if (op.kind != OP_CONV) continue;
+    const ConvRoute r = conv_route(op, precision, false, h2_stale);
+    if (r.kernel == CONV_FIRST && op.ca.src0 == x8 && (mask & 4)) le.tz_first = cm::conv_first_const_ztiles(op.ca.bz, op.ca.ntz, P);
+    if (r.kernel == CONV_FIN && op.ca.out == eps_cl && op.ca.Zo == P + F && (mask & 3)) {
+      le.zo_first = P; le.zo_end = P + F;
+      // (the update addresses x by the conv's channels: one tensor geometry for both; LDS rows for at most 8 frames)
+      if ((mask & 2) && Cin == Cout && op.ca.Co == Cout && op.ca.out_cs == 8 && F <= 8) le.fuse = (mask & 8) ? 2 : 1;
+    }
+  }
+  return le;
+}
+
 // f16 ACTIVATIONS (round 4; reduced-precision plan = BASELINE configs[4]; the reference's autocast stores every conv output as
 // fp16, ddpm.py:116-120): a tensor is stored as _Float16 when the kernel that produces it can write f16 and every kernel that reads
 // it can read f16 (route_takes_h16).  That covers the full- and half-resolution tensors of a grid with >= 4
@@ -1730,7 +1768,7 @@ int run_conv_qr(cm_model *m, const Op &op, ConvForm form, int B, hipStream_t st,
   return 0;
 }
 
-int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab) {
+int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
   const ConvRoute route = conv_route(op, m->precision, m->train_fwd, m->h2_stale, op.in0 && op.in0->part && op.in0->nslots > 0);
   if (route.kernel == CONV_NONE) return 0;
   if (route.kernel == CONV_QR) return run_conv_qr(m, op, route.form, B, st, b0);
@@ -1850,13 +1888,17 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab)
     }
     case CONV_FIRST:
       if (op.stat_act) op.stat_act->nslots = ns_tile;
+      if (le && op.ca.src0 == m->x8) ca.tz_first = le->tz_first;   // (a later loop step: the constant z tiles stay)
       CM_HIP(cm::launch_conv_first(ca, op.first_cin, op.d_wfirst, st));
       break;
     case CONV_FIN: {
       const ConvForm f = route.form;      // (launch_conv_fin's modes: 0 six bf16 terms, 1 f16, 2 three bf16 terms, 3 h2)
       ca.by = op.fin_by; ca.bx = op.fin_bx;
       ca.h2_oscale = op.h2_oscale;
-      CM_HIP(cm::launch_conv_fin(ca, f == FORM_F16 ? op.d_wfin16 : f == FORM_H2 ? op.d_wfin_h2 : op.d_wfin, f == FORM_F16 ? 1 : f == FORM_H2 ? 3 : f == FORM_B3 ? 2 : 0, st));
+      const bool ends = le && le->zo_end && op.ca.out == m->eps_cl;     // (a loop step: future planes only, the update in the tail)
+      if (ends) { ca.zo_first = le->zo_first; ca.zo_end = le->zo_end; }
+      CM_HIP(cm::launch_conv_fin(ca, f == FORM_F16 ? op.d_wfin16 : f == FORM_H2 ? op.d_wfin_h2 : op.d_wfin, f == FORM_F16 ? 1 : f == FORM_H2 ? 3 : f == FORM_B3 ? 2 : 0, st,
+                                 ends && le->fuse ? le->step : nullptr, ends ? le->fuse : 0));
       break;
     }
     case CONV_SMALLN:
@@ -1904,7 +1946,7 @@ int run_combine(cm_model *m, cm::CombineArgs &cb, hipStream_t st) {
 // Launch the op list for the `B` samples starting at sample `b0` on stream `st`.
 // Every sample-indexed pointer is offset by b0, so two disjoint sub-batches can run
 // concurrently on two streams (`slab` selects the stream's K-split scratch region).
-int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
+int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0, const LoopEnds *le = nullptr) {
   for (size_t oi = 0; oi < m->ops.size(); ++oi) {
     Op &op = m->ops[oi];
     // the fused attention block runs in the inference plan, its four generic ops in the training forward
@@ -1934,7 +1976,7 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0) {
     }
     switch (op.kind) {
       case OP_CONV:
-        if (run_conv(m, op, B, st, b0, slab)) return 1;
+        if (run_conv(m, op, B, st, b0, slab, le)) return 1;
         break;
       case OP_STATS: {
         const Act *t = op.act;
@@ -2615,6 +2657,10 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     CM_HIP(cm::launch_mass_apply(ma, ls));
     return 0;
   };
+  // the UNet's two end convs inside the loop (loop_ends_plan); step 0 of the call always runs the first conv whole: the past has
+  // just been assembled, and the weights may have changed since the last call
+  const LoopEnds ends = m->dit ? LoopEnds{} : loop_ends_plan(m->ops, m->x8, m->eps_cl, m->loop_ends, m->precision, m->h2_stale, c.past_len,
+                                                             c.future_len, c.in_channels, c.out_channels);
   const bool graph = opts->use_graph && !m->profile && lanes == 1 && !stream && order.size() >= 3;
   if (graph) {
     // hipGraph replay: one captured step (the kernels read their per-step scalars from a device table indexed by a
@@ -2628,23 +2674,26 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     CM_HIP(hipMemcpyAsync(m->d_steptab, rows.data(), rows.size() * sizeof(cm::StepRow), hipMemcpyHostToDevice, st));
     CM_HIP(hipMemsetAsync(m->d_kctr, 0xFF, sizeof(int), st));   // -1
     CM_HIP(hipStreamSynchronize(st));                            // `rows` is host memory of this call
-    auto enqueue_step = [&]() -> int {
+    auto enqueue_step = [&](bool first) -> int {
       CM_HIP(cm::launch_step_begin(m->tbuf, B, m->d_steptab, m->d_kctr, st));
-      if (denoise(m, B, st, 0, 0)) return 1;
       cm::StepArgs al = base_args();
       al.B = B; al.x = m->xstate; al.eps_cl = m->eps_cl; al.x8 = m->x8;
       al.sample_id_base = opts->sample_id_base;
       al.tab = m->d_steptab; al.kctr = m->d_kctr; al.row_stride = (long long)B * per; al.boff = 0;
       al.hist = d_history; al.noise = d_noise;
-      CM_HIP(cm::launch_sampler_step(al, st));
+      LoopEnds le = ends;
+      le.step = &al;
+      if (first) le.tz_first = 0;
+      if (denoise(m, B, st, 0, 0, &le)) return 1;
+      if (!ends.fuse) CM_HIP(cm::launch_sampler_step(al, st));
       if (mass && mass_step(0, B, 0.f, d_history, m->d_steptab, 0, st)) return 1;
       return 0;
     };
-    if (enqueue_step()) return 1;
+    if (enqueue_step(true)) return 1;
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     CM_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-    const int rc_cap = enqueue_step();
+    const int rc_cap = enqueue_step(false);
     hipError_t ec = hipStreamEndCapture(st, &g);
     if (rc_cap || ec != hipSuccess) { if (g) hipGraphDestroy(g); return rc_cap ? 1 : fail("graph capture failed: %s", hipGetErrorString(ec)); }
     ec = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
@@ -2665,7 +2714,6 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       const cm::StepRow &r = rows[k];
       al.step = r.step; al.c_x = r.c_x; al.c_eps = r.c_eps; al.c_noise = r.c_noise; al.draw = r.draw; al.guid = r.guid;
       if (k == 0) CM_HIP(cm::launch_fill_t(m->tbuf + b0, Bn, t, ls));
-      if (denoise(m, Bn, ls, b0, ln)) return 1;
       al.B = Bn;
       if (k + 1 < order.size()) { al.t_next = m->tbuf + b0; al.t_next_v = order[k + 1]; }
       al.x = m->xstate + (size_t)b0 * per;
@@ -2674,7 +2722,11 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       al.sample_id_base = opts->sample_id_base + b0;
       al.hist = d_history ? d_history + (k + 1) * B * per + (size_t)b0 * per : nullptr;
       al.noise = (d_noise && al.draw) ? d_noise + k * B * per + (size_t)b0 * per : nullptr;
-      CM_HIP(cm::launch_sampler_step(al, ls));
+      LoopEnds le = ends;
+      le.step = &al;
+      if (k == 0) le.tz_first = 0;
+      if (denoise(m, Bn, ls, b0, ln, &le)) return 1;
+      if (!ends.fuse) CM_HIP(cm::launch_sampler_step(al, ls));
       if (mass && mass_step(b0, Bn, r.mass, al.hist, nullptr, 0, ls)) return 1;
     }
     return 0;
@@ -2907,12 +2959,28 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
   const cm::ConvArgs &a = op.ca;
   const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);
-  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s %d", op.label.c_str(), a.ntaps, a.stride, a.par,
+  // after them, for the two end convs of the UNet: what a sampling-loop step leaves out ("loop_ztiles <first tile of later steps>/<ntz>",
+  // 0 = every step launches all tiles; "loop_planes <first>:<end> fuse <variant>")
+  const LoopEnds le = loop_ends_plan(m->ops, m->x8, m->eps_cl, m->loop_ends, m->precision, m->h2_stale, m->cfg.past_len, m->cfg.future_len,
+                                     m->cfg.in_channels, m->cfg.out_channels);
+  char tail[64] = "";
+  if (r.kernel == CONV_FIRST && a.src0 == m->x8) snprintf(tail, sizeof tail, " loop_ztiles %d/%d", le.tz_first, a.ntz);
+  if (r.kernel == CONV_FIN && a.out == m->eps_cl && le.zo_end) snprintf(tail, sizeof tail, " loop_planes %d:%d fuse %d", le.zo_first, le.zo_end, le.fuse);
+  snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s %d%s", op.label.c_str(), a.ntaps, a.stride, a.par,
            a.C0 + a.C1, a.Co, a.Zo, a.Yo, a.Xo, op.NB, op.MB, a.bz, a.by, a.bx, op.ks,
            (op.small_n ? 1 : 0) | (op.first_k ? 2 : 0) | (op.stat_act ? 4 : 0) | (op.skip_if_fused ? 8 : 0) | (a.CK == 32 ? 16 : 0),
            op.out_act ? op.out_act->C : a.Co,        // (channel stride of the output tensor, cm_debug_conv_io's h_out)
            a.C0, a.C1, op.wino ? 1 : 0,              // (channels of the two sources; does the Winograd launcher take the op)
-           kConvKernelName[r.kernel], (int)r.form);
+           kConvKernelName[r.kernel], (int)r.form, tail);
+  return 0;
+}
+
+// Test hook, exported but outside the public header (the binding table is fixed): which of the loop's end-conv savings the handle
+// takes (cm_model::loop_ends; 0 restores whole convs and the separate sampler launch, 7 is the default).
+extern "C" int cm_debug_loop_ends(cm_model *m, int32_t mask) {
+  CM_NOT_DIT(m, "cm_debug_loop_ends");
+  if (!m || mask < 0 || mask > 15) return fail("bad argument");
+  m->loop_ends = mask;
   return 0;
 }
 

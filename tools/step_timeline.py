@@ -9,7 +9,9 @@ pat = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/prof_seq/*/*_kernel_trac
 f = sorted(glob.glob(pat))[-1]
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "sampler_step" in r["Kernel_Name"]]
+# a step runs from one launch of the UNet's first conv to the next (the sampler update has no launch of its own when the
+# last conv applies it in its tail)
+idx = [i for i, r in enumerate(rows) if "conv_first_kernel" in r["Kernel_Name"]]
 a, b = idx[-2], idx[-1]
 t0 = int(rows[a]["Start_Timestamp"])
 tot = collections.defaultdict(lambda: [0, 0.0])
