@@ -100,7 +100,7 @@ int dit_finalize(cm_model *m) {
   const size_t B = (size_t)c.max_batch, rows = B * d.tok, D = (size_t)c.hidden_size;
   const size_t vox = (size_t)m->L() * c.rows * c.cols * 8;
   if (dev_alloc(m, (void **)&m->tbuf, B * sizeof(long long))) return 1;
-  CM_HIP(hipMemset(m->tbuf, 0, B * sizeof(long long)));
+  CM_HIP(hipMemset(m->tbuf, 0xff, B * sizeof(long long)));   // -1: "no forward has written this sample" (dit_debug_activation)
   if (dev_alloc(m, (void **)&m->x8, B * vox * sizeof(float))) return 1;
   if (dev_alloc(m, (void **)&m->eps_cl, B * vox * sizeof(float))) return 1;
   CM_HIP(hipMemset(m->x8, 0, B * vox * sizeof(float)));
@@ -129,7 +129,9 @@ int dit_finalize(cm_model *m) {
 
 // One DiT4D_V4.forward (DiT4D_V4.py:347-375) for the B samples starting at b0: reads x8 and tbuf, writes eps_cl frames
 // of the future slots.  Capturable: no allocation, synchronisation or host read; t comes from tbuf on the device.
-int dit_forward(cm_model *m, int B, hipStream_t st, int b0) {
+// `nblocks`: stop after that many blocks (depth: the whole forward with the final layer; fewer: the residual stream X is
+// left as that stage wrote it and eps_cl is untouched -- dit_debug_activation).
+int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
   const cm_dit_plan &d = *m->dit;
   const cm_dit_config &c = d.cfg;
   const int D = c.hidden_size, D3 = 3 * D, mlp = c.mlp_hidden, nq = d.Tp - d.qs;
@@ -154,7 +156,7 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0) {
   a.x8 = m->x8 + (size_t)b0 * vox; a.W = d.w[9]; a.bias = d.w[10]; a.Y = X; a.ldy = D; a.spos = d.w[0]; a.tpos = d.w[1];
   CM_HIP(cm::launch_dit_gemm(a, st));
   cm::DitAttnArgs at{QKV, AO, B, d.Tp, d.Ns, d.qs, D, c.num_heads};
-  for (int i = 0; i < c.depth; ++i) {
+  for (int i = 0; i < nblocks; ++i) {
     const float *const *w = d.w.data() + DIT_HEAD + DIT_PER_BLOCK * i;
     const int mo = i * 9 * D;
     // spatial self-attention (DiT4D_V4.py:160-169)
@@ -182,6 +184,7 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0) {
     a.A = Hm; a.lda = mlp; a.W = w[10]; a.bias = w[11]; a.Y = X; a.ldy = D; a.off_gate = mo + 8 * D;
     CM_HIP(cm::launch_dit_gemm(a, st));
   }
+  if (nblocks < c.depth) return 0;
   // final layer + unpatchify, future slots only: slots < qs hold past frames only (:223-225, :93-99)
   const float *const *wf = d.w.data() + DIT_HEAD + DIT_PER_BLOCK * c.depth;
   a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_UNPATCH, M, d.Nout, D);
@@ -215,7 +218,39 @@ int dit_cost(const cm_model *m, int B, double *flops, double *bytes) {
 
 // `le`: what a cm_sample_loop step leaves out at the ends of the UNet (LoopEnds; null: the whole forward)
 int denoise(cm_model *m, int B, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
-  return m->dit ? dit_forward(m, B, st, b0) : run_ops(m, B, st, b0, slab, le);
+  return m->dit ? dit_forward(m, B, st, b0, m->dit->cfg.depth) : run_ops(m, B, st, b0, slab, le);
+}
+
+// cm_debug_activation of a DiT handle: "patch_embed" or "blocks.<i>" -> the residual stream [B][T_p * N_s][D] after that
+// stage, as a forward hook on the reference module sees it.  x8 and tbuf still hold the last forward's inputs, so the
+// forward is run again from them, stopped after the stage, and X copied out; B is the number of leading samples whose t a
+// forward has written (dit_finalize leaves -1; samples past the last batch are those of an earlier, larger one).
+int dit_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity, int64_t shape[5]) {
+  const cm_dit_plan &d = *m->dit;
+  const cm_dit_config &c = d.cfg;
+  int nblocks = -1;
+  if (!std::strcmp(name, "patch_embed")) {
+    nblocks = 0;
+  } else if (!std::strncmp(name, "blocks.", 7) && name[7] >= '0' && name[7] <= '9') {
+    char *end = nullptr;
+    const long i = std::strtol(name + 7, &end, 10);
+    if (!*end && i >= 0 && i < c.depth) nblocks = (int)i + 1;
+  }
+  if (nblocks < 0) return fail("no DiT activation named %s (patch_embed, blocks.0 .. blocks.%d)", name, c.depth - 1);
+  DevGuard g(m->device);
+  CM_HIP(hipDeviceSynchronize());
+  std::vector<long long> t((size_t)c.max_batch);
+  CM_HIP(hipMemcpy(t.data(), m->tbuf, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  int B = 0;
+  while (B < c.max_batch && t[B] >= 0 && t[B] < TIME_ROWS) ++B;
+  if (B == 0) return fail("cm_debug_activation: no forward has run on this DiT handle");
+  const int64_t n = (int64_t)B * d.tok * c.hidden_size;
+  if (capacity < n) return fail("capacity %lld < %lld", (long long)capacity, (long long)n);
+  if (dit_forward(m, B, m->stream, 0, nblocks)) return 1;
+  CM_HIP(hipStreamSynchronize(m->stream));
+  CM_HIP(hipMemcpy(h_out, d.X, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  if (shape) { shape[0] = B; shape[1] = d.tok; shape[2] = c.hidden_size; shape[3] = 1; shape[4] = 1; }
+  return 0;
 }
 
 }  // namespace

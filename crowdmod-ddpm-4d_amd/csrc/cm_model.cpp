@@ -2443,9 +2443,9 @@ int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t
 }
 
 int cm_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity, int64_t shape[5]) {
-  CM_NOT_DIT(m, "cm_debug_activation");
   if (!m || !name || !h_out) return fail("null argument");
   if (!m->finalized) return fail("model not finalized");
+  if (m->dit) return dit_debug_activation(m, name, h_out, capacity, shape);
   auto it = m->act_by_name.find(name);
   if (it == m->act_by_name.end()) return fail("no activation named %s", name);
   const Act *a = it->second;

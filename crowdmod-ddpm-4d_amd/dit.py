@@ -163,6 +163,20 @@ class DiT4D_V4:
         native.check(L.cm_unet_forward_host(h, fut.ctypes.data, tt.ctypes.data, pst.ctypes.data, out.ctypes.data, B))
         return out
 
+    def debug_activation(self, name: str) -> np.ndarray:
+        """Residual stream [B, T_p * N_s, D] of the last forward after `blocks.<i>` (what a forward hook on that module
+        of the reference sees) or `patch_embed` (the tokens entering blocks.0, position embeddings added); samples
+        beyond the last batch are those of an earlier, larger batch.
+        Test hook: the library re-runs the forward from the inputs it still holds, up to the named stage."""
+        if self._handle is None:
+            raise RuntimeError("no forward has run yet")
+        cap = self._native_max_batch * self.cfg.t_p * self.cfg.n_s * self.cfg.hidden_size
+        buf = np.empty(cap, dtype=np.float32)
+        shape = (C.c_int64 * 5)()
+        native.check(native.lib().cm_debug_activation(self._handle, name.encode(), buf.ctypes.data, cap, shape))
+        shp = tuple(int(v) for v in shape)[:3]
+        return buf[: int(np.prod(shp))].reshape(shp).copy()
+
     def cost(self, B: int):
         f, b = C.c_double(), C.c_double()
         native.check(native.lib().cm_model_cost(self._handle, B, C.byref(f), C.byref(b)))

@@ -57,8 +57,9 @@ typedef struct cm_unet_config {
 /* Hyper-parameters of reference DiT4D_V4.__init__ (models/backbones/DiT4D_V4.py:235-254) plus the tensor geometry, as
  * DDPM_model builds it for arch "DDPM-DiT" (models/diffusion/ddpm.py:88-104).  A DiT handle is the same opaque cm_model,
  * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 only)
- * / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it; every
- * other handle entry point (training, dropout width, debug and conv hooks, profiling, FLOP splits) returns non-zero. */
+ * / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it, and
+ * cm_debug_activation serves "patch_embed" and "blocks.<i>" (see there); every other handle entry point (training,
+ * dropout width, the conv and loop debug hooks, profiling, FLOP splits) returns non-zero. */
 typedef struct cm_dit_config {
   int32_t in_channels;                    /* mprops_count                                        */
   int32_t out_channels;
@@ -154,7 +155,12 @@ int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t
                 void *stream);
 /* Test hook: copy an internal activation (by reference module name, e.g.
  * "encoder_blocks.0") of the last forward to the host in reference layout
- * [B,C,H,W,L].  `shape` receives {B,C,H,W,L}. */
+ * [B,C,H,W,L].  `shape` receives {B,C,H,W,L}.
+ * DiT handle: `name` is "patch_embed" or "blocks.<i>"; the tensor is the residual stream [B, T_p*N_s, D] after that
+ * stage (blocks.<i>: what a forward hook on the reference module sees; patch_embed: the tokens entering blocks.0,
+ * i.e. with both position embeddings added), `shape` receives {B, T_p*N_s, D, 1, 1}.  Read-only: the
+ * last forward's inputs are still in the workspace, and the forward is run again from them up to the named stage.  B
+ * is the batch of the last forward (samples of an earlier, larger batch follow it); fails before the first forward. */
 int cm_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity,
                         int64_t shape[5]);
 

@@ -25,7 +25,7 @@ def _modulate(x, shift, scale):
     return x * (1.0 + sc) + sh
 
 
-def _mha(q_in, kv_in, W, b, Wo, bo, heads):
+def _mha(q_in, kv_in, W, b, Wo, bo, heads, tap=None):
     """nn.MultiheadAttention(batch_first) in eval: packed in_proj rows q, k, v; softmax(q k^T / sqrt(hd)) v; out_proj."""
     D = q_in.shape[-1]
     hd = D // heads
@@ -37,20 +37,28 @@ def _mha(q_in, kv_in, W, b, Wo, bo, heads):
         return x.reshape(*x.shape[:-1], heads, hd).swapaxes(-2, -3)     # [..., heads, S, hd]
     q, k, v = split(q), split(k), split(v)
     s = q @ k.swapaxes(-1, -2) / np.sqrt(hd)
+    top = float(s.max()) if tap is not None else None
     s = np.exp(s - s.max(-1, keepdims=True))
-    o = (s / s.sum(-1, keepdims=True)) @ v
+    s = s / s.sum(-1, keepdims=True)
+    if tap is not None:
+        tap.append((top, s.max(-1)))
+    o = s @ v
     o = o.swapaxes(-2, -3).reshape(*q_in.shape[:-1], D)
     return o @ Wo.T + bo
 
 
-def forward(params, cfg: dit_spec.DiTConfig, fut, t, past, blocks=None):
+def forward(params, cfg: dit_spec.DiTConfig, fut, t, past, blocks=None, stem=None, qs=None, tap=None):
     """DiT4D_V4.forward(future, t, past) (:347-375) -> [B, C, H, W, F]; `blocks`, if a list, receives every block's
-    output [B, T_p * N_s, D] (what a forward hook on model.blocks[i] sees)."""
+    output [B, T_p * N_s, D] (what a forward hook on model.blocks[i] sees) and `stem`, if a list, the tokens entering
+    blocks[0] (patch embedding plus both position embeddings, :366-367).  `qs` overrides the first query slot
+    past_len // pt (negative controls only); `tap`, if a list, receives (largest raw logit, top softmax weight of every
+    query) of each attention call."""
     P = {k: np.asarray(v, dtype=np.float64) for k, v in params.items()}
     D, heads, p, pt = cfg.hidden_size, cfg.num_heads, cfg.patch_size, cfg.t_patch_size
     x = np.concatenate([past, fut], axis=4).astype(np.float64)                      # (B, C, H, W, P+F)  :357-358
     B, C, H, W, L = x.shape
-    hp, wp, Tp, Ns, qs = H // p, W // p, L // pt, (H // p) * (W // p), cfg.past_len // pt
+    hp, wp, Tp, Ns = H // p, W // p, L // pt, (H // p) * (W // p)
+    qs = cfg.past_len // pt if qs is None else qs
     t = np.asarray(t, dtype=np.int64)
     # conditioning (:363): time_blocks = table -> Linear -> SiLU -> Linear (embeddings.py:22-31); time_proj = Linear, SiLU
     e = _silu(P["dif_time_embeddings.time_blocks.0.weight"][t] @ P["dif_time_embeddings.time_blocks.1.weight"].T
@@ -63,6 +71,8 @@ def forward(params, cfg: dit_spec.DiTConfig, fut, t, past, blocks=None):
     tok = xc.reshape(B, Tp * Ns, C * pt * p * p) @ P["patch_embed.proj.weight"].reshape(D, -1).T + P["patch_embed.proj.bias"]
     tok = tok.reshape(B, Tp, Ns, D) + P["spatial_pos_embed"][0][None, None] + P["temporal_pos_embed"][0, :Tp][None, :, None]
     x = tok.reshape(B, Tp * Ns, D)                                                  # :338-345
+    if stem is not None:
+        stem.append(x.copy())
     for i in range(cfg.depth):
         b = f"blocks.{i}."
         m = sc @ P[b + "adaLN_modulation.1.weight"].T + P[b + "adaLN_modulation.1.bias"]
@@ -71,13 +81,13 @@ def forward(params, cfg: dit_spec.DiTConfig, fut, t, past, blocks=None):
         xs = x.reshape(B, Tp, Ns, D)
         h = _modulate(_ln(xs), ch[0], ch[1])
         a = _mha(h, h, P[b + "spatial_attn.in_proj_weight"], P[b + "spatial_attn.in_proj_bias"],
-                 P[b + "spatial_attn.out_proj.weight"], P[b + "spatial_attn.out_proj.bias"], heads)
+                 P[b + "spatial_attn.out_proj.weight"], P[b + "spatial_attn.out_proj.bias"], heads, tap)
         xs = xs + ch[2][:, None, None] * a
         # temporal cross-attention per (sample, patch): keys / values all slots, queries slots >= qs (:173-198)
         xt = xs.transpose(0, 2, 1, 3).copy()                                        # (B, N_s, T_p, D)
         kv = _modulate(_ln(xt), ch[3], ch[4])
         a = _mha(kv[:, :, qs:], kv, P[b + "temporal_attn.in_proj_weight"], P[b + "temporal_attn.in_proj_bias"],
-                 P[b + "temporal_attn.out_proj.weight"], P[b + "temporal_attn.out_proj.bias"], heads)
+                 P[b + "temporal_attn.out_proj.weight"], P[b + "temporal_attn.out_proj.bias"], heads, tap)
         xt[:, :, qs:] += ch[5][:, None, None] * a
         x = xt.transpose(0, 2, 1, 3).reshape(B, Tp * Ns, D)
         # MLP with the exact-erf GELU (:201-202, :128-131)
