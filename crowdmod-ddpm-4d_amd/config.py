@@ -96,14 +96,15 @@ class Resolved:
     nsamples: int
     nsamples4plots: int
     train: Optional[AttrDict] = None
-    dit: Optional["DiTKeys"] = None   # arch DDPM-DiT: the MODEL.DDPM.DIT section
+    dit: Optional["DiTKeys"] = None   # arch DDPM-DiT: the MODEL.DDPM.DIT section; arch FM-DiT: MODEL.FM.DIT
 
 
 @dataclass
 class DiTKeys:
-    """MODEL.DDPM.DIT as models/diffusion/ddpm.py:88-104 reads it."""
+    """MODEL.DDPM.DIT as models/diffusion/ddpm.py:88-104 reads it, or MODEL.FM.DIT as
+    models/flow_matching/flow_matching.py:72-84 does (no T_PATCH_SIZE: t_patch_size is None)."""
     patch_size: int
-    t_patch_size: int
+    t_patch_size: Optional[int]
     hidden_size: int
     depth: int
     num_heads: int
@@ -138,16 +139,23 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
 
     train = _first(back.get("TRAIN"), gen.get("TRAIN"), cfg.get("TRAIN"))
     dit = None
-    if arch == "DDPM-DiT":
-        # attribute access on the DIT node in the reference (ddpm.py:95-103): a missing key is an error naming it
+    if arch in ("DDPM-DiT", "FM-DiT"):
+        # attribute access on the DIT node in the reference (ddpm.py:95-103, flow_matching.py:77-83): a missing key is
+        # an error naming it
         def req(key):
             if key not in back:
                 raise KeyError(f"MODEL.{gen_key}.{back_key}.{key} is missing (needed by arch {arch})")
             return back[key]
-        dit = DiTKeys(int(req("PATCH_SIZE")), int(req("T_PATCH_SIZE")), int(req("HIDDEN_SIZE")), int(req("DEPTH")),
-                      int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")), str(req("CONDITION")),
-                      float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
-        if dit.condition != "Past":
+        if arch == "FM-DiT":
+            # FM_model does not pass CONDITION on (DiT2D keeps its default "Past"): read, not required
+            dit = DiTKeys(int(req("PATCH_SIZE")), None, int(req("HIDDEN_SIZE")), int(req("DEPTH")),
+                          int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")),
+                          str(back.get("CONDITION", "Past")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
+        else:
+            dit = DiTKeys(int(req("PATCH_SIZE")), int(req("T_PATCH_SIZE")), int(req("HIDDEN_SIZE")), int(req("DEPTH")),
+                          int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")),
+                          str(req("CONDITION")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
+        if arch == "DDPM-DiT" and dit.condition != "Past":
             raise NotImplementedError(f"DIT.CONDITION {dit.condition!r}: only 'Past' (the configuration every reference config uses)")
     mult = tuple(int(v) for v in bk("BASE_CH_MULT", (1, 2, 4)))
     attn = tuple(bool(v) for v in bk("APPLY_ATTENTION", (False, False, True, False)))

@@ -12,6 +12,8 @@
 //   dit_attn_*        softmax(q k^T / 8) v per head (head dim 64) on the vector ALUs: spatial self-attention over the
 //                     N_s tokens of one (sample, slot), temporal cross-attention of the future slots of one (sample,
 //                     patch) over all T_p slots.
+//   dit_attn_full     the DiT2D variant (models/backbones/DiT2D.py): one self-attention over all S = T_p * N_s tokens of
+//                     a sample, q k^T and P v both on v_mfma_f32_32x32x2_f32 with a streaming softmax.
 // Determinism: every output element is written by one thread with a fixed summation order (k ascending in one fma
 // chain; fixed butterfly reductions), no atomics, and a sample only reads its own rows -- a chain's result does not
 // depend on the batch it runs in, the batch lane, or graph replay.
@@ -236,6 +238,101 @@ __global__ __launch_bounds__(256) void dit_attn_temporal_kernel(const DitAttnArg
   }
 }
 
+// Full self-attention of DiT2D (DiT2D.py:105, 283-289): softmax(q k^T / 8) v over the S = T_p * N_s token rows of one
+// (sample, head); one wave per 32-query tile, keys streamed in chunks of 32 with a running max and denominator, so no
+// array bounds S.  Both products run on the exact-fp32 matrix instruction:
+//   S^T = k q^T   A = k (row: key, k: head channel), B = q^T / 8: a lane's 16 accumulator values are 16 keys of ONE query
+//                 (column = lane & 31), so the row max and sum are in-register plus one cross-half shuffle;
+//   O^T = v^T P^T A = v^T (row: head channel, k: key), B = P^T: accumulator value r of a lane is key (r & 3) + 8 (r >> 2)
+//                 + 4 (lane >> 5) of its query, which is exactly the B operand (k = lane >> 5) of a step that contracts
+//                 that key pair -- P goes from the first product's registers into the second without a round trip, and
+//                 the O^T columns are again one query per lane (the rescale by exp(m_old - m_new) is per lane).
+// Tail keys (S is no multiple of 32: ATC has 216) get the score -inf, hence the weight exactly 0; their addresses and
+// those of tail query rows are clamped to row S - 1 of the same sample and tail query rows are not stored.
+__global__ __launch_bounds__(64) void dit_attn_full_kernel(const DitAttnArgs a) {
+  const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+  const int S = a.Tp * a.Ns, nqt = (S + 31) / 32, E3 = 3 * a.E;
+  const int qt = blockIdx.x % nqt;
+  const long long bh = blockIdx.x / nqt;
+  const int h = (int)(bh % a.heads);
+  const long long b = bh / a.heads;
+  const float *base = a.qkv + b * S * E3 + h * 64;
+  const int q = qt * 32 + c;
+  float qv[32];   // q / 8 (exact) at the head channels 2 s + hf this lane feeds to step s
+  {
+    const float4 *qr = (const float4 *)(base + (long long)min(q, S - 1) * E3);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float4 v = qr[i];
+      qv[2 * i] = (hf ? v.y : v.x) * 0.125f;
+      qv[2 * i + 1] = (hf ? v.w : v.z) * 0.125f;
+    }
+  }
+  float m = -INFINITY, den = 0.f;
+  dit_f32x16 o0, o1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+  // Software pipeline: a chunk's V rows are requested before its q k^T chain and the next chunk's K row before its
+  // softmax and P v chain, so that each load has 32 matrix instructions to land behind.
+  float kc[32];   // the chunk's K operands, picked like qv
+  auto load_k = [&](int k0) {
+    const float4 *kr = (const float4 *)(base + a.E + (long long)min(k0 + c, S - 1) * E3);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const float4 v = kr[i];
+      kc[2 * i] = hf ? v.y : v.x;
+      kc[2 * i + 1] = hf ? v.w : v.z;
+    }
+  };
+  load_k(0);
+  const float *vb = base + 2 * a.E + c;
+  for (int k0 = 0; k0 < S; k0 += 32) {
+    float v0[16], v1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float *vr = vb + (long long)min(k0 + (r & 3) + 8 * (r >> 2) + 4 * hf, S - 1) * E3;
+      v0[r] = vr[0];
+      v1[r] = vr[32];
+    }
+    dit_f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kc[i], qv[i], s, 0, 0, 0);
+    load_k(k0 + 32);   // past the last chunk: row S - 1 again, never used
+    float cmax = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (k0 + (r & 3) + 8 * (r >> 2) + 4 * hf >= S) s[r] = -INFINITY;
+      cmax = fmaxf(cmax, s[r]);
+    }
+    cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+    const float mn = fmaxf(m, cmax);        // finite from the first chunk on: every chunk holds a key < S
+    const float alpha = expf(m - mn);       // first chunk: exp(-inf) = 0
+    float csum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = expf(s[r] - mn); csum += s[r]; }
+    csum += __shfl_xor(csum, 32, 64);
+    den = den * alpha + csum;
+    m = mn;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0[r], s[r], o0, 0, 0, 0);
+      o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[r], s[r], o1, 0, 0, 0);
+    }
+  }
+  if (q >= S) return;
+  // O^T: column = query, row = head channel (r & 3) + 8 (r >> 2) + 4 hf (+ 32 in o1): four consecutive channels per r >> 2
+  float *orow = a.out + (b * S + q) * a.E + h * 64 + 4 * hf;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    *(float4 *)(orow + 8 * g) = make_float4(o0[4 * g] / den, o0[4 * g + 1] / den, o0[4 * g + 2] / den, o0[4 * g + 3] / den);
+    *(float4 *)(orow + 32 + 8 * g) = make_float4(o1[4 * g] / den, o1[4 * g + 1] / den, o1[4 * g + 2] / den, o1[4 * g + 3] / den);
+  }
+}
+
 }  // namespace
 
 hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st) {
@@ -265,6 +362,15 @@ hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st) {
   if (a.Tp < 1 || a.Tp > TP_MAX || a.qs >= a.Tp) return hipErrorInvalidValue;
   const long long nw = (long long)a.B * a.Ns * a.heads;
   hipLaunchKernelGGL(dit_attn_temporal_kernel, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st) {
+  const long long S = (long long)a.Tp * a.Ns;
+  if (S < 1 || a.E != 64 * a.heads) return hipErrorInvalidValue;
+  const long long nblk = (long long)a.B * a.heads * ((S + 31) / 32);
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dit_attn_full_kernel, dim3((unsigned)nblk), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

@@ -3,12 +3,21 @@
 // sees the sampler geometry through cm_model::cfg and calls denoise(), which runs dit_forward instead of run_ops.
 // Kernels: cm_dit.hip.  Nothing here writes plan state at launch time: the two batch lanes of cm_sample_loop enqueue
 // dit_forward from two host threads on disjoint workspace rows.
+//
+// The DiT2D denoiser of arch "FM-DiT" (models/backbones/DiT2D.py) is the same plan with `full` set: t_patch_size 1 (its
+// per-frame Conv2d patchify is the Conv3d gather with one frame per slot, weight order (C, p, p), token order (frame,
+// h_p, w_p); its unpatchify is the scatter with pt = 1), one self-attention over all T_p * N_s tokens per block instead
+// of the spatial / temporal pair, 6 modulation chunks per block instead of 9, and 10 tensors per block instead of 14.
 
 struct cm_dit_plan {
   cm_dit_config cfg{};
+  bool full = false;           // DiT2D: one full self-attention per block (cm_model_create_dit2d)
   int Ns = 0, Tp = 0, qs = 0, tok = 0, Kp = 0, Nout = 0, ldmod = 0;
+  int nchunk() const { return full ? 6 : 9; }                  // modulation chunks per block
+  int per_block() const { return full ? 10 : 14; }             // state_dict tensors per block
   float *X = nullptr, *QKV = nullptr, *AO = nullptr, *Hm = nullptr;   // [max_batch * tok][D | 3D | D | mlp_hidden]
   float *modtab = nullptr;     // [1000][depth * 9D + 2D]: per block shift1 scale1 gate1 shift2 ... gate3, then the final layer's
+                               // (DiT2D: depth * 6D + 2D, shift1 scale1 gate1 shift2 scale2 gate2)
   std::vector<const float *> w;  // device copies of the state_dict tensors, in state_dict order
 };
 
@@ -16,8 +25,43 @@ namespace {
 
 // state_dict order of DiT4D_V4: own parameters first (spatial_pos_embed, temporal_pos_embed: DiT4D_V4.py:289-295), then the
 // child modules in registration order (dif_time_embeddings, time_proj, patch_embed, blocks, final_layer).
-constexpr int DIT_HEAD = 11;     // tensors before blocks.0
-constexpr int DIT_PER_BLOCK = 14;
+constexpr int DIT_HEAD = 11;     // tensors before blocks.0 (both variants)
+
+// state_dict order of DiT2D: spatial_pos_embed, temporal_pos_embed (DiT2D.py:196-201 -- registered after time_embeddings
+// and patch_embed, but a module's own parameters come first), then time_embeddings, time_proj, patch_embed, blocks,
+// final_layer.
+void dit2d_build_params(cm_model *m) {
+  const cm_dit_config &c = m->dit->cfg;
+  const int64_t D = c.hidden_size, tx = D * c.time_multiple, p = c.patch_size;
+  add_param(m, "spatial_pos_embed", {1, m->dit->Ns, D});
+  add_param(m, "temporal_pos_embed", {1, c.t_max, D});
+  add_param(m, "time_embeddings.time_blocks.0.weight", {TIME_ROWS, D});
+  add_param(m, "time_embeddings.time_blocks.1.weight", {tx, D});
+  add_param(m, "time_embeddings.time_blocks.1.bias", {tx});
+  add_param(m, "time_embeddings.time_blocks.3.weight", {tx, tx});
+  add_param(m, "time_embeddings.time_blocks.3.bias", {tx});
+  add_param(m, "time_proj.0.weight", {D, tx});
+  add_param(m, "time_proj.0.bias", {D});
+  add_param(m, "patch_embed.proj.weight", {D, c.in_channels, p, p});
+  add_param(m, "patch_embed.proj.bias", {D});
+  for (int i = 0; i < c.depth; ++i) {
+    const std::string b = "blocks." + std::to_string(i) + ".";
+    add_param(m, b + "attn.in_proj_weight", {3 * D, D});
+    add_param(m, b + "attn.in_proj_bias", {3 * D});
+    add_param(m, b + "attn.out_proj.weight", {D, D});
+    add_param(m, b + "attn.out_proj.bias", {D});
+    add_param(m, b + "mlp.0.weight", {c.mlp_hidden, D});
+    add_param(m, b + "mlp.0.bias", {c.mlp_hidden});
+    add_param(m, b + "mlp.3.weight", {D, c.mlp_hidden});
+    add_param(m, b + "mlp.3.bias", {D});
+    add_param(m, b + "adaLN_modulation.1.weight", {6 * D, D});
+    add_param(m, b + "adaLN_modulation.1.bias", {6 * D});
+  }
+  add_param(m, "final_layer.linear.weight", {m->dit->Nout, D});
+  add_param(m, "final_layer.linear.bias", {m->dit->Nout});
+  add_param(m, "final_layer.adaLN_modulation.1.weight", {2 * D, D});
+  add_param(m, "final_layer.adaLN_modulation.1.bias", {2 * D});
+}
 
 void dit_build_params(cm_model *m) {
   const cm_dit_config &c = m->dit->cfg;
@@ -63,6 +107,7 @@ cm::DitGemmArgs dit_gemm_args(int pro, int epi, long long M, int N, int K) {
 
 // Conditioning tables for all 1000 t (DiT4D_V4.py:363, 134-137, 216): e = time_blocks(t), c = SiLU(time_proj(e)); every
 // adaLN_modulation applies SiLU(c) before its Linear.  The table row t holds each block's 9 chunks and the final layer's 2.
+// DiT2D computes the same chain (DiT2D.py:275, 94-97, 117-119) with 6 chunks per block.
 int dit_build_tables(cm_model *m) {
   cm_dit_plan &d = *m->dit;
   const cm_dit_config &c = d.cfg;
@@ -82,11 +127,12 @@ int dit_build_tables(cm_model *m) {
   a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_SILU2, TIME_ROWS, D, tx);
   a.A = e; a.lda = tx; a.W = d.w[7]; a.bias = d.w[8]; a.Y = cs; a.ldy = D;
   CM_HIP(cm::launch_dit_gemm(a, st));
+  const int nch = d.nchunk(), pb = d.per_block();
   for (int i = 0; i <= c.depth; ++i) {
     const bool fin = i == c.depth;
-    const int wi = fin ? DIT_HEAD + DIT_PER_BLOCK * c.depth + 2 : DIT_HEAD + DIT_PER_BLOCK * i + 12;
-    a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, TIME_ROWS, fin ? 2 * D : 9 * D, D);
-    a.A = cs; a.lda = D; a.W = d.w[wi]; a.bias = d.w[wi + 1]; a.Y = d.modtab + (size_t)i * 9 * D; a.ldy = d.ldmod;
+    const int wi = fin ? DIT_HEAD + pb * c.depth + 2 : DIT_HEAD + pb * i + pb - 2;
+    a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, TIME_ROWS, fin ? 2 * D : nch * D, D);
+    a.A = cs; a.lda = D; a.W = d.w[wi]; a.bias = d.w[wi + 1]; a.Y = d.modtab + (size_t)i * nch * D; a.ldy = d.ldmod;
     CM_HIP(cm::launch_dit_gemm(a, st));
   }
   CM_HIP(hipStreamSynchronize(st));
@@ -156,9 +202,28 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
   a.x8 = m->x8 + (size_t)b0 * vox; a.W = d.w[9]; a.bias = d.w[10]; a.Y = X; a.ldy = D; a.spos = d.w[0]; a.tpos = d.w[1];
   CM_HIP(cm::launch_dit_gemm(a, st));
   cm::DitAttnArgs at{QKV, AO, B, d.Tp, d.Ns, d.qs, D, c.num_heads};
+  const int nch = d.nchunk(), pb = d.per_block();
   for (int i = 0; i < nblocks; ++i) {
-    const float *const *w = d.w.data() + DIT_HEAD + DIT_PER_BLOCK * i;
-    const int mo = i * 9 * D;
+    const float *const *w = d.w.data() + DIT_HEAD + pb * i;
+    const int mo = i * nch * D;
+    if (d.full) {
+      // self-attention over all tokens of the sample, gated residual on every row (DiT2D.py:104-106)
+      a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
+      a.A = X; a.lda = D; a.W = w[0]; a.bias = w[1]; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
+      CM_HIP(cm::launch_dit_gemm(a, st));
+      CM_HIP(cm::launch_dit_attn_full(at, st));
+      a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, D);
+      a.A = AO; a.lda = D; a.W = w[2]; a.bias = w[3]; a.Y = X; a.ldy = D; a.off_gate = mo + 2 * D;
+      CM_HIP(cm::launch_dit_gemm(a, st));
+      // MLP (:107-108)
+      a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_GELU, M, mlp, D);
+      a.A = X; a.lda = D; a.W = w[4]; a.bias = w[5]; a.Y = Hm; a.ldy = mlp; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
+      CM_HIP(cm::launch_dit_gemm(a, st));
+      a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, mlp);
+      a.A = Hm; a.lda = mlp; a.W = w[6]; a.bias = w[7]; a.Y = X; a.ldy = D; a.off_gate = mo + 5 * D;
+      CM_HIP(cm::launch_dit_gemm(a, st));
+      continue;
+    }
     // spatial self-attention (DiT4D_V4.py:160-169)
     a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
     a.A = X; a.lda = D; a.W = w[0]; a.bias = w[1]; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
@@ -185,12 +250,13 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
     CM_HIP(cm::launch_dit_gemm(a, st));
   }
   if (nblocks < c.depth) return 0;
-  // final layer + unpatchify, future slots only: slots < qs hold past frames only (:223-225, :93-99)
-  const float *const *wf = d.w.data() + DIT_HEAD + DIT_PER_BLOCK * c.depth;
+  // final layer + unpatchify, future slots only: slots < qs hold past frames only (:223-225, :93-99; DiT2D computes
+  // every frame and slices, DiT2D.py:292-296 -- rows are independent)
+  const float *const *wf = d.w.data() + DIT_HEAD + pb * c.depth;
   a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_UNPATCH, M, d.Nout, D);
   future_rows(a, nq);
   a.A = X; a.lda = D; a.W = wf[0]; a.bias = wf[1]; a.Y = m->eps_cl + (size_t)b0 * vox;
-  a.off_shift = c.depth * 9 * D; a.off_scale = c.depth * 9 * D + D;
+  a.off_shift = c.depth * nch * D; a.off_scale = c.depth * nch * D + D;
   CM_HIP(cm::launch_dit_gemm(a, st));
   return 0;
 }
@@ -202,7 +268,12 @@ int dit_cost(const cm_model *m, int B, double *flops, double *bytes) {
   const cm_dit_config &c = d.cfg;
   const double D = c.hidden_size, mlp = c.mlp_hidden, tok = d.tok, Ns = d.Ns, Tp = d.Tp, nq = d.Tp - d.qs;
   double f = 2.0 * tok * d.Kp * D;
-  const double blk = 2.0 * (2.0 * tok * D * 3.0 * D)          // two packed q|k|v projections
+  const double blk = d.full
+                   ? 2.0 * tok * D * 3.0 * D                    // packed q|k|v projection
+                     + 4.0 * tok * tok * D                      // q k^T and P V over all S = tok keys
+                     + 2.0 * tok * D * D                        // out-projection
+                     + 2.0 * (2.0 * tok * D * mlp)              // MLP
+                   : 2.0 * (2.0 * tok * D * 3.0 * D)          // two packed q|k|v projections
                      + 4.0 * Tp * Ns * Ns * D                   // spatial q k^T and P V
                      + 2.0 * tok * D * D                        // spatial out-projection
                      + 4.0 * Ns * nq * Tp * D                   // temporal q k^T and P V
@@ -253,7 +324,67 @@ int dit_debug_activation(cm_model *m, const char *name, float *h_out, int64_t ca
   return 0;
 }
 
+// The handle of an admitted configuration (the callers have checked it); `full`: the DiT2D variant.
+int dit_make_handle(const cm_dit_config &c, bool full, cm_model **out) {
+  if (c.device >= 0) {
+    int ndev = 0;
+    CM_HIP(hipGetDeviceCount(&ndev));
+    if (c.device >= ndev) return fail("device %d not available (%d devices)", c.device, ndev);
+  }
+  const int Ns = (c.rows / c.patch_size) * (c.cols / c.patch_size), Tp = (c.past_len + c.future_len) / c.t_patch_size;
+  auto m = std::make_unique<cm_model>();
+  m->cfg.in_channels = c.in_channels; m->cfg.out_channels = c.out_channels;
+  m->cfg.rows = c.rows; m->cfg.cols = c.cols; m->cfg.past_len = c.past_len; m->cfg.future_len = c.future_len;
+  m->cfg.time_multiple = c.time_multiple; m->cfg.max_batch = c.max_batch; m->cfg.device = c.device;
+  m->device = c.device;
+  m->dit = new cm_dit_plan;
+  cm_dit_plan &d = *m->dit;
+  d.cfg = c;
+  d.full = full;
+  d.Ns = Ns; d.Tp = Tp; d.qs = c.past_len / c.t_patch_size; d.tok = Tp * Ns;
+  d.Kp = c.in_channels * c.t_patch_size * c.patch_size * c.patch_size;
+  d.Nout = c.t_patch_size * c.out_channels * c.patch_size * c.patch_size;
+  d.ldmod = c.depth * d.nchunk() * c.hidden_size + 2 * c.hidden_size;
+  if (full) dit2d_build_params(m.get()); else dit_build_params(m.get());
+  if (m->device >= 0) {
+    DevGuard g(m->device);
+    CM_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    for (int i = 1; i < 4; ++i) {
+      CM_HIP(hipStreamCreateWithFlags(&m->lane_stream[i], hipStreamNonBlocking));
+      CM_HIP(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
+    }
+    CM_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
+  }
+  *out = m.release();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int cm_model_create_dit2d(const cm_dit2d_config *cfg, cm_model **out) {
+  if (!cfg || !out) return fail("null argument");
+  const cm_dit2d_config &c = *cfg;
+  if (c.in_channels < 1 || c.in_channels > 8 || c.out_channels < 1 || c.out_channels > 8) return fail("in/out channels must be in [1,8]");
+  if (c.max_batch < 1) return fail("max_batch must be >= 1");
+  if (c.depth < 1 || c.time_multiple < 1 || c.past_len < 1 || c.future_len < 1) return fail("depth, time_multiple, past_len and future_len must be >= 1");
+  if (c.patch_size < 1) return fail("patch_size must be >= 1");
+  if (c.rows < 1 || c.cols < 1 || c.rows % c.patch_size || c.cols % c.patch_size)
+    return fail("grid %dx%d is not divisible by patch_size %d (DiT2D.py:17-20)", c.rows, c.cols, c.patch_size);
+  const int L = c.past_len + c.future_len;
+  if (L > c.t_max) return fail("past_len + future_len = %d frames exceed the t_max = %d rows of temporal_pos_embed (DiT2D.py:244)", L, c.t_max);
+  if (c.num_heads < 1 || c.hidden_size < 1 || c.hidden_size % c.num_heads)
+    return fail("hidden_size %d is not divisible by num_heads %d", c.hidden_size, c.num_heads);
+  if (c.hidden_size / c.num_heads != 64) return fail("head dim %d: the DiT attention kernels are built for head dim 64", c.hidden_size / c.num_heads);
+  if (c.mlp_hidden < 64 || c.mlp_hidden % 64) return fail("mlp_hidden %d must be a positive multiple of 64", c.mlp_hidden);
+  const long long S = (long long)L * (c.rows / c.patch_size) * (c.cols / c.patch_size);
+  if (S > 1024) return fail("%lld tokens per sample ((past_len + future_len) * patches): the DiT2D plan admits at most 1024", S);
+  cm_dit_config v{};
+  v.in_channels = c.in_channels; v.out_channels = c.out_channels; v.rows = c.rows; v.cols = c.cols;
+  v.past_len = c.past_len; v.future_len = c.future_len; v.patch_size = c.patch_size; v.t_patch_size = 1;
+  v.hidden_size = c.hidden_size; v.depth = c.depth; v.num_heads = c.num_heads; v.mlp_hidden = c.mlp_hidden;
+  v.time_multiple = c.time_multiple; v.t_max = c.t_max; v.max_batch = c.max_batch; v.device = c.device;
+  return dit_make_handle(v, true, out);
+}
 
 extern "C" int cm_model_create_dit(const cm_dit_config *cfg, cm_model **out) {
   if (!cfg || !out) return fail("null argument");
@@ -276,33 +407,5 @@ extern "C" int cm_model_create_dit(const cm_dit_config *cfg, cm_model **out) {
   if (Ns > 64) return fail("%d spatial patches: the spatial attention kernel holds at most 64", Ns);
   if (Tp > 8) return fail("%d temporal slots: the temporal attention kernel holds at most 8", Tp);
   if (c.past_len / c.t_patch_size >= Tp) return fail("no future temporal slot: past_len / t_patch_size = %d of %d", c.past_len / c.t_patch_size, Tp);
-  if (c.device >= 0) {
-    int ndev = 0;
-    CM_HIP(hipGetDeviceCount(&ndev));
-    if (c.device >= ndev) return fail("device %d not available (%d devices)", c.device, ndev);
-  }
-  auto m = std::make_unique<cm_model>();
-  m->cfg.in_channels = c.in_channels; m->cfg.out_channels = c.out_channels;
-  m->cfg.rows = c.rows; m->cfg.cols = c.cols; m->cfg.past_len = c.past_len; m->cfg.future_len = c.future_len;
-  m->cfg.time_multiple = c.time_multiple; m->cfg.max_batch = c.max_batch; m->cfg.device = c.device;
-  m->device = c.device;
-  m->dit = new cm_dit_plan;
-  cm_dit_plan &d = *m->dit;
-  d.cfg = c;
-  d.Ns = Ns; d.Tp = Tp; d.qs = c.past_len / c.t_patch_size; d.tok = Tp * Ns;
-  d.Kp = c.in_channels * c.t_patch_size * c.patch_size * c.patch_size;
-  d.Nout = c.t_patch_size * c.out_channels * c.patch_size * c.patch_size;
-  d.ldmod = c.depth * 9 * c.hidden_size + 2 * c.hidden_size;
-  dit_build_params(m.get());
-  if (m->device >= 0) {
-    DevGuard g(m->device);
-    CM_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    for (int i = 1; i < 4; ++i) {
-      CM_HIP(hipStreamCreateWithFlags(&m->lane_stream[i], hipStreamNonBlocking));
-      CM_HIP(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
-    }
-    CM_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-  }
-  *out = m.release();
-  return 0;
+  return dit_make_handle(c, false, out);
 }

@@ -464,12 +464,14 @@ struct DitGemmArgs {
 };
 struct DitAttnArgs {
   const float *qkv;               // [B][T_p * N_s][3E] (q | k | v)
-  float *out;                     // spatial: [B][T_p * N_s][E]; temporal: [B][(T_p - qs) * N_s][E]
+  float *out;                     // spatial, full: [B][T_p * N_s][E]; temporal: [B][(T_p - qs) * N_s][E]
   int B, Tp, Ns, qs, E, heads;    // head dim E / heads = 64
 };
 hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st);
 hipError_t launch_dit_attn_spatial(const DitAttnArgs &a, hipStream_t st);
 hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st);
+// DiT2D: one self-attention over all T_p * N_s tokens of a sample (any count), on the fp32 matrix instruction
+hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st);
 
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.

@@ -189,7 +189,7 @@ struct cm_schedule {
 };
 
 struct cm_train_state;
-struct cm_dit_plan;   // cm_dit_host.inc: the DiT4D_V4 backbone (null on a UNet handle)
+struct cm_dit_plan;   // cm_dit_host.inc: the DiT4D_V4 or DiT2D backbone (null on a UNet handle)
 void cm_free_train_state(cm_train_state *t);  // cm_train_host.inc (host-side struct only; device buffers live in allocs)
 struct cm_model {
   cm_unet_config cfg{};   // DiT handle: the sampler geometry (channels, grid, frames, max_batch, device) only
@@ -2170,11 +2170,12 @@ std::vector<int> visit_order(const cm_schedule *s, const cm_sample_opts *o) {
 
 namespace {
 // entry points of the UNet plan that a DiT handle does not have
-int refuse_dit(const char *what) {
-  return fail("%s: not available on a DDPM-DiT (DiT4D_V4) handle, only on the UNet backbone", what);
+int refuse_dit(const cm_model *m, const char *what) {
+  return fail("%s: not available on a %s handle, only on the UNet backbone", what,
+              m->dit->full ? "FM-DiT (DiT2D)" : "DDPM-DiT (DiT4D_V4)");
 }
 }  // namespace
-#define CM_NOT_DIT(m, what) do { if ((m) && (m)->dit) return refuse_dit(what); } while (0)
+#define CM_NOT_DIT(m, what) do { if ((m) && (m)->dit) return refuse_dit(m, what); } while (0)
 
 // ================================================================================
 // C ABI
@@ -2317,7 +2318,7 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
 int cm_model_set_precision(cm_model *m, int32_t precision) {
   if (!m) return fail("null model handle");
   if (m->finalized) return fail("precision must be chosen before cm_model_finalize");
-  if (m->dit && precision != CM_PRECISION_F32) return refuse_dit("a precision other than CM_PRECISION_F32");
+  if (m->dit && precision != CM_PRECISION_F32) return refuse_dit(m, "a precision other than CM_PRECISION_F32");
   if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16 && precision != CM_PRECISION_F32R && precision != CM_PRECISION_F32X)
     return fail("unknown precision %d", precision);
   m->precision = precision;

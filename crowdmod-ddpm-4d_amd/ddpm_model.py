@@ -60,6 +60,8 @@ class DDPM_model:
         self.from_fixed_past = from_fixed_past
         self.device = int(device)
         self.seed = int(seed)
+        if arch not in self._ARCHS:
+            raise ValueError(f"Unknown Architecture {arch}")
         self.denoiser_cfg = self._get_denoiser_cfg()
         self.res = cfgmod.resolve(cfg, arch)
         self.denoiser = self._get_denoiser()
@@ -97,6 +99,15 @@ class DDPM_model:
                             patch_size=d.patch_size, hidden_size=d.hidden_size, depth=d.depth, num_heads=d.num_heads,
                             mlp_ratio=d.mlp_ratio, dropout_rate=d.dropout_rate, time_multiple=d.time_emb_mult,
                             condition=d.condition, device=self.device, max_batch=max(1, r.batch_size), seed=self.seed)
+        if self.arch == "FM-DiT":
+            # flow_matching.py:72-84: CONDITION and t_max are not passed on (DiT2D's defaults "Past" and 8)
+            from .dit import DiT2D
+            d = r.dit
+            return DiT2D(input_channels=self.mprops_count, output_channels=self.mprops_count, grid_rows=r.rows,
+                         grid_cols=r.cols, patch_size=d.patch_size, hidden_size=d.hidden_size, depth=d.depth,
+                         num_heads=d.num_heads, mlp_ratio=d.mlp_ratio, dropout_rate=d.dropout_rate,
+                         time_multiple=d.time_emb_mult, past_len=r.past_len, future_len=r.future_len,
+                         device=self.device, max_batch=max(1, r.batch_size), seed=self.seed)
         return UNet(input_channels=self.mprops_count, output_channels=self.mprops_count,
                     num_res_blocks=r.num_res_blocks, base_channels=r.base_ch,
                     base_channels_multiples=r.base_ch_mult, apply_attention=r.apply_attention,
@@ -352,6 +363,19 @@ class DDPM_model:
         self.denoiser.load_state_dict(checkpoint.load_model_state(model_fullname))
         return self
 
+    def _metrics_chains(self, pasts, sampler: DDPM, nb: int):
+        """The `nb` chains of one generate_metrics batch with the configured sampler (ddpm.py:371-377)."""
+        import logging
+        r = self.res
+        if r.sampler == "DDPM":
+            x, _ = self._generate_ddpm(pasts, sampler, nb)
+            logging.info("L1 norm %.2f using %s guidance", float(np.mean(np.abs(x[:, 0]))), r.guidance)
+        elif r.sampler == "DDIM":
+            x, _ = self._generate_ddim(pasts, np.arange(0, r.timesteps - 1, r.ddim_divider), sampler, nb)
+        else:
+            raise ValueError(f"{r.sampler} sampler not supported")
+        return x
+
     def generate_metrics(self, batched_test_data, chunkRepdPastSeq, metric, batches_to_use, samples_per_batch,
                          model_fullname=None, output_dir=None, *, rng: Optional[np.random.Generator] = None, eps=None):
         """ddpm.py:336-392: per test batch draw `samples_per_batch / chunkRepdPastSeq` past windows, repeat each
@@ -380,13 +404,7 @@ class DDPM_model:
             pasts, futures = past_test[idx], future_test[idx]
             nb = len(idx)
             logging.info("Computing sampling on batch %d: %d chains (%d pasts x %d repeats)", count + 1, nb, -(-nb // chunk), chunk)
-            if r.sampler == "DDPM":
-                x, _ = self._generate_ddpm(pasts, sampler, nb)
-                logging.info("L1 norm %.2f using %s guidance", float(np.mean(np.abs(x[:, 0]))), r.guidance)
-            elif r.sampler == "DDIM":
-                x, _ = self._generate_ddim(pasts, np.arange(0, r.timesteps - 1, r.ddim_divider), sampler, nb)
-            else:
-                raise ValueError(f"{r.sampler} sampler not supported")
+            x = self._metrics_chains(pasts, sampler, nb)
             preds.append(x)
             gts.append(futures)
             count += 1

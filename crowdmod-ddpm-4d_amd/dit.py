@@ -1,9 +1,10 @@
-"""Host-side mirror of the reference DiT4D_V4 denoiser (/root/reference/models/backbones/DiT4D_V4.py:228-375).
+"""Host-side mirrors of the reference DiT4D_V4 denoiser (/root/reference/models/backbones/DiT4D_V4.py:228-375, arch
+"DDPM-DiT") and of DiT2D (models/backbones/DiT2D.py:130-296 there, arch "FM-DiT").
 
 Same constructor arguments and call convention as the reference --
 `denoiser(future[B,C,H,W,F], t[B] int64, past[B,C,H,W,P]) -> [B,C,H,W,F]` -- and the `nn.Module` surface the DDPM
 driver touches (`eval/to/state_dict/load_state_dict`, `ensure` like `UNet.ensure`).  All arithmetic runs in
-libcrowdmod_hip.so (cm_model_create_dit, cm_dit.hip); inference only.
+libcrowdmod_hip.so (cm_model_create_dit / cm_model_create_dit2d, cm_dit.hip); inference only.
 """
 from __future__ import annotations
 
@@ -12,11 +13,16 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import dit_spec, native
+from . import dit2d_spec, dit_spec, native
 from .unet import _is_torch
 
 
 class DiT4D_V4:
+    _NAME = "DiT4D_V4"
+    _SPEC = dit_spec
+    _CREATE = "cm_model_create_dit"
+    _TABLE = "dif_time_embeddings.time_blocks.0.weight"   # the frozen sinusoid table: a buffer-like Embedding
+
     def __init__(self, input_channels=4, output_channels=4, grid_rows=12, grid_cols=36, past_len=5, future_len=3,
                  t_patch_size=2, patch_size=4, hidden_size=256, depth=6, num_heads=4, mlp_ratio=4.0, dropout_rate=0.1,
                  time_multiple=4, total_time_steps=1000, condition="Past", T_max=32, *, device: int = 0,
@@ -35,8 +41,11 @@ class DiT4D_V4:
         self.max_batch = int(max_batch)
         self._native_max_batch = 0
         self.training = False
-        self._shapes = dit_spec.param_shapes(self.cfg)
-        self._params: Dict[str, np.ndarray] = dit_spec.init_params(self.cfg, seed if seed is not None else 0)
+        self._init_state(seed)
+
+    def _init_state(self, seed):
+        self._shapes = self._SPEC.param_shapes(self.cfg)
+        self._params: Dict[str, np.ndarray] = self._SPEC.init_params(self.cfg, seed if seed is not None else 0)
         self._handle = None
 
     # -- nn.Module surface ---------------------------------------------------------
@@ -46,11 +55,11 @@ class DiT4D_V4:
 
     def train(self, mode: bool = True):
         if mode:
-            raise NotImplementedError("DiT4D_V4 training is not implemented on this path (inference only)")
+            raise NotImplementedError(f"{self._NAME} training is not implemented on this path (inference only)")
         return self.eval()
 
     def train_init(self, *a, **kw):
-        raise NotImplementedError("DiT4D_V4 training is not implemented on this path (inference only)")
+        raise NotImplementedError(f"{self._NAME} training is not implemented on this path (inference only)")
 
     def to(self, device=None):
         if isinstance(device, int) and device != self.device:
@@ -59,7 +68,7 @@ class DiT4D_V4:
         return self
 
     def parameters(self):
-        return [v for k, v in self._params.items() if k != "dif_time_embeddings.time_blocks.0.weight"]
+        return [v for k, v in self._params.items() if k != self._TABLE]
 
     def state_dict(self) -> Dict[str, np.ndarray]:
         return {k: v.copy() for k, v in self._params.items()}
@@ -73,7 +82,7 @@ class DiT4D_V4:
         missing = [k for k in self._shapes if k not in got]
         unexpected = [k for k in got if k not in self._shapes]
         if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for DiT4D_V4: missing keys {missing}, "
+            raise RuntimeError(f"Error(s) in loading state_dict for {self._NAME}: missing keys {missing}, "
                                f"unexpected keys {unexpected}")
         for k, shp in self._shapes.items():
             if k in got:
@@ -108,7 +117,7 @@ class DiT4D_V4:
         """Create (or re-create for a larger batch) the native model; the geometry is the constructor's."""
         g = self.cfg
         if (rows, cols, past_len, future_len) != (g.grid_rows, g.grid_cols, g.past_len, g.future_len):
-            raise ValueError(f"geometry {(rows, cols, past_len, future_len)} differs from the DiT4D_V4 built for "
+            raise ValueError(f"geometry {(rows, cols, past_len, future_len)} differs from the {self._NAME} built for "
                              f"{(g.grid_rows, g.grid_cols, g.past_len, g.future_len)}")
         if self._handle is not None and max(batch, self.max_batch) <= self._native_max_batch:
             return self._handle
@@ -117,7 +126,7 @@ class DiT4D_V4:
         L = native.lib()
         c = self.native_config(self.max_batch, self.device)
         h = C.c_void_p()
-        native.check(L.cm_model_create_dit(C.byref(c), C.byref(h)))
+        native.check(getattr(L, self._CREATE)(C.byref(c), C.byref(h)))
         try:
             for name, arr in self._params.items():
                 arr = np.ascontiguousarray(arr, dtype=np.float32)
@@ -134,7 +143,7 @@ class DiT4D_V4:
         return self.forward(future, t, past)
 
     def forward(self, future, t, past=None):
-        """DiT4D_V4.forward (DiT4D_V4.py:347-375), eval mode.  numpy in -> numpy out (host staging); torch CUDA
+        """DiT4D_V4.forward (DiT4D_V4.py:347-375) / DiT2D.forward (DiT2D.py:255-296), eval mode.  numpy in -> numpy out (host staging); torch CUDA
         tensors in -> torch CUDA tensor out (device pointers)."""
         if past is None:
             raise ValueError("condition='Past' needs the past frames")
@@ -181,3 +190,50 @@ class DiT4D_V4:
         f, b = C.c_double(), C.c_double()
         native.check(native.lib().cm_model_cost(self._handle, B, C.byref(f), C.byref(b)))
         return f.value, b.value
+
+
+class DiT2D(DiT4D_V4):
+    """The reference's DiT2D (DiT2D.py:152-168: same constructor arguments; `past_len` / `future_len`, which the
+    reference reads off the tensors of each call, size the native plan; they default to the 5 + 3 frames of every
+    reference config and follow the tensors of a call, see `ensure`).  Everything but the constructor and the native config is DiT4D_V4's."""
+    _NAME = "DiT2D"
+    _SPEC = dit2d_spec
+    _CREATE = "cm_model_create_dit2d"
+    _TABLE = "time_embeddings.time_blocks.0.weight"
+
+    def __init__(self, input_channels=4, output_channels=4, grid_rows=12, grid_cols=36, patch_size=4, hidden_size=256,
+                 depth=6, num_heads=4, mlp_ratio=4.0, dropout_rate=0.1, time_multiple=4, total_time_steps=1000,
+                 condition="Past", t_max=8, *, past_len: int = 5, future_len: int = 3, device: int = 0,
+                 max_batch: int = 64, seed: Optional[int] = 42):
+        if condition != "Past":
+            raise NotImplementedError("only condition='Past' (the configuration every reference config uses)")
+        if int(total_time_steps) != 1000:
+            raise NotImplementedError("total_time_steps other than 1000 (the reference never sets it)")
+        self.cfg = dit2d_spec.DiT2DConfig(int(input_channels), int(output_channels), int(grid_rows), int(grid_cols),
+                                          int(past_len), int(future_len), int(patch_size), int(hidden_size), int(depth),
+                                          int(num_heads), float(mlp_ratio), float(dropout_rate), int(time_multiple),
+                                          condition, int(t_max))
+        self.input_channels = self.cfg.input_channels
+        self.condition = condition
+        self.device = int(device)
+        self.max_batch = int(max_batch)
+        self._native_max_batch = 0
+        self.training = False
+        self._init_state(seed)
+
+    def native_config(self, max_batch: int, device: int) -> native.cm_dit2d_config:
+        c, g = native.cm_dit2d_config(), self.cfg
+        c.in_channels, c.out_channels = g.input_channels, g.output_channels
+        c.rows, c.cols, c.past_len, c.future_len = g.grid_rows, g.grid_cols, g.past_len, g.future_len
+        c.patch_size, c.hidden_size, c.depth = g.patch_size, g.hidden_size, g.depth
+        c.num_heads, c.mlp_hidden, c.time_multiple, c.t_max = g.num_heads, g.mlp_hidden, g.time_multiple, g.t_max
+        c.max_batch, c.device = int(max_batch), int(device)
+        return c
+
+    def ensure(self, rows: int, cols: int, past_len: int, future_len: int, batch: int):
+        """As DiT4D_V4.ensure; the frame counts follow the call, as in the reference (no parameter depends on them)."""
+        if (past_len, future_len) != (self.cfg.past_len, self.cfg.future_len):
+            import dataclasses
+            self._release()
+            self.cfg = dataclasses.replace(self.cfg, past_len=int(past_len), future_len=int(future_len))
+        return super().ensure(rows, cols, past_len, future_len, batch)

@@ -1,7 +1,7 @@
-"""Host-side mirror of the reference's flow-matching driver on the UNet backbone
-(/root/reference/models/flow_matching/flow_matching.py:14-250, arch "FM-UNet").
+"""Host-side mirror of the reference's flow-matching driver
+(/root/reference/models/flow_matching/flow_matching.py:14-250, archs "FM-UNet" and "FM-DiT").
 
-The velocity predictor is the same native UNet; sampling is the Euler integrator
+The velocity predictor is the same native UNet, or the native DiT2D (dit.py; sampling only); sampling is the Euler integrator
     x <- x + (1/N) u(x, idx_i, past),  t_i = linspace(0,1,N)[i],  idx_i = clamp(t_i * TIME_MAX_POS).long()
 run as ONE device-resident loop (cm_sample_loop with CM_SAMPLER_FM_EULER); the reference maps the
 "Heun" integrator name to the Euler routine as well (flow_matching.py:44-47), and so does this class.
@@ -21,7 +21,7 @@ from .diffusion import DDPM
 
 
 class FM_model(DDPM_model):
-    _ARCHS = ("FM-UNet",)
+    _ARCHS = ("FM-UNet", "FM-DiT")
 
     def __init__(self, cfg, arch, mprops_count, output_dir=None, from_fixed_past=False, *, device: int = 0, seed: int = 42):
         super().__init__(cfg, arch, mprops_count, output_dir, from_fixed_past, device=device, seed=seed)
@@ -105,7 +105,17 @@ class FM_model(DDPM_model):
                                           epoch_tag, self.w_type)
         return os.path.join(self.cfg.DATA_FS.SAVE_DIR, name)
 
+    def _metrics_chains(self, pasts, sampler, nb):
+        """flow_matching.py:306-333: generate_metrics draws its chains with the configured integrator."""
+        try:
+            integrator = self.integrators[self.integrator]
+        except KeyError:
+            raise ValueError(f"Unsupported INTEGRATOR '{self.integrator}'. Available: {list(self.integrators.keys())}")
+        return integrator(pasts, nb)
+
     def train(self, batched_train_data, baseline_ckpt=None, *, log=None, grad_sync=None, save=True, loss_sync=None):
+        if self.arch == "FM-DiT":
+            raise NotImplementedError(f"training {self.arch} is not implemented on this path (sampling only)")
         keep = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
         self._keep_override = keep
         return super().train(batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save,

@@ -42,6 +42,15 @@ class cm_dit_config(C.Structure):
     ]
 
 
+class cm_dit2d_config(C.Structure):
+    _fields_ = [
+        ("in_channels", C.c_int32), ("out_channels", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+        ("past_len", C.c_int32), ("future_len", C.c_int32), ("patch_size", C.c_int32),
+        ("hidden_size", C.c_int32), ("depth", C.c_int32), ("num_heads", C.c_int32), ("mlp_hidden", C.c_int32),
+        ("time_multiple", C.c_int32), ("t_max", C.c_int32), ("max_batch", C.c_int32), ("device", C.c_int32),
+    ]
+
+
 class cm_sample_opts(C.Structure):
     _fields_ = [
         ("sampler", C.c_int32), ("guidance", C.c_int32), ("lambda_guidance", C.c_float),
@@ -73,6 +82,7 @@ SIGNATURES = {
     "cm_device_synchronize": (C.c_int, [C.c_int]),
     "cm_model_create": (C.c_int, [C.POINTER(cm_unet_config), C.POINTER(_P)]),
     "cm_model_create_dit": (C.c_int, [C.POINTER(cm_dit_config), C.POINTER(_P)]),
+    "cm_model_create_dit2d": (C.c_int, [C.POINTER(cm_dit2d_config), C.POINTER(_P)]),
     "cm_model_destroy": (C.c_int, [_P]),
     "cm_model_num_params": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "cm_model_param_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

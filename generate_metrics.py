@@ -32,16 +32,18 @@ def main(argv=None):
     ap.add_argument('--arch', type=str, default='DDPM-UNet')
     ap.add_argument('--data-npy', type=str, default=None, help='test sequences [N,C,ROWS,COLS,T] (.npy)')
     ap.add_argument('--test-windows', type=int, default=None, help='synthetic test windows per batch (default: BATCH_SIZE)')
-    ap.add_argument('--timesteps', type=int, default=None, help='override MODEL.DDPM.TIMESTEPS (smoke runs)')
+    ap.add_argument('--timesteps', type=int, default=None, help='override MODEL.DDPM.TIMESTEPS, or MODEL.FM.INTEGRATOR_STEPS.EULER for FM-DiT (smoke runs)')
     ap.add_argument('--device', type=int, default=0)
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
-    if args.arch not in ("DDPM-UNet", "DDPM-DiT"):
-        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet and DDPM-DiT on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-DiT"):
+        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet, DDPM-DiT and FM-DiT on this path")
     from crowdmod_ddpm_4d_amd.ddpm_model import DDPM_model
     from generate_samples import model_fullname, windows
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
-    if args.timesteps:
+    if args.timesteps and args.arch == "FM-DiT":
+        cfg.MODEL.FM.INTEGRATOR_STEPS.EULER = int(args.timesteps)
+    elif args.timesteps:
         cfg.MODEL.DDPM.TIMESTEPS = int(args.timesteps)
     res = cfgmod.resolve(cfg, args.arch)
     mprops = 3   # generate_metrics.py:60 of the reference
@@ -51,8 +53,13 @@ def main(argv=None):
     else:
         samples_per_batch, chunk = res.batch_size * args.chunk_repd_past_seq, args.chunk_repd_past_seq
     out_dir = os.path.join(cfg.DATA_FS.get("OUTPUT_DIR", "output"), "metrics")
-    model = DDPM_model(cfg, args.arch, mprops, output_dir=out_dir, device=args.device)
-    ckpt = model_fullname(cfg, args.arch, args.model_sample_to_load)
+    if args.arch == "FM-DiT":
+        from crowdmod_ddpm_4d_amd.flow_matching import FM_model
+        model = FM_model(cfg, args.arch, mprops, output_dir=out_dir, device=args.device)
+        ckpt = model.checkpoint_path(args.model_sample_to_load)
+    else:
+        model = DDPM_model(cfg, args.arch, mprops, output_dir=out_dir, device=args.device)
+        ckpt = model_fullname(cfg, args.arch, args.model_sample_to_load)
     if os.path.isfile(ckpt):
         logging.info("model full name: %s", ckpt)
         model.load_checkpoint(ckpt)

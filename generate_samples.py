@@ -62,18 +62,18 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
-    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-UNet"):
-        raise SystemExit(f"{args.arch}: only DDPM-UNet, DDPM-DiT and FM-UNet are implemented on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-UNet", "FM-DiT"):
+        raise SystemExit(f"{args.arch}: only DDPM-UNet, DDPM-DiT, FM-UNet and FM-DiT are implemented on this path")
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
     res = cfgmod.resolve(cfg, args.arch)
     mprops = 3  # generate_samples.py:76 of the reference
-    if args.arch == "FM-UNet":
+    if args.arch.startswith("FM-"):
         from crowdmod_ddpm_4d_amd.flow_matching import FM_model as Model
     else:
         Model = DDPM_model
     model = Model(cfg, args.arch, mprops, output_dir=cfg.DATA_FS.get("OUTPUT_DIR", "output"),
                   from_fixed_past=args.from_fixed_past, device=args.device)
-    ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch == "FM-UNet" else \
+    ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch.startswith("FM-") else \
         model_fullname(cfg, args.arch, args.model_sample_to_load)
     if os.path.isfile(ckpt):
         logging.info("model full name: %s", ckpt)

@@ -77,6 +77,26 @@ typedef struct cm_dit_config {
   int32_t device;                         /* HIP device ordinal; < 0: host-only handle            */
 } cm_dit_config;
 
+/* Hyper-parameters of reference DiT2D.__init__ (models/backbones/DiT2D.py:152-168) plus the tensor geometry, as FM_model
+ * builds it for arch "FM-DiT" (models/flow_matching/flow_matching.py:72-84): one patch embedding per frame, one
+ * self-attention over all (past_len + future_len) * (rows / patch_size) * (cols / patch_size) tokens of a sample per
+ * block.  The handle is the same opaque cm_model and serves the entry points a cm_dit_config handle serves. */
+typedef struct cm_dit2d_config {
+  int32_t in_channels;                    /* mprops_count                                        */
+  int32_t out_channels;
+  int32_t rows, cols;                     /* MACROPROPS.ROWS / COLS (multiples of patch_size)    */
+  int32_t past_len, future_len;           /* DATASET.PAST_LEN / FUTURE_LEN                       */
+  int32_t patch_size;                     /* PATCH_SIZE                                          */
+  int32_t hidden_size;                    /* HIDDEN_SIZE = num_heads * 64                        */
+  int32_t depth;                          /* DEPTH                                               */
+  int32_t num_heads;                      /* NUM_HEADS                                           */
+  int32_t mlp_hidden;                     /* int(HIDDEN_SIZE * MLP_RATIO), a multiple of 64      */
+  int32_t time_multiple;                  /* TIME_EMB_MULT                                       */
+  int32_t t_max;                          /* rows of temporal_pos_embed (constructor default 8, which FM_model keeps) */
+  int32_t max_batch;                      /* workspace is sized for this batch                   */
+  int32_t device;                         /* HIP device ordinal; < 0: host-only handle            */
+} cm_dit2d_config;
+
 /* ---- errors / info ------------------------------------------------------ */
 const char *cm_last_error(void);
 int cm_abi_version(void);
@@ -98,6 +118,11 @@ int cm_model_create(const cm_unet_config *cfg, cm_model **out);
  * than temporal_pos_embed has (t_max / t_patch_size), hidden_size not divisible by num_heads, a head dim other than 64,
  * mlp_hidden not a multiple of 64, more than 64 spatial patches or 8 temporal slots. */
 int cm_model_create_dit(const cm_dit_config *cfg, cm_model **out);
+/* DiT2D.__init__ (DiT2D.py:152-214): 15 + 10 * depth state_dict tensors in the reference's order.  Refused with a status
+ * that names the limit: channels outside [1,8], a grid not divisible by patch_size, past_len + future_len above t_max
+ * (DiT2D.py:244), hidden_size not divisible by num_heads, a head dim other than 64, mlp_hidden not a positive multiple
+ * of 64, more than 1024 tokens per sample.  There is no limit on the patches per frame. */
+int cm_model_create_dit2d(const cm_dit2d_config *cfg, cm_model **out);
 int cm_model_destroy(cm_model *m);
 /* state_dict() enumeration: names and shapes are the reference's (169 tensors
  * for config/ATC.yml; conv weights [Co,Ci,kH,kW,kL]). */
@@ -215,7 +240,8 @@ typedef struct cm_sample_opts {
                              after the loop has finished, with a non-zero status (and the count in
                              cm_last_error) if any element is NaN / Inf -- the sampler-output health check
                              (the reference's analogue is the NaN stop of its training loop, ddpm.py:183-192) */
-  /* CM_SAMPLER_FM_EULER -- FM_model.sampling_with_euler (models/flow_matching/flow_matching.py:203-224):
+  /* CM_SAMPLER_FM_EULER -- FM_model.sampling_with_euler (models/flow_matching/flow_matching.py:203-224), on any
+   * denoiser handle (UNet, DiT4D_V4, DiT2D):
    * x <- x + (1/N) u(x, idx_i, past) for t_i = linspace(0,1,N)[i], idx_i = clamp(t_i * TIME_MAX_POS, 0,
    * TIME_MAX_POS-1) truncated; the schedule handle is not consulted. */
   int32_t fm_steps;        /* cfg.MODEL.FM.INTEGRATOR_STEPS.EULER                 */

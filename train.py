@@ -59,7 +59,7 @@ def main():
     ap.add_argument('--device', type=int, default=None)
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
-    if args.arch not in ("DDPM-UNet", "FM-UNet"):
+    if args.arch not in ("DDPM-UNet", "FM-UNet", "FM-DiT"):   # FM-DiT: FM_model.train raises NotImplementedError
         raise SystemExit(f"{args.arch}: only the UNet-backbone generators (DDPM-UNet, FM-UNet) are implemented on this path")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", 0))
@@ -72,7 +72,7 @@ def main():
     if args.epochs is not None and res.train is not None:
         res.train["EPOCHS"] = int(args.epochs)
     mprops = 3  # train.py:61 of the reference
-    model = (FM_model if args.arch == "FM-UNet" else DDPM_model)(cfg, args.arch, mprops, device=device)
+    model = (FM_model if args.arch.startswith("FM-") else DDPM_model)(cfg, args.arch, mprops, device=device)
     if args.epochs is not None:
         model.res = res
     nparams = sum(int(np.prod(v.shape)) for k, v in model.denoiser.state_dict().items()
