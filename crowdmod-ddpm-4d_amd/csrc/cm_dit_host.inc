@@ -288,8 +288,8 @@ int dit_cost(const cm_model *m, int B, double *flops, double *bytes) {
 }
 
 // `le`: what a cm_sample_loop step leaves out at the ends of the UNet (LoopEnds; null: the whole forward)
-int denoise(cm_model *m, int B, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
-  return m->dit ? dit_forward(m, B, st, b0, m->dit->cfg.depth) : run_ops(m, B, st, b0, slab, le);
+int denoise(cm_model *m, const FwdPlan &plan, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
+  return m->dit ? dit_forward(m, plan.ctx.B, st, b0, m->dit->cfg.depth) : run_ops(m, plan, st, b0, slab, le);
 }
 
 // cm_debug_activation of a DiT handle: "patch_embed" or "blocks.<i>" -> the residual stream [B][T_p * N_s][D] after that

@@ -350,7 +350,7 @@ Op route_class_op(int rc, int precision) {
   static float frag[4];
   static Act src, skip, out;
   const bool p32 = precision == CM_PRECISION_F32, p16 = precision == CM_PRECISION_F16;
-  src.part = frag; src.nslots = 8; skip.C = 64; out.C = 64;
+  src.part = frag; skip.C = 64; out.C = 64;
   Op op;
   op.kind = OP_CONV; op.cls = K_CONV3;
   op.in0 = &src; op.out_act = &out;
@@ -367,7 +367,10 @@ Op route_class_op(int rc, int precision) {
       EXPECT(resolve_conv(nullptr, op) == 0 && op.wino && op.MB == 4);        // (a Winograd op that fits its tile touches no device)
       if (!p16) { EXPECT(cm::conv_wino_b6_ok(a.bz, a.by, a.bx, a.Co, a.Zo)); op.d_wwino_b6 = frag; }
       if (p32) op.d_wwino_h2 = frag;
-      if (p16) { op.d_wwino16 = frag; op.f16d = true; op.d_w16d = frag; }     // (Z >= 4 on both grids: the direct f16 kernel)
+      if (p16) {                                                              // (Z >= 4 on both grids: the direct f16 kernel)
+        op.d_wwino16 = frag; op.f16d = true; op.d_w16d = frag;
+        EXPECT(cm::conv_f16d_pick(a.Zo, a.Yo, a.Xo, &op.f16d_bz, &op.f16d_by, &op.f16d_bx, &op.f16d_mbw));
+      }
       if (skipc) { op.d_s2w = op.d_bias_fused = frag; op.skip0 = &skip; op.pm_off = 0; if (p16) op.d_w16d_skip = frag; }
       break;
     }
@@ -388,6 +391,7 @@ Op route_class_op(int rc, int precision) {
     case RC_UPS_STATS: case RC_UPS_NO_STATS:
       grid(8, 12, 36, 64, 64); a.Zs = 4; a.Ys = 6; a.Xs = 18; a.par = 1; a.ntaps = 8; a.td = 2; op.stat_act = &out; op.NB = 2;
       op.ups = true;
+      EXPECT(cm::conv_ups_pick(a.Zs, a.Ys, a.Xs, &op.ups_tz, &op.ups_ty, &op.ups_tx, &op.ups_mbw, &op.ups_planes));
       if (!p16) op.d_wups_b6 = frag;
       if (p32) op.d_wups_h2 = frag;
       if (p16) { op.d_wups16 = frag; op.d_wfrag16 = frag; }
@@ -448,8 +452,12 @@ void test_conv_route() {
             for (int dbg = 0; dbg < 3; ++dbg) {   // plain, dbg_raw, dbg_raw + dbg_h2
               Op op = route_class_op(rc, plans[pi]);
               op.h2_off = off; op.dbg_raw = dbg >= 1; op.dbg_h2 = dbg == 2;
-              const bool src_stats = rc != RC_UPS_NO_STATS;
-              const ConvRoute r = conv_route(op, plans[pi], train, stale, src_stats);
+              const bool src_stats = rc != RC_UPS_NO_STATS;            // does an earlier op of the forward write the source's slots?
+              FwdCtx ctx;
+              ctx.precision = plans[pi]; ctx.train_fwd = train; ctx.h2_stale = stale;
+              OpPlan planned;
+              EXPECT(plan_conv(op, ctx, src_stats ? 8 : 0, &planned).empty());
+              const ConvRoute r = planned.route;
               ++walked;
               // the table: h2 where the default plan has it and nothing withdraws it, else what F32X runs
               const bool h2_live = !stale && !off && dbg != 1;
@@ -461,7 +469,7 @@ void test_conv_route() {
               if (train) EXPECT(r.form != FORM_F16 && r.form != FORM_B3 && r.kernel != CONV_F16D && r.kernel != CONV_1X1_F16 && r.kernel != CONV_NONE);
               if (train && r.kernel == CONV_QR) EXPECT(op.train_qr && op.d_wqr_b6);
               if (op.ks > 1) EXPECT(r.kernel == CONV_QR || r.kernel == CONV_KSPLIT);
-              // the kernel FAMILY depends on the plan and on training / inference only: what plan_slot_consumers and plan_h16 decide
+              // the kernel FAMILY depends on the plan and on training / inference only: what plan_h16 decides
               // at finalize still holds when h2 goes stale, a bound is withdrawn or a debug hook steers the form
               EXPECT(r.kernel == conv_route(op, plans[pi], train, false).kernel);
               // f16 tensors: plan_h16 and the launch-time check ask route_takes_h16; it accepts what ConvArgs::h16 documents, no more
@@ -495,6 +503,273 @@ void test_conv_route() {
     walked += 3;
   }
   printf("test_conv_route: %d combinations walked\n", walked);
+}
+
+// plan_forward: everything a forward's launches depend on -- which ops run, each conv's route, the slot count of every statistics
+// tensor, who finalises each GroupNorm -- decided in one pure walk.  Hand-built op lists (route_class_op wired through Act objects
+// and OP_GNFIN ops) are asserted against written-out tables for the four precision plans x inference / training, and every plan
+// against the invariants of check_plan.
+struct PlanList {
+  std::vector<std::unique_ptr<Act>> acts;   // (the ops point into them)
+  std::vector<Op> ops;
+  Act *act(int C, int Z, int Y, int X) {
+    static float buf[4];
+    acts.push_back(std::make_unique<Act>());
+    Act *a = acts.back().get();
+    a->C = C; a->Z = Z; a->Y = Y; a->X = X; a->part = a->cnt = buf;
+    return a;
+  }
+  // a conv of class `rc`: sources in0 (+ in1), output `out` (its statistics too when the class writes them), normalised by op `gn`
+  int conv(int rc, int precision, const Act *in0, Act *out, int gn = -1, const Act *in1 = nullptr) {
+    Op op = route_class_op(rc, precision);
+    op.in0 = in0; op.in1 = in1; op.out_act = out;
+    if (op.stat_act) op.stat_act = out;
+    op.gn_op = gn;
+    if (gn < 0) op.ca.gn = nullptr;
+    else if (op.qr) ops[gn].qr_consumer = true;               // (add_conv)
+    op.label = "conv" + std::to_string(ops.size());
+    ops.push_back(op);
+    return (int)ops.size() - 1;
+  }
+  int gnfin(const Act *g0, const Act *g1 = nullptr) {
+    Op op;
+    op.kind = OP_GNFIN; op.cls = K_NORM; op.g0 = g0; op.g1 = g1; op.label = "gn" + std::to_string(ops.size());
+    ops.push_back(op);
+    return (int)ops.size() - 1;
+  }
+};
+
+bool operator==(const OpPlan &a, const OpPlan &b) {
+  return a.launch == b.launch && a.route.kernel == b.route.kernel && a.route.form == b.route.form && a.ns_out == b.ns_out && a.ns0 == b.ns0 &&
+         a.ns1 == b.ns1 && a.fin == b.fin && a.carries == b.carries;
+}
+
+FwdCtx plan_ctx(int precision, bool train, bool stale = false, int B = 2) {
+  FwdCtx c;
+  c.precision = precision; c.train_fwd = train; c.h2_stale = stale; c.B = B;
+  return c;
+}
+
+// the invariants of every plan
+void check_plan(const std::vector<Op> &ops, const FwdCtx &ctx) {
+  const FwdPlan P = plan_forward(ops, ctx);
+  EXPECT(P.err.empty() && P.ops.size() == ops.size());
+  EXPECT(plan_forward(ops, ctx).ops == P.ops);                 // planning twice gives equal plans
+  const int n = (int)ops.size();
+  std::map<const Act *, int> written;                          // by the launched ops so far
+  for (int i = 0; i < n; ++i) {
+    const Op &op = ops[i];
+    const OpPlan &p = P.ops[i];
+    const bool in_ctx = op.kind == OP_ATTNBLK ? !ctx.train_fwd : !(op.in_attn_block && !ctx.train_fwd);
+    if (!in_ctx) { EXPECT(!p.launch && p.fin == FIN_NONE && p.carries < 0 && p.ns_out == 0); continue; }
+    if (op.kind == OP_CONV) {
+      EXPECT(p.route.kernel == conv_route(op, ctx.precision, ctx.train_fwd, ctx.h2_stale).kernel);   // the family: conv_route's, always
+      EXPECT(p.launch == (p.route.kernel != CONV_NONE));
+      if (p.route.kernel == CONV_UPS && p.route.form == FORM_H2) EXPECT(p.ns0 >= 1 && written.count(op.in0) && written[op.in0] == p.ns0);
+    }
+    if (p.carries >= 0) {
+      EXPECT(p.launch && p.carries > i && ops[p.carries].kind == OP_GNFIN && P.ops[p.carries].fin == FIN_COMBINE);
+      EXPECT(op.kind == OP_ATTNBLK || p.route.kernel == CONV_KSPLIT);
+    }
+    if (p.ns_out) {
+      EXPECT(p.launch && p.ns_out >= 1 && p.ns_out <= MAX_SLOTS);
+      written[op.kind == OP_CONV ? op.stat_act : op.kind == OP_ATTNBLK ? op.ab_out : op.act] = p.ns_out;
+    }
+    if (op.kind != OP_GNFIN) { EXPECT(p.fin == FIN_NONE); continue; }
+    // exactly one disposition, and its counterpart agrees
+    EXPECT(p.fin != FIN_NONE && p.launch == (p.fin == FIN_ALONE));
+    int carriers = 0, cons = -1, ncons = 0;
+    for (int j = 0; j < n; ++j) {
+      if (P.ops[j].carries == i) ++carriers;
+      if (ops[j].kind == OP_CONV && ops[j].gn_op == i && P.ops[j].launch) { if (cons < 0) cons = j; ++ncons; }
+    }
+    EXPECT(carriers == (p.fin == FIN_COMBINE ? 1 : 0));
+    // a finalisation left to a consumer has exactly one launched consumer, and that launch does take the slots
+    if (p.fin == FIN_QR || p.fin == FIN_WINO) EXPECT(ncons == 1);
+    if (p.fin == FIN_WINO) EXPECT(cons > i && wino_merges(ops[cons], P.ops[cons].route, ctx.B));
+    if (p.fin == FIN_QR) EXPECT(!ctx.train_fwd && op.qr_consumer && cons > i && P.ops[cons].route.kernel == CONV_QR);
+    if (p.fin == FIN_WINO) EXPECT(!ctx.train_fwd && cons > i && P.ops[cons].route.form != FORM_FP32 && P.ops[cons].route.kernel == CONV_WINO && p.ns0 <= 16 && p.ns1 <= 16 &&
+                                  (!op.g1 || op.g1->V() == op.g0->V()));
+    if (op.qr_consumer && !ctx.train_fwd) EXPECT(p.fin == FIN_QR);
+    // every slot count a consumer reads was assigned by an earlier launched op
+    EXPECT(written.count(op.g0) && p.ns0 == written[op.g0] && p.ns0 >= 1 && p.ns0 <= MAX_SLOTS);
+    if (op.g1) EXPECT(written.count(op.g1) && p.ns1 == written[op.g1] && p.ns1 >= 1 && p.ns1 <= MAX_SLOTS);
+  }
+}
+
+void test_forward_plan() {
+  const int plans[4] = {CM_PRECISION_F32, CM_PRECISION_F32X, CM_PRECISION_F32R, CM_PRECISION_F16};
+  const ConvForm infer_form[4] = {FORM_H2, FORM_B6, FORM_B3, FORM_FP32};   // of the whole-sample quarter-resolution conv
+  int walked = 0;
+  for (int pi = 0; pi < 4; ++pi) {
+    const int prec = plans[pi];
+    const bool p16 = prec == CM_PRECISION_F16;
+    // ---- K-split conv -> GNFIN -> quarter-resolution conv -> GNFIN -> quarter-resolution conv -------------------------------------
+    // at 2 x 3 x 9 (54 voxels: two slots from either kernel) and at 2 x 6 x 6 (72 voxels: three slots from a K-split combine, four
+    // from conv_qr2, and too many voxels for a combine to carry a finalisation)
+    for (int tq = 0; tq < 2; ++tq)
+      for (int big = 0; big < 2; ++big) {
+        PlanList L;
+        const int Y = big ? 6 : 3, X = big ? 6 : 9, ks_ns = big ? 3 : 2, qr_ns = big ? 4 : 2;
+        Act *s = L.act(64, 4, 2 * Y, 2 * X), *a = L.act(128, 2, Y, X), *b = L.act(128, 2, Y, X), *c = L.act(128, 2, Y, X);
+        const int qclass = tq ? RC_QUARTER : RC_QUARTER_NO_TRAIN_QR;
+        L.conv(RC_KSPLIT, prec, s, a);                 // 0
+        L.gnfin(a);                                    // 1
+        L.conv(qclass, prec, a, b, 1);                 // 2
+        L.gnfin(b);                                    // 3
+        L.conv(qclass, prec, b, c, 3);                 // 4
+        for (int i : {0, 2, 4}) {
+          cm::ConvArgs &g = L.ops[i].ca;
+          g.Yo = Y; g.Xo = X; g.Ys = (i ? 1 : 2) * Y; g.Xs = (i ? 1 : 2) * X;
+        }
+        for (int stale = 0; stale < 2; ++stale) {
+          const FwdCtx ctx = plan_ctx(prec, false, stale);
+          check_plan(L.ops, ctx);
+          const FwdPlan P = plan_forward(L.ops, ctx);
+          // inference: both finalisations belong to their conv_qr2 consumers, the combine carries nothing
+          EXPECT(P.ops[0].route.kernel == CONV_KSPLIT && P.ops[0].ns_out == ks_ns && P.ops[0].carries == -1);
+          EXPECT(P.ops[1].fin == FIN_QR && !P.ops[1].launch && P.ops[1].ns0 == ks_ns);
+          EXPECT(P.ops[2].route.kernel == CONV_QR && P.ops[2].ns_out == qr_ns);
+          if (!big) EXPECT(P.ops[2].route.form == ((pi == 0 && stale) ? FORM_B6 : infer_form[pi]));
+          EXPECT(P.ops[3].fin == FIN_QR && P.ops[3].ns0 == qr_ns && P.ops[4].route.kernel == CONV_QR && P.ops[4].carries == -1);
+          ++walked;
+        }
+        const FwdCtx ctx = plan_ctx(prec, true);
+        check_plan(L.ops, ctx);
+        const FwdPlan P = plan_forward(L.ops, ctx);
+        // training: the K-split conv's combine carries the finalisation (the backward needs its mean / rstd rows) where the geometry
+        // allows; with train_qr (32-bit plans) the consumer is conv_qr2, a one-pass kernel, so the next finalisation launches alone;
+        // without, the consumer is the K-split kernel -- with ITS slot count, not the inference plan's -- and its combine carries the next
+        const bool qr_trains = tq && !p16;
+        EXPECT(P.ops[0].route.kernel == CONV_KSPLIT && P.ops[0].ns_out == ks_ns && P.ops[0].carries == (big ? -1 : 1));
+        EXPECT(P.ops[1].fin == (big ? FIN_ALONE : FIN_COMBINE) && P.ops[1].launch == (big != 0) && P.ops[1].ns0 == ks_ns);
+        EXPECT(P.ops[2].route.kernel == (qr_trains ? CONV_QR : CONV_KSPLIT) && P.ops[2].ns_out == (qr_trains ? qr_ns : ks_ns));
+        if (!big) EXPECT(P.ops[2].route.form == (qr_trains ? FORM_B6 : FORM_FP32));
+        const bool carried = !qr_trains && !big;
+        EXPECT(P.ops[2].carries == (carried ? 3 : -1) && P.ops[3].fin == (carried ? FIN_COMBINE : FIN_ALONE) && P.ops[3].launch == !carried &&
+               P.ops[3].ns0 == P.ops[2].ns_out);
+        ++walked;
+      }
+    // ---- stride-2 generic conv -> GNFIN -> half-resolution Winograd conv: 16 slots, 18 slots ----------------------
+    for (int many = 0; many < 2; ++many)
+      for (int w16 = 0; w16 < 2; ++w16) {            // w16: under the f16 plan, the consumer outside the direct f16 kernel (Winograd on f16 fragments)
+        PlanList L;
+        Act *s = L.act(32, 8, 12, 36), *h = L.act(64, 4, 6, 18), *o = L.act(64, 4, 6, 18);
+        L.conv(RC_STRIDE2, prec, s, h);              // 0
+        L.gnfin(h);                                  // 1
+        L.conv(RC_WINO_HALF, prec, h, o, 1);         // 2
+        Op &prod = L.ops[0];
+        prod.ca.ntz = 2; prod.ca.nty = 1; prod.ca.ntx = many ? 3 : 2; prod.MB = many ? 3 : 4;      // 16 or 18 slots
+        if (w16) L.ops[2].f16d = false;
+        const bool wino = !p16 || w16;               // the consumer's inference route is the Winograd kernel on split or f16 fragments
+        for (const int B : {2, 64}) {
+          const FwdCtx ctx = plan_ctx(prec, false, false, B);
+          check_plan(L.ops, ctx);
+          const FwdPlan P = plan_forward(L.ops, ctx);
+          EXPECT(P.ops[0].route.kernel == CONV_GENERIC && P.ops[0].ns_out == (many ? 18 : 16) && P.ops[1].ns0 == P.ops[0].ns_out);
+          EXPECT(P.ops[2].route.kernel == (wino ? CONV_WINO : CONV_F16D));
+          // f16 fragments: the persistent kernel only when the two-tile grid fills the chip (4 tiles x 64 samples = 256 workgroups)
+          const bool merged = !many && wino && (!p16 || B == 64);
+          EXPECT(P.ops[1].fin == (merged ? FIN_WINO : FIN_ALONE) && P.ops[1].launch == !merged);
+          if (wino) EXPECT(P.ops[2].ns_out == 2 * 1 * 2 * 4);   // 2 x 6 x 10 tiles on 4 x 6 x 18, four sub-blocks each
+          ++walked;
+        }
+        const FwdCtx ctx = plan_ctx(prec, true);
+        check_plan(L.ops, ctx);
+        const FwdPlan P = plan_forward(L.ops, ctx);
+        EXPECT(P.ops[1].fin == FIN_ALONE && P.ops[1].launch && P.ops[2].route.kernel == CONV_WINO && P.ops[2].route.form == (p16 ? FORM_FP32 : FORM_B6));
+        ++walked;
+      }
+    // ---- Winograd conv with statistics -> upsample conv --------------------------------------------------------------------------
+    {
+      PlanList L;
+      Act *s = L.act(64, 4, 6, 18), *h = L.act(64, 4, 6, 18), *u = L.act(64, 8, 12, 36);
+      L.conv(RC_WINO_HALF, prec, s, h);              // 0
+      L.conv(RC_UPS_STATS, prec, h, u);              // 1
+      const ConvForm six[4] = {FORM_B6, FORM_B6, FORM_B3, FORM_F16};
+      for (int stale = 0; stale < 2; ++stale) {
+        const FwdCtx ctx = plan_ctx(prec, false, stale);
+        check_plan(L.ops, ctx);
+        const FwdPlan P = plan_forward(L.ops, ctx);
+        EXPECT(P.ops[0].route.kernel == (p16 ? CONV_F16D : CONV_WINO) && P.ops[0].ns_out >= 1 && P.ops[1].ns0 == P.ops[0].ns_out);
+        EXPECT(P.ops[1].route.kernel == CONV_UPS && P.ops[1].route.form == ((pi == 0 && !stale) ? FORM_H2 : six[pi]));   // h2 on the default plan
+        ++walked;
+      }
+      check_plan(L.ops, plan_ctx(prec, true));
+      // no earlier op writes the source's slots: the six-term form
+      std::vector<Op> alone(L.ops.begin() + 1, L.ops.end());
+      check_plan(alone, plan_ctx(prec, false));
+      const FwdPlan P = plan_forward(alone, plan_ctx(prec, false));
+      EXPECT(P.ops[0].route.kernel == CONV_UPS && P.ops[0].route.form == six[pi] && P.ops[0].ns0 == 0);
+      ++walked;
+    }
+    // ---- K-split conv -> attention block (four generic ops + the fused one) -> GNFIN -> 1x1x1 conv ----------------------------------
+    {
+      PlanList L;
+      Act *s = L.act(64, 4, 6, 18), *x = L.act(128, 2, 3, 9), *qkv = L.act(384, 2, 3, 9), *core = L.act(128, 2, 3, 9), *o = L.act(128, 2, 3, 9),
+          *y = L.act(384, 2, 3, 9);
+      L.conv(RC_KSPLIT, prec, s, x);                 // 0
+      L.gnfin(x);                                    // 1  attention.group_norm
+      L.conv(RC_1X1, prec, x, qkv, 1);               // 2
+      { Op at; at.kind = OP_ATTN; at.cls = K_ATTN; at.S = 54; at.E = 128; L.ops.push_back(at); }   // 3
+      L.conv(RC_1X1_STATS, prec, core, o);           // 4  out_proj (+ residual), statistics
+      for (int i = 1; i <= 4; ++i) L.ops[i].in_attn_block = true;
+      { Op fb; fb.kind = OP_ATTNBLK; fb.cls = K_ATTN; fb.ab_x = x; fb.ab_out = o; fb.S = 54; fb.E = 128; fb.ab_gn = 1; fb.ab_qkv = 2; fb.ab_outc = 4; L.ops.push_back(fb); }   // 5
+      L.gnfin(o);                                    // 6
+      L.conv(RC_1X1, prec, o, y, 6);                 // 7
+      check_plan(L.ops, plan_ctx(prec, false));
+      FwdPlan P = plan_forward(L.ops, plan_ctx(prec, false));
+      // inference: the fused block; its head-sum combine carries the next finalisation; the K-split conv in front of it carries nothing
+      // (the block normalises its input itself)
+      for (int i = 1; i <= 4; ++i) EXPECT(!P.ops[i].launch);
+      EXPECT(P.ops[0].carries == -1 && P.ops[5].launch && P.ops[5].ns_out == 2 && P.ops[5].carries == 6 && P.ops[6].fin == FIN_COMBINE && P.ops[6].ns0 == 2);
+      check_plan(L.ops, plan_ctx(prec, true));
+      P = plan_forward(L.ops, plan_ctx(prec, true));
+      // training: the four generic ops instead; the K-split conv's combine carries the block's own GroupNorm
+      EXPECT(!P.ops[5].launch && P.ops[0].carries == 1 && P.ops[1].fin == FIN_COMBINE && P.ops[2].launch && P.ops[3].launch && P.ops[4].launch);
+      EXPECT(P.ops[4].ns_out == 1 && P.ops[6].fin == FIN_ALONE && P.ops[6].launch && P.ops[6].ns0 == 1);
+      walked += 2;
+    }
+    // ---- a concat finalisation whose two sources disagree on the voxel count: never carried, never merged ---------------------------
+    {
+      PlanList L;
+      Act *s = L.act(32, 8, 12, 36), *h = L.act(64, 4, 6, 18), *a = L.act(128, 2, 3, 9), *o = L.act(64, 4, 6, 18);
+      L.conv(RC_STRIDE2, prec, s, h);                // 0
+      L.conv(RC_KSPLIT, prec, h, a);                 // 1
+      L.gnfin(a, h);                                 // 2
+      L.conv(RC_WINO_HALF_SKIP, prec, a, o, 2, h);   // 3
+      for (int train = 0; train < 2; ++train) {
+        check_plan(L.ops, plan_ctx(prec, train));
+        const FwdPlan P = plan_forward(L.ops, plan_ctx(prec, train));
+        EXPECT(P.ops[1].carries == -1 && P.ops[2].fin == FIN_ALONE && P.ops[2].launch && P.ops[2].ns0 == 2 && P.ops[2].ns1 == 1);
+        // the stand-alone launch path reports the existing error (before it launches anything)
+        EXPECT(run_gnfin(L.ops[2], P.ops[2], 2, nullptr, 0) != 0 && std::string(cm_last_error()) == "concat sources disagree on voxel count");
+        ++walked;
+      }
+      // the same list with equal voxel counts is carried
+      L.acts[1]->Z = 2; L.acts[1]->Y = 3; L.acts[1]->X = 9;
+      check_plan(L.ops, plan_ctx(prec, false));
+      EXPECT(plan_forward(L.ops, plan_ctx(prec, false)).ops[2].fin == FIN_COMBINE);
+      ++walked;
+    }
+  }
+  // a statistics tensor nobody writes, and a slot count beyond the buffers: errors of the plan, not of a launch
+  {
+    PlanList L;
+    Act *a = L.act(128, 2, 3, 9), *b = L.act(128, 2, 3, 9);
+    L.gnfin(a);
+    L.conv(RC_WINO_HALF, CM_PRECISION_F32, a, b, 0);
+    EXPECT(!plan_forward(L.ops, plan_ctx(CM_PRECISION_F32, false)).err.empty());
+    PlanList M;
+    Act *s = M.act(32, 8, 12, 36), *h = M.act(64, 4, 6, 18);
+    M.conv(RC_STRIDE2, CM_PRECISION_F32, s, h);
+    M.ops[0].ca.ntz = 4; M.ops[0].ca.nty = 6; M.ops[0].ca.ntx = 6; M.ops[0].MB = 4;               // 576 slots
+    EXPECT(!plan_forward(M.ops, plan_ctx(CM_PRECISION_F32, false)).err.empty());
+    M.ops[0].ca.ntz = 2;                                                                            // 288
+    EXPECT(plan_forward(M.ops, plan_ctx(CM_PRECISION_F32, false)).err.empty());
+    walked += 3;
+  }
+  printf("test_forward_plan: %d plans checked\n", walked);
 }
 
 // The sampling loop's launch ranges of the UNet's two end convs (loop_ends_plan, conv_first_const_ztiles, conv_fin_zloop)
@@ -608,6 +883,7 @@ int main() {
   test_round3_packers();
   test_wino_form_dispatch();
   test_conv_route();
+  test_forward_plan();
   test_loop_ends();
   test_misc_errors();
   printf("selftest ok: %d checks\n", g_checks);

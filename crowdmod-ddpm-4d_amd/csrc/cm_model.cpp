@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -66,12 +67,10 @@ struct Act {
   std::string name;
   float *d = nullptr;
   float *g = nullptr;     // gradient buffer (training)
-  bool gset = false;      // has received a contribution in the current backward pass
   int C = 0, Z = 0, Y = 0, X = 0;
-  float *part = nullptr;  // [B][nslots][C][2] per-slot (mean, M2) of every channel
-  float *cnt = nullptr;   // [B][nslots] rows behind each slot
+  float *part = nullptr;  // [B][slots][C][2] per-slot (mean, M2) of every channel; the slot count is the producer's, a fact of
+  float *cnt = nullptr;   // [B][slots] rows behind each slot                          the forward's plan (plan_forward)
   int nslice = 1;         // slots when the stand-alone statistics kernel fills them
-  int nslots = 0;         // slots of the last producer (fused conv epilogue or stats kernel)
   bool h16 = false;       // reduced-precision plan: the tensor is stored as _Float16 (same layout and strides; plan_h16)
   int V() const { return Z * Y * X; }
 };
@@ -138,10 +137,6 @@ struct Op {
   bool train_qr = false;        // the training forward may take conv_qr2 as well (set by train_setup once the geometry is checked)
   long long wqr_floats = 0;
   bool qr_consumer = false; // OP_GNFIN whose only consumer is a qr conv: that kernel finalises the statistics itself
-  bool from_slots = false;  // OP_GNFIN (inference plan): its only consumer's inference route is the Winograd kernel on split or f16 fragments,
-                            //   which finalises the statistics from the producers' slot partials itself when they are few (plan_slot_consumers
-                            //   asks conv_route; run_ops / run_conv decide per launch)
-  bool fin_skipped[4] = {false, false, false, false};   // per batch lane: this step's launch of the op was skipped on that promise
   bool first_k = false;     // the UNet's first conv on its dedicated kernel (cm_conv_io.hip); resolve_conv withdraws it when no tile fits
   int first_cin = 4;        //   input channels it contracts per tap: 4 (C <= 4) or 8
   float *d_wfirst = nullptr;
@@ -157,7 +152,6 @@ struct Op {
   std::string label;
   double prof_ms = 0;
   int64_t prof_n = 0;
-  mutable int prof_B = 0;   // batch of the last launch (profile report): the one field a launch writes
   // stats
   const Act *act = nullptr;
   // gn finalize
@@ -178,6 +172,28 @@ struct Op {
   float *d_win = nullptr, *d_wout = nullptr;   // reference-layout copies of in_proj_weight / out_proj.weight
   std::string win_name, wout_name;
 };
+
+enum ConvKernel { CONV_NONE, CONV_QR, CONV_KSPLIT, CONV_UPS, CONV_F16D, CONV_WINO, CONV_FIRST, CONV_FIN, CONV_SMALLN, CONV_1X1_F16, CONV_GENERIC };
+const char *const kConvKernelName[] = {"none", "qr", "ksplit", "ups", "f16d", "wino", "first", "fin", "smalln", "1x1_f16", "generic"};
+// (= ConvArgs::f16 where a kernel takes it)  fp32 matrix instructions; f16 operands; six bf16 cross terms of exact three-way splits;
+// their three leading terms (relaxed plan); three f16 cross terms of two-way splits ("h2", bounded operands)
+enum ConvForm { FORM_FP32 = 0, FORM_F16 = 1, FORM_B6 = 2, FORM_B3 = 3, FORM_H2 = 4 };
+struct ConvRoute { ConvKernel kernel; ConvForm form; };
+
+// The plan of one forward (plan_forward).  B: the batch of ONE enqueue (a lane's share); only conv_wino_p_taken under the f16 plan reads it
+struct FwdCtx { int precision = CM_PRECISION_F32; bool train_fwd = false, h2_stale = false; int B = 1; };
+// Who turns the slot statistics behind an OP_GNFIN into scale / shift rows, in order of precedence: its whole-sample quarter-resolution
+// consumer; the second pass of the K-split conv / attention block that produces g0; its Winograd consumer (few slots); its own launch
+enum FinBy { FIN_NONE, FIN_QR, FIN_COMBINE, FIN_WINO, FIN_ALONE };
+struct OpPlan {
+  bool launch = false;       // the op enqueues something in this context
+  ConvRoute route{CONV_NONE, FORM_FP32};
+  int ns_out = 0;            // statistics slots per sample this op writes (conv: stat_act; OP_STATS: act; OP_ATTNBLK: ab_out), 0 = none
+  int ns0 = 0, ns1 = 0;      // slots of the statistics behind it: OP_GNFIN g0 / g1 (whoever finalises reads them here); conv: in0 (h2 upsample form)
+  FinBy fin = FIN_NONE;      // OP_GNFIN of this context
+  int carries = -1;          // K-split conv / attention block: the OP_GNFIN its second pass finalises (FIN_COMBINE)
+};
+struct FwdPlan { FwdCtx ctx; std::vector<OpPlan> ops; std::string err; };   // one entry per op; err: the list cannot run in this context
 
 }  // namespace
 
@@ -209,6 +225,7 @@ struct cm_model {
   std::vector<std::unique_ptr<Act>> acts;
   std::map<std::string, Act *> act_by_name;
   std::vector<Op> ops;
+  FwdPlan plan;           // of the last forward: assigned by the entry point on the calling thread; the launches and debug hooks only read it
   std::map<std::string, float *> dparam;  // raw uploaded small tensors
 
   // persistent device buffers
@@ -221,14 +238,10 @@ struct cm_model {
   float *d_time[7] = {nullptr};  // device copies: table, W1, b1, W2, b2, Wd_all, bd_all
   struct cm_train_state *train = nullptr;
   float *dropmask = nullptr;    // [B][nproj] Dropout3d keep-mask/(1-p) of the current training forward
-  bool train_fwd = false;
   // h2 fragments are built from the weights at load time; an optimizer step leaves them behind (the device repack kernels maintain
   // the bf16 fragments only).  Stale => the inference forward runs the six-term form; the next inference entry point re-derives them
   // from the master weights (refresh_h2, cm_train_host.inc) -- once per train -> sample transition.
   bool h2_stale = false;
-  // run_ops -> run_conv / fused attention: the GroupNorm finalisation op that follows a K-split layer and can ride in
-  // its second pass (cm::launch_combine_gn); `fin_done` reports that it did
-  // (the hand-off itself lives in thread-local variables, tl_fin_*: batch lanes enqueue from their own host threads)
   // training step: time-embedding projections of the batch computed from the live weights
   float *train_temb = nullptr;  // [B][nproj], row b
   long long *train_iota = nullptr;
@@ -260,6 +273,7 @@ struct cm_model {
   int64_t prof_n[K_NCLASS] = {0};
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> prof_events[4];   // per batch lane (each lane's thread appends to its own)
   hipEvent_t prof_base = nullptr;                 // time origin of a profiled call (recorded on the call's stream)
+  int prof_B = 0;                                 // batch of one enqueue of the profiled call (profile report)
   float prof_union_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // per class: length of the UNION of its launch intervals over all lanes
 
   int L() const { return cfg.past_len + cfg.future_len; }
@@ -1514,13 +1528,8 @@ int resolve_conv(cm_model *m, Op &op) {
 // ------------------------------------------------------------------------------
 // add_conv decides what CAN run (the fragment sets it packs), resolve_conv fixes the geometry, conv_route decides what DOES run in
 // a given context; the launchers then pick their own template instantiation.  Everything that needs to know the kernel or the
-// operand form of a conv -- the launch, the FLOP accounting, the f16-tensor plan, the slot-consumer plan, the debug hooks -- asks here.
-enum ConvKernel { CONV_NONE, CONV_QR, CONV_KSPLIT, CONV_UPS, CONV_F16D, CONV_WINO, CONV_FIRST, CONV_FIN, CONV_SMALLN, CONV_1X1_F16, CONV_GENERIC };
-const char *const kConvKernelName[] = {"none", "qr", "ksplit", "ups", "f16d", "wino", "first", "fin", "smalln", "1x1_f16", "generic"};
-// (= ConvArgs::f16 where a kernel takes it)  fp32 matrix instructions; f16 operands; six bf16 cross terms of exact three-way splits;
-// their three leading terms (relaxed plan); three f16 cross terms of two-way splits ("h2", bounded operands)
-enum ConvForm { FORM_FP32 = 0, FORM_F16 = 1, FORM_B6 = 2, FORM_B3 = 3, FORM_H2 = 4 };
-struct ConvRoute { ConvKernel kernel; ConvForm form; };
+// operand form of a conv -- the FLOP accounting, the f16-tensor plan, the debug hooks -- asks here, and so does plan_forward (below),
+// which decides the rest: which ops run, every tensor's statistics slots, who finalises each GroupNorm.  The launch code only executes.
 
 // Bit mask of the op's tensors that are stored as _Float16 (ConvArgs::h16; plan_h16): half the bytes per element.  The training
 // forward never sees them (training refuses f16 handles); with the skip conv fused in, its sources take the residual's place.
@@ -1532,9 +1541,8 @@ int h16_mask(const Op &op, bool train_fwd) {
 }
 
 // Pure function of the resolved op and the context: no device pointer is dereferenced (fragment pointers count as present /
-// absent), no stream, no model.  `ups_src_stats` is the one input that is launch state: the upsample conv takes h2 only when its
-// source tensor carries slot statistics NOW (written by the producer's launch); callers without a launch assume it does.
-ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale, bool ups_src_stats = true) {
+// absent), no stream, no model.  (plan_conv withdraws the upsample conv's h2 form where no earlier op writes its source's slot statistics.)
+ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale) {
   static const bool no_train_qr = cm::diag_env("CM_NO_TRAIN_QR") != nullptr, no_train_b6 = cm::diag_env("CM_NO_TRAIN_B6") != nullptr;
   const bool infer = !train_fwd;
   // the six-term fragments serve the training forward as well (exact splits, fp32 accumulate; they follow every optimizer step);
@@ -1557,7 +1565,7 @@ ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale,
   }
   if (op.ks > 1) return {CONV_KSPLIT, FORM_FP32};
   if (op.ups && (op.d_wups16 || !(op.d_wfrag16 && infer)))
-    return {CONV_UPS, form(op.d_wups16, six_ok ? op.d_wups_b6 : nullptr, ups_src_stats ? op.d_wups_h2 : nullptr)};
+    return {CONV_UPS, form(op.d_wups16, six_ok ? op.d_wups_b6 : nullptr, op.d_wups_h2)};
   if (op.wino && op.f16d && infer) return {CONV_F16D, FORM_F16};
   if (op.wino)
     return {CONV_WINO, form(op.d_wwino16, (op.d_wwino_b6 && six_ok && cm::conv_wino_b6_ok(g.bz, g.by, g.bx, g.Co, g.Zo)) ? op.d_wwino_b6 : nullptr, op.d_wwino_h2)};
@@ -1581,7 +1589,7 @@ ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale,
 
 // Which routes read / write tensors stored as _Float16, by the launch's tensor mask (h16_mask): the direct f16 conv (source, residual,
 // fused skip source, output), the f16 stage-once upsample conv (source, output), the first conv (output), the last conv (sources).
-// plan_h16 flags a tensor only when every kernel around it passes; run_conv refuses a launch that does not.
+// plan_h16 flags a tensor only when every kernel around it passes; plan_forward refuses a launch that does not.
 bool route_takes_h16(ConvRoute r, int mask) {
   switch (r.kernel) {
     case CONV_F16D: return true;
@@ -1651,23 +1659,87 @@ int plan_h16(cm_model *m) {
   return 0;
 }
 
-// GroupNorm finalisations whose only consumer is a Winograd conv of the table-driven kernel: that kernel can merge the producers'
-// slot partials itself when they are few (<= 32 per sample: the half- and quarter-resolution layers) -- decided per launch in
-// run_ops / run_conv, here only the structural part.  (conv_qr2 has finalised its own input this way since round 3.)
-int plan_slot_consumers(cm_model *m) {
-  if (cm::diag_env("CM_NO_SLOT_GN")) return 0;
-  const int nops = (int)m->ops.size();
-  for (int i = 0; i < nops; ++i) {
-    Op &g = m->ops[i];
-    if (g.kind != OP_GNFIN || g.qr_consumer || g.in_attn_block) continue;
-    int ncons = 0, cons = -1;
-    for (int j = 0; j < nops; ++j)
-      if (m->ops[j].kind == OP_CONV && m->ops[j].gn_op == i) { ++ncons; cons = j; }
-    if (ncons != 1) continue;
-    const ConvRoute r = conv_route(m->ops[cons], m->precision, false, false);
-    g.from_slots = r.kernel == CONV_WINO && r.form != FORM_FP32;
+// The conv part of a plan entry: the op's route in `ctx` and the slot count of the statistics it writes, that of the kernel family that
+// runs.  `src_slots`: slots an earlier op writes for the source tensor (the upsample conv's h2 form reads them), 0 = none.  Returns an error text or "".
+std::string plan_conv(const Op &op, const FwdCtx &ctx, int src_slots, OpPlan *p) {
+  ConvRoute r = conv_route(op, ctx.precision, ctx.train_fwd, ctx.h2_stale);
+  if (r.kernel == CONV_UPS && r.form == FORM_H2 && src_slots <= 0) {
+    Op plain = op; plain.d_wups_h2 = nullptr;
+    r = conv_route(plain, ctx.precision, ctx.train_fwd, ctx.h2_stale);
   }
-  return 0;
+  p->route = r; p->launch = r.kernel != CONV_NONE; p->ns_out = 0; p->ns0 = src_slots;
+  // only some kernels read / write f16 tensors (plan_h16); anything else would misread them silently
+  const int h16 = h16_mask(op, ctx.train_fwd);
+  if (p->launch && h16 && r.kernel != CONV_QR && !route_takes_h16(r, h16))
+    return "conv " + op.label + ": f16 tensors (mask " + std::to_string(h16) + ") reach a kernel without f16 tensor support";
+  if (!p->launch || !op.stat_act) return "";
+  cm::ConvArgs a = op.ca;
+  int ns = a.ntz * a.nty * a.ntx * op.MB * (a.par ? 8 : 1);                      // of the resolved tile, unless:
+  if (r.kernel == CONV_QR) ns = a.Yo * a.Xo > 32 ? 4 : 2;
+  if (r.kernel == CONV_KSPLIT) ns = (a.Zo * a.Yo * a.Xo + 31) / 32;             // of the combine pass: one per 32 voxels
+  if (r.kernel == CONV_UPS) { a.bz = op.ups_tz; a.by = op.ups_ty; a.bx = op.ups_tx; ns = cm::conv_ups_slots(a, op.ups_mbw); }
+  if (r.kernel == CONV_F16D) { a.bz = op.f16d_bz; a.by = op.f16d_by; a.bx = op.f16d_bx; ns = cm::conv_f16d_slots(a, op.f16d_mbw); }
+  if (ns < 1 || ns > MAX_SLOTS) return "conv " + op.label + ": " + std::to_string(ns) + " statistics slots, outside [1, " + std::to_string(MAX_SLOTS) + "]";
+  p->ns_out = ns;
+  return "";
+}
+
+// Does conv `c` on route `r` merge the slot partials behind its GroupNorm itself at batch B?  Only conv_wino_p_kernel does (the launcher's own test)
+bool wino_merges(const Op &c, ConvRoute r, int B) {
+  cm::ConvArgs a = c.ca;
+  a.B = B; a.f16 = r.form == FORM_F16 ? a.f16 : (int)r.form;
+  return r.kernel == CONV_WINO && r.form != FORM_FP32 && a.gn && cm::conv_wino_p_taken(a, r.form == FORM_F16, true);
+}
+
+// Everything the launches of one forward depend on, in one walk over the op list: which ops run, each conv's route, every tensor's
+// statistics slot count, one disposition (FinBy) per GroupNorm finalisation.  Pure: no device memory, no stream, no model state --
+// only, through conv_wino_p_taken under the f16 plan, the current device's CU count (256 where there is no device: the self-test).
+FwdPlan plan_forward(const std::vector<Op> &ops, const FwdCtx &ctx) {
+  static const bool no_fuse = cm::diag_env("CM_NO_FUSE_GNFIN") != nullptr, no_slot_gn = cm::diag_env("CM_NO_SLOT_GN") != nullptr;
+  FwdPlan P{ctx, std::vector<OpPlan>(ops.size()), ""};
+  const bool infer = !ctx.train_fwd; const int n = (int)ops.size();
+  std::map<const Act *, int> slots;      // per tensor: what the launched ops walked so far write
+  auto slots_of = [&](const Act *t) { return slots.count(t) ? slots[t] : 0; };
+  // the fused attention block runs in the inference plan, its four generic ops in the training forward
+  auto in_ctx = [&](const Op &o) { return o.kind == OP_ATTNBLK ? infer : !(o.in_attn_block && infer); };
+  for (int i = 0; i < n && P.err.empty(); ++i) {
+    const Op &op = ops[i];
+    OpPlan &p = P.ops[i];
+    if (!in_ctx(op)) continue;
+    p.launch = op.kind != OP_GNFIN;
+    const Act *two_pass = nullptr; int pc = 0, pv = 0;   // output (channels, voxels) of a K-split conv / attention block: its second pass can carry a finalisation
+    if (op.kind == OP_CONV) {
+      P.err = plan_conv(op, ctx, (op.in0 && op.in0->part) ? slots_of(op.in0) : 0, &p);
+      if (p.ns_out) slots[op.stat_act] = p.ns_out;
+      if (p.route.kernel == CONV_KSPLIT) { two_pass = op.stat_act; pc = op.ca.Co; pv = op.ca.Zo * op.ca.Yo * op.ca.Xo; }
+    } else if (op.kind == OP_STATS) {
+      slots[op.act] = p.ns_out = op.act->nslice;
+    } else if (op.kind == OP_ATTNBLK) {
+      slots[op.ab_out] = p.ns_out = (op.S + 31) / 32; two_pass = op.ab_out; pc = op.E; pv = op.S;
+    } else if (op.kind == OP_GNFIN && p.fin != FIN_COMBINE) {      // (FIN_COMBINE: decided at its producer, below)
+      p.ns0 = slots_of(op.g0); p.ns1 = op.g1 ? slots_of(op.g1) : 0;
+      if (p.ns0 < 1 || (op.g1 && p.ns1 < 1)) P.err = op.label + ": no earlier op of the forward writes its statistics";
+      int cons = -1, ncons = 0;
+      for (int j = i + 1; j < n; ++j) if (ops[j].kind == OP_CONV && ops[j].gn_op == i) { cons = j; ++ncons; }
+      // few slots and a single consumer on the table-driven Winograd kernel: it merges them in its prologue
+      // (<= 16 slots: measured -0.7 % on the ATC step, -1.6 % on the 24x72 f16 plan; HERMES-CR-120's half resolution has 24 slots
+      //  per tensor and up to 192 channels -- there the merge in 256 workgroups cost more than the launch, +0.5 %)
+      const bool merge = ncons == 1 && infer && !no_slot_gn && p.ns0 <= 16 && (!op.g1 || (p.ns1 <= 16 && op.g1->V() == op.g0->V())) &&
+                         wino_merges(ops[cons], conv_route(ops[cons], ctx.precision, false, ctx.h2_stale), ctx.B);
+      p.fin = (op.qr_consumer && infer) ? FIN_QR : merge ? FIN_WINO : FIN_ALONE; p.launch = p.fin == FIN_ALONE;   // (FIN_QR: cm_conv_qr.hip finalises its own input)
+    }
+    // the next op of this context, when it finalises the tensor just produced: in the second pass (cm::launch_combine_gn, with the
+    // mean / rstd rows when training), if the launcher's own predicate takes the geometry
+    int j = i + 1;
+    while (j < n && !in_ctx(ops[j])) ++j;
+    if (!two_pass || no_fuse || j == n || ops[j].kind != OP_GNFIN || ops[j].g0 != two_pass || (ops[j].qr_consumer && infer)) continue;
+    const Act *g1 = ops[j].g1;
+    cm::CombineArgs cb{};
+    cb.C = pc; cb.V = pv; cb.B = ctx.B; cb.nslots = p.ns_out; cb.stat_part = two_pass->part; cb.fin_C1 = g1 ? g1->C : 0; cb.fin_groups = GN_GROUPS;
+    if ((g1 && (g1->V() != pv || slots_of(g1) < 1)) || !cm::combine_gn_ok(cb)) continue;
+    p.carries = j; P.ops[j].fin = FIN_COMBINE; P.ops[j].ns0 = p.ns_out; P.ops[j].ns1 = g1 ? slots_of(g1) : 0;
+  }
+  return P;
 }
 
 // Time-embedding tables for all 1000 rows (embeddings.py:24-30 + layers.py:35,62).
@@ -1703,48 +1775,61 @@ int build_time_table(cm_model *m) {
 }
 
 // ------------------------------------------------------------------------------
-// forward
+// forward: the launch code executes a plan (plan_forward) and writes nothing into the op list
 // ------------------------------------------------------------------------------
-// One convolution op of the plan for the `B` samples starting at `b0` (see run_ops).
-int run_combine(cm_model *m, cm::CombineArgs &cb, hipStream_t st);
-struct Op;
-static thread_local const Op *tl_fin_next = nullptr;   // GroupNorm finalisation waiting to ride on the next K-split second pass
-static thread_local int tl_fin_b0 = 0;
-static thread_local bool tl_fin_done = false;
+// `ns` slots of tensor t's statistics for the samples from b0: (partials, rows behind each slot)
+float *slot_part(const Act *t, int ns, int b0) { return t->part + (size_t)b0 * ns * t->C * 2; }
+float *slot_cnt(const Act *t, int ns, int b0) { return t->cnt + (size_t)b0 * ns; }
 
-// the stand-alone GroupNorm finalisation `g` (an OP_GNFIN) for the `B` samples from `b0`; `mr`: its mean / rstd rows (training), or null
-int run_gnfin(const Op &g, float *mr, int B, hipStream_t st, int b0) {
-  const Act *g0 = g.g0, *g1 = g.g1;
-  const int Ct = g0->C + (g1 ? g1->C : 0);
-  CM_HIP(cm::launch_gn_finalize(g0->part + (size_t)b0 * g0->nslots * g0->C * 2, g0->cnt + (size_t)b0 * g0->nslots, g0->nslots, g0->C,
-                                g1 ? g1->part + (size_t)b0 * g1->nslots * g1->C * 2 : nullptr, g1 ? g1->cnt + (size_t)b0 * g1->nslots : nullptr,
-                                g1 ? g1->nslots : 0, g1 ? g1->C : 0, g0->V(), g.gamma, g.beta, GN_GROUPS, GN_EPS,
-                                g.gn_out + (size_t)b0 * 2 * Ct, mr ? mr + (size_t)b0 * 2 * Ct : nullptr, B, st));
+// the stand-alone GroupNorm finalisation `g` (an OP_GNFIN, plan entry `gp`) for the `B` samples from `b0`
+int run_gnfin(const Op &g, const OpPlan &gp, int B, hipStream_t st, int b0) {
+  const Act *g0 = g.g0, *g1 = g.g1; const int Ct = g0->C + (g1 ? g1->C : 0);
+  if (g1 && g1->V() != g0->V()) return fail("concat sources disagree on voxel count");
+  CM_HIP(cm::launch_gn_finalize(slot_part(g0, gp.ns0, b0), slot_cnt(g0, gp.ns0, b0), gp.ns0, g0->C,
+                                g1 ? slot_part(g1, gp.ns1, b0) : nullptr, g1 ? slot_cnt(g1, gp.ns1, b0) : nullptr,
+                                g1 ? gp.ns1 : 0, g1 ? g1->C : 0, g0->V(), g.gamma, g.beta, GN_GROUPS, GN_EPS,
+                                g.gn_out + (size_t)b0 * 2 * Ct, g.gn_mr ? g.gn_mr + (size_t)b0 * 2 * Ct : nullptr, B, st));
   return 0;
 }
 
-// the whole-sample kernel of the lowest resolution (inference plan): the GroupNorm statistics of its sources come raw
-int run_conv_qr(cm_model *m, const Op &op, ConvForm form, int B, hipStream_t st, int b0) {
-  const Op &gop = m->ops[op.gn_op];
+// Second pass of a K-split layer (or the head sum of the fused attention block) for the samples from b0: with the GroupNorm
+// finalisation of the op that consumes its output when the plan says it carries one (`fin` = OpPlan::carries >= 0)
+int run_combine(cm::CombineArgs &cb, const std::vector<Op> &ops, const FwdPlan &plan, int fin, int b0, hipStream_t st) {
+  if (fin >= 0) {
+    const Op &f = ops[fin];
+    const Act *g1 = f.g1;
+    const int Ct = cb.C + (g1 ? g1->C : 0), ns1 = plan.ops[fin].ns1;
+    cb.fin_gamma = f.gamma; cb.fin_beta = f.beta;
+    cb.fin_gn = f.gn_out + (size_t)b0 * 2 * Ct; cb.fin_mr = f.gn_mr ? f.gn_mr + (size_t)b0 * 2 * Ct : nullptr;
+    if (g1) { cb.fin_p1 = slot_part(g1, ns1, b0); cb.fin_n1 = slot_cnt(g1, ns1, b0); cb.fin_ns1 = ns1; cb.fin_C1 = g1->C; }
+    cb.fin_groups = GN_GROUPS; cb.fin_eps = GN_EPS;
+  }
+  CM_HIP(fin >= 0 ? cm::launch_combine_gn(cb, st) : cm::launch_ksplit_combine(cb, st));
+  return 0;
+}
+
+// the whole-sample kernel of the lowest resolution: the GroupNorm statistics of its sources come raw (FIN_QR)
+int run_conv_qr(const cm_model *m, const Op &op, const FwdPlan &plan, const OpPlan &p, hipStream_t st, int b0) {
+  const Op &gop = m->ops[op.gn_op]; const OpPlan &gp = plan.ops[op.gn_op];
   const Act *g0 = gop.g0, *g1 = gop.g1;
   const cm::ConvArgs &ca = op.ca;
-  const size_t V = (size_t)ca.Zo * ca.Yo * ca.Xo;
+  const bool train = plan.ctx.train_fwd; const size_t V = (size_t)ca.Zo * ca.Yo * ca.Xo;
   cm::QrArgs q{};
   q.src0 = ca.src0 + (size_t)b0 * V * ca.C0; q.C0 = ca.C0;
   q.src1 = ca.src1 ? ca.src1 + (size_t)b0 * V * ca.C1 : nullptr; q.C1 = ca.C1;
-  q.part0 = g0->part + (size_t)b0 * g0->nslots * g0->C * 2; q.cnt0 = g0->cnt + (size_t)b0 * g0->nslots; q.ns0 = g0->nslots;
-  if (g1) { q.part1 = g1->part + (size_t)b0 * g1->nslots * g1->C * 2; q.cnt1 = g1->cnt + (size_t)b0 * g1->nslots; q.ns1 = g1->nslots; }
+  q.part0 = slot_part(g0, gp.ns0, b0); q.cnt0 = slot_cnt(g0, gp.ns0, b0); q.ns0 = gp.ns0;
+  if (g1) { q.part1 = slot_part(g1, gp.ns1, b0); q.cnt1 = slot_cnt(g1, gp.ns1, b0); q.ns1 = gp.ns1; }
   if (g0->C != ca.C0 || (g1 ? g1->C : 0) != ca.C1) return fail("quarter-resolution conv %s: statistics and sources disagree", op.label.c_str());
   q.gamma = gop.gamma; q.beta = gop.beta; q.groups = GN_GROUPS; q.eps = GN_EPS; q.silu = ca.silu;
   if (op.dbg_raw) { q.gamma = q.beta = nullptr; q.raw = 1; q.silu = 0; }
   q.wq = op.d_wqr; q.bias = ca.bias;
   q.wq6 = op.d_wqr_b6;
-  q.three = form == FORM_B3 ? 1 : 0;
+  q.three = p.route.form == FORM_B3 ? 1 : 0;
   // default plan, inference-only handle: the f16 two-way-split form (bounded input: GroupNorm + SiLU inside the kernel)
-  if (form == FORM_H2) { q.wq6 = op.d_wqr_h2; q.three = 2; q.h2_oscale = op.h2_oscale; }
+  if (p.route.form == FORM_H2) { q.wq6 = op.d_wqr_h2; q.three = 2; q.h2_oscale = op.h2_oscale; }
   q.temb = ca.temb; q.temb_stride = ca.temb_stride; q.tidx = ca.tidx + b0;
   q.resid = ca.resid ? ca.resid + (size_t)b0 * V * ca.res_cs : nullptr; q.res_cs = ca.res_cs;
-  if (m->train_fwd) {
+  if (train) {
     // training forward (six-term form only, see run_conv): Dropout3d multipliers on the activated input, the time-embedding rows
     // of this batch, the block's skip conv as its own op (its output arrives as the residual)
     if (op.pm_off >= 0) { q.pm = m->dropmask + (size_t)b0 * m->nproj + op.pm_off; q.pm_stride = m->nproj; }
@@ -1756,65 +1841,47 @@ int run_conv_qr(cm_model *m, const Op &op, ConvForm form, int B, hipStream_t st,
     q.resid = nullptr;
     q.bias = op.d_bias_fused;
   }
-  q.out = ca.out + (size_t)b0 * V * ca.out_cs; q.out_cs = ca.out_cs; q.Co = ca.Co; q.B = B; q.Y = ca.Yo; q.X = ca.Xo;
-  const int ns = ca.Yo * ca.Xo > 32 ? 4 : 2;
-  q.stat_C = op.stat_act->C;
-  q.stat_part = op.stat_act->part + (size_t)b0 * ns * q.stat_C * 2;
-  q.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns;
-  op.stat_act->nslots = ns;
-  op.prof_B = B;
-  if (m->train_fwd && !cm::conv_qr2_b6_ok(q)) return fail("quarter-resolution conv %s: no six-term form for the training forward", op.label.c_str());
+  q.out = ca.out + (size_t)b0 * V * ca.out_cs; q.out_cs = ca.out_cs; q.Co = ca.Co; q.B = plan.ctx.B; q.Y = ca.Yo; q.X = ca.Xo;
+  q.stat_C = op.stat_act->C; q.stat_part = slot_part(op.stat_act, p.ns_out, b0); q.stat_cnt = slot_cnt(op.stat_act, p.ns_out, b0);
+  if (train && !cm::conv_qr2_b6_ok(q)) return fail("quarter-resolution conv %s: no six-term form for the training forward", op.label.c_str());
   CM_HIP(cm::launch_conv_qr(q, st));
   return 0;
 }
 
-int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
-  const ConvRoute route = conv_route(op, m->precision, m->train_fwd, m->h2_stale, op.in0 && op.in0->part && op.in0->nslots > 0);
+// One convolution op of the list (plan entry `p`) for the plan's batch of samples starting at `b0` (see run_ops).
+int run_conv(const cm_model *m, const Op &op, const FwdPlan &plan, const OpPlan &p, hipStream_t st, int b0, int slab, const LoopEnds *le = nullptr) {
+  const ConvRoute route = p.route;
+  const bool train = plan.ctx.train_fwd; const int B = plan.ctx.B;
   if (route.kernel == CONV_NONE) return 0;
-  if (route.kernel == CONV_QR) return run_conv_qr(m, op, route.form, B, st, b0);
+  if (route.kernel == CONV_QR) return run_conv_qr(m, op, plan, p, st, b0);
   cm::ConvArgs ca = op.ca;
   ca.B = B;
-  op.prof_B = B;
   ca.nts = (B + ca.bs - 1) / ca.bs;
   const size_t Vs = (size_t)ca.Zs * ca.Ys * ca.Xs, Vo = (size_t)ca.Zo * ca.Yo * ca.Xo;
   // f16 tensors of the reduced-precision plan (plan_h16): half the bytes per element, so half the float offset; the mask tells the
   // kernel which of its tensors they are
-  ca.h16 = h16_mask(op, m->train_fwd);
-  auto adv = [&](const float *p, size_t elems, int bit) { return p + ((ca.h16 & bit) ? elems / 2 : elems); };
+  ca.h16 = h16_mask(op, train);
+  auto adv = [&](auto *ptr, size_t elems, int bit) { return ptr + ((ca.h16 & bit) ? elems / 2 : elems); };
   ca.src0 = adv(ca.src0, (size_t)b0 * Vs * ca.C0, 1);
   if (ca.src1) ca.src1 = adv(ca.src1, (size_t)b0 * Vs * ca.C1, 2);
   if (ca.gn) ca.gn += (size_t)b0 * 2 * (ca.C0 + ca.C1);
   ca.tidx += b0;
-  if (m->train_fwd && op.pm_off >= 0) { ca.pm = m->dropmask + (size_t)b0 * m->nproj + op.pm_off; ca.pm_stride = m->nproj; }
+  if (train && op.pm_off >= 0) { ca.pm = m->dropmask + (size_t)b0 * m->nproj + op.pm_off; ca.pm_stride = m->nproj; }
   if (m->use_train_temb && op.temb_off >= 0) { ca.temb = m->train_temb + op.temb_off; ca.tidx = m->train_iota + b0; }
   if (ca.resid) ca.resid = adv(ca.resid, (size_t)b0 * Vo * ca.res_cs, 8);
-  if (op.d_s2w && !m->train_fwd) {
+  if (op.d_s2w && !train) {
     if (!op.wino && 32 * op.MB > cm::conv_halo_voxels(ca)) return fail("fused skip conv: tile rows exceed the staged box");
     ca.s2w = op.d_s2w;
-    ca.s2src0 = adv(op.skip0->d, (size_t)b0 * Vo * op.skip0->C, 16); ca.s2C0 = op.skip0->C;
-    ca.s2src1 = op.skip1 ? adv(op.skip1->d, (size_t)b0 * Vo * op.skip1->C, 32) : nullptr; ca.s2C1 = op.skip1 ? op.skip1->C : 0;
+    ca.s2src0 = adv((const float *)op.skip0->d, (size_t)b0 * Vo * op.skip0->C, 16); ca.s2C0 = op.skip0->C;
+    ca.s2src1 = op.skip1 ? adv((const float *)op.skip1->d, (size_t)b0 * Vo * op.skip1->C, 32) : nullptr; ca.s2C1 = op.skip1 ? op.skip1->C : 0;
     ca.resid = nullptr;
     ca.bias = op.d_bias_fused;
   }
-  ca.out = const_cast<float *>(adv(ca.out, (size_t)b0 * Vo * ca.out_cs, 4));
-  // only some kernels read / write f16 tensors; anything else here would misread them silently
-  if (ca.h16 && !route_takes_h16(route, ca.h16))
-    return fail("conv %s: f16 tensors (mask %d) reach a kernel without f16 tensor support", op.label.c_str(), ca.h16);
-  // Statistics slots of the output tensor.  Its slot count is written ONCE per launch, in the arm of the kernel that runs, with
-  // that kernel's count: the batch lanes enqueue from two host threads, and the other lane's gn_finalize reads it -- a generic
-  // count first and the upsample / f16 kernel's own count afterwards left a window in which that reader saw the wrong number of
-  // slots (a rare wrong statistic: the one-off failure of the two-lane bit-identity test in round 4).  All lanes write the same value.
-  auto stat_slots = [&](int ns) -> int {
-    if (!op.stat_act) return 0;
-    if (ns > MAX_SLOTS) return fail("statistics slots %d exceed %d", ns, MAX_SLOTS);
-    ca.stat_C = op.stat_act->C;
-    ca.stat_ns = ns;
-    ca.stat_part = op.stat_act->part + (size_t)b0 * ns * ca.stat_C * 2;
-    ca.stat_cnt = op.stat_act->cnt + (size_t)b0 * ns;
-    return 0;
-  };
-  const int ns_tile = ca.ntz * ca.nty * ca.ntx * op.MB * (ca.par ? 8 : 1);   // of the resolved tile (every kernel but the upsample / direct f16 / K-split ones)
-  if (stat_slots(ns_tile)) return 1;
+  ca.out = adv(ca.out, (size_t)b0 * Vo * ca.out_cs, 4);
+  if (op.stat_act) {   // statistics slots of the output tensor: the plan's count for the kernel that runs
+    ca.stat_C = op.stat_act->C; ca.stat_ns = p.ns_out;
+    ca.stat_part = slot_part(op.stat_act, p.ns_out, b0); ca.stat_cnt = slot_cnt(op.stat_act, p.ns_out, b0);
+  }
   switch (route.kernel) {
     case CONV_NONE: case CONV_QR: break;   // (taken above)
     case CONV_KSPLIT: {
@@ -1830,11 +1897,8 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab,
       cb.bias = ca.bias; cb.temb = ca.temb; cb.temb_stride = ca.temb_stride; cb.tidx = ca.tidx;
       cb.resid = ca.resid; cb.res_cs = ca.res_cs;
       cb.out = ca.out; cb.C = ka.Co; cb.V = V; cb.B = B;
-      cb.nslots = (V + 31) / 32;
-      cb.stat_part = op.stat_act->part + (size_t)b0 * cb.nslots * cb.C * 2;
-      cb.stat_cnt = op.stat_act->cnt + (size_t)b0 * cb.nslots;
-      op.stat_act->nslots = cb.nslots;
-      return run_combine(m, cb, st);
+      cb.nslots = p.ns_out; cb.stat_part = ca.stat_part; cb.stat_cnt = ca.stat_cnt;
+      return run_combine(cb, m->ops, plan, p.carries, b0, st);
     }
     case CONV_UPS:
       // upsample conv: stage-once parity kernel with its own source tile / statistics slots
@@ -1843,14 +1907,11 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab,
       ca.f16 = route.form;
       if (route.form == FORM_H2) {
         // default plan, inference-only handle: h2 with the sample's block exponent from the source tensor's slot statistics
-        const Act *si = op.in0;
         ca.wfrag = op.d_wups_h2; ca.h2_oscale = op.h2_oscale;
-        ca.gp0 = si->part + (size_t)b0 * si->nslots * si->C * 2; ca.gc0 = si->cnt + (size_t)b0 * si->nslots; ca.gns0 = si->nslots;
+        ca.gp0 = slot_part(op.in0, p.ns0, b0); ca.gc0 = slot_cnt(op.in0, p.ns0, b0); ca.gns0 = p.ns0;
       }
       ca.bz = op.ups_tz; ca.by = op.ups_ty; ca.bx = op.ups_tx;
       ca.ntz = ca.Zs / ca.bz; ca.nty = ca.Ys / ca.by; ca.ntx = ca.Xs / ca.bx;
-      if (stat_slots(cm::conv_ups_slots(ca, op.ups_mbw))) return 1;
-      if (op.stat_act) op.stat_act->nslots = ca.stat_ns;
       CM_HIP(cm::launch_conv_ups(ca, op.ups_mbw, op.ups_planes, op.NB, st));
       break;
     case CONV_F16D:
@@ -1858,8 +1919,6 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab,
       ca.bz = op.f16d_bz; ca.by = op.f16d_by; ca.bx = op.f16d_bx;
       ca.wfrag = op.d_w16d;
       if (ca.s2w) ca.s2w = op.d_w16d_skip;
-      if (stat_slots(cm::conv_f16d_slots(ca, op.f16d_mbw))) return 1;
-      if (op.stat_act) op.stat_act->nslots = ca.stat_ns;
       CM_HIP(cm::launch_conv_f16d(ca, op.f16d_mbw, st));
       break;
     case CONV_WINO: {
@@ -1867,27 +1926,17 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab,
       ca.wfrag = f16 ? op.d_wwino16 : route.form == FORM_H2 ? op.d_wwino_h2 : route.form == FORM_FP32 ? op.d_wwino : op.d_wwino_b6;
       if (!f16) ca.f16 = route.form;
       if (route.form == FORM_H2) ca.h2_oscale = op.h2_oscale;
-      // The GroupNorm of the input from the producers' slot partials when run_ops skipped the gn_finalize launch on the promise that
-      // this route merges them (few slots; plan_slot_consumers: the kernel family of a route depends on nothing a launch can change).
-      // Only conv_wino_p_kernel does; conv_wino_p_taken is the launcher's own test for it -- otherwise the skipped launch happens now.
-      if (ca.gn && op.gn_op >= 0 && m->ops[op.gn_op].fin_skipped[slab & 3] && !m->train_fwd) {
-        const Op &g = m->ops[op.gn_op];
-        const Act *g0 = g.g0, *g1 = g.g1;
-        if (cm::conv_wino_p_taken(ca, f16, true)) {
-          ca.gp0 = g0->part + (size_t)b0 * g0->nslots * g0->C * 2; ca.gc0 = g0->cnt + (size_t)b0 * g0->nslots; ca.gns0 = g0->nslots;
-          if (g1) { ca.gp1 = g1->part + (size_t)b0 * g1->nslots * g1->C * 2; ca.gc1 = g1->cnt + (size_t)b0 * g1->nslots; ca.gns1 = g1->nslots; }
-          ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS;
-          ca.gn = nullptr;
-        } else if (run_gnfin(g, nullptr, B, st, b0)) {
-          return 1;
-        }
+      // FIN_WINO: the GroupNorm of the input from the producers' slot partials, merged in the kernel's prologue
+      if (ca.gn && op.gn_op >= 0 && plan.ops[op.gn_op].fin == FIN_WINO) {
+        const Op &g = m->ops[op.gn_op]; const OpPlan &gp = plan.ops[op.gn_op];
+        ca.gp0 = slot_part(g.g0, gp.ns0, b0); ca.gc0 = slot_cnt(g.g0, gp.ns0, b0); ca.gns0 = gp.ns0;
+        if (g.g1) { ca.gp1 = slot_part(g.g1, gp.ns1, b0); ca.gc1 = slot_cnt(g.g1, gp.ns1, b0); ca.gns1 = gp.ns1; }
+        ca.gs_gamma = g.gamma; ca.gs_beta = g.beta; ca.gs_groups = GN_GROUPS; ca.gs_eps = GN_EPS; ca.gn = nullptr;
       }
-      if (op.stat_act) op.stat_act->nslots = ns_tile;
       CM_HIP(cm::launch_conv_wino(ca, f16, st));
       break;
     }
     case CONV_FIRST:
-      if (op.stat_act) op.stat_act->nslots = ns_tile;
       if (le && op.ca.src0 == m->x8) ca.tz_first = le->tz_first;   // (a later loop step: the constant z tiles stay)
       CM_HIP(cm::launch_conv_first(ca, op.first_cin, op.d_wfirst, st));
       break;
@@ -1910,108 +1959,53 @@ int run_conv(cm_model *m, const Op &op, int B, hipStream_t st, int b0, int slab,
       break;
     case CONV_GENERIC:
       if (route.form == FORM_F16) { ca.wfrag = op.d_wfrag16; ca.wpar_stride = op.wpar_stride16; ca.f16 = 1; }   // f16 operands, fp32 accumulate
-      if (op.stat_act) op.stat_act->nslots = ns_tile;
       CM_HIP(cm::launch_conv(ca, op.MB, op.NB, st));
       break;
   }
   return 0;
 }
 
-// Second pass of a K-split layer (or the head sum of the fused attention block): with the consumer's GroupNorm
-// finalisation fused when run_ops found one waiting (tl_fin_next) and the shapes allow it.
-int run_combine(cm_model *m, cm::CombineArgs &cb, hipStream_t st) {
-  static const bool no_fuse = cm::diag_env("CM_NO_FUSE_GNFIN") != nullptr;
-  const Op *f = tl_fin_next;
-  tl_fin_done = false;
-  if (f && !no_fuse && (!f->g1 || f->g1->V() == cb.V)) {
-    const Act *g1 = f->g1;
-    const int b0 = tl_fin_b0, Ct = cb.C + (g1 ? g1->C : 0);
-    cb.fin_gamma = f->gamma; cb.fin_beta = f->beta;
-    cb.fin_gn = f->gn_out + (size_t)b0 * 2 * Ct;
-    cb.fin_mr = f->gn_mr ? f->gn_mr + (size_t)b0 * 2 * Ct : nullptr;
-    cb.fin_p1 = g1 ? g1->part + (size_t)b0 * g1->nslots * g1->C * 2 : nullptr;
-    cb.fin_n1 = g1 ? g1->cnt + (size_t)b0 * g1->nslots : nullptr;
-    cb.fin_ns1 = g1 ? g1->nslots : 0; cb.fin_C1 = g1 ? g1->C : 0;
-    cb.fin_groups = GN_GROUPS; cb.fin_eps = GN_EPS;
-    if (cm::combine_gn_ok(cb)) {
-      CM_HIP(cm::launch_combine_gn(cb, st));
-      tl_fin_done = true;
-      return 0;
-    }
-  }
-  CM_HIP(cm::launch_ksplit_combine(cb, st));
-  return 0;
-}
-
-// Launch the op list for the `B` samples starting at sample `b0` on stream `st`.
+// Launch the op list as `plan` says, for plan.ctx.B samples starting at sample `b0` on stream `st`.
 // Every sample-indexed pointer is offset by b0, so two disjoint sub-batches can run
 // concurrently on two streams (`slab` selects the stream's K-split scratch region).
-int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0, const LoopEnds *le = nullptr) {
-  for (size_t oi = 0; oi < m->ops.size(); ++oi) {
-    Op &op = m->ops[oi];
-    // the fused attention block runs in the inference plan, its four generic ops in the training forward
-    if (op.kind == OP_ATTNBLK ? m->train_fwd : (op.in_attn_block && !m->train_fwd)) continue;
+int run_ops(cm_model *m, const FwdPlan &plan, hipStream_t st, int b0 = 0, int slab = 0, const LoopEnds *le = nullptr) {
+  const std::vector<Op> &ops = m->ops; const int B = plan.ctx.B;
+  for (size_t oi = 0; oi < ops.size(); ++oi) {
+    const Op &op = ops[oi]; const OpPlan &p = plan.ops[oi];
+    if (!p.launch) continue;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (m->profile) {
       CM_HIP(hipEventCreate(&e0));
       CM_HIP(hipEventCreate(&e1));
       CM_HIP(hipEventRecord(e0, st));
     }
-    {
-      static const bool sync_ops = cm::diag_env("CM_SYNC_OPS") != nullptr;   // debugging: name every op and drain the device before it
-      if (sync_ops) {
-        const hipError_t e = hipDeviceSynchronize();
-        fprintf(stderr, "[cm] forward reaches op %zu %s (%s)\n", oi, op.label.c_str(), hipGetErrorString(e));
-        fflush(stderr);
-      }
-    }
-    // a K-split layer's second pass can carry the GroupNorm finalisation of the op that consumes its output
-    tl_fin_next = nullptr; tl_fin_done = false;
-    size_t fin_at = 0;
-    if ((op.kind == OP_CONV && op.ks > 1) || op.kind == OP_ATTNBLK) {
-      const Act *produced = op.kind == OP_CONV ? op.out_act : op.ab_out;
-      size_t j = oi + 1;
-      while (j < m->ops.size() && (m->ops[j].kind == OP_ATTNBLK ? m->train_fwd : (m->ops[j].in_attn_block && !m->train_fwd))) ++j;
-      if (j < m->ops.size() && m->ops[j].kind == OP_GNFIN && m->ops[j].g0 == produced && !(m->ops[j].qr_consumer && !m->train_fwd)) { tl_fin_next = &m->ops[j]; tl_fin_b0 = b0; fin_at = j; }
+    static const bool sync_ops = cm::diag_env("CM_SYNC_OPS") != nullptr;   // debugging: name every op and drain the device before it
+    if (sync_ops) {
+      const hipError_t e = hipDeviceSynchronize();
+      fprintf(stderr, "[cm] forward reaches op %zu %s (%s)\n", oi, op.label.c_str(), hipGetErrorString(e));
+      fflush(stderr);
     }
     switch (op.kind) {
       case OP_CONV:
-        if (run_conv(m, op, B, st, b0, slab, le)) return 1;
+        if (run_conv(m, op, plan, p, st, b0, slab, le)) return 1;
         break;
-      case OP_STATS: {
-        const Act *t = op.act;
-        CM_HIP(cm::launch_chan_stats(t->d + (size_t)b0 * t->V() * t->C, B, t->V(), t->C, t->nslice,
-                                     t->part + (size_t)b0 * t->nslice * t->C * 2, t->cnt + (size_t)b0 * t->nslice, st));
-        const_cast<Act *>(t)->nslots = t->nslice;
+      case OP_STATS:
+        CM_HIP(cm::launch_chan_stats(op.act->d + (size_t)b0 * op.act->V() * op.act->C, B, op.act->V(), op.act->C, p.ns_out,
+                                     slot_part(op.act, p.ns_out, b0), slot_cnt(op.act, p.ns_out, b0), st));
         break;
-      }
-      case OP_GNFIN: {
-        if (op.qr_consumer && !m->train_fwd) break;   // its consumer finalises the statistics itself (cm_conv_qr.hip)
-        op.fin_skipped[slab & 3] = false;
-        // (<= 16 slots: measured -0.7 % on the ATC step, -1.6 % on the 24x72 f16 plan; HERMES-CR-120's half resolution has 24 slots
-        //  per tensor and up to 192 channels -- there the merge in 256 workgroups cost more than the launch, +0.5 %)
-        const auto few = [](const Act *t) { return t->nslots <= 16; };
-        if (op.from_slots && !m->train_fwd && few(op.g0) && (!op.g1 || few(op.g1)) &&
-            (!op.g1 || op.g1->V() == op.g0->V())) {
-          op.fin_skipped[slab & 3] = true;            // few slots: the consuming Winograd conv merges them in its prologue (run_conv)
-          break;
-        }
-        if (op.g1 && op.g1->V() != op.g0->V()) return fail("concat sources disagree on voxel count");
-        if (run_gnfin(op, op.gn_mr, B, st, b0)) return 1;
+      case OP_GNFIN:                     // FIN_ALONE (every other disposition launches nothing here)
+        if (run_gnfin(op, p, B, st, b0)) return 1;
         break;
-      }
-      case OP_ATTN:
+      case OP_ATTN: {
         // reduced-precision plan, inference: QK^T and PV on f16 matrix-core operands (the fp32 plan and every training
         // forward keep the exact fp32 kernel)
-        if (m->precision == CM_PRECISION_F16 && !m->train_fwd && op.E / ATTN_HEADS == 32 && !cm::diag_env("CM_NO_ATTN_F16"))
-          CM_HIP(cm::launch_attn_core_f16(op.qkv + (size_t)b0 * op.S * 3 * op.E, op.aout + (size_t)b0 * op.S * op.E, B, op.S,
-                                          op.E, ATTN_HEADS, st));
-        else
-          CM_HIP(cm::launch_attn_core(op.qkv + (size_t)b0 * op.S * 3 * op.E, op.aout + (size_t)b0 * op.S * op.E, B, op.S,
-                                      op.E, ATTN_HEADS, st));
+        const bool f16 = plan.ctx.precision == CM_PRECISION_F16 && !plan.ctx.train_fwd && op.E / ATTN_HEADS == 32 && !cm::diag_env("CM_NO_ATTN_F16");
+        CM_HIP((f16 ? cm::launch_attn_core_f16 : cm::launch_attn_core)(op.qkv + (size_t)b0 * op.S * 3 * op.E, op.aout + (size_t)b0 * op.S * op.E,
+                                                                      B, op.S, op.E, ATTN_HEADS, st));
         break;
+      }
       case OP_ATTNBLK: {
-        const Op &gop = m->ops[op.ab_gn], &qop = m->ops[op.ab_qkv], &oop = m->ops[op.ab_outc];
+        const Op &gop = ops[op.ab_gn], &qop = ops[op.ab_qkv], &oop = ops[op.ab_outc];
         float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
         const size_t xoff = (size_t)b0 * op.S * op.E;
         cm::AttnBlockArgs aa{};
@@ -2024,11 +2018,8 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0, const 
         cb.bias = oop.ca.bias; cb.temb = nullptr; cb.tidx = m->tbuf;
         cb.resid = aa.x; cb.res_cs = op.E;
         cb.out = op.ab_out->d + xoff; cb.C = op.E; cb.V = op.S; cb.B = B;
-        cb.nslots = (op.S + 31) / 32;
-        cb.stat_part = op.ab_out->part + (size_t)b0 * cb.nslots * cb.C * 2;
-        cb.stat_cnt = op.ab_out->cnt + (size_t)b0 * cb.nslots;
-        op.ab_out->nslots = cb.nslots;
-        if (run_combine(m, cb, st)) return 1;
+        cb.nslots = p.ns_out; cb.stat_part = slot_part(op.ab_out, p.ns_out, b0); cb.stat_cnt = slot_cnt(op.ab_out, p.ns_out, b0);
+        if (run_combine(cb, ops, plan, p.carries, b0, st)) return 1;
         break;
       }
     }
@@ -2036,8 +2027,6 @@ int run_ops(cm_model *m, int B, hipStream_t st, int b0 = 0, int slab = 0, const 
       CM_HIP(hipEventRecord(e1, st));
       m->prof_events[slab & 3].push_back({(int)oi, {e0, e1}});
     }
-    if (tl_fin_done) oi = fin_at;   // (the ops in between are the ones this mode skips anyway)
-    tl_fin_next = nullptr; tl_fin_done = false;
   }
   return 0;
 }
@@ -2056,8 +2045,8 @@ int prof_begin(cm_model *m, hipStream_t st) {
 // time during which at least one launch of the class was running (all offsets against prof_base).
 int prof_collect(cm_model *m, hipStream_t st) {
   if (!m->profile) return 0;
-  CM_HIP(hipDeviceSynchronize());
-  (void)st;
+  CM_HIP(hipDeviceSynchronize()); (void)st;
+  m->prof_B = m->plan.ctx.B;
   std::vector<std::pair<float, float>> iv[K_NCLASS];
   for (int ln = 0; ln < 4; ++ln) {
     for (auto &pe : m->prof_events[ln]) {
@@ -2108,6 +2097,26 @@ int check_ready(cm_model *m, int B) {
   if (!m->finalized) return fail("cm_model_finalize has not been called");
   if (B < 1 || B > m->cfg.max_batch) return fail("batch %d outside [1, max_batch=%d]", B, m->cfg.max_batch);
   return 0;
+}
+
+// Entry points plan on the calling thread, before anything is enqueued; their own plan goes into cm_model::plan, which nothing else writes.
+int make_plan(const cm_model *m, bool train_fwd, int B, FwdPlan *plan) {
+  *plan = plan_forward(m->ops, FwdCtx{m->precision, train_fwd, m->h2_stale, B});
+  return plan->err.empty() ? 0 : fail("%s", plan->err.c_str());
+}
+
+// A debug hook launches ONE, possibly modified, conv against what the last forward left: `plan` becomes that forward's plan at batch B in the
+// inference context, entry `index` planned again for `op` (`src_slots` > 0: its source statistics, just recomputed in that many slots).  Where
+// that forward left the GroupNorm to this conv's slot merge and this launch cannot merge, it is finalised here.
+int plan_debug_conv(const cm_model *m, const Op &op, int index, int B, int src_slots, hipStream_t st, FwdPlan *plan) {
+  if (!m->plan.err.empty() || m->plan.ops.size() != m->ops.size()) return fail("no forward has run on this handle");
+  *plan = m->plan; plan->ctx = FwdCtx{m->precision, false, m->h2_stale, B};
+  OpPlan &p = plan->ops[index], &gp = plan->ops[std::max(op.gn_op, 0)];
+  p.carries = -1;                    // a hook's second pass is the plain combine: no other op's scale / shift rows are touched
+  if (const std::string err = plan_conv(op, plan->ctx, src_slots > 0 ? src_slots : p.ns0, &p); !err.empty()) return fail("%s", err.c_str());
+  if (!op.ca.gn || op.gn_op < 0 || gp.fin != FIN_WINO || wino_merges(op, p.route, B)) return 0;
+  gp.fin = FIN_ALONE;
+  return run_gnfin(m->ops[op.gn_op], gp, B, st, 0);
 }
 
 // torch.linspace / cumprod semantics of forward.py:15-27 (see oracle/unet_numpy.py:
@@ -2341,7 +2350,6 @@ int cm_model_finalize(cm_model *m) {
   for (Op &op : m->ops)
     if (op.kind == OP_CONV && resolve_conv(m, op)) return 1;
   if (plan_h16(m)) return 1;
-  if (plan_slot_consumers(m)) return 1;
   if (build_time_table(m)) return 1;
   const size_t per = (size_t)m->per_sample();
   const size_t per_past = (size_t)c.in_channels * c.rows * c.cols * c.past_len;
@@ -2365,10 +2373,10 @@ int cm_unet_forward(cm_model *m, const float *d_future, const int64_t *d_t, cons
   DevGuard g(m->device);
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   const cm_unet_config &c = m->cfg;
-  if (prof_begin(m, st)) return 1;
+  if (make_plan(m, false, B, &m->plan) || prof_begin(m, st)) return 1;
   CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
   CM_HIP(cm::launch_assemble_input(d_past, d_future, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
-  if (denoise(m, B, st, 0, 0)) return 1;
+  if (denoise(m, m->plan, st, 0, 0)) return 1;
   CM_HIP(cm::launch_extract_output(m->eps_cl, 8, d_out, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st));
   return prof_collect(m, st);
 }
@@ -2417,16 +2425,14 @@ int cm_unet_forward_train(cm_model *m, const float *d_future, const int64_t *d_t
   DevGuard g(m->device);
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   const cm_unet_config &c = m->cfg;
+  if (make_plan(m, true, B, &m->plan)) return 1;
   if (d_dropmask)
     CM_HIP(hipMemcpyAsync(m->dropmask, d_dropmask, (size_t)B * m->nproj * sizeof(float), hipMemcpyDeviceToDevice, st));
   else
     CM_HIP(cm::launch_dropout_mask(m->dropmask, B, m->nproj, p, seed, sample_id_base, 0, st));
   CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
   CM_HIP(cm::launch_assemble_input(d_past, d_future, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
-  m->train_fwd = true;
-  const int rc = run_ops(m, B, st);
-  m->train_fwd = false;
-  if (rc) return 1;
+  if (run_ops(m, m->plan, st)) return 1;
   CM_HIP(cm::launch_extract_output(m->eps_cl, 8, d_out, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st));
   return 0;
 }
@@ -2606,6 +2612,9 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
     off[ln] = o;
     o += Bl[ln];
   }
+  // one plan per distinct lane batch (the lanes' batches differ by at most one sample), built here: the lane threads only read them
+  FwdPlan odd_plan;
+  if (make_plan(m, false, Bl[0], &m->plan) || (Bl[lanes - 1] != Bl[0] && make_plan(m, false, Bl[lanes - 1], &odd_plan))) return 1;
   if (lanes > 1) {
     CM_HIP(hipEventRecord(m->ev_fork, st));
     for (int ln = 1; ln < lanes; ++ln) CM_HIP(hipStreamWaitEvent(sts[ln], m->ev_fork, 0));
@@ -2685,7 +2694,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       LoopEnds le = ends;
       le.step = &al;
       if (first) le.tz_first = 0;
-      if (denoise(m, B, st, 0, 0, &le)) return 1;
+      if (denoise(m, m->plan, st, 0, 0, &le)) return 1;
       if (!ends.fuse) CM_HIP(cm::launch_sampler_step(al, st));
       if (mass && mass_step(0, B, 0.f, d_history, m->d_steptab, 0, st)) return 1;
       return 0;
@@ -2726,7 +2735,7 @@ int cm_sample_loop(cm_model *m, const cm_schedule *s, const float *d_past, const
       LoopEnds le = ends;
       le.step = &al;
       if (k == 0) le.tz_first = 0;
-      if (denoise(m, Bn, ls, b0, ln, &le)) return 1;
+      if (denoise(m, Bn == m->plan.ctx.B ? m->plan : odd_plan, ls, b0, ln, &le)) return 1;
       if (!ends.fuse) CM_HIP(cm::launch_sampler_step(al, ls));
       if (mass && mass_step(b0, Bn, r.mass, al.hist, nullptr, 0, ls)) return 1;
     }
@@ -2891,9 +2900,9 @@ int cm_profile_report(cm_model *m, char *buf, int64_t capacity) {
     const double us = op.prof_ms * 1e3 / op.prof_n;
     if (op.kind == OP_CONV) {
       const cm::ConvArgs &a = op.ca;
-      const double tf = op.flops_per_sample * op.prof_B / (us * 1e-6) / 1e12;
+      const double tf = op.flops_per_sample * m->prof_B / (us * 1e-6) / 1e12;
       snprintf(line, sizeof(line), "%-52s %9.1f us %7.2f TF %8.1f MF/sample B%d ks%d  %s%d NB%d box %dx%dx%dx%d grid %dx%d CK%d lds %zu\n", op.label.c_str(), us, tf,
-               op.flops_per_sample / 1e6, op.prof_B, op.ks,
+               op.flops_per_sample / 1e6, m->prof_B, op.ks,
                "MB", op.MB, op.NB, a.bs, a.bz, a.by, a.bx, a.nts * a.ntz * a.nty * a.ntx,
                (a.Co + 32 * op.NB - 1) / (32 * op.NB), a.CK, cm::conv_lds_bytes(a, op.MB, op.NB));
     } else {
@@ -2998,7 +3007,7 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   CM_NOT_DIT(m, "cm_debug_conv_io");
   if (check_ready(m, B)) return 1;
   if (!h_in0 || !h_out || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
-  Op &op = m->ops[index];
+  const Op &op = m->ops[index];
   if (op.kind != OP_CONV || !op.in0 || !op.out_act) return fail("op %d is not a convolution", index);
   if ((op.in1 != nullptr) != (h_in1 != nullptr)) return fail("op %d has %d source tensors", index, op.in1 ? 2 : 1);
   DevGuard g(m->device);
@@ -3016,18 +3025,16 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   tmp.skip_if_fused = false;
   tmp.dbg_h2 = mode == 2;
   if (mode == 1) { tmp.d_wwino_b6 = nullptr; tmp.d_wqr_b6 = nullptr; tmp.d_wups_b6 = nullptr; }
-  const int ns_keep = op.stat_act ? op.stat_act->nslots : 0;
-  const int ns_in_keep = op.in0->nslots;
+  int src_slots = 0;
   if (mode == 2 && op.ups && op.in0->part) {
-    // the upsample conv's h2 form takes its per-sample scale from the source tensor's slot statistics: those of the caller's data
+    // the upsample conv's h2 form scales each sample by its source's slot statistics: the caller's data, in nslice slots, this launch only
     const Act *t = op.in0;
-    CM_HIP(cm::launch_chan_stats(t->d, B, t->V(), t->C, t->nslice, t->part, t->cnt, st));
-    const_cast<Act *>(t)->nslots = t->nslice;
+    src_slots = t->nslice;
+    CM_HIP(cm::launch_chan_stats(t->d, B, t->V(), t->C, src_slots, t->part, t->cnt, st));
   }
-  const int rc = run_conv(m, tmp, B, st, 0, 0);
+  FwdPlan plan;
+  const int rc = plan_debug_conv(m, tmp, index, B, src_slots, st, &plan) || run_conv(m, tmp, plan, plan.ops[index], st, 0, 0);
   const hipError_t e = hipStreamSynchronize(st);
-  if (op.stat_act) op.stat_act->nslots = ns_keep;
-  const_cast<Act *>(op.in0)->nslots = ns_in_keep;
   if (rc) return 1;
   if (e != hipSuccess) return fail("debug conv launch failed: %s", hipGetErrorString(e));
   CM_HIP(hipMemcpy(h_out, op.out_act->d, (size_t)B * Vo * op.out_act->C * sizeof(float), hipMemcpyDeviceToHost));
@@ -3043,7 +3050,7 @@ int cm_debug_wino_form_counts(int64_t counts[16], int32_t reset) {
   return 0;
 }
 
-// The statistics slots the last launch of conv op `index` wrote for its output tensor: h_part [B][nslots][C][2] (mean, M2), h_cnt
+// The statistics slots conv op `index` writes for its output tensor in the last forward's plan: h_part [B][nslots][C][2] (mean, M2), h_cnt
 // [B][nslots] rows behind each slot.  h_part / h_cnt may be null: only *nslots / *C are returned (size the buffers, call again).
 int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, float *h_cnt, int32_t *nslots, int32_t *C) {
   CM_NOT_DIT(m, "cm_debug_conv_stats");
@@ -3052,12 +3059,12 @@ int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, fl
   const Op &op = m->ops[index];
   if (op.kind != OP_CONV || !op.stat_act || !op.stat_act->part) return fail("op %d writes no statistics", index);
   const Act *t = op.stat_act;
-  *nslots = t->nslots;
-  *C = t->C;
+  const int ns = (size_t)index < m->plan.ops.size() ? m->plan.ops[index].ns_out : 0;   // of the last forward's plan
+  *nslots = ns; *C = t->C;
   DevGuard g(m->device);
   CM_HIP(hipStreamSynchronize(m->stream));
-  if (h_part) CM_HIP(hipMemcpy(h_part, t->part, (size_t)B * t->nslots * t->C * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  if (h_cnt) CM_HIP(hipMemcpy(h_cnt, t->cnt, (size_t)B * t->nslots * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_part) CM_HIP(hipMemcpy(h_part, t->part, (size_t)B * ns * t->C * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_cnt) CM_HIP(hipMemcpy(h_cnt, t->cnt, (size_t)B * ns * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -3068,11 +3075,11 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
   CM_NOT_DIT(m, "cm_debug_time_conv");
   if (check_ready(m, B)) return 1;
   if (!us || index < 0 || index >= (int)m->ops.size() || iters < 1) return fail("bad argument");
-  Op &op = m->ops[index];
-  if (op.kind != OP_CONV || ((op.first_k || op.wino) && MB > 0)) return fail("op %d is not a tunable convolution", index);
+  const Op &own = m->ops[index];
+  if (own.kind != OP_CONV || ((own.first_k || own.wino) && MB > 0)) return fail("op %d is not a tunable convolution", index);
   DevGuard g(m->device);
   hipStream_t st = m->stream;
-  const Op saved = op;
+  Op op = own; op.skip_if_fused = false;   // the timed copy: the list keeps the op's own geometry (the device tables are shared, see below)
   int rc = 0;
   if (MB > 0) {
     cm::ConvArgs &a = op.ca;
@@ -3084,7 +3091,6 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
       a.ntz = (a.Zo / osd + bz - 1) / bz; a.nty = (a.Yo / osd + by - 1) / by; a.ntx = (a.Xo / osd + bx - 1) / bx;
       if (cm::conv_lds_bytes(a, MB, op.NB) > 80 * 1024) rc = fail("tile needs too much LDS");  // two workgroups per CU
       if (!rc && op.small_n && (MB & (MB - 1))) rc = fail("small-N kernel needs a power-of-two MB");
-      if (!rc && op.stat_act && a.ntz * a.nty * a.ntx * MB * (a.par ? 8 : 1) > MAX_SLOTS) rc = fail("too many statistics slots");
       if (!rc && cm::conv_halo_voxels(a) > 16384) rc = fail("halo box too large");
     }
     if (!rc) {
@@ -3095,13 +3101,14 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
       if (e != hipSuccess) rc = fail("table upload failed");
     }
   }
+  FwdPlan plan;
+  if (!rc) rc = plan_debug_conv(m, op, index, B, 0, st, &plan);
   if (!rc) {
-    op.skip_if_fused = false;          // (`saved` restores it)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 2 && !rc; ++i) rc = run_conv(m, op, B, st, 0, 0);
+    for (int i = 0; i < 2 && !rc; ++i) rc = run_conv(m, op, plan, plan.ops[index], st, 0, 0);
     hipEventRecord(e0, st);
-    for (int i = 0; i < iters && !rc; ++i) rc = run_conv(m, op, B, st, 0, 0);
+    for (int i = 0; i < iters && !rc; ++i) rc = run_conv(m, op, plan, plan.ops[index], st, 0, 0);
     hipEventRecord(e1, st);
     hipError_t e = hipStreamSynchronize(st);
     if (!rc && e != hipSuccess) rc = fail("timed launch failed: %s", hipGetErrorString(e));
@@ -3109,14 +3116,12 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
     if (!rc) { hipEventElapsedTime(&ms, e0, e1); *us = ms * 1e3f / (float)iters; }
     hipEventDestroy(e0); hipEventDestroy(e1);
   }
-  // restore the op's own geometry and tables
-  const bool changed = MB > 0;
-  op = saved;
-  if (changed) {
-    std::vector<int> hv((size_t)cm::conv_halo_voxels(op.ca)), mt((size_t)32 * op.MB);
-    cm::conv_build_tables(op.ca, op.MB, hv.data(), mt.data());
-    CM_HIP(hipMemcpy(op.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
-    CM_HIP(hipMemcpy(op.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice));
+  // the device tables back to the op's own geometry
+  if (MB > 0) {
+    std::vector<int> hv((size_t)cm::conv_halo_voxels(own.ca)), mt((size_t)32 * own.MB);
+    cm::conv_build_tables(own.ca, own.MB, hv.data(), mt.data());
+    CM_HIP(hipMemcpy(own.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
+    CM_HIP(hipMemcpy(own.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice));
   }
   return rc;
 }

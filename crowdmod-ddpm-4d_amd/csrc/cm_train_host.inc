@@ -13,6 +13,7 @@
 // upsampled tensor (wgrad) and a 2x2x2 sum-pool (dgrad).
 
 struct cm_train_state {
+  std::set<const Act *> gset;  // backward pass: tensors whose gradient buffer has received a contribution
   // flat parameter storage in state_dict order: master weights, gradients, Adam moments
   size_t nfloats = 0;
   std::map<std::string, size_t> poff;
@@ -606,10 +607,8 @@ int train_setup(cm_model *m) {
 }
 
 // accumulate a channels-last gradient slice into an activation's gradient buffer
-int accum_act(cm_model *m, const Act *t, const float *src, int src_cs, int B, hipStream_t st) {
-  Act *a = const_cast<Act *>(t);
-  CM_HIP(cm::launch_add_into(a->g, a->C, src, src_cs, a->C, (long long)B * a->V(), a->gset ? 1 : 0, st));
-  a->gset = true;
+int accum_act(cm_model *m, const Act *a, const float *src, int src_cs, int B, hipStream_t st) {
+  CM_HIP(cm::launch_add_into(a->g, a->C, src, src_cs, a->C, (long long)B * a->V(), m->train->gset.insert(a).second ? 0 : 1, st));
   return 0;
 }
 
@@ -625,8 +624,8 @@ int backward_ops(cm_model *m, int B, hipStream_t st) {
 
 int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
   cm_train_state *T = m->train;
-  for (auto &a : m->acts) a->gset = false;
-  m->act_by_name.at("final")->gset = true;  // written by mse_grad
+  std::set<const Act *> &gset = T->gset;
+  gset = {m->act_by_name.at("final")};      // written by mse_grad
   T->bs_cursor = 0;
   if (!T->bs_ready) {
     // the deferred job tables are appended during the first COMPLETE pass: a first pass that returned early (an
@@ -654,19 +653,19 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       // qkv is the op's input tensor, aout its output: locate their activations by pointer
       Act *qa = nullptr, *oa = nullptr;
       for (auto &a : m->acts) { if (a->d == op.qkv) qa = a.get(); if (a->d == op.aout) oa = a.get(); }
-      if (!qa || !oa || !oa->gset) return fail("attention backward: missing gradient");
+      if (!qa || !oa || !gset.count(oa)) return fail("attention backward: missing gradient");
       const size_t need = cm::attn_bwd_scratch_floats(m->cfg.max_batch, op.S, op.E, ATTN_HEADS);
       if (need > T->attn_big_floats) {              // (large token counts only: the S x S matrices go to a global slab)
         if (dev_alloc(m, (void **)&T->attn_big, need * sizeof(float))) return 1;
         T->attn_big_floats = need;
       }
       CM_HIP(cm::launch_attn_bwd(op.qkv, oa->g, qa->g, B, op.S, op.E, ATTN_HEADS, need ? T->attn_big : nullptr, st));
-      qa->gset = true;
+      gset.insert(qa);
       continue;
     }
     if (op.kind != OP_CONV) continue;
-    Act *out = const_cast<Act *>(op.out_act);
-    if (!out->gset) return fail("backward: no gradient reached %s", op.label.c_str());
+    const Act *out = op.out_act;
+    if (!gset.count(out)) return fail("backward: no gradient reached %s", op.label.c_str());
     const float *dY = out->g;
     const int Cy = out->C, Co = op.ca.Co;
     const int Vo = out->V();
@@ -696,7 +695,7 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
     if (D.wwg) {
       cm::ConvArgs wa = D.wwa;
       wa.B = B;
-      if (m->train_fwd && op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
+      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
       const int ncb = (Co + 31) / 32, nkb = (wa.C0 + wa.C1 + 31) / 32;
       const long ntile = (long)wa.ntz * wa.nty * wa.ntx * B;
       const size_t per_g = (size_t)ncb * nkb * 48 * 1024;
@@ -754,7 +753,7 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       // 1x1x1 convs (skip convs, attention projections): flat-row kernel, NKB input blocks per workgroup
       cm::ConvArgs wa = D.wa;
       wa.B = B;
-      if (m->train_fwd && op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
+      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
       const int Ctot = wa.C0 + wa.C1;
       const int ncb = (Co + 31) / 32, nkb = (Ctot + 31) / 32;
       const int NKB = nkb % 4 == 0 ? 4 : (nkb % 3 == 0 ? 3 : (nkb % 2 == 0 ? 2 : 1));
@@ -771,7 +770,7 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       cm::ConvArgs wa = D.wa;
       const int wMB = D.wMB;
       wa.B = B; wa.nts = B; wa.ks = 1;
-      if (m->train_fwd && op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
+      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
       const int Ctot = wa.C0 + wa.C1;
       const int ncb = (Co + 31) / 32, nkb = (Ctot + 31) / 32;
       const long ntile = (long)wa.ntz * wa.nty * wa.ntx * B;
@@ -826,16 +825,15 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
     }
     const int Ctot = op.ca.C0 + op.ca.C1;
     if (op.ca.par) {
-      Act *in = const_cast<Act *>(op.in0);
-      CM_HIP(cm::launch_sumpool2(T->scrA, in->g, B, op.ca.Zs, op.ca.Ys, op.ca.Xs, in->C, in->gset ? 1 : 0, st));
-      in->gset = true;
+      const Act *in = op.in0;
+      CM_HIP(cm::launch_sumpool2(T->scrA, in->g, B, op.ca.Zs, op.ca.Ys, op.ca.Xs, in->C, gset.insert(in).second ? 0 : 1, st));
     } else if (op.gn_op >= 0) {
       Op &gop = m->ops[op.gn_op];
       cm::GnbArgs ga{};
       ga.x0 = op.in0->d; ga.x1 = op.in1 ? op.in1->d : nullptr; ga.C0 = op.ca.C0; ga.C1 = op.ca.C1;
       ga.dA = T->scrA; ga.dA_cs = Ctot;
       ga.gn = gop.gn_out; ga.mr = gop.gn_mr; ga.gamma = gop.gamma;
-      ga.pm = (m->train_fwd && op.pm_off >= 0) ? m->dropmask + op.pm_off : nullptr; ga.pm_stride = m->nproj;
+      ga.pm = op.pm_off >= 0 ? m->dropmask + op.pm_off : nullptr; ga.pm_stride = m->nproj;
       ga.silu = op.ca.silu;
       ga.V = op.in0->V(); ga.B = B; ga.groups = GN_GROUPS;
       ga.nsl = std::max(1, std::min(MAX_SLICES, ga.V / 128));
@@ -843,12 +841,10 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       T->bs_cursor += (size_t)m->cfg.max_batch * 2 * Ctot;
       if (T->bs_cursor > T->bs_pool_floats) return fail("batch-sum pool overflow");
       ga.part = T->gnb_part; ga.coef = T->gnb_coef; ga.dgb = dgb;
-      Act *i0 = const_cast<Act *>(op.in0), *i1 = const_cast<Act *>(op.in1);
-      ga.g0 = i0->g; ga.acc0 = i0->gset ? 1 : 0;
-      ga.g1 = i1 ? i1->g : nullptr; ga.acc1 = (i1 && i1->gset) ? 1 : 0;
+      ga.g1 = op.in1 ? op.in1->g : nullptr; ga.acc1 = (op.in1 && gset.count(op.in1)) ? 1 : 0;
+      ga.g0 = op.in0->g; ga.acc0 = gset.insert(op.in0).second ? 0 : 1;
+      if (op.in1) gset.insert(op.in1);
       CM_HIP(cm::launch_gn_backward(ga, st));
-      i0->gset = true;
-      if (i1) i1->gset = true;
       if (!T->bs_ready) {
         T->bs_jobs.push_back({dgb, grad_of(m, gop.gname), Ctot, 2 * Ctot});
         T->bs_jobs.push_back({dgb + Ctot, grad_of(m, gop.bename), Ctot, 2 * Ctot});
@@ -959,6 +955,7 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
   cm_train_state *T = m->train;
   const cm_unet_config &c = m->cfg;
   const long long per = (long long)m->per_sample();
+  if (make_plan(m, true, B, &m->plan)) return 1;
   if (d_dropmask)
     CM_HIP(hipMemcpyAsync(m->dropmask, d_dropmask, (size_t)B * m->nproj * sizeof(float), hipMemcpyDeviceToDevice, st));
   else
@@ -968,9 +965,8 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
                              c.base_channels, c.base_channels * c.time_multiple, m->nproj, B, nullptr, T->train_temb,
                              m->tbuf, st));
   CM_HIP(cm::launch_assemble_input(d_past, d_xt, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
-  m->train_fwd = true;
   m->use_train_temb = true;
-  int rc = run_ops(m, B, st);
+  int rc = run_ops(m, m->plan, st);
   m->use_train_temb = false;
   if (!rc) {
     hipError_t e = cm::launch_extract_output(m->eps_cl, 8, T->pred, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st);
@@ -982,7 +978,6 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
     if (e != hipSuccess) rc = fail("loss kernels failed");
   }
   if (!rc) rc = backward_ops(m, B, st);
-  m->train_fwd = false;
   if (rc) return 1;
   if (apply_update && apply_adam(m, st)) return 1;
   CM_HIP(hipMemcpyAsync(h_loss, m->mse_loss, sizeof(float), hipMemcpyDeviceToHost, st));

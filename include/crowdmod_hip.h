@@ -329,7 +329,7 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
  * diagnostic run -- the Winograd launcher takes its generic kernel instead of a specialised launch form: the two must agree
  * bit for bit (tests/test_gpu_wino_forms.py). */
 int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B);
-/* Statistics slots the last launch of conv op `index` wrote: h_part [B][*nslots][*C][2], h_cnt [B][*nslots]; with null buffers
+/* Statistics slots of conv op `index`, in the slot count of the last forward's plan: h_part [B][*nslots][*C][2], h_cnt [B][*nslots]; with null buffers
  * only the two sizes are returned. */
 int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, float *h_cnt, int32_t *nslots, int32_t *C);
 /* Launches of the table-driven Winograd kernel per launch form since the last reset (process-wide): counts[0] = the generic kernel,
