@@ -442,6 +442,25 @@ bool attn_block_ok(int S, int E, int heads, int groups);
 size_t attn_block_lds_bytes(int S, int E, int heads);
 hipError_t launch_attn_block(const AttnBlockArgs &a, hipStream_t st);
 
+// The same block as ONE launch, one workgroup per sample (attn_sample_kernel): nothing crosses a workgroup, so the head sum, the
+// out-projection bias, the residual and the slot statistics of the result happen in the same launch.  Both projections run in the
+// h2 form (f16 two-way splits, three cross terms, fp32 accumulate) on fragments packed by the host (cm_model.cpp: pack_attn_h2, attn_pack_h2); q k^T and
+// P v stay on the fp32 matrix instruction.  E = 128, 4 heads, 8 groups, 1 <= S <= 64 (attn_sample_ok).
+struct AttnSampleArgs {
+  const float *x;                 // [B][S][E] block input (channels-last), also the residual
+  const float *gamma, *beta;      // [E] attention.group_norm affine
+  const float *win_h2, *b_in;     // in-projection fragments [24 column blocks][4 k steps][hi, mid][64 lanes][8 halves]; in_proj_bias [3E]
+  const float *wout_h2, *b_out;   // out-projection fragments [8][4][2][64][8 halves]; out_proj.bias [E]
+  float in_oscale, out_oscale;    // 2^-k of the two weight scales
+  float *out;                     // [B][S][E]
+  float *stat_part, *stat_cnt;    // slot statistics of `out` as ksplit_combine_kernel writes them ([B][nslots][E][2], [B][nslots]); or null
+  int B, S, nslots;
+  float eps;
+};
+bool attn_sample_ok(int S, int E, int heads, int groups);
+size_t attn_sample_lds_bytes();
+hipError_t launch_attn_sample(const AttnSampleArgs &a, hipStream_t st);
+
 // DiT4D_V4 denoiser (cm_dit.hip): one token GEMM with fused prologue / epilogue, and the two attention kernels.
 enum { DIT_PRO_NONE = 0, DIT_PRO_LN = 1, DIT_PRO_PATCH = 2 };
 enum { DIT_EPI_BIAS = 0, DIT_EPI_SILU = 1, DIT_EPI_SILU2 = 2, DIT_EPI_GELU = 3, DIT_EPI_GATE = 4, DIT_EPI_PATCH = 5,

@@ -171,6 +171,10 @@ struct Op {
   int ab_gn = -1, ab_qkv = -1, ab_outc = -1;   // indices of the ops whose device parameters it reads
   float *d_win = nullptr, *d_wout = nullptr;   // reference-layout copies of in_proj_weight / out_proj.weight
   std::string win_name, wout_name;
+  // default plan, S <= 64: the block as one whole-sample launch (attn_sample_kernel) on h2 fragments of the two weights
+  // (pack_attn_h2 of w * 2^k; ab_*_oscale = 2^-k, 0 = no fragments: all-zero or non-finite weights)
+  float *d_win_h2 = nullptr, *d_wout_h2 = nullptr;
+  float ab_in_oscale = 0.f, ab_out_oscale = 0.f;
 };
 
 enum ConvKernel { CONV_NONE, CONV_QR, CONV_KSPLIT, CONV_UPS, CONV_F16D, CONV_WINO, CONV_FIRST, CONV_FIN, CONV_SMALLN, CONV_1X1_F16, CONV_GENERIC };
@@ -192,6 +196,7 @@ struct OpPlan {
   int ns0 = 0, ns1 = 0;      // slots of the statistics behind it: OP_GNFIN g0 / g1 (whoever finalises reads them here); conv: in0 (h2 upsample form)
   FinBy fin = FIN_NONE;      // OP_GNFIN of this context
   int carries = -1;          // K-split conv / attention block: the OP_GNFIN its second pass finalises (FIN_COMBINE)
+  bool attn_sample = false;  // OP_ATTNBLK: one whole-sample launch (attn_sample_kernel) instead of the head launch + combine
 };
 struct FwdPlan { FwdCtx ctx; std::vector<OpPlan> ops; std::string err; };   // one entry per op; err: the list cannot run in this context
 
@@ -547,6 +552,26 @@ static inline void bf16_split3(float w, uint16_t out[3]) {
     out[t] = f32_to_bf16_bits(rem);
     rem -= bf16_bits_to_f32(out[t]);
   }
+}
+
+// h2 fragments of a dense weight W [N][K] (reference layout: mhsa.in_proj_weight, mhsa.out_proj.weight) for the whole-sample
+// attention kernel (cm_attn_block.hip: attn_sample_kernel): [16-column block][32-deep k step][hi, mid][lane][8 halves],
+// lane = 16 g + (n % 16), k = 32 step + 8 g + i; f16 hi / mid of w * scale.  Returned as floats holding two halves each.
+std::vector<float> pack_attn_h2(const float *W, int N, int K, float scale) {
+  const int ncb = N / 16, nks = K / 32;
+  std::vector<uint16_t> out((size_t)ncb * nks * 2 * 64 * 8, 0);
+  for (int cb = 0; cb < ncb; ++cb)
+    for (int ks = 0; ks < nks; ++ks)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int i = 0; i < 8; ++i) {
+          const int n = cb * 16 + (lane & 15), k = ks * 32 + 8 * (lane >> 4) + i;
+          uint16_t t3[3];
+          f16_split2(W[(size_t)n * K + k], scale, t3);
+          for (int tm = 0; tm < 2; ++tm) out[(((((size_t)cb * nks + ks) * 2 + tm) * 64) + lane) * 8 + i] = t3[tm];
+        }
+  std::vector<float> packed(out.size() / 2);
+  std::memcpy(packed.data(), out.data(), out.size() * 2);
+  return packed;
 }
 
 // bf16 x 3 fragments of ONE parity class for the stage-once upsample kernel (cm_conv_ups.hip, PREC = 2): [32-channel column
@@ -986,6 +1011,17 @@ static float h2_pack_ups(const float *w_ref, int Co, int Ci_ref, std::vector<flo
   return ws;
 }
 
+// h2 fragments of an attention block's two weights (reference layout [3E][E], [E][E]); *osc_* = 2^-k of each, 0 where the weight has no
+// scale (all-zero or non-finite: the fragments are zeros and the plan keeps the two-launch path)
+static void attn_pack_h2(const float *w_in, const float *w_out, int E, std::vector<float> *f_in, std::vector<float> *f_out, float *osc_in,
+                         float *osc_out) {
+  const float wsi = h2_wscale(w_in, (size_t)3 * E * E), wso = h2_wscale(w_out, (size_t)E * E);
+  *f_in = pack_attn_h2(w_in, 3 * E, E, wsi);
+  *f_out = pack_attn_h2(w_out, E, E, wso);
+  *osc_in = wsi > 0.f ? 1.f / wsi : 0.f;
+  *osc_out = wso > 0.f ? 1.f / wso : 0.f;
+}
+
 int add_conv(cm_model *m, const ConvSpec &s) {
   Op op;
   op.kind = OP_CONV;
@@ -1408,6 +1444,11 @@ int build_ops(cm_model *m) {
         fb.win_name = ap + ".mhsa.in_proj_weight"; fb.wout_name = ap + ".mhsa.out_proj.weight";
         if (upload(m, P(m, fb.win_name).host, &fb.d_win)) return 1;
         if (upload(m, P(m, fb.wout_name).host, &fb.d_wout)) return 1;
+        if (m->precision == CM_PRECISION_F32 && !cm::diag_env("CM_NO_H2") && cm::attn_sample_ok(fb.S, fb.E, ATTN_HEADS, GN_GROUPS)) {
+          std::vector<float> fi, fo;
+          attn_pack_h2(P(m, fb.win_name).host.data(), P(m, fb.wout_name).host.data(), fb.E, &fi, &fo, &fb.ab_in_oscale, &fb.ab_out_oscale);
+          if (upload(m, fi, &fb.d_win_h2) || upload(m, fo, &fb.d_wout_h2)) return 1;
+        }
         for (int i = nops - 4; i < nops; ++i) m->ops[i].in_attn_block = true;
         const size_t need = (size_t)ATTN_HEADS * m->cfg.max_batch * fb.S * fb.E;
         m->ks_scratch_floats = std::max(m->ks_scratch_floats, need);
@@ -1691,6 +1732,14 @@ bool wino_merges(const Op &c, ConvRoute r, int B) {
   return r.kernel == CONV_WINO && r.form != FORM_FP32 && a.gn && cm::conv_wino_p_taken(a, r.form == FORM_F16, true);
 }
 
+// Does an OP_ATTNBLK of this context qualify for the whole-sample launch (attn_sample_kernel: both projections in the h2 form)?  The
+// default plan's inference forward with current fragments, like every h2 conv; plan_forward adds: no finalisation carried.
+bool attn_sample_planned(const Op &op, const FwdCtx &ctx) {
+  static const bool off = cm::diag_env("CM_NO_ATTN_SAMPLE") != nullptr;
+  return !off && !ctx.train_fwd && ctx.precision == CM_PRECISION_F32 && !ctx.h2_stale && op.d_win_h2 && op.d_wout_h2 &&
+         op.ab_in_oscale > 0.f && op.ab_out_oscale > 0.f && cm::attn_sample_ok(op.S, op.E, ATTN_HEADS, GN_GROUPS);
+}
+
 // Everything the launches of one forward depend on, in one walk over the op list: which ops run, each conv's route, every tensor's
 // statistics slot count, one disposition (FinBy) per GroupNorm finalisation.  Pure: no device memory, no stream, no model state --
 // only, through conv_wino_p_taken under the f16 plan, the current device's CU count (256 where there is no device: the self-test).
@@ -1732,12 +1781,16 @@ FwdPlan plan_forward(const std::vector<Op> &ops, const FwdCtx &ctx) {
     // mean / rstd rows when training), if the launcher's own predicate takes the geometry
     int j = i + 1;
     while (j < n && !in_ctx(ops[j])) ++j;
-    if (!two_pass || no_fuse || j == n || ops[j].kind != OP_GNFIN || ops[j].g0 != two_pass || (ops[j].qr_consumer && infer)) continue;
-    const Act *g1 = ops[j].g1;
-    cm::CombineArgs cb{};
-    cb.C = pc; cb.V = pv; cb.B = ctx.B; cb.nslots = p.ns_out; cb.stat_part = two_pass->part; cb.fin_C1 = g1 ? g1->C : 0; cb.fin_groups = GN_GROUPS;
-    if ((g1 && (g1->V() != pv || slots_of(g1) < 1)) || !cm::combine_gn_ok(cb)) continue;
-    p.carries = j; P.ops[j].fin = FIN_COMBINE; P.ops[j].ns0 = p.ns_out; P.ops[j].ns1 = g1 ? slots_of(g1) : 0;
+    if (two_pass && !no_fuse && j < n && ops[j].kind == OP_GNFIN && ops[j].g0 == two_pass && !(ops[j].qr_consumer && infer)) {
+      const Act *g1 = ops[j].g1;
+      cm::CombineArgs cb{};
+      cb.C = pc; cb.V = pv; cb.B = ctx.B; cb.nslots = p.ns_out; cb.stat_part = two_pass->part; cb.fin_C1 = g1 ? g1->C : 0; cb.fin_groups = GN_GROUPS;
+      if (!(g1 && (g1->V() != pv || slots_of(g1) < 1)) && cm::combine_gn_ok(cb)) {
+        p.carries = j; P.ops[j].fin = FIN_COMBINE; P.ops[j].ns0 = p.ns_out; P.ops[j].ns1 = g1 ? slots_of(g1) : 0;
+      }
+    }
+    // the attention block as one whole-sample launch: nothing for a second pass to carry, so only where none is planned
+    if (op.kind == OP_ATTNBLK) p.attn_sample = attn_sample_planned(op, ctx) && p.carries < 0;
   }
   return P;
 }
@@ -1965,6 +2018,37 @@ int run_conv(const cm_model *m, const Op &op, const FwdPlan &plan, const OpPlan 
   return 0;
 }
 
+// The fused attention block `op` (plan entry `p`) for the plan.ctx.B samples from b0: the whole-sample launch where the plan takes it,
+// else the (head, sample) launch and the head sum
+int run_attn_block(const cm_model *m, const Op &op, const FwdPlan &plan, const OpPlan &p, hipStream_t st, int b0, int slab) {
+  const std::vector<Op> &ops = m->ops; const int B = plan.ctx.B;
+  const Op &gop = ops[op.ab_gn], &qop = ops[op.ab_qkv], &oop = ops[op.ab_outc];
+  const size_t xoff = (size_t)b0 * op.S * op.E;
+  if (p.attn_sample) {
+    cm::AttnSampleArgs as{};
+    as.x = op.ab_x->d + xoff; as.gamma = gop.gamma; as.beta = gop.beta;
+    as.win_h2 = op.d_win_h2; as.b_in = qop.ca.bias; as.wout_h2 = op.d_wout_h2; as.b_out = oop.ca.bias;
+    as.in_oscale = op.ab_in_oscale; as.out_oscale = op.ab_out_oscale;
+    as.out = op.ab_out->d + xoff; as.B = B; as.S = op.S; as.nslots = p.ns_out; as.eps = GN_EPS;
+    as.stat_part = slot_part(op.ab_out, p.ns_out, b0); as.stat_cnt = slot_cnt(op.ab_out, p.ns_out, b0);
+    CM_HIP(cm::launch_attn_sample(as, st));
+    return 0;
+  }
+  float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
+  cm::AttnBlockArgs aa{};
+  aa.x = op.ab_x->d + xoff; aa.gamma = gop.gamma; aa.beta = gop.beta;
+  aa.w_in = op.d_win; aa.b_in = qop.ca.bias; aa.w_out = op.d_wout;
+  aa.part = scratch; aa.B = B; aa.S = op.S; aa.E = op.E; aa.heads = ATTN_HEADS; aa.groups = GN_GROUPS; aa.eps = GN_EPS;
+  CM_HIP(cm::launch_attn_block(aa, st));
+  cm::CombineArgs cb{};
+  cb.part = scratch; cb.S = ATTN_HEADS; cb.stride = (long long)B * op.S * op.E;
+  cb.bias = oop.ca.bias; cb.temb = nullptr; cb.tidx = m->tbuf;
+  cb.resid = aa.x; cb.res_cs = op.E;
+  cb.out = op.ab_out->d + xoff; cb.C = op.E; cb.V = op.S; cb.B = B;
+  cb.nslots = p.ns_out; cb.stat_part = slot_part(op.ab_out, p.ns_out, b0); cb.stat_cnt = slot_cnt(op.ab_out, p.ns_out, b0);
+  return run_combine(cb, ops, plan, p.carries, b0, st);
+}
+
 // Launch the op list as `plan` says, for plan.ctx.B samples starting at sample `b0` on stream `st`.
 // Every sample-indexed pointer is offset by b0, so two disjoint sub-batches can run
 // concurrently on two streams (`slab` selects the stream's K-split scratch region).
@@ -2004,24 +2088,9 @@ int run_ops(cm_model *m, const FwdPlan &plan, hipStream_t st, int b0 = 0, int sl
                                                                       B, op.S, op.E, ATTN_HEADS, st));
         break;
       }
-      case OP_ATTNBLK: {
-        const Op &gop = ops[op.ab_gn], &qop = ops[op.ab_qkv], &oop = ops[op.ab_outc];
-        float *scratch = m->ks_scratch + (size_t)slab * m->ks_scratch_floats;
-        const size_t xoff = (size_t)b0 * op.S * op.E;
-        cm::AttnBlockArgs aa{};
-        aa.x = op.ab_x->d + xoff; aa.gamma = gop.gamma; aa.beta = gop.beta;
-        aa.w_in = op.d_win; aa.b_in = qop.ca.bias; aa.w_out = op.d_wout;
-        aa.part = scratch; aa.B = B; aa.S = op.S; aa.E = op.E; aa.heads = ATTN_HEADS; aa.groups = GN_GROUPS; aa.eps = GN_EPS;
-        CM_HIP(cm::launch_attn_block(aa, st));
-        cm::CombineArgs cb{};
-        cb.part = scratch; cb.S = ATTN_HEADS; cb.stride = (long long)B * op.S * op.E;
-        cb.bias = oop.ca.bias; cb.temb = nullptr; cb.tidx = m->tbuf;
-        cb.resid = aa.x; cb.res_cs = op.E;
-        cb.out = op.ab_out->d + xoff; cb.C = op.E; cb.V = op.S; cb.B = B;
-        cb.nslots = p.ns_out; cb.stat_part = slot_part(op.ab_out, p.ns_out, b0); cb.stat_cnt = slot_cnt(op.ab_out, p.ns_out, b0);
-        if (run_combine(cb, ops, plan, p.carries, b0, st)) return 1;
+      case OP_ATTNBLK:
+        if (run_attn_block(m, op, plan, p, st, b0, slab)) return 1;
         break;
-      }
     }
     if (m->profile) {
       CM_HIP(hipEventRecord(e1, st));
@@ -2961,11 +3030,17 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count) {
 }
 
 // One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags out_C C0 C1 wino kernel form" or "other <label>";
-// kernel (a name of kConvKernelName) and form (a ConvForm number) are the op's inference route (conv_route).
+// kernel (a name of kConvKernelName) and form (a ConvForm number) are the op's inference route (conv_route).  A fused attention block:
+// "other <label> attn_sample_kernel" or "... attn_head_kernel", what the handle's inference plan launches for it.
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
   CM_NOT_DIT(m, "cm_debug_conv_info");
   if (!m || !m->finalized || !buf || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
+  if (op.kind == OP_ATTNBLK) {   // ... "other <label> <kernel>": what the handle's inference plan launches for the block
+    const FwdPlan pl = plan_forward(m->ops, FwdCtx{m->precision, false, m->h2_stale, m->plan.ctx.B});
+    snprintf(buf, (size_t)capacity, "other %s %s", op.label.c_str(), pl.ops[index].attn_sample ? "attn_sample_kernel" : "attn_head_kernel");
+    return 0;
+  }
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
   const cm::ConvArgs &a = op.ca;
   const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);
@@ -2993,6 +3068,52 @@ extern "C" int cm_debug_loop_ends(cm_model *m, int32_t mask) {
   m->loop_ends = mask;
   return 0;
 }
+
+// Test hook, exported like cm_debug_loop_ends (tests/test_gpu_attn_sample.py): the fused attention block at op `index` ALONE on the
+// caller's input h_x (host, channels-last [B][S][E]).  mode 0: the (head, sample) launch and the head sum; mode 1: the whole-sample
+// launch -- an error, never the other path, where this handle's inference plan at batch B does not take it.  The hook's second pass
+// carries no finalisation.  h_out: [B][S][E]; h_part / h_cnt (may be null): the slot statistics written, [B][ceil(S / 32)][E][2]
+// (mean, M2) and [B][ceil(S / 32)].
+extern "C" int cm_debug_attn_block(cm_model *m, int32_t index, int32_t mode, const float *h_x, float *h_out, float *h_part, float *h_cnt,
+                                   int32_t B) {
+  CM_NOT_DIT(m, "cm_debug_attn_block");
+  if (check_ready(m, B)) return 1;
+  if (!h_x || !h_out || index < 0 || index >= (int)m->ops.size() || mode < 0 || mode > 1) return fail("bad argument");
+  const Op &op = m->ops[index];
+  if (op.kind != OP_ATTNBLK) return fail("op %d is not a fused attention block", index);
+  DevGuard g(m->device);
+  if (m->h2_stale && refresh_h2(m)) return 1;
+  FwdPlan plan;
+  if (make_plan(m, false, B, &plan)) return 1;
+  OpPlan &p = plan.ops[index];
+  if (mode == 1 && !p.attn_sample) return fail("op %d: the plan does not take the whole-sample attention kernel", index);
+  p.attn_sample = mode == 1; p.carries = -1;
+  hipStream_t st = m->stream;
+  const size_t n = (size_t)B * op.S * op.E;
+  CM_HIP(hipMemcpy(op.ab_x->d, h_x, n * sizeof(float), hipMemcpyHostToDevice));
+  const int rc = run_attn_block(m, op, plan, p, st, 0, 0);
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc) return 1;
+  if (e != hipSuccess) return fail("debug attention launch failed: %s", hipGetErrorString(e));
+  CM_HIP(hipMemcpy(h_out, op.ab_out->d, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_part) CM_HIP(hipMemcpy(h_part, op.ab_out->part, (size_t)B * p.ns_out * op.E * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (h_cnt) CM_HIP(hipMemcpy(h_cnt, op.ab_out->cnt, (size_t)B * p.ns_out * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Test hook (tests/test_gpu_attn_sample.py, tests/test_attn_sample_cpu.py): the host-side pack of the whole-sample attention kernel's
+// weight fragments.  w: [N][K] (N % 16 == 0, K % 32 == 0); halves: N * K * 2 f16 bit patterns in the kernel's order
+// ([N / 16][K / 32][hi, mid][64 lanes][8]); *scale: the power of two the weights were multiplied by (0: none).  No device is touched.
+extern "C" int cm_debug_attn_pack(const float *w, int32_t N, int32_t K, uint16_t *halves, float *scale) {
+  if (!w || !halves || !scale || N < 16 || K < 32 || N % 16 || K % 32) return fail("bad argument");
+  *scale = h2_wscale(w, (size_t)N * K);
+  const std::vector<float> f = pack_attn_h2(w, N, K, *scale);
+  std::memcpy(halves, f.data(), f.size() * sizeof(float));
+  return 0;
+}
+
+// ... and its shape predicate (1: the whole-sample kernel admits S tokens of E channels in `heads` heads and `groups` groups)
+extern "C" int cm_debug_attn_sample_ok(int32_t S, int32_t E, int32_t heads, int32_t groups) { return cm::attn_sample_ok(S, E, heads, groups) ? 1 : 0; }
 
 // Test hook (tests/test_gpu_six_term_hostile.py): conv op `index` ALONE on the caller's data -- no GroupNorm / SiLU on load, no
 // time-embedding row, no residual, no fused skip conv; the bias stays.  h_in0 / h_in1: host, channels-last
@@ -3137,6 +3258,14 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
   if (!m || !m->finalized || !flops) return fail("model not finalized");
   for (int i = 0; i < 8; ++i) flops[i] = 0;
   if (b16) for (int i = 0; i < 8; ++i) b16[i] = 0;
+  // the two projections of an attention block that the plan runs as one whole-sample launch: h2 form, three 16-bit products
+  // (the generic conv ops stand in for them here; q k^T and P v stay on the fp32 instruction, counted with OP_ATTN)
+  std::vector<char> h2_attn(m->ops.size(), 0);
+  {
+    const FwdPlan pl = plan_forward(m->ops, FwdCtx{m->precision, false, m->h2_stale, B});
+    for (size_t i = 0; i < m->ops.size(); ++i)
+      if (m->ops[i].kind == OP_ATTNBLK && pl.ops[i].attn_sample) h2_attn[m->ops[i].ab_qkv] = h2_attn[m->ops[i].ab_outc] = 1;
+  }
   for (const Op &op : m->ops) {
     if (op.kind == OP_ATTN) { flops[op.cls] += 4.0 * op.S * (double)op.S * op.E * B; continue; }
     if (op.kind != OP_CONV) continue;
@@ -3177,6 +3306,7 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
         // two-plane source: 6 of 8 (row block, z tap) pairs; two-plane grid: the padding-plane tap is never issued
         if (cm::conv_zsplit_variant(a, op.MB, op.NB)) f *= a.par ? 6.0 / 8.0 : 18.0 / 27.0;
     }
+    if (h2_attn[&op - m->ops.data()]) mult16 = 3.0;
     if (b16 && mult16 > 0.0) b16[op.cls] += mult16 * f * B;
     else flops[op.cls] += f * B;
   }

@@ -191,6 +191,14 @@ int refresh_h2(cm_model *m) {
   };
   std::vector<float> w, gam, bet, frag;
   for (Op &op : m->ops) {
+    if (op.kind == OP_ATTNBLK && op.d_win_h2 && op.d_wout_h2) {   // the whole-sample attention kernel's two weights
+      std::vector<float> wo, fi, fo;
+      if (fetch(op.win_name, &w) || fetch(op.wout_name, &wo)) return 1;
+      attn_pack_h2(w.data(), wo.data(), op.E, &fi, &fo, &op.ab_in_oscale, &op.ab_out_oscale);
+      CM_HIP(hipMemcpy(op.d_win_h2, fi.data(), fi.size() * sizeof(float), hipMemcpyHostToDevice));
+      CM_HIP(hipMemcpy(op.d_wout_h2, fo.data(), fo.size() * sizeof(float), hipMemcpyHostToDevice));
+      continue;
+    }
     if (op.kind != OP_CONV || !(op.d_wwino_h2 || op.d_wqr_h2 || op.d_wfin_h2 || op.d_wups_h2)) continue;
     const int Co = op.ca.Co, Ci = op.ca.C0 + op.ca.C1;
     if (fetch(op.wname, &w)) return 1;

@@ -184,6 +184,48 @@ def check(rc: int) -> None:
         raise NativeError(msg.decode("utf-8", "replace") if msg else f"libcrowdmod_hip call failed ({rc})")
 
 
+# Test hooks exported outside the public header (SIGNATURES mirrors the header): bound on first use.
+_HOOKS = {
+    "cm_debug_attn_block": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
+    "cm_debug_attn_pack": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_float)]),
+    "cm_debug_attn_sample_ok": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+}
+
+
+def hook(name: str):
+    fn = getattr(lib(), name)
+    fn.restype, fn.argtypes = _HOOKS[name]
+    return fn
+
+
+def debug_attn_block(handle, index: int, mode: int, x: np.ndarray):
+    """One fused attention block (op `index`) of a UNet handle on the host array x [B, S, E] (channels-last).
+    mode 0: the (head, sample) launch and the head sum; mode 1: the whole-sample kernel (NativeError where the
+    handle's plan does not take it).  Returns (out [B, S, E], slot partials [B, ns, E, 2], slot counts [B, ns])."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    B, S, E = x.shape
+    ns = (S + 31) // 32
+    out = np.empty_like(x)
+    part = np.empty((B, ns, E, 2), np.float32)
+    cnt = np.empty((B, ns), np.float32)
+    check(hook("cm_debug_attn_block")(handle, index, mode, x.ctypes.data, out.ctypes.data, part.ctypes.data,
+                                      cnt.ctypes.data, B))
+    return out, part, cnt
+
+
+def debug_attn_pack(w: np.ndarray):
+    """Host-side h2 fragment pack of a dense weight [N, K] for the whole-sample attention kernel: (hi, mid) as float32
+    arrays [N, K] of the f16 values (un-permuted from the kernel's lane order) and the power-of-two scale."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    N, K = w.shape
+    halves = np.empty(N * K * 2, np.uint16)
+    scale = C.c_float(0.0)
+    check(hook("cm_debug_attn_pack")(w.ctypes.data, N, K, halves.ctypes.data, C.byref(scale)))
+    f = halves.view(np.float16).astype(np.float32).reshape(N // 16, K // 32, 2, 4, 16, 8)   # [cb][ks][term][g][n % 16][i]
+    t = f.transpose(2, 0, 4, 1, 3, 5).reshape(2, N, K)                                      # [term][cb, n % 16][ks, g, i]
+    return t[0], t[1], float(scale.value)
+
+
 def device_count() -> int:
     n = C.c_int(0)
     check(lib().cm_device_count(C.byref(n)))

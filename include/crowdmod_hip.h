@@ -317,6 +317,9 @@ int cm_mass_preservation_grad(int32_t device, const float *d_x, int32_t B, int32
  * remap off); flags < 0 returns to the environment value.  Results are only defined for 0 / 4096 / 2048 / 512. */
 int cm_debug_conv_flags(int32_t flags);
 int cm_debug_conv_count(const cm_model *m, int32_t *count);
+/* One line of text per op of the plan.  A convolution: "conv <label> ..." (fields: cm_model.cpp).  A fused attention block:
+ * "other <label> <kernel>", <kernel> = attn_sample_kernel or attn_head_kernel -- what this handle's inference plan launches for
+ * the block at the batch of its last forward (planned again on each call, not a record of a launch).  Anything else: "other <label>". */
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity);
 /* Test hook: conv op `index` alone on caller data (no GroupNorm / SiLU / time row / residual / fused skip; bias stays).
  * h_in0 / h_in1: host channels-last [B][Zs][Ys][Xs][C0 / C1]; h_out: host [B][Zo][Yo][Xo][C of the output tensor -- the last
