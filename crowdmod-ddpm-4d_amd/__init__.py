@@ -16,7 +16,7 @@ from . import config  # noqa: F401,E402
 def __getattr__(name):
     # native-backed modules are imported lazily so that `import crowdmod_ddpm_4d_amd`
     # works on a box without the built library (e.g. for prng / spec / config only)
-    if name in ("native", "unet", "dit", "diffusion", "ddpm_model"):
+    if name in ("native", "unet", "dit", "convrnn", "diffusion", "ddpm_model"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     if name in ("UNet",):

@@ -97,6 +97,7 @@ class Resolved:
     nsamples4plots: int
     train: Optional[AttrDict] = None
     dit: Optional["DiTKeys"] = None   # arch DDPM-DiT: the MODEL.DDPM.DIT section; arch FM-DiT: MODEL.FM.DIT
+    convrnn: Optional["ConvRNNKeys"] = None   # arch ConvRNN: the MODEL.CONVRNN section
 
 
 @dataclass
@@ -115,6 +116,36 @@ class DiTKeys:
     train: Optional[AttrDict]
 
 
+@dataclass
+class ConvRNNKeys:
+    """MODEL.CONVRNN as models/convRNN/convRNN.py:29-46,108-109 reads it."""
+    cell_class: str
+    teacher_forcing: bool
+    enc_hidden: Tuple[int, ...]
+    forc_hidden: Tuple[int, ...]
+    enc_kernels: Tuple[int, ...]
+    forc_kernels: Tuple[int, ...]
+    epochs: int
+
+
+def resolve_convrnn(cfg) -> ConvRNNKeys:
+    node = (cfg.get("MODEL", {}) or {}).get("CONVRNN", None)
+    if not node:
+        raise KeyError("MODEL.CONVRNN is missing (needed by arch ConvRNN)")
+
+    def req(key):
+        if key not in node:
+            raise KeyError(f"MODEL.CONVRNN.{key} is missing (needed by arch ConvRNN)")
+        return node[key]
+    cell = str(req("CELL_CLASS"))
+    if cell not in ("ConvGRUCell", "ConvLSTMCell"):
+        raise ValueError(f"Unsupported cell class: {cell}")   # convRNN.py:31-34
+    train = node.get("TRAIN", None) or {}
+    return ConvRNNKeys(cell, bool(node.get("TEACHER_FORCING", False)), tuple(int(v) for v in req("ENC_HIDDEN_CH")),
+                       tuple(int(v) for v in req("FORC_HIDDEN_CH")), tuple(int(v) for v in req("ENC_KERNELS")),
+                       tuple(int(v) for v in req("FORC_KERNELS")), int(train.get("EPOCHS", 0)))
+
+
 def _first(*vals, default=None):
     for v in vals:
         if v is not None:
@@ -126,7 +157,11 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
     """Accept MODEL.DDPM.UNET.* (current), MODEL.DDPM.* + MODEL.* (4test) and the flat
     MODEL.* / DIFFUSION.* / TRAIN.* generation."""
     model = cfg.get("MODEL", {})
-    gen_key, back_key = arch.upper().split("-")
+    convrnn = None
+    if arch == "ConvRNN":   # no generator / backbone pair: the UNet and sampler fields below keep their defaults
+        gen_key, back_key, convrnn = "CONVRNN", "", resolve_convrnn(cfg)
+    else:
+        gen_key, back_key = arch.upper().split("-")
     gen = model.get(gen_key, {}) or {}
     back = gen.get(back_key, {}) or {}
     diff = cfg.get("DIFFUSION", {}) or {}
@@ -172,5 +207,5 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
         time_emb_mult=int(bk("TIME_EMB_MULT", 4)), condition=str(bk("CONDITION", "Past")),
         nsamples=int(_first(model.get("NSAMPLES"), diff.get("NSAMPLES"), default=1280)),
         nsamples4plots=int(_first(model.get("NSAMPLES4PLOTS"), diff.get("NSAMPLES4PLOTS"), default=20)),
-        train=train, dit=dit,
+        train=train, dit=dit, convrnn=convrnn,
     )

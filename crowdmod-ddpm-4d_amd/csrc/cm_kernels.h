@@ -492,6 +492,30 @@ hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st);
 // DiT2D: one self-attention over all T_p * N_s tokens of a sample (any count), on the fp32 matrix instruction
 hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st);
 
+// ConvRNN forecaster (cm_convrnn.hip): one implicit-GEMM 2-D convolution with fused epilogues, and the frame packer.
+enum { CRNN_GEO_S1 = 0, CRNN_GEO_S2 = 1, CRNN_GEO_T4 = 2 };   // 3x3 stride 1 pad 1; 3x3 stride 2 pad 1; transposed 4x4 stride 2 pad 1
+enum { CRNN_EPI_LEAKY = 0, CRNN_EPI_GRU_GATES = 1, CRNN_EPI_GRU_CAND = 2, CRNN_EPI_LSTM = 3, CRNN_EPI_LAST = 4 };
+struct CrnnConvArgs {
+  int geo, epi;
+  const float *x0, *x1;           // sources, channels-last [B][Hi][Wi][C0 | C1], concatenated on channels (x1 null: C1 = 0)
+  long long bs0, bs1;             // elements between two samples of a source
+  int C0, C1;                     // multiples of 8
+  const float *W;                 // packed [N][K], K = taps * (C0 + C1), k = tap * (C0 + C1) + c; CRNN_GEO_T4: [4 parity classes][N][K]
+  int B, Hi, Wi, Ho, Wo, N;
+  float *y;                       // LEAKY: [B][Ho][Wo][N]; GRU_GATES: r * h_prev [..][N/2]; GRU_CAND / LSTM: the new h [..][N | N/4]
+  float *u;                       // GRU_GATES: writes u [..][N/2]; GRU_CAND: reads it
+  const float *hprev;             // GRU_GATES / GRU_CAND: h_prev [B][Ho][Wo][hid]
+  float *c;                       // LSTM: the cell state [B][Ho][Wo][N/4], updated in place
+  float *out; int Ft, t;          // LAST: result [B][N][Ho][Wo][Ft] (reference layout), frame t
+  float *win; long long win_bs;   // LAST: or null; the window frame [Ho][Wo][8] this step frees (exp on channels 0 and 3), sample stride
+  int exp_out;                    // LAST: exp on channels 0 and 3 of `out` as well
+};
+hipError_t launch_crnn_conv(const CrnnConvArgs &a, hipStream_t st);
+// Frames [B][4][H][W][L] (reference layout) into window slots slot0 .. slot0 + L - 1 of win [B][nslots][H][W][8]; channels 4-7 get 0.
+hipError_t launch_crnn_pack_frames(const float *src, float *win, int B, int H, int W, int L, int nslots, int slot0, hipStream_t st);
+// State [B][h][w][C] (channels-last) into [B][C][h][w].
+hipError_t launch_crnn_state_nchw(const float *src, float *dst, int B, int C, int h, int w, hipStream_t st);
+
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.
 struct StepRow { int t; float c_x, c_eps, c_noise, guid; int draw; int step; float mass; };   // mass: MassApplyArgs::c

@@ -51,6 +51,15 @@ class cm_dit2d_config(C.Structure):
     ]
 
 
+class cm_convrnn_config(C.Structure):
+    _fields_ = [
+        ("in_channels", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("past_len", C.c_int32),
+        ("future_len", C.c_int32), ("cell", C.c_int32),
+        ("enc_hidden", C.c_int32 * 6), ("forc_hidden", C.c_int32 * 7), ("enc_kernels", C.c_int32 * 6),
+        ("forc_kernels", C.c_int32 * 7), ("max_batch", C.c_int32), ("device", C.c_int32),
+    ]
+
+
 class cm_sample_opts(C.Structure):
     _fields_ = [
         ("sampler", C.c_int32), ("guidance", C.c_int32), ("lambda_guidance", C.c_float),
@@ -62,6 +71,7 @@ class cm_sample_opts(C.Structure):
 
 SAMPLER_DDPM, SAMPLER_DDIM, SAMPLER_FM_EULER = 0, 1, 2
 PRECISION_F32, PRECISION_F16, PRECISION_F32R, PRECISION_F32X = 0, 1, 2, 3
+CELL_GRU, CELL_LSTM = 0, 1
 GUIDANCE_NONE, GUIDANCE_SPARSITY, GUIDANCE_MASS_PRESERVATION = 0, 1, 2
 TABLES = ("beta", "alpha", "alpha_bar", "sqrt_alpha_bar", "one_by_sqrt_alpha", "sqrt_one_minus_alpha_bar")
 
@@ -135,6 +145,17 @@ SIGNATURES = {
     "cm_train_get_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
     "cm_train_set_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
     "cm_train_opt_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
+    "cm_convrnn_create": (C.c_int, [C.POINTER(cm_convrnn_config), C.POINTER(_P)]),
+    "cm_convrnn_destroy": (C.c_int, [_P]),
+    "cm_convrnn_num_params": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "cm_convrnn_param_info": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "cm_convrnn_set_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "cm_convrnn_get_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "cm_convrnn_finalize": (C.c_int, [_P]),
+    "cm_convrnn_forecast": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    "cm_convrnn_forecast_host": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
+    "cm_convrnn_debug_state": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "cm_convrnn_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 

@@ -36,24 +36,30 @@ def main(argv=None):
     ap.add_argument('--device', type=int, default=0)
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
-    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-DiT"):
-        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet, DDPM-DiT and FM-DiT on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-DiT", "ConvRNN"):
+        raise SystemExit(f"{args.arch}: generate_metrics is implemented for DDPM-UNet, DDPM-DiT, FM-DiT and ConvRNN on this path")
     from crowdmod_ddpm_4d_amd.ddpm_model import DDPM_model
     from generate_samples import model_fullname, windows
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
-    if args.timesteps and args.arch == "FM-DiT":
+    if args.arch == "ConvRNN":
+        pass                                    # a deterministic forecaster: no sampler steps to override
+    elif args.timesteps and args.arch == "FM-DiT":
         cfg.MODEL.FM.INTEGRATOR_STEPS.EULER = int(args.timesteps)
     elif args.timesteps:
         cfg.MODEL.DDPM.TIMESTEPS = int(args.timesteps)
     res = cfgmod.resolve(cfg, args.arch)
-    mprops = 3   # generate_metrics.py:60 of the reference
+    mprops = 4 if args.arch == "ConvRNN" else 3   # generate_metrics.py:60 of the reference; the forecaster takes all four
     # generate_metrics.py:63-68: NSAMPLES chains in chunks of 20 repeats, or BATCH_SIZE * chunk when the flag is given
     if args.chunk_repd_past_seq is None:
         samples_per_batch, chunk = res.nsamples, 20
     else:
         samples_per_batch, chunk = res.batch_size * args.chunk_repd_past_seq, args.chunk_repd_past_seq
     out_dir = os.path.join(cfg.DATA_FS.get("OUTPUT_DIR", "output"), "metrics")
-    if args.arch == "FM-DiT":
+    if args.arch == "ConvRNN":
+        from crowdmod_ddpm_4d_amd.convrnn import ConvRNN_model
+        model = ConvRNN_model(cfg, args.arch, mprops, output_dir=out_dir, device=args.device)
+        ckpt = model.checkpoint_path(args.model_sample_to_load)
+    elif args.arch == "FM-DiT":
         from crowdmod_ddpm_4d_amd.flow_matching import FM_model
         model = FM_model(cfg, args.arch, mprops, output_dir=out_dir, device=args.device)
         ckpt = model.checkpoint_path(args.model_sample_to_load)
@@ -77,6 +83,8 @@ def main(argv=None):
             p = prng.normal(11, f"metrics/past/{bi}", int(np.prod(sp))).reshape(sp)
             f = prng.normal(11, f"metrics/future/{bi}", int(np.prod(sf))).reshape(sf)
             p[:, 0], f[:, 0] = np.maximum(p[:, 0], 0), np.maximum(f[:, 0], 0)      # density is non-negative
+            if mprops > 3:
+                p[:, 3], f[:, 3] = np.abs(p[:, 3]), np.abs(f[:, 3])                # and so is the variance channel
             batches.append((p, f))
     logging.info("=======>>>> Init metrics compute for %s dataset with %s architecture: %d chains per batch (%d repeats)",
                  cfg.DATASET.get("NAME", "?"), args.arch, samples_per_batch, chunk)

@@ -62,18 +62,20 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
-    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-UNet", "FM-DiT"):
-        raise SystemExit(f"{args.arch}: only DDPM-UNet, DDPM-DiT, FM-UNet and FM-DiT are implemented on this path")
+    if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-UNet", "FM-DiT", "ConvRNN"):
+        raise SystemExit(f"{args.arch}: only DDPM-UNet, DDPM-DiT, FM-UNet, FM-DiT and ConvRNN are implemented on this path")
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
     res = cfgmod.resolve(cfg, args.arch)
-    mprops = 3  # generate_samples.py:76 of the reference
-    if args.arch.startswith("FM-"):
+    mprops = 4 if args.arch == "ConvRNN" else 3  # generate_samples.py:76 of the reference; the forecaster takes all four
+    if args.arch == "ConvRNN":
+        from crowdmod_ddpm_4d_amd.convrnn import ConvRNN_model as Model
+    elif args.arch.startswith("FM-"):
         from crowdmod_ddpm_4d_amd.flow_matching import FM_model as Model
     else:
         Model = DDPM_model
     model = Model(cfg, args.arch, mprops, output_dir=cfg.DATA_FS.get("OUTPUT_DIR", "output"),
                   from_fixed_past=args.from_fixed_past, device=args.device)
-    ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch.startswith("FM-") else \
+    ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch.startswith("FM-") or args.arch == "ConvRNN" else \
         model_fullname(cfg, args.arch, args.model_sample_to_load)
     if os.path.isfile(ckpt):
         logging.info("model full name: %s", ckpt)
@@ -90,6 +92,8 @@ def main():
         shape_f = (n, mprops, res.rows, res.cols, res.future_len)
         past = prng.normal(7, "cli/past", int(np.prod(shape_p))).reshape(shape_p)
         fut = prng.normal(7, "cli/future", int(np.prod(shape_f))).reshape(shape_f)
+        if mprops > 3:   # the forecaster's density and variance channels are non-negative
+            past[:, [0, 3]], fut[:, [0, 3]] = np.abs(past[:, [0, 3]]), np.abs(fut[:, [0, 3]])
     pred, idx, pasts, futures = model.sampling([(past, fut)], args.plot_type, None, args.plot_mprop, args.plot_past,
                                                args.same_past_seq, None)
     os.makedirs(model.output_dir, exist_ok=True)

@@ -386,6 +386,53 @@ int cm_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel
  * returns them) and refresh the eval-mode time-embedding table. */
 int cm_train_sync(cm_model *m);
 
+/* ---- ConvRNN forecaster: replaces Forecaster(...) (models/convRNN/forecaster.py) and
+ * ConvRNN_model._generate_convRNN (models/convRNN/convRNN.py:223-231) -----------------------------------
+ * The deterministic ConvGRU / ConvLSTM encoder-forecaster baseline of arch "ConvRNN".  It has no timestep and no
+ * sampler, so it is a handle of its own.  Inference only.  Exact fp32 on v_mfma_f32_32x32x2_f32 throughout. */
+enum { CM_CELL_GRU = 0, CM_CELL_LSTM = 1 };
+typedef struct cm_convrnn_config {
+  int32_t in_channels;                    /* mprops_count: 4 (channels 0 and 3 are indexed)       */
+  int32_t rows, cols;                     /* MACROPROPS.ROWS / COLS: multiples of 4               */
+  int32_t past_len, future_len;           /* DATASET.PAST_LEN / FUTURE_LEN, each >= 1             */
+  int32_t cell;                           /* MODEL.CONVRNN.CELL_CLASS: CM_CELL_GRU / CM_CELL_LSTM */
+  int32_t enc_hidden[6], forc_hidden[7];  /* ENC_HIDDEN_CH, FORC_HIDDEN_CH                        */
+  int32_t enc_kernels[6], forc_kernels[7];/* ENC_KERNELS, FORC_KERNELS                            */
+  int32_t max_batch;                      /* workspace is sized for this batch                    */
+  int32_t device;                         /* HIP device ordinal; < 0: host-only handle (names, shapes, set / get) */
+} cm_convrnn_config;
+typedef struct cm_convrnn cm_convrnn;
+/* Refused with a status that names the violated constraint (the reference would fail in torch.cat or in a conv):
+ * in_channels != 4; rows or cols no multiple of 4; enc_kernels other than [3,3,3,3,3,3] or forc_kernels other than
+ * [3,4,3,4,3,3,3]; a channel count that is no multiple of 8 in [8, 1024]; feed-through counts enc_hidden[2] ==
+ * enc_hidden[1], enc_hidden[4] == enc_hidden[3], forc_hidden[0] == enc_hidden[5]; shared-state counts forc_hidden[1] ==
+ * enc_hidden[5], forc_hidden[3] == enc_hidden[3], forc_hidden[5] == enc_hidden[1]; past_len or future_len < 1;
+ * max_batch * rows * cols above 2^31 - 64. */
+int cm_convrnn_create(const cm_convrnn_config *cfg, cm_convrnn **out);
+int cm_convrnn_destroy(cm_convrnn *m);
+/* state_dict() enumeration in the reference's order (bias=False: weights only): encoder.encoder_cell_list.0-5, then
+ * forecaster_cell_list.0-6; 25 tensors with GRU cells, 13 with LSTM cells. */
+int cm_convrnn_num_params(const cm_convrnn *m, int32_t *count);
+int cm_convrnn_param_info(const cm_convrnn *m, int32_t index, const char **name, int64_t shape[4], int32_t *ndim);
+int cm_convrnn_set_param(cm_convrnn *m, const char *name, const float *h_data, int64_t numel);
+int cm_convrnn_get_param(const cm_convrnn *m, const char *name, float *h_data, int64_t numel);
+/* Packs the weights once and allocates the workspace; fails if a tensor was never set or on a host-only handle. */
+int cm_convrnn_finalize(cm_convrnn *m);
+/* Forecaster.forward(x_obs, target_obs, teacher_forcing) -- forecaster.py:89-176: all future_len steps behind one call,
+ * hidden states zero at its start.
+ *   d_past [B,4,H,W,P], d_target [B,4,H,W,F] (read only under teacher forcing; may be NULL otherwise),
+ *   d_out [B,4,H,W,F]: the raw frames, or with exp_output != 0 with exp on channels 0 and 3 (convRNN.py:228-229). */
+int cm_convrnn_forecast(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing,
+                        int32_t exp_output, float *d_out, int32_t B, void *stream);
+/* Same with host buffers (synchronous). */
+int cm_convrnn_forecast_host(cm_convrnn *m, const float *h_past, const float *h_target, int32_t teacher_forcing,
+                             int32_t exp_output, float *h_out, int32_t B);
+/* Test hook: the hidden state the last call left, as [B,C,h,w]; level 0 quarter, 1 half, 2 full resolution; which 0 = h,
+ * 1 = c (LSTM only).  The caller has synchronised the stream of that call. */
+int cm_convrnn_debug_state(cm_convrnn *m, int32_t level, int32_t which, float *h_out, int64_t capacity, int64_t shape[4]);
+/* Algorithmic FLOPs and bytes of one forecast at batch B. */
+int cm_convrnn_cost(const cm_convrnn *m, int32_t B, double *flops, double *bytes);
+
 #ifdef __cplusplus
 }
 #endif
