@@ -6,6 +6,7 @@
 #include "cm_model.cpp"
 
 #include <cstdlib>
+#include <limits>
 #include <random>
 
 namespace {
@@ -92,6 +93,223 @@ void test_plan_and_params() {
   EXPECT(cm_model_create(nullptr, &m) != 0);
 }
 
+// fragment element i holds source element idx[i], or the zero padding where idx[i] is -1
+void expect_gather(const std::vector<float> &frag, const std::vector<int> &idx, const std::vector<float> &src) {
+  EXPECT(frag.size() == idx.size());
+  for (size_t i = 0; i < idx.size(); ++i) {
+    EXPECT(idx[i] >= -1 && idx[i] < (int)src.size());
+    if (idx[i] >= 0) EXPECT(frag[i] == src[(size_t)idx[i]]); else EXPECT(frag[i] == 0.f);
+  }
+}
+
+// ---- fragment digests ------------------------------------------------------------------------------------------------------------
+// Every packer's output bytes on fixed inputs, as 64-bit FNV-1a digests recorded from the packers as they stood before the layouts moved
+// to cm_pack.h: a refactor of a layout must leave every fragment bit for bit what it was.
+uint64_t fnv1a(const void *p, size_t n, uint64_t h = 0xcbf29ce484222325ull) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001b3ull; }
+  return h;
+}
+template <class T>
+uint64_t digest(const std::vector<T> &v, long long extra = 0) {
+  return fnv1a(&extra, sizeof extra, fnv1a(v.data(), v.size() * sizeof(T)));
+}
+// Weights built from raw generator words by integer arithmetic alone (no library distribution): a full 24-bit significand (23 random
+// fraction bits), both signs, magnitudes over eight binades [2^-4, 2^4) -- so a changed summation order, or a fold in float instead of
+// double, changes a digest.
+std::vector<float> digest_weights(std::mt19937 &rng, size_t n) {
+  std::vector<float> w(n);
+  for (auto &v : w) {
+    const uint32_t r = rng();
+    const uint32_t u = (r & 0x80000000u) | ((123u + ((r >> 24) & 7u)) << 23) | (r & 0x7fffffu);
+    std::memcpy(&v, &u, 4);
+  }
+  return w;
+}
+
+struct Digest { std::string name; uint64_t d; };
+
+std::vector<Digest> fragment_digests() {
+  std::vector<Digest> out;
+  std::mt19937 rng(20260);
+  auto tag = [](const char *what, std::initializer_list<int> dims) {
+    std::string s = what;
+    for (int d : dims) s += "_" + std::to_string(d);
+    return s;
+  };
+  // generic layout, and its f16 flavour on the base, three-chunk and one-parity-class cases
+  struct Gen { int Co, Ci, ntaps, Ci_pad, CK, NB; bool f16; };
+  const Gen gens[] = {{32, 32, 27, 32, 32, 1, true},   {40, 24, 27, 24, 8, 2, false},   {32, 3, 27, 8, 8, 1, false},
+                      {64, 96, 27, 96, 32, 2, true},   {128, 192, 1, 192, 64, 2, false}, {64, 64, 8, 64, 32, 2, true}};
+  for (const Gen &c : gens) {
+    const std::vector<float> W = digest_weights(rng, (size_t)c.Co * c.Ci * c.ntaps);
+    // (8 taps: one parity class, already in its own e order)
+    const std::vector<float> wi = c.ntaps == 8 ? W : to_internal_taps(W.data(), c.Co, c.Ci, c.ntaps);
+    out.push_back({tag("taps", {c.Co, c.Ci, c.ntaps}), digest(wi)});
+    out.push_back({tag("conv", {c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB}), digest(pack_conv(wi.data(), c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB))});
+    if (c.f16)
+      out.push_back({tag("conv_f16", {c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB}), digest(pack_conv_f16(wi.data(), c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB))});
+  }
+  // parity fold + the 8-class concatenation through each per-class packer
+  for (auto cc : {std::make_pair(32, 32), std::make_pair(64, 96)}) {
+    const int Co = cc.first, Ci = cc.second, NB = Co > 32 ? 2 : 1;
+    const std::vector<float> W = digest_weights(rng, (size_t)Co * Ci * 27);
+    const std::vector<float> wp = parity_weights(to_internal_taps(W.data(), Co, Ci, 27), Co, Ci);
+    out.push_back({tag("parity", {Co, Ci}), digest(wp)});
+    const float ws = h2_wscale(wp.data(), wp.size());
+    EXPECT(ws > 0.f);
+    long long stride = 0;
+    const std::vector<float> g = pack_parity_classes(wp, &stride, [&](const float *w8) { return pack_conv(w8, Co, Ci, 8, Ci, 32, NB); });
+    out.push_back({tag("parity_conv", {Co, Ci}), digest(g, stride)});
+    const std::vector<float> b6 = pack_parity_classes(wp, &stride, [&](const float *w8) { return pack_ups_b6(w8, Co, Ci); });
+    out.push_back({tag("parity_ups_b6", {Co, Ci}), digest(b6, stride)});
+    const std::vector<float> h2 = pack_parity_classes(wp, &stride, [&](const float *w8) { return pack_ups_b6(w8, Co, Ci, ws); });
+    out.push_back({tag("parity_ups_h2", {Co, Ci}), digest(h2, stride)});
+    const std::vector<float> f16 = pack_parity_classes(wp, &stride, [&](const float *w8) { return pack_ups_f16(w8, Co, Ci); });
+    out.push_back({tag("parity_ups_f16", {Co, Ci}), digest(f16, stride)});
+  }
+  // whole-sample quarter-resolution kernel: (32, 16) has the padded 16-channel step (2 channels per wave)
+  for (auto cc : {std::make_pair(32, 16), std::make_pair(64, 64), std::make_pair(128, 192)}) {
+    const int Co = cc.first, Ci = cc.second;
+    const std::vector<float> wi = digest_weights(rng, (size_t)Co * Ci * 27), w2 = digest_weights(rng, (size_t)Co * Ci);
+    const std::vector<float> wq = pack_qr(wi, Co, Ci);
+    out.push_back({tag("qr", {Co, Ci}), digest(wq)});
+    out.push_back({tag("qr_b6", {Co, Ci}), digest(pack_qr_b6(wq, Co, Ci))});
+    out.push_back({tag("qr_h2", {Co, Ci}), digest(pack_qr_b6(wq, Co, Ci, h2_wscale(wq.data(), wq.size())))});
+    out.push_back({tag("qr_skip", {Co, Ci}), digest(pack_qr_skip(w2.data(), Co, Ci))});
+  }
+  // first conv (Co = 32): 3 and 4 of 4 input channels, 5 and 8 of 8
+  for (int Ci : {3, 4, 5, 8}) {
+    const std::vector<float> wi = digest_weights(rng, (size_t)32 * Ci * 27);
+    out.push_back({tag("first", {32, Ci}), digest(pack_first(wi.data(), 32, Ci, Ci <= 4 ? 4 : 8))});
+  }
+  // small-N last conv: 3 and 4 of 4 output channels, 5 and 8 of 8; 3 of 8 padded input channels
+  for (int Co : {3, 4, 5, 8}) {
+    const std::vector<float> wi = digest_weights(rng, (size_t)Co * 32 * 27);
+    out.push_back({tag("small", {Co, 32, 32, 32}), digest(pack_small(wi.data(), Co, 32, 32, 32, Co <= 4 ? 4 : 8))});
+  }
+  {
+    const std::vector<float> wi = digest_weights(rng, (size_t)3 * 3 * 27);
+    out.push_back({tag("small", {3, 3, 8, 8}), digest(pack_small(wi.data(), 3, 3, 8, 8, 4))});
+  }
+  // Winograd: fp32, f16, six-term and h2
+  for (auto cc : {std::make_pair(32, 16), std::make_pair(64, 96)}) {
+    const int Co = cc.first, Ci = cc.second;
+    const std::vector<float> wi = digest_weights(rng, (size_t)Co * Ci * 27);
+    const std::vector<float> ww = pack_wino(wi, Co, Ci, Ci);
+    out.push_back({tag("wino", {Co, Ci}), digest(ww)});
+    out.push_back({tag("wino_f16", {Co, Ci}), digest(pack_wino_f16(wi, Co, Ci, Ci))});
+    out.push_back({tag("wino_b6", {Co, Ci}), digest(pack_wino_b6(ww))});
+    out.push_back({tag("wino_h2", {Co, Ci}), digest(pack_wino_b6(ww, h2_wscale(ww.data(), ww.size())))});
+  }
+  // f16 plan: direct kernel, 1x1x1 (96 of 128 output channels in the second tile)
+  {
+    const std::vector<float> wi = digest_weights(rng, (size_t)64 * 32 * 27), w1 = digest_weights(rng, (size_t)96 * 32);
+    for (int NB : {1, 2}) out.push_back({tag("f16d", {64, 32, 27, NB}), digest(pack_f16d(wi.data(), 64, 32, 27, NB))});
+    for (int NB : {1, 2}) out.push_back({tag("1x1_f16", {96, 32, NB}), digest(pack_1x1_f16(w1.data(), 96, 32, NB))});
+  }
+  // whole-sample attention kernel
+  for (auto nk : {std::make_pair(48, 32), std::make_pair(128, 128)}) {
+    const std::vector<float> w = digest_weights(rng, (size_t)nk.first * nk.second);
+    out.push_back({tag("attn_h2", {nk.first, nk.second}), digest(pack_attn_h2(w.data(), nk.first, nk.second, h2_wscale(w.data(), w.size())))});
+  }
+  // the whole h2 helper (scale + fragments) from a reference-layout weight; all-zero weights and weights with one infinity have no
+  // scale and get no fragments
+  struct H2 { H2Kind kind; const char *name; int Co, Ci; };
+  const H2 h2s[] = {{H2_FIN, "h2_fin", 3, 32}, {H2_WINO, "h2_wino", 64, 96}, {H2_QR, "h2_qr", 64, 64}, {H2_UPS, "h2_ups", 32, 32}};
+  for (const H2 &c : h2s) {
+    std::vector<float> w = digest_weights(rng, (size_t)c.Co * c.Ci * 27), frag;
+    const float ws = h2_fragments(c.kind, w.data(), c.Co, c.Ci, &frag);
+    EXPECT(ws > 0.f && (c.kind == H2_FIN) == frag.empty());
+    long long ws_bits = 0;
+    std::memcpy(&ws_bits, &ws, 4);
+    out.push_back({tag(c.name, {c.Co, c.Ci}), digest(frag, ws_bits)});
+    frag.clear();
+    w[w.size() / 3] = std::numeric_limits<float>::infinity();
+    EXPECT(h2_fragments(c.kind, w.data(), c.Co, c.Ci, &frag) == 0.f && frag.empty());
+    std::fill(w.begin(), w.end(), 0.f);
+    EXPECT(h2_fragments(c.kind, w.data(), c.Co, c.Ci, &frag) == 0.f && frag.empty());
+  }
+  return out;
+}
+
+void test_fragment_digests() {
+  static const struct { const char *name; uint64_t d; } want[] = {
+      {"taps_32_32_27", 0x820a5de693853861ull},
+      {"conv_32_32_27_32_32_1", 0xfbc284684e8b9771ull},
+      {"conv_f16_32_32_27_32_32_1", 0x22bfedb98083e5d7ull},
+      {"taps_40_24_27", 0x3008ce9498a90dd8ull},
+      {"conv_40_24_27_24_8_2", 0xf34a22de97258540ull},
+      {"taps_32_3_27", 0x2fa3ac24aa9974e8ull},
+      {"conv_32_3_27_8_8_1", 0xd52e2501401ccc70ull},
+      {"taps_64_96_27", 0xde6d731ca3c825f5ull},
+      {"conv_64_96_27_96_32_2", 0x4c42cbe1a7d7d469ull},
+      {"conv_f16_64_96_27_96_32_2", 0xb4d5fafb0c4f0fceull},
+      {"taps_128_192_1", 0x67bbf4fd37aa7a2dull},
+      {"conv_128_192_1_192_64_2", 0xafa843c6b6359db1ull},
+      {"taps_64_64_8", 0x778dd0a9b8267264ull},
+      {"conv_64_64_8_64_32_2", 0x0b2d450649c17bfcull},
+      {"conv_f16_64_64_8_64_32_2", 0xf6bb147c91004590ull},
+      {"parity_32_32", 0x42dbd1be1df39487ull},
+      {"parity_conv_32_32", 0xa5b8ec34ad30ad4bull},
+      {"parity_ups_b6_32_32", 0x5b7d83fc367af890ull},
+      {"parity_ups_h2_32_32", 0x30faf7615c981d88ull},
+      {"parity_ups_f16_32_32", 0xd394af8fa3c998b6ull},
+      {"parity_64_96", 0xc4b58d87886dc5d9ull},
+      {"parity_conv_64_96", 0x8193d7884570537dull},
+      {"parity_ups_b6_64_96", 0x09a99acba4c69f68ull},
+      {"parity_ups_h2_64_96", 0x038a11f5b1f6e67eull},
+      {"parity_ups_f16_64_96", 0xe3fa39dc94e2b1a9ull},
+      {"qr_32_16", 0x58412134865cfbf6ull},
+      {"qr_b6_32_16", 0x0ef963b4b36a00e9ull},
+      {"qr_h2_32_16", 0x075325de759b7942ull},
+      {"qr_skip_32_16", 0xa1d0aa697ee6ea36ull},
+      {"qr_64_64", 0xa490111431f27e05ull},
+      {"qr_b6_64_64", 0x402032d474195320ull},
+      {"qr_h2_64_64", 0x43b749f659ceac49ull},
+      {"qr_skip_64_64", 0xd8a30f37caf41c6cull},
+      {"qr_128_192", 0x051db83360196265ull},
+      {"qr_b6_128_192", 0x0e53e1d8ad010f43ull},
+      {"qr_h2_128_192", 0xaba34ab55ac37a0dull},
+      {"qr_skip_128_192", 0x1f49c64dae5c1eb6ull},
+      {"first_32_3", 0x85e622c61b8ea8beull},
+      {"first_32_4", 0x14dde78bee8b9713ull},
+      {"first_32_5", 0xe0048aca83c63c7cull},
+      {"first_32_8", 0x1b31c6efd1f9199dull},
+      {"small_3_32_32_32", 0x82f64ac22f6431c8ull},
+      {"small_4_32_32_32", 0x7faa7f1290d32e13ull},
+      {"small_5_32_32_32", 0xd6bd6fb6ed697861ull},
+      {"small_8_32_32_32", 0xb6fca231c0852828ull},
+      {"small_3_3_8_8", 0xd9507e0d72aee490ull},
+      {"wino_32_16", 0xe60e5c814351dbf7ull},
+      {"wino_f16_32_16", 0x30db97b589846670ull},
+      {"wino_b6_32_16", 0x03be74e468ffd285ull},
+      {"wino_h2_32_16", 0x35026faa11129b4dull},
+      {"wino_64_96", 0x13c797f5d6645704ull},
+      {"wino_f16_64_96", 0x547b13a77069a2bbull},
+      {"wino_b6_64_96", 0x614bdcfacf53fdacull},
+      {"wino_h2_64_96", 0xeccc0c63cc596680ull},
+      {"f16d_64_32_27_1", 0x45dd1faefb431eb9ull},
+      {"f16d_64_32_27_2", 0x32f04be83c18b49dull},
+      {"1x1_f16_96_32_1", 0x6fe1fa8106ae219dull},
+      {"1x1_f16_96_32_2", 0x6e31becb0d7be2c5ull},
+      {"attn_h2_48_32", 0xe991c10c27ae644aull},
+      {"attn_h2_128_128", 0x5a7f2dfc5cdbe892ull},
+      {"h2_fin_3_32", 0xa1c5362786b728f9ull},
+      {"h2_wino_64_96", 0xc4e14f6f365d2323ull},
+      {"h2_qr_64_64", 0x613cd27fece883f3ull},
+      {"h2_ups_32_32", 0xbf8bbe9249def9eeull},
+  };
+  const std::vector<Digest> got = fragment_digests();
+  EXPECT(got.size() == sizeof want / sizeof want[0]);
+  for (size_t i = 0; i < got.size(); ++i) {
+    if (got[i].name != want[i].name || got[i].d != want[i].d)
+      fprintf(stderr, "fragment digest %zu: %s 0x%016llx, recorded %s 0x%016llx\n", i, got[i].name.c_str(), (unsigned long long)got[i].d,
+              want[i].name, (unsigned long long)want[i].d);
+    EXPECT(got[i].name == want[i].name && got[i].d == want[i].d);
+  }
+}
+
 void test_packers() {
   std::mt19937 rng(2);
   std::uniform_real_distribution<float> U(-1.f, 1.f);
@@ -103,7 +321,7 @@ void test_packers() {
     for (auto &v : W) v = U(rng);
     const std::vector<float> wi = to_internal_taps(W.data(), c.Co, c.Ci, c.ntaps);
     EXPECT(wi.size() == W.size());
-    const std::vector<float> wf = pack_conv_weights(wi.data(), c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB);
+    const std::vector<float> wf = pack_conv(wi.data(), c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB);
     const int TN = 32 * c.NB, ntn = (c.Co + TN - 1) / TN;
     EXPECT(wf.size() == (size_t)ntn * (c.Ci_pad / c.CK) * c.ntaps * (c.CK / 8) * c.NB * 256);
     // every reference weight appears exactly once; everything else is zero padding
@@ -125,12 +343,75 @@ void test_packers() {
     // index version (training re-pack): same positions are filled
     std::vector<int> src((size_t)c.Co * c.Ci * c.ntaps);
     for (size_t i = 0; i < src.size(); ++i) src[i] = (int)i;
-    const std::vector<int> pi = pack_conv_indices(src, 1, c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB);
-    EXPECT(pi.size() == wf.size());
-    for (size_t i = 0; i < pi.size(); ++i) {
-      EXPECT(pi[i] >= -1 && pi[i] < (int)src.size());
-      if (pi[i] >= 0) EXPECT(wf[i] == wi[(size_t)pi[i]]); else EXPECT(wf[i] == 0.f);
-    }
+    const std::vector<int> pi = pack_conv(src.data(), c.Co, c.Ci, c.ntaps, c.Ci_pad, c.CK, c.NB, -1);
+    expect_gather(wf, pi, wi);
+  }
+}
+
+// Values against indices, for every layout that is packed as values when a handle loads and as indices for the re-pack after an
+// optimizer step: the one template, on the positions 0, 1, 2, ... of the source, must name for every fragment element the source
+// element the value packer put there.
+void test_value_index_layouts() {
+  std::mt19937 rng(7);
+  auto iota_of = [](size_t n) { std::vector<int> v(n); std::iota(v.begin(), v.end(), 0); return v; };
+  // quarter-resolution kernel and its fused skip; the data gradient packs W'[ci][co][flipped tap] with Co and Ci swapped
+  for (auto cc : {std::make_pair(32, 16), std::make_pair(64, 64), std::make_pair(128, 192), std::make_pair(64, 128)}) {
+    const int Co = cc.first, Ci = cc.second;
+    const std::vector<float> wi = digest_weights(rng, (size_t)Co * Ci * 27), w2 = digest_weights(rng, (size_t)Co * Ci);
+    expect_gather(pack_qr(wi, Co, Ci), pack_qr(iota_of(wi.size()), Co, Ci), wi);
+    expect_gather(pack_qr_skip(w2.data(), Co, Ci), pack_qr_skip(iota_of(w2.size()).data(), Co, Ci), w2);
+    if (Ci % 32) continue;
+    std::vector<int> src((size_t)Ci * Co * 27);                  // train_setup's data-gradient map
+    std::vector<float> wt(src.size());
+    for (int ci = 0; ci < Ci; ++ci)
+      for (int co = 0; co < Co; ++co)
+        for (int t = 0; t < 27; ++t) {
+          src[((size_t)ci * Co + co) * 27 + t] = (int)(((size_t)co * Ci + ci) * 27 + (26 - t));
+          wt[((size_t)ci * Co + co) * 27 + t] = wi[((size_t)co * Ci + ci) * 27 + (26 - t)];
+        }
+    expect_gather(pack_qr(wt, Ci, Co), pack_qr(src, Ci, Co), wi);
+    expect_gather(pack_conv(wt.data(), Ci, Co, 27, Co, 32, Ci > 32 ? 2 : 1), pack_conv(src.data(), Ci, Co, 27, Co, 32, Ci > 32 ? 2 : 1, -1), wi);
+  }
+  // first conv: 3 / 4 of 4 input channels, 5 / 8 of 8
+  for (int Ci : {3, 4, 5, 8}) {
+    const std::vector<float> wi = digest_weights(rng, (size_t)32 * Ci * 27);
+    const int cin = Ci <= 4 ? 4 : 8;
+    expect_gather(pack_first(wi.data(), 32, Ci, cin), pack_first(iota_of(wi.size()).data(), 32, Ci, cin, -1), wi);
+  }
+  // small-N last conv: 3 / 4 of 4 output channels, 5 / 8 of 8; 3 of 8 padded input channels
+  struct Small { int Co, Ci, Ci_pad, CK; };
+  for (const Small &c : {Small{3, 32, 32, 32}, Small{4, 32, 32, 32}, Small{5, 32, 32, 32}, Small{8, 32, 32, 32}, Small{3, 3, 8, 8}}) {
+    const std::vector<float> wi = digest_weights(rng, (size_t)c.Co * c.Ci * 27);
+    const int nco = c.Co <= 4 ? 4 : 8;
+    expect_gather(pack_small(wi.data(), c.Co, c.Ci, c.Ci_pad, c.CK, nco), pack_small(iota_of(wi.size()).data(), c.Co, c.Ci, c.Ci_pad, c.CK, nco, -1), wi);
+  }
+  // parity fold: the 8 indexed sources of an element, summed in double in list order and rounded once, are the value fold bit for
+  // bit -- before and after the per-class packing
+  for (auto cc : {std::make_pair(32, 32), std::make_pair(40, 24)}) {
+    const int Co = cc.first, Ci = cc.second, NB = Co > 32 ? 2 : 1, CK = Ci % 32 ? 8 : 32;
+    const std::vector<float> wi = digest_weights(rng, (size_t)Co * Ci * 27);
+    const std::vector<float> wp = parity_weights(wi, Co, Ci);
+    const std::vector<Src8> sp = parity_sources(iota_of(wi.size()), Co, Ci);
+    long long sv = 0, si = 0;
+    const std::vector<float> fv = pack_parity_classes(wp, &sv, [&](const float *w8) { return pack_conv(w8, Co, Ci, 8, Ci, CK, NB); });
+    const std::vector<Src8> fi = pack_parity_classes(sp, &si, [&](const Src8 *s8) { return pack_conv(s8, Co, Ci, 8, Ci, CK, NB, kNoSrc8); });
+    EXPECT(sv == si && sv * 8 == (long long)fv.size());
+    auto expect_fold = [&](const std::vector<float> &v, const std::vector<Src8> &idx) {
+      EXPECT(v.size() == idx.size());
+      for (size_t i = 0; i < v.size(); ++i) {
+        double acc = 0;
+        bool ended = false;
+        for (int k = 0; k < 8; ++k) {
+          const int j = idx[i][k];
+          EXPECT(j >= -1 && j < (int)wi.size() && !(ended && j >= 0));   // (sources first, then -1s)
+          if (j >= 0) acc += (double)wi[(size_t)j]; else ended = true;
+        }
+        const float folded = (float)acc;
+        EXPECT(std::memcmp(&v[i], &folded, 4) == 0);
+      }
+    };
+    expect_fold(wp, sp);
+    expect_fold(fv, fi);
   }
 }
 
@@ -879,6 +1160,8 @@ int main() {
   test_schedule();
   test_plan_and_params();
   test_packers();
+  test_fragment_digests();
+  test_value_index_layouts();
   test_tile_planner();
   test_round3_packers();
   test_wino_form_dispatch();

@@ -77,7 +77,7 @@ struct ConvArgs {
   int silu;            // apply SiLU after the affine (GroupNorm->SiLU fused on load)
   const float *pm;     // optional per-(sample, input channel) multiplier applied after the activation:
   int pm_stride;       //   the Dropout3d keep-mask / (1-p) of training mode (layers.py:42,71); row stride
-  const float *wfrag;  // weights in MFMA fragment order (see pack_conv_weights)
+  const float *wfrag;  // weights in MFMA fragment order (cm_pack.h: pack_conv)
   const float *bias;   // [Co padded to TN]
   const float *temb;   // [rows][temb_stride] time-embedding projection table, or null
   int temb_stride;
@@ -750,7 +750,6 @@ struct TimeBwdArgs {
 hipError_t launch_time_bwd(const TimeBwdArgs &a, hipStream_t st);
 hipError_t launch_adam(float *p, const float *g, float *m, float *v, long long n, float lr, float b1, float b2,
                        float eps, float wd, int step, hipStream_t st);
-hipError_t launch_gather_pack(const float *W, const int *idx, int nk, float *packed, long long n, hipStream_t st);
 // Winograd-transformed weights (cm_conv_wino.hip layout, pack_wino) re-derived from the master parameters after an optimizer
 // step: element (n tile, chunk, xi_y, z tap, k half, xi_x, lane, jj) = sum_{dy,dx} G[xi_y][dy] G[xi_x][dx] W[idx27[(co, ci)][dz, dy, dx]].
 // idx27: [Co][Ci][27] indices into the flat parameter buffer (internal tap order; the data gradient passes the flipped /

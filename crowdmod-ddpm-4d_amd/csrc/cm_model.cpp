@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <numeric>
 #include <set>
 #include <string>
 #include <thread>
@@ -20,6 +21,9 @@
 
 #include "../../include/crowdmod_hip.h"
 #include "cm_kernels.h"
+#include "cm_pack.h"
+
+using namespace cm_pack;
 
 namespace {
 
@@ -415,333 +419,9 @@ Act *new_act(cm_model *m, const std::string &name, int C, int Z, int Y, int X, b
 
 const Param &P(const cm_model *m, const std::string &name) { return m->params[m->pindex.at(name)]; }
 
-// ------------------------------------------------------------------------------
-// weight packing: reference [Co][Ci][kH][kW][kL] (or [Co][Ci]) -> fragment order
-//   wfrag[ntile][chunk][step = tap*K8 + j][nb][lane][jj]
-//     = W[co = ntile*TN + nb*32 + (lane&31)][ci = chunk*CK + 8j + 4(lane>>5) + jj][tap]
-// with internal tap (dz,dy,dx) = reference [kH=dy][kW=dx][kL=dz]; zero beyond Co / Ci.
-// One wave-load of a step is 64 lanes x 16 B = 1 KiB contiguous.
-// ------------------------------------------------------------------------------
-// Reference conv weight [Co][Ci][kH][kW][kL] -> internal tap order [Co][Ci][t], t = (dz*3 + dy)*3 + dx
-// with (dz,dy,dx) = (kL,kH,kW)  (the internal layout is [Z=frames][Y=rows][X=cols]).
-std::vector<float> to_internal_taps(const float *W, int Co, int Ci, int ntaps) {
-  std::vector<float> out((size_t)Co * Ci * ntaps);
-  for (size_t cc = 0; cc < (size_t)Co * Ci; ++cc)
-    for (int t = 0; t < ntaps; ++t) {
-      const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;
-      const int tap_ref = (ntaps == 27) ? (dy * 3 + dx) * 3 + dz : 0;
-      out[cc * ntaps + t] = W[cc * ntaps + tap_ref];
-    }
-  return out;
-}
-
-// nn.Upsample(x2, nearest) followed by a 3x3x3 conv (layers.py:93-94) collapses, for each
-// parity p of the output voxel u = 2i + p, to a 2x2x2 conv over source voxels i + e + p - 1:
-// along one axis tap d of the upsampled grid reads source floor((2i + p + d - 1)/2), i.e.
-//   p = 0: d=0 -> i-1 (e=0), d=1,2 -> i (e=1);    p = 1: d=0,1 -> i (e=0), d=2 -> i+1 (e=1).
-// Taps that land on the same source voxel are summed here (in double, rounded once).
-// in: internal order [Co][Ci][27]; out: [8 parities][Co][Ci][8], e index = (ez*2 + ey)*2 + ex.
-std::vector<float> parity_weights(const std::vector<float> &Wi, int Co, int Ci) {
-  std::vector<float> out((size_t)8 * Co * Ci * 8, 0.f);
-  auto emap = [](int p, int d) { return p == 0 ? (d == 0 ? 0 : 1) : (d == 2 ? 1 : 0); };
-  for (int p = 0; p < 8; ++p) {
-    const int pz = (p >> 2) & 1, py = (p >> 1) & 1, px = p & 1;
-    for (size_t cc = 0; cc < (size_t)Co * Ci; ++cc) {
-      double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int dz = 0; dz < 3; ++dz)
-        for (int dy = 0; dy < 3; ++dy)
-          for (int dx = 0; dx < 3; ++dx)
-            acc[(emap(pz, dz) * 2 + emap(py, dy)) * 2 + emap(px, dx)] += (double)Wi[cc * 27 + (dz * 3 + dy) * 3 + dx];
-      for (int e = 0; e < 8; ++e) out[((size_t)p * Co * Ci + cc) * 8 + e] = (float)acc[e];
-    }
-  }
-  return out;
-}
-
-uint16_t f32_to_f16_bits(float f);
-// IEEE binary16 bits -> float (exact)
-static inline float f16_bits_to_f32(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-  uint32_t exp = (h >> 10) & 0x1fu, man = h & 0x3ffu, x;
-  if (exp == 0) {
-    if (man == 0) { x = sign; }
-    else {
-      int e = -1;
-      do { ++e; man <<= 1; } while (!(man & 0x400u));
-      x = sign | ((uint32_t)(127 - 15 - e) << 23) | ((man & 0x3ffu) << 13);
-    }
-  } else if (exp == 31) {
-    x = sign | 0x7f800000u | (man << 13);
-  } else {
-    x = sign | ((exp + 127 - 15) << 23) | (man << 13);
-  }
-  float f;
-  std::memcpy(&f, &x, 4);
-  return f;
-}
-
-// f16 version of pack_conv_weights (same order, 4 halves per lane and step), returned as floats holding two halves each
-std::vector<float> pack_conv_weights_f16(const float *W, int Co, int Ci, int ntaps, int Ci_pad, int CK, int NB) {
-  const int TN = 32 * NB, ntn = (Co + TN - 1) / TN, nch = Ci_pad / CK, K8 = CK / 8, nsteps = ntaps * K8;
-  std::vector<uint16_t> out((size_t)ntn * nch * nsteps * NB * 64 * 4, 0);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int s = 0; s < nsteps; ++s) {
-        const int t = s / K8, j = s % K8;
-        for (int nb = 0; nb < NB; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int jj = 0; jj < 4; ++jj, ++o) {
-              const int co = nt * TN + nb * 32 + (lane & 31);
-              const int ci = ch * CK + 8 * j + 4 * (lane >> 5) + jj;
-              if (co < Co && ci < Ci) out[o] = f32_to_f16_bits(W[((size_t)co * Ci + ci) * ntaps + t]);
-            }
-      }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// f16 fragments of ONE parity class for the stage-once upsample kernel (cm_conv_ups.hip, F16): [32-channel column block]
-// [32-channel chunk][tap 8][16-channel group m][lane][8 halves], lane = 32 hh + (co % 32), ci = chunk * 32 + 16 m + 8 hh + i.
-// W: [Co][Ci][8] (parity_weights of one class).  Returned as floats holding two halves each.
-std::vector<float> pack_ups_f16(const float *W, int Co, int Ci) {
-  const int ncb = Co / 32, nch = Ci / 32;
-  std::vector<uint16_t> out((size_t)ncb * nch * 8 * 2 * 64 * 8, 0);
-  size_t o = 0;
-  for (int cb = 0; cb < ncb; ++cb)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int t = 0; t < 8; ++t)
-        for (int mg = 0; mg < 2; ++mg)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int i = 0; i < 8; ++i, ++o) {
-              const int co = cb * 32 + (lane & 31), ci = ch * 32 + 16 * mg + 8 * (lane >> 5) + i;
-              out[o] = f32_to_f16_bits(W[((size_t)co * Ci + ci) * 8 + t]);
-            }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// round-to-nearest-even fp32 -> bf16 (bits)
-static inline uint16_t f32_to_bf16_bits(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float bf16_bits_to_f32(uint16_t h) {
-  const uint32_t u = (uint32_t)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-// exact three-way bf16 split of an fp32 value: w = hi + mid + lo (each rounded to nearest from the running remainder;
-// 8 + 8 + 8 mantissa bits, the remainders are exact in fp32)
-// h2 terms of one weight (cm_kernels.h: cm_split2_f16): f16 hi / mid of w * scale, third slot zero
-static inline void f16_split2(float w, float scale, uint16_t out[3]) {
-  const float v = w * scale;
-  out[0] = f32_to_f16_bits(v);
-  out[1] = f32_to_f16_bits(v - f16_bits_to_f32(out[0]));
-  out[2] = 0;
-}
-static inline void bf16_split3(float w, uint16_t out[3]) {
-  float rem = w;
-  for (int t = 0; t < 3; ++t) {
-    out[t] = f32_to_bf16_bits(rem);
-    rem -= bf16_bits_to_f32(out[t]);
-  }
-}
-
-// h2 fragments of a dense weight W [N][K] (reference layout: mhsa.in_proj_weight, mhsa.out_proj.weight) for the whole-sample
-// attention kernel (cm_attn_block.hip: attn_sample_kernel): [16-column block][32-deep k step][hi, mid][lane][8 halves],
-// lane = 16 g + (n % 16), k = 32 step + 8 g + i; f16 hi / mid of w * scale.  Returned as floats holding two halves each.
-std::vector<float> pack_attn_h2(const float *W, int N, int K, float scale) {
-  const int ncb = N / 16, nks = K / 32;
-  std::vector<uint16_t> out((size_t)ncb * nks * 2 * 64 * 8, 0);
-  for (int cb = 0; cb < ncb; ++cb)
-    for (int ks = 0; ks < nks; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int i = 0; i < 8; ++i) {
-          const int n = cb * 16 + (lane & 15), k = ks * 32 + 8 * (lane >> 4) + i;
-          uint16_t t3[3];
-          f16_split2(W[(size_t)n * K + k], scale, t3);
-          for (int tm = 0; tm < 2; ++tm) out[(((((size_t)cb * nks + ks) * 2 + tm) * 64) + lane) * 8 + i] = t3[tm];
-        }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// bf16 x 3 fragments of ONE parity class for the stage-once upsample kernel (cm_conv_ups.hip, PREC = 2): [32-channel column
-// block][32-channel chunk][tap 8][16-channel group m][term hi / mid / lo][lane][8 bf16], lane = 32 hh + (co % 32),
-// ci = chunk * 32 + 16 m + 8 hh + i.  W: [Co][Ci][8] (parity_weights of one class).  Returned as floats holding two bf16 each.
-// h2_scale > 0: the h2 form -- f16 hi / mid of w * h2_scale in the first two term slots (third slot zero)
-std::vector<float> pack_ups_b6(const float *W, int Co, int Ci, float h2_scale = 0.f) {
-  const int ncb = Co / 32, nch = Ci / 32;
-  std::vector<uint16_t> out((size_t)ncb * nch * 8 * 2 * 3 * 64 * 8, 0);
-  for (int cb = 0; cb < ncb; ++cb)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int t = 0; t < 8; ++t)
-        for (int mg = 0; mg < 2; ++mg)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int i = 0; i < 8; ++i) {
-              const int co = cb * 32 + (lane & 31), ci = ch * 32 + 16 * mg + 8 * (lane >> 5) + i;
-              uint16_t t3[3];
-              if (h2_scale > 0.f) f16_split2(W[((size_t)co * Ci + ci) * 8 + t], h2_scale, t3);
-              else bf16_split3(W[((size_t)co * Ci + ci) * 8 + t], t3);
-              for (int tm = 0; tm < 3; ++tm)
-                out[(((((((size_t)cb * nch + ch) * 8 + t) * 2 + mg) * 3 + tm) * 64) + lane) * 8 + i] = t3[tm];
-            }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-std::vector<float> pack_conv_weights(const float *W, int Co, int Ci, int ntaps, int Ci_pad, int CK, int NB) {
-  const int TN = 32 * NB, ntn = (Co + TN - 1) / TN, nch = Ci_pad / CK, K8 = CK / 8, nsteps = ntaps * K8;
-  std::vector<float> out((size_t)ntn * nch * nsteps * NB * 64 * 4, 0.f);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int s = 0; s < nsteps; ++s) {
-        const int t = s / K8, j = s % K8;
-        for (int nb = 0; nb < NB; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int jj = 0; jj < 4; ++jj, ++o) {
-              const int co = nt * TN + nb * 32 + (lane & 31);
-              const int ci = ch * CK + 8 * j + 4 * (lane >> 5) + jj;
-              if (co < Co && ci < Ci) out[o] = W[((size_t)co * Ci + ci) * ntaps + t];
-            }
-      }
-  return out;
-}
-
-// Winograd F(2x2, 3x3) weights over the in-plane taps (dy, dx), one 4x4 transform G g G^T per (co, ci, dz):
-//   G = (1,0,0), (1/2,1/2,1/2), (1/2,-1/2,1/2), (0,0,1).
-// Layout (cm_conv_wino.hip): [n tile][16-channel chunk][xi_y][step = (dz*2 + k8)*4 + xi_x][lane][jj] with
-// lane = 32*hh + (co % 32), ci = chunk*16 + 8*k8 + 4*hh + jj.  `wi` is the internal tap order [Co][Ci][27].
-// With `ii` (global indices of the taps) the same walk emits, per packed element, the 9 (index, coefficient)
-// terms for the device-side re-pack after an optimizer step.
-void pack_wino(const std::vector<float> *wi, const std::vector<int> *ii, int Co, int Ci, int Ci_pad, std::vector<float> *out,
-               std::vector<int> *oidx, std::vector<float> *ocoef) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int ntn = (Co + 31) / 32, nch = Ci_pad / 16;
-  const size_t total = (size_t)ntn * nch * 4 * 24 * 64 * 4;
-  if (out) out->assign(total, 0.f);
-  if (oidx) { oidx->assign(total * 9, -1); ocoef->assign(total * 9, 0.f); }
-  for (int co = 0; co < Co; ++co)
-    for (int ci = 0; ci < Ci; ++ci)
-      for (int dz = 0; dz < 3; ++dz)
-        for (int xy = 0; xy < 4; ++xy)
-          for (int xx = 0; xx < 4; ++xx) {
-            const int nt = co / 32, r = co % 32, chunk = ci / 16, k8 = (ci % 16) / 8, hh = (ci % 8) / 4, jj = ci % 4;
-            const size_t o = ((((((size_t)nt * nch + chunk) * 4 + xy) * 24 + (dz * 2 + k8) * 4 + xx) * 64) + hh * 32 + r) * 4 + jj;
-            double acc = 0;
-            for (int dy = 0; dy < 3; ++dy)
-              for (int dx = 0; dx < 3; ++dx) {
-                const size_t t = ((size_t)co * Ci + ci) * 27 + (dz * 3 + dy) * 3 + dx;
-                const double c = G[xy][dy] * G[xx][dx];
-                if (wi) acc += c * (double)(*wi)[t];
-                if (oidx && c != 0.0) { (*oidx)[o * 9 + dy * 3 + dx] = (*ii)[t]; (*ocoef)[o * 9 + dy * 3 + dx] = (float)c; }
-              }
-            if (out) (*out)[o] = (float)acc;
-          }
-}
-
-// IEEE binary16 bits of a float (round to nearest even; overflow -> infinity, like a device cast)
-uint16_t f32_to_f16_bits(float f) {
-  uint32_t x;
-  std::memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u;
-  const int32_t exp = (int32_t)((x >> 23) & 0xff) - 127 + 15;
-  uint32_t man = x & 0x7fffffu;
-  if (((x >> 23) & 0xff) == 0xff) return (uint16_t)(sign | 0x7c00u | (man ? 0x200u : 0));
-  if (exp >= 31) return (uint16_t)(sign | 0x7c00u);
-  if (exp <= 0) {
-    if (exp < -10) return (uint16_t)sign;
-    man |= 0x800000u;
-    const int shift = 14 - exp;
-    uint32_t h = man >> shift;
-    const uint32_t rem = man & ((1u << shift) - 1), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (h & 1))) ++h;
-    return (uint16_t)(sign | h);
-  }
-  uint32_t h = ((uint32_t)exp << 10) | (man >> 13);
-  const uint32_t rem = man & 0x1fffu;
-  if (rem > 0x1000u || (rem == 0x1000u && (h & 1))) ++h;
-  return (uint16_t)(sign | h);
-}
-
-// f16 packing of the Winograd weights (cm_conv_wino.hip, F16): [n tile][chunk][xi_y][dz][xi_x][lane][8 halves],
-// lane = 32*hh + co % 32, ci = chunk*16 + 8*hh + j.  Returned as floats holding two halves each (upload helper).
-std::vector<float> pack_wino_f16(const std::vector<float> &wi, int Co, int Ci, int Ci_pad) {
-  static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-  const int ntn = (Co + 31) / 32, nch = Ci_pad / 16;
-  std::vector<uint16_t> out((size_t)ntn * nch * 4 * 3 * 4 * 64 * 8, 0);
-  for (int co = 0; co < Co; ++co)
-    for (int ci = 0; ci < Ci; ++ci)
-      for (int dz = 0; dz < 3; ++dz)
-        for (int xy = 0; xy < 4; ++xy)
-          for (int xx = 0; xx < 4; ++xx) {
-            const int nt = co / 32, r = co % 32, chunk = ci / 16, hh = (ci % 16) / 8, j = ci % 8;
-            double acc = 0;
-            for (int dy = 0; dy < 3; ++dy)
-              for (int dx = 0; dx < 3; ++dx) acc += G[xy][dy] * G[xx][dx] * (double)wi[((size_t)co * Ci + ci) * 27 + (dz * 3 + dy) * 3 + dx];
-            const size_t o = (((((((size_t)nt * nch + chunk) * 4 + xy) * 3 + dz) * 4 + xx) * 64) + hh * 32 + r) * 8 + j;
-            out[o] = f32_to_f16_bits((float)acc);
-          }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// Six-term bf16 form of the Winograd layers (conv_wino_p_kernel<..., B6>): the fp32 fragments of pack_wino
-// ([n tile][chunk][xi_y][step = (dz * 2 + k8) * 4 + xi_x][lane][4], ci = chunk * 16 + 8 k8 + 4 hh + jj) split exactly into three
-// bf16 terms and regrouped as [n tile][chunk][xi_y][dz][xi_x][term][lane][8 bf16], ci = chunk * 16 + 8 hh + j.  The device
-// re-derives the same thing after an optimizer step (wino_b6_repack_kernel): one definition, two places -- the self-test
-// compares them element by element.
-// h2_scale > 0: the h2 form instead -- f16 hi / mid of w * h2_scale in the first two term slots (same layout, third slot zero)
-std::vector<float> pack_wino_b6(const std::vector<float> &ww, float h2_scale = 0.f) {
-  std::vector<uint16_t> out(ww.size() * 3, 0);
-  for (size_t i = 0; i < ww.size(); ++i) {
-    const int jj = (int)(i & 3), lane = (int)((i >> 2) & 63);
-    size_t q = i >> 8;
-    const int step = (int)(q % 24); q /= 24;
-    const int xy = (int)(q & 3);
-    const size_t tc = q >> 2;
-    const int xx = step & 3, k8 = (step >> 2) & 1, dz = step >> 3;
-    const int r = lane & 31, hs = lane >> 5, cl = 8 * k8 + 4 * hs + jj, hd = cl >> 3, j = cl & 7;
-    uint16_t t3[3];
-    if (h2_scale > 0.f) f16_split2(ww[i], h2_scale, t3);
-    else bf16_split3(ww[i], t3);
-    for (int tm = 0; tm < 3; ++tm)
-      out[(((((((tc * 4 + xy) * 3 + dz) * 4 + xx) * 3 + tm) * 64) + 32 * hd + r) * 8) + j] = t3[tm];
-  }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// f16 fragments of a 1x1x1 conv for conv1x1_f16_kernel: [n tile][16-channel group][block][lane 64][8 halves],
-// lane (r, h) of block nb holds W[co = (nt NB + nb) 32 + r][ci = 16 g + 8 h + j]; W is [Co][Ci]
-std::vector<float> pack_1x1_f16(const float *W, int Co, int Ci, int NB) {
-  const int TN = 32 * NB, ntn = (Co + TN - 1) / TN, ng = Ci / 16;
-  std::vector<uint16_t> out((size_t)ntn * ng * NB * 64 * 8, 0);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int g = 0; g < ng; ++g)
-      for (int nb = 0; nb < NB; ++nb)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j, ++o) {
-            const int co = (nt * NB + nb) * 32 + (lane & 31), ci = 16 * g + 8 * (lane >> 5) + j;
-            if (co < Co) out[o] = f32_to_f16_bits(W[(size_t)co * Ci + ci]);
-          }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
+// Weight fragments: every layout (generic MFMA order, parity fold of the upsample conv, Winograd, quarter resolution, first / last
+// conv, attention) with its f16 / split flavours is defined once in cm_pack.h -- for the values packed here when a handle loads and
+// for the index maps the device re-packs through after an optimizer step (cm_train_host.inc: train_setup).
 
 int pick_ck(int C0, int C1) {
   for (int ck : {32, 16, 8})
@@ -878,95 +558,12 @@ struct ConvSpec {
   std::string skip_w, skip_b;
 };
 
-// f16 fragments of the direct f16 kernel (cm_conv_f16.hip): [Co/(32 NB)][Ci/16][taps][NB][lane][8 halves] with
-// co = 32 NB nt + 32 nb + lane % 32, ci = 16 c + 8 (lane / 32) + j; `w` is [Co][Ci][taps] (taps = 27 internal order, or 1)
-std::vector<float> pack_f16d(const float *w, int Co, int Ci, int taps, int NB) {
-  const int ntn = Co / (32 * NB), nc = Ci / 16;
-  std::vector<uint16_t> out((size_t)ntn * nc * taps * NB * 64 * 8, 0);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int c = 0; c < nc; ++c)
-      for (int t = 0; t < taps; ++t)
-        for (int nb = 0; nb < NB; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j, ++o) {
-              const int co = nt * 32 * NB + nb * 32 + (lane & 31), ci = 16 * c + 8 * (lane >> 5) + j;
-              out[o] = f32_to_f16_bits(w[((size_t)co * Ci + ci) * taps + t]);
-            }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-
-// Weights of the whole-sample quarter-resolution kernel (cm_conv_qr.hip): [Co/32][g = k8*9 + dy*3 + dx][dz][lane][jj]
-// with co = 32 nt + lane % 32, ci = 8 k8 + 4 (lane / 32) + jj; `wi` in the internal tap order [Co][Ci][(dz*3 + dy)*3 + dx].
-std::vector<float> pack_qr(const std::vector<float> &wi, int Co, int Ci) {
-  const int ntn = Co / 32, K8 = Ci / 8, ng = 9 * K8;
-  std::vector<float> out((size_t)ntn * ng * 3 * 64 * 4, 0.f);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int g = 0; g < ng; ++g)
-      for (int dz = 0; dz < 3; ++dz)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int jj = 0; jj < 4; ++jj, ++o) {
-            const int k8 = g / 9, t9 = g % 9, dy = t9 / 3, dx = t9 % 3;
-            const int co = nt * 32 + (lane & 31), ci = 8 * k8 + 4 * (lane >> 5) + jj;
-            out[o] = wi[((size_t)co * Ci + ci) * 27 + (dz * 3 + dy) * 3 + dx];
-          }
-  return out;
-}
-// Six-term bf16 form of conv_qr2 (B6): the fp32 fragments of pack_qr split exactly into three bf16 terms and regrouped by wave
-// (wave w owns the channels [w Ci/8, (w+1) Ci/8), padded with zeros to whole 16-channel steps):
-// [Co/32][wave 8][step][tap 9][dz][term][lane][8 bf16], ci = wave * Ci/8 + 16 step + 8 hh + j.  `wq` is pack_qr's output.
-// The device re-derives it after an optimizer step with the same index arithmetic (qr_b6_repack_kernel).
-std::vector<float> pack_qr_b6(const std::vector<float> &wq, int Co, int Ci, float h2_scale = 0.f) {
-  const int ntn = Co / 32, K8 = Ci / 8, ng = 9 * K8, cw = Ci / 8, nsw = (cw + 15) / 16;
-  std::vector<uint16_t> out((size_t)ntn * 8 * nsw * 9 * 3 * 3 * 64 * 8, 0);
-  for (size_t i = 0; i < wq.size(); ++i) {
-    const int jj = (int)(i & 3), lane = (int)((i >> 2) & 63);
-    size_t q = i >> 8;
-    const int dz = (int)(q % 3); q /= 3;
-    const int g = (int)(q % ng);
-    const int nt = (int)(q / ng);
-    const int k8 = g / 9, t9 = g % 9, ci = 8 * k8 + 4 * (lane >> 5) + jj, r = lane & 31;
-    const int wv = ci / cw, cl = ci % cw, st = cl / 16, hd = (cl % 16) / 8, j = cl % 8;
-    uint16_t t3[3];
-    if (h2_scale > 0.f) f16_split2(wq[i], h2_scale, t3);
-    else bf16_split3(wq[i], t3);
-    for (int tm = 0; tm < 3; ++tm)
-      out[(((((((size_t)(nt * 8 + wv) * nsw + st) * 9 + t9) * 3 + dz) * 3 + tm) * 64) + 32 * hd + r) * 8 + j] = t3[tm];
-  }
-  std::vector<float> packed(out.size() / 2);
-  std::memcpy(packed.data(), out.data(), out.size() * 2);
-  return packed;
-}
-// its fused 1x1x1 skip weights: [Co/32][Cs/8][lane][jj]; `w2` is [Co][Cs]
-std::vector<float> pack_qr_skip(const float *w2, int Co, int Cs) {
-  const int ntn = Co / 32, ngs = Cs / 8;
-  std::vector<float> out((size_t)ntn * ngs * 64 * 4, 0.f);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int gs = 0; gs < ngs; ++gs)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int jj = 0; jj < 4; ++jj, ++o)
-          out[o] = w2[(size_t)(nt * 32 + (lane & 31)) * Cs + 8 * gs + 4 * (lane >> 5) + jj];
-  return out;
-}
-
 // ---- "h2" arithmetic (cm_kernels.h: cm_split2_f16): operand range management ---------------------------------------------------
-// f16 has 5 exponent bits.  Weights: packed as w * 2^k with max |w| 2^k in [4096, 8192) (their mid terms ~ 2^-11 of that stay normal
-// numbers; 8x headroom below 65504); the kernel multiplies its fp32 accumulators by 2^-k (exact).  Activations: a GroupNorm output
+// f16 has 5 exponent bits.  Weights: packed as w * 2^k (cm_pack.h: h2_wscale); the kernel multiplies its fp32 accumulators by 2^-k
+// (exact).  Activations: a GroupNorm output
 // satisfies |z| < sqrt(n) for a group of n elements, so |SiLU(gamma z + beta)| <= sqrt(n) max|gamma| + max|beta|, times `gain` for a
 // linear input transform (4 for the Winograd B^T d B: sums of four values).  A layer whose bound exceeds 32000 keeps the six-term
 // bf16 form (bf16 has the exponent range of fp32).
-static float h2_wscale(const float *w, size_t n) {
-  float mx = 0.f;
-  for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));
-  if (!(mx > 0.f) || !std::isfinite(mx)) return 0.f;
-  int e = 0;
-  (void)std::frexp(mx, &e);                        // mx = f * 2^e, f in [0.5, 1)
-  return std::ldexp(1.0f, 13 - e);                 // mx * 2^(13 - e) in [4096, 8192)
-}
 static bool h2_bound_ok(const std::vector<float> &g, const std::vector<float> &b, const Op &gop, double gain);
 static bool h2_act_bounded(const cm_model *m, const Op &gop, double gain) {
   return h2_bound_ok(P(m, gop.gname).host, P(m, gop.bename).host, gop, gain);
@@ -981,34 +578,23 @@ static bool h2_bound_ok(const std::vector<float> &g, const std::vector<float> &b
   return std::isfinite(bound) && bound <= 32000.0;
 }
 
-// h2 fragments of one layer from its weights in the REFERENCE layout (load time: add_conv; after training: refresh_h2).  Return the
-// weight scale 2^k (0: none -- all-zero or non-finite weights).
-static float h2_pack_wino(const float *w_ref, int Co, int Ci_ref, int Ci_pad, std::vector<float> *out) {
-  const std::vector<float> wi = to_internal_taps(w_ref, Co, Ci_ref, 27);
-  std::vector<float> ww;
-  pack_wino(&wi, nullptr, Co, Ci_ref, Ci_pad, &ww, nullptr, nullptr);
-  const float ws = h2_wscale(ww.data(), ww.size());
-  if (ws > 0.f) *out = pack_wino_b6(ww, ws);
-  return ws;
+// h2 fragments and weight scale 2^k (0: none) of a conv op from its weight in the REFERENCE layout (cm_pack.h: h2_fragments); add_conv
+// uploads them at load time, refresh_h2 copies them over the same buffer after training.  Every h2 layer has Ci_ref == Ci_pad.
+static float h2_pack(const Op &op, H2Kind kind, const float *w_ref, std::vector<float> *frag) {
+  return h2_fragments(kind, w_ref, op.ca.Co, op.ca.C0 + op.ca.C1, frag);
 }
-static float h2_pack_qr(const float *w_ref, int Co, int Ci_ref, std::vector<float> *out) {
-  const std::vector<float> wq = pack_qr(to_internal_taps(w_ref, Co, Ci_ref, 27), Co, Ci_ref);
-  const float ws = h2_wscale(wq.data(), wq.size());
-  if (ws > 0.f) *out = pack_qr_b6(wq, Co, Ci_ref, ws);
-  return ws;
-}
-static float h2_pack_ups(const float *w_ref, int Co, int Ci_ref, std::vector<float> *out) {
-  const std::vector<float> wp = parity_weights(to_internal_taps(w_ref, Co, Ci_ref, 27), Co, Ci_ref);
-  const size_t per = (size_t)Co * Ci_ref * 8;
-  const float ws = h2_wscale(wp.data(), wp.size());
-  if (ws > 0.f) {
-    out->clear();
-    for (int p8 = 0; p8 < 8; ++p8) {
-      const std::vector<float> one = pack_ups_b6(wp.data() + p8 * per, Co, Ci_ref, ws);
-      out->insert(out->end(), one.begin(), one.end());
-    }
-  }
-  return ws;
+// load time: the op takes the h2 form `kind` if its weights have a scale (H2_FIN: packed on the device from d_wfin_src)
+static int add_h2(cm_model *m, Op &op, H2Kind kind, const float *w_ref, float **d_frag) {
+  std::vector<float> frag;
+  const float ws = h2_pack(op, kind, w_ref, &frag);
+  if (!(ws > 0.f)) return 0;
+  if (kind == H2_FIN) {
+    if (dev_alloc(m, (void **)d_frag, cm::CM_FIN_W_FLOATS * sizeof(float))) return 1;
+    CM_HIP(cm::launch_fin_pack(op.d_wfin_src, *d_frag, op.ca.Co, 2, m->stream, ws));
+    CM_HIP(hipStreamSynchronize(m->stream));
+  } else if (upload(m, frag, d_frag)) return 1;
+  op.h2_oscale = 1.f / ws;
+  return 0;
 }
 
 // h2 fragments of an attention block's two weights (reference layout [3E][E], [E][E]); *osc_* = 2^-k of each, 0 where the weight has no
@@ -1073,31 +659,23 @@ int add_conv(cm_model *m, const ConvSpec &s) {
   const int Ci_pad = a.C0 + a.C1;
   if (Ci_ref > Ci_pad || (s.ci_valid < 0 && Ci_ref != Ci_pad))
     return fail("conv %s: weight has %d input channels, sources provide %d", s.wname.c_str(), Ci_ref, Ci_pad);
-  const std::vector<float> wi = to_internal_taps(w.host.data(), (int)w.shape[0], Ci_ref, s.ntaps);
+  const int Co_ref = (int)w.shape[0];
+  const std::vector<float> wi = to_internal_taps(w.host.data(), Co_ref, Ci_ref, s.ntaps);
+  const std::vector<float> wp = parity ? parity_weights(wi, Co_ref, Ci_ref) : std::vector<float>();   // [8 classes][Co][Ci][8]
   std::vector<float> wf;
   if (parity) {
-    const std::vector<float> wp = parity_weights(wi, (int)w.shape[0], Ci_ref);
-    const size_t per = (size_t)w.shape[0] * Ci_ref * 8;
-    for (int p8 = 0; p8 < 8; ++p8) {
-      std::vector<float> one = pack_conv_weights(wp.data() + p8 * per, (int)w.shape[0], Ci_ref, 8, Ci_pad, a.CK, op.NB);
-      a.wpar_stride = (long long)one.size();
-      wf.insert(wf.end(), one.begin(), one.end());
-    }
+    wf = pack_parity_classes(wp, &a.wpar_stride, [&](const float *w8) { return pack_conv(w8, Co_ref, Ci_ref, 8, Ci_pad, a.CK, op.NB); });
     if (m->precision == CM_PRECISION_F16 && a.CK == 32) {   // reduced-precision plan: the same fragments as f16
-      std::vector<float> wf16;
-      for (int p8 = 0; p8 < 8; ++p8) {
-        std::vector<float> one = pack_conv_weights_f16(wp.data() + p8 * per, (int)w.shape[0], Ci_ref, 8, Ci_pad, a.CK, op.NB);
-        op.wpar_stride16 = (long long)one.size();
-        wf16.insert(wf16.end(), one.begin(), one.end());
-      }
+      const std::vector<float> wf16 =
+          pack_parity_classes(wp, &op.wpar_stride16, [&](const float *w8) { return pack_conv_f16(w8, Co_ref, Ci_ref, 8, Ci_pad, a.CK, op.NB); });
       if (upload(m, wf16, &op.d_wfrag16)) return 1;
     }
   } else {
-    wf = pack_conv_weights(wi.data(), (int)w.shape[0], Ci_ref, s.ntaps, Ci_pad, a.CK, op.NB);
+    wf = pack_conv(wi.data(), Co_ref, Ci_ref, s.ntaps, Ci_pad, a.CK, op.NB);
     // reduced-precision plan: 1x1x1 convs without output statistics (attention in-projection, unfused skip convs) on f16 operands
     if (m->precision == CM_PRECISION_F16 && s.ntaps == 1 && s.stride == 1 && !s.ups && !s.stats && !s.temb && Ci_ref == Ci_pad &&
         a.C0 % 16 == 0 && a.C1 % 16 == 0 && !cm::diag_env("CM_NO_1X1_F16") &&
-        upload(m, pack_1x1_f16(wi.data(), (int)w.shape[0], Ci_ref, op.NB), &op.d_w1x1_16))
+        upload(m, pack_1x1_f16(wi.data(), Co_ref, Ci_ref, op.NB), &op.d_w1x1_16))
       return 1;
   }
   // upsample convs: the source tile staged once for four parity classes (cm_conv_ups.hip) when a tile fits
@@ -1106,35 +684,16 @@ int add_conv(cm_model *m, const ConvSpec &s) {
       (a.Zs / op.ups_tz) * (a.Ys / op.ups_ty) * (a.Xs / op.ups_tx) * 8 * op.ups_mbw <= MAX_SLOTS)   // (its statistics slots must fit)
     op.ups = true;
   if (op.ups && m->precision != CM_PRECISION_F16 && Ci_ref == Ci_pad && Ci_ref % 32 == 0 && !cm::diag_env("CM_NO_UPS_B6")) {
-    const std::vector<float> wp = parity_weights(wi, (int)w.shape[0], Ci_ref);
-    const size_t per = (size_t)w.shape[0] * Ci_ref * 8;
-    std::vector<float> wb6;
-    for (int p8 = 0; p8 < 8; ++p8) {
-      const std::vector<float> one = pack_ups_b6(wp.data() + p8 * per, (int)w.shape[0], Ci_ref);
-      op.wups_b6_stride = (long long)one.size();
-      wb6.insert(wb6.end(), one.begin(), one.end());
-    }
+    const std::vector<float> wb6 = pack_parity_classes(wp, &op.wups_b6_stride, [&](const float *w8) { return pack_ups_b6(w8, Co_ref, Ci_ref); });
     if (upload(m, wb6, &op.d_wups_b6)) return 1;
     // default plan: h2 with a per-sample scale taken from the source tensor's slot statistics (cm_conv_ups.hip, PREC = 4) -- the
     // source is a block output with statistics (every conv_2 / attention output carries them)
-    if (m->precision == CM_PRECISION_F32 && !cm::diag_env("CM_NO_H2") && !cm::diag_env("CM_NO_UPS_H2") && s.s0->part) {
-      std::vector<float> wh2;
-      const float ws = h2_pack_ups(w.host.data(), (int)w.shape[0], Ci_ref, &wh2);
-      if (ws > 0.f) {
-        if (upload(m, wh2, &op.d_wups_h2)) return 1;
-        op.h2_oscale = 1.f / ws;
-      }
-    }
+    if (m->precision == CM_PRECISION_F32 && !cm::diag_env("CM_NO_H2") && !cm::diag_env("CM_NO_UPS_H2") && s.s0->part &&
+        add_h2(m, op, H2_UPS, w.host.data(), &op.d_wups_h2))
+      return 1;
   }
   if (op.ups && m->precision == CM_PRECISION_F16 && Ci_ref == Ci_pad && Ci_ref % 32 == 0 && !cm::diag_env("CM_NO_UPS_F16")) {
-    const std::vector<float> wp = parity_weights(wi, (int)w.shape[0], Ci_ref);
-    const size_t per = (size_t)w.shape[0] * Ci_ref * 8;
-    std::vector<float> w16;
-    for (int p8 = 0; p8 < 8; ++p8) {
-      const std::vector<float> one = pack_ups_f16(wp.data() + p8 * per, (int)w.shape[0], Ci_ref);
-      op.wups16_stride = (long long)one.size();
-      w16.insert(w16.end(), one.begin(), one.end());
-    }
+    const std::vector<float> w16 = pack_parity_classes(wp, &op.wups16_stride, [&](const float *w8) { return pack_ups_f16(w8, Co_ref, Ci_ref); });
     if (upload(m, w16, &op.d_wups16)) return 1;
   }
   // the UNet's last conv (base -> C channels): vector-ALU kernel instead of a 32-wide MFMA tile
@@ -1142,16 +701,7 @@ int add_conv(cm_model *m, const ConvSpec &s) {
       !cm::diag_env("CM_NO_SMALLN")) {
     op.small_n = true;
     op.small_nco = s.Co <= 4 ? 4 : 8;
-    const int nco = op.small_nco, nch = Ci_pad / a.CK;
-    std::vector<float> ws((size_t)nch * 27 * a.CK * nco, 0.f);
-    for (int ch = 0; ch < nch; ++ch)
-      for (int t = 0; t < 27; ++t)
-        for (int ci = 0; ci < a.CK; ++ci)
-          for (int co = 0; co < s.Co; ++co) {
-            const int cig = ch * a.CK + ci;
-            if (cig < Ci_ref) ws[(((size_t)ch * 27 + t) * a.CK + ci) * nco + co] = wi[((size_t)co * Ci_ref + cig) * 27 + t];
-          }
-    if (upload(m, ws, &op.d_wsmall)) return 1;
+    if (upload(m, pack_small(wi.data(), s.Co, Ci_ref, Ci_pad, a.CK, op.small_nco), &op.d_wsmall)) return 1;
     // the same layer on the matrix core (round 4): 27 taps x 4 channels = 108 columns of a GEMM over the 32 input channels
     if (s.Co <= 4 && Ci_ref == 32 && Ci_pad == 32 && !s.s1 && !cm::diag_env("CM_NO_FIN") && cm::conv_fin_pick(s.out->Y, s.out->X, &op.fin_by, &op.fin_bx)) {
       if (upload(m, w.host, &op.d_wfin_src)) return 1;
@@ -1166,8 +716,7 @@ int add_conv(cm_model *m, const ConvSpec &s) {
     }
   }
   if (op.wino) {
-    std::vector<float> ww;
-    pack_wino(&wi, nullptr, s.Co, Ci_ref, Ci_pad, &ww, nullptr, nullptr);
+    const std::vector<float> ww = pack_wino(wi, s.Co, Ci_ref, Ci_pad);
     if (upload(m, ww, &op.d_wwino)) return 1;
     if (m->precision == CM_PRECISION_F16 && upload(m, pack_wino_f16(wi, s.Co, Ci_ref, Ci_pad), &op.d_wwino16)) return 1;
     op.wwino_floats = (long long)ww.size();
@@ -1192,16 +741,7 @@ int add_conv(cm_model *m, const ConvSpec &s) {
       s.Co % 32 == 0 && Ci_ref <= 8 && !cm::diag_env("CM_NO_FIRSTK")) {
     op.first_k = true;
     op.first_cin = Ci_ref <= 4 ? 4 : 8;
-    const int cin = op.first_cin, NS = 27 * cin / 2, hc = cin / 2, ntn = s.Co / 32;
-    std::vector<float> wp((size_t)ntn * NS * 64, 0.f);
-    for (int nt = 0; nt < ntn; ++nt)
-      for (int t = 0; t < 27; ++t)
-        for (int pp = 0; pp < hc; ++pp)
-          for (int lane = 0; lane < 64; ++lane) {
-            const int co = nt * 32 + (lane & 31), ci = hc * (lane >> 5) + pp;   // MFMA (t, pp) contracts k = {hc*hh + pp}
-            if (ci < Ci_ref) wp[((size_t)nt * NS + t * hc + pp) * 64 + lane] = wi[((size_t)co * Ci_ref + ci) * 27 + t];
-          }
-    if (upload(m, wp, &op.d_wfirst)) return 1;
+    if (upload(m, pack_first(wi.data(), s.Co, Ci_ref, op.first_cin), &op.d_wfirst)) return 1;
   }
   float *dw = nullptr, *db = nullptr;
   if (upload(m, wf, &dw)) return 1;
@@ -1222,23 +762,9 @@ int add_conv(cm_model *m, const ConvSpec &s) {
     for (int i = (int)m->ops.size() - 1; i >= 0; --i)
       if (m->ops[i].kind == OP_GNFIN && m->ops[i].gn_out == s.gn) { op.gn_op = i; break; }
   const bool h2_plan = m->precision == CM_PRECISION_F32 && !cm::diag_env("CM_NO_H2") && s.gn && op.gn_op >= 0 && s.silu;
-  if (op.fin && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 1.0)) {
-    const float ws = h2_wscale(w.host.data(), w.host.size());
-    if (ws > 0.f) {
-      if (dev_alloc(m, (void **)&op.d_wfin_h2, cm::CM_FIN_W_FLOATS * sizeof(float))) return 1;
-      CM_HIP(cm::launch_fin_pack(op.d_wfin_src, op.d_wfin_h2, s.Co, 2, m->stream, ws));
-      CM_HIP(hipStreamSynchronize(m->stream));
-      op.h2_oscale = 1.f / ws;
-    }
-  }
-  if (op.wino && op.d_wwino_b6 && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 4.0)) {
-    std::vector<float> wh2;
-    const float ws = h2_pack_wino(w.host.data(), s.Co, Ci_ref, Ci_pad, &wh2);
-    if (ws > 0.f) {
-      if (upload(m, wh2, &op.d_wwino_h2)) return 1;
-      op.h2_oscale = 1.f / ws;
-    }
-  }
+  if (op.fin && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 1.0) && add_h2(m, op, H2_FIN, w.host.data(), &op.d_wfin_h2)) return 1;
+  if (op.wino && op.d_wwino_b6 && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 4.0) && add_h2(m, op, H2_WINO, w.host.data(), &op.d_wwino_h2))
+    return 1;
   // Tiny-spatial layers (one 54-voxel tile per sample at quarter resolution): the only way to
   // more parallelism AND less weight traffic per workgroup is to split K over workgroups;
   // a second pass sums the partials in a fixed order and applies the epilogue.
@@ -1260,7 +786,7 @@ int add_conv(cm_model *m, const ConvSpec &s) {
     const Param &b2 = P(m, s.skip_b);
     const int Ci2 = (int)w2.shape[1];
     if (Ci2 == s.skip0->C + (s.skip1 ? s.skip1->C : 0) && (int)w2.shape[0] == s.Co) {
-      std::vector<float> w2f = pack_conv_weights(w2.host.data(), s.Co, Ci2, 1, Ci2, 32, op.NB);
+      std::vector<float> w2f = pack_conv(w2.host.data(), s.Co, Ci2, 1, Ci2, 32, op.NB);
       if (upload(m, w2f, &op.d_s2w)) return 1;
       std::vector<float> bf((size_t)co_pad, 0.f);
       for (int i = 0; i < s.Co; ++i) bf[i] = b.host[i] + b2.host[i];
@@ -1292,14 +818,7 @@ int add_conv(cm_model *m, const ConvSpec &s) {
         op.wqr_floats = (long long)wq.size();
         if (m->precision != CM_PRECISION_F16 && Ci_ref % 64 == 0 && !cm::diag_env("CM_NO_QR_B6") && upload(m, pack_qr_b6(wq, s.Co, Ci_ref), &op.d_wqr_b6))
           return 1;
-        if (op.d_wqr_b6 && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 1.0)) {
-          std::vector<float> wh2;
-          const float ws = h2_pack_qr(w.host.data(), s.Co, Ci_ref, &wh2);
-          if (ws > 0.f) {
-            if (upload(m, wh2, &op.d_wqr_h2)) return 1;
-            op.h2_oscale = 1.f / ws;
-          }
-        }
+        if (op.d_wqr_b6 && h2_plan && h2_act_bounded(m, m->ops[op.gn_op], 1.0) && add_h2(m, op, H2_QR, w.host.data(), &op.d_wqr_h2)) return 1;
       }
       if (op.d_s2w) {
         const Param &w2 = P(m, s.skip_w);

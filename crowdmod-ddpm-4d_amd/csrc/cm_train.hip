@@ -1572,20 +1572,8 @@ hipError_t launch_adam(float *p, const float *g, float *m, float *v, long long n
   return hipGetLastError();
 }
 
-// packed[i] = sum_{k<8} W[idx[i][k]]  (idx < 0: skipped) -- re-packs a master weight tensor into
+// dst[e] = sum_{k<nk} W[idx[e][k]]  (idx < 0: skipped) -- re-packs a master weight tensor into
 // an MFMA fragment layout (forward, data-gradient or parity layout) after an optimizer step.
-__global__ void gather_pack_kernel(const float *__restrict__ W, const int *__restrict__ idx, int nk,
-                                   float *__restrict__ packed, long long n) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  float s = 0.f;
-  for (int k = 0; k < nk; ++k) {
-    const int j = idx[i * nk + k];
-    if (j >= 0) s += W[j];
-  }
-  packed[i] = s;
-}
-
 // All re-packs of one optimizer step in ONE launch: job j covers the global element range
 // [start[j], start[j+1]); a thread finds its job by bisection over the (few hundred) starts.
 __global__ void gather_pack_jobs_kernel(const float *__restrict__ W, const PackJob *__restrict__ jobs, const int *__restrict__ blk2job) {
@@ -1649,11 +1637,6 @@ __global__ void wino_pack_jobs_kernel(const float *__restrict__ W, const WinoPac
 hipError_t launch_wino_pack_jobs(const float *W, const WinoPackJob *jobs, const int *blk2job, long long nblocks, hipStream_t st) {
   if (nblocks <= 0) return hipSuccess;
   hipLaunchKernelGGL(wino_pack_jobs_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, W, jobs, blk2job);
-  return hipGetLastError();
-}
-
-hipError_t launch_gather_pack(const float *W, const int *idx, int nk, float *packed, long long n, hipStream_t st) {
-  hipLaunchKernelGGL(gather_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, idx, nk, packed, n);
   return hipGetLastError();
 }
 

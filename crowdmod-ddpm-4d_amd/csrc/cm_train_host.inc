@@ -23,7 +23,7 @@ struct cm_train_state {
   int step = 0;
   hipEvent_t ev_dy = nullptr, ev_wdone = nullptr;   // backward: weight-gradient launches run on a second stream (see backward_ops)
   // derived device tensors refreshed from pbuf after every optimizer step
-  struct Derived { float *dst; int *d_idx; float *d_coef; int nk; long long n; bool bwd_only; };
+  struct Derived { float *dst; int *d_idx; int nk; long long n; bool bwd_only; };
   std::vector<Derived> derived;
   cm::PackJob *d_jobs = nullptr;   // the same list as one device-side job table
   int *d_blk2job = nullptr; long long pack_blocks = 0;   // workgroup -> job (each job owns whole workgroups)
@@ -93,54 +93,27 @@ namespace {
 
 float *grad_of(cm_model *m, const std::string &name) { return m->train->gbuf + m->train->poff.at(name); }
 
-// global (pbuf) index of reference weight element [co][ci][tap_ref]
+// positions in the flat parameter buffer (pbuf) of a conv weight's elements, in the internal tap order [Co][Ci][t]: the layouts of
+// cm_pack.h, fed with these instead of the values, give the index maps of the device re-pack
 std::vector<int> ref_index_internal(cm_model *m, const std::string &wname, int Co, int Ci, int ntaps) {
-  const size_t base = m->train->poff.at(wname);
-  std::vector<int> out((size_t)Co * Ci * ntaps);
-  for (size_t cc = 0; cc < (size_t)Co * Ci; ++cc)
-    for (int t = 0; t < ntaps; ++t) {
-      const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;
-      const int tap_ref = (ntaps == 27) ? (dy * 3 + dx) * 3 + dz : 0;
-      out[cc * ntaps + t] = (int)(base + cc * ntaps + tap_ref);
-    }
-  return out;
+  std::vector<int> ref((size_t)Co * Ci * ntaps);
+  std::iota(ref.begin(), ref.end(), (int)m->train->poff.at(wname));
+  return to_internal_taps(ref.data(), Co, Ci, ntaps);
 }
 
-// index version of pack_conv_weights: src holds nk source indices per internal element [Co][Ci][ntaps][nk]
-std::vector<int> pack_conv_indices(const std::vector<int> &src, int nk, int Co, int Ci, int ntaps, int Ci_pad, int CK, int NB) {
-  const int TN = 32 * NB, ntn = (Co + TN - 1) / TN, nch = Ci_pad / CK, K8 = CK / 8, nsteps = ntaps * K8;
-  std::vector<int> out((size_t)ntn * nch * nsteps * NB * 64 * 4 * nk, -1);
-  size_t o = 0;
-  for (int nt = 0; nt < ntn; ++nt)
-    for (int ch = 0; ch < nch; ++ch)
-      for (int s = 0; s < nsteps; ++s) {
-        const int t = s / K8, j = s % K8;
-        for (int nb = 0; nb < NB; ++nb)
-          for (int lane = 0; lane < 64; ++lane)
-            for (int jj = 0; jj < 4; ++jj, ++o) {
-              const int co = nt * TN + nb * 32 + (lane & 31);
-              const int ci = ch * CK + 8 * j + 4 * (lane >> 5) + jj;
-              if (co < Co && ci < Ci)
-                for (int k = 0; k < nk; ++k) out[o * nk + k] = src[(((size_t)co * Ci + ci) * ntaps + t) * nk + k];
-            }
-      }
-  return out;
-}
-
-int add_derived(cm_model *m, float *dst, const std::vector<int> &idx, int nk, bool bwd_only = false,
-                const std::vector<float> *coef = nullptr) {
+// a device tensor re-derived from pbuf after every optimizer step: element i = sum over its nk indices (-1: none) of pbuf[index]
+int add_derived(cm_model *m, float *dst, const int *idx, size_t count, int nk, bool bwd_only = false) {
   cm_train_state::Derived d;
-  d.dst = dst; d.nk = nk; d.n = (long long)(idx.size() / nk); d.bwd_only = bwd_only; d.d_coef = nullptr;
-  if (dev_alloc(m, (void **)&d.d_idx, idx.size() * sizeof(int))) return 1;
-  CM_HIP(hipMemcpy(d.d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
-  if (coef) {
-    if (coef->size() != idx.size()) return fail("derived tensor: coefficient / index size mismatch");
-    if (dev_alloc(m, (void **)&d.d_coef, coef->size() * sizeof(float))) return 1;
-    CM_HIP(hipMemcpy(d.d_coef, coef->data(), coef->size() * sizeof(float), hipMemcpyHostToDevice));
-  }
+  d.dst = dst; d.nk = nk; d.n = (long long)(count / nk); d.bwd_only = bwd_only;
+  if (dev_alloc(m, (void **)&d.d_idx, count * sizeof(int))) return 1;
+  CM_HIP(hipMemcpy(d.d_idx, idx, count * sizeof(int), hipMemcpyHostToDevice));
   m->train->derived.push_back(d);
   return 0;
 }
+int add_derived(cm_model *m, float *dst, const std::vector<int> &idx, int nk, bool bwd_only = false) {
+  return add_derived(m, dst, idx.data(), idx.size(), nk, bwd_only);
+}
+int add_derived(cm_model *m, float *dst, const std::vector<Src8> &idx) { return add_derived(m, dst, idx[0].data(), idx.size() * 8, 8); }
 
 int add_derived_wino(cm_model *m, float *dst, const std::vector<int> &idx27, int Co, int Ci, int Ci_pad) {
   cm_train_state::DerivedWino d;
@@ -200,7 +173,6 @@ int refresh_h2(cm_model *m) {
       continue;
     }
     if (op.kind != OP_CONV || !(op.d_wwino_h2 || op.d_wqr_h2 || op.d_wfin_h2 || op.d_wups_h2)) continue;
-    const int Co = op.ca.Co, Ci = op.ca.C0 + op.ca.C1;
     if (fetch(op.wname, &w)) return 1;
     op.h2_off = false;
     if (!op.d_wups_h2) {                             // (the upsample conv takes its range from the data, not from a GroupNorm bound)
@@ -209,20 +181,12 @@ int refresh_h2(cm_model *m) {
       if (fetch(gop.gname, &gam) || fetch(gop.bename, &bet)) return 1;
       if (!h2_bound_ok(gam, bet, gop, op.d_wwino_h2 ? 4.0 : 1.0)) { op.h2_off = true; continue; }
     }
-    float ws = 0.f;
-    float *dst = nullptr;
-    if (op.d_wfin_h2) {
-      ws = h2_wscale(w.data(), w.size());
-      if (ws > 0.f) CM_HIP(cm::launch_fin_pack(T->pbuf + T->poff[op.wname], op.d_wfin_h2, Co, 2, m->stream, ws));
-    } else if (op.d_wwino_h2) {
-      ws = h2_pack_wino(w.data(), Co, Ci, Ci, &frag); dst = op.d_wwino_h2;
-    } else if (op.d_wqr_h2) {
-      ws = h2_pack_qr(w.data(), Co, Ci, &frag); dst = op.d_wqr_h2;
-    } else {
-      ws = h2_pack_ups(w.data(), Co, Ci, &frag); dst = op.d_wups_h2;
-    }
+    const H2Kind kind = op.d_wfin_h2 ? H2_FIN : op.d_wwino_h2 ? H2_WINO : op.d_wqr_h2 ? H2_QR : H2_UPS;
+    float *dst = kind == H2_WINO ? op.d_wwino_h2 : kind == H2_QR ? op.d_wqr_h2 : op.d_wups_h2;
+    const float ws = h2_pack(op, kind, w.data(), &frag);
     if (!(ws > 0.f)) { op.h2_off = true; continue; }
-    if (dst) CM_HIP(hipMemcpy(dst, frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (kind == H2_FIN) CM_HIP(cm::launch_fin_pack(T->pbuf + T->poff[op.wname], op.d_wfin_h2, op.ca.Co, 2, m->stream, ws));
+    else CM_HIP(hipMemcpy(dst, frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice));
     op.h2_oscale = 1.f / ws;
   }
   CM_HIP(hipStreamSynchronize(m->stream));
@@ -239,7 +203,7 @@ int repack_all(cm_model *m, hipStream_t st) {
     long long total = 0;
     for (auto &d : T->derived) {
       cm::PackJob j{};
-      j.dst = d.dst; j.idx = d.d_idx; j.coef = d.d_coef; j.start = total; j.nk = d.nk;
+      j.dst = d.dst; j.idx = d.d_idx; j.coef = nullptr; j.start = total; j.nk = d.nk;
       j.n = d.n; j.blk0 = (long long)b2j.size();
       for (long long k = 0; k < (d.n + 255) / 256; ++k) b2j.push_back((int)jobs.size());
       jobs.push_back(j);
@@ -386,33 +350,20 @@ int train_setup(cm_model *m) {
     const std::vector<int> ii = ref_index_internal(m, op.wname, Co, Ci, nt);
     // forward packed weights
     if (op.ca.par) {
-      auto emap = [](int p, int d) { return p == 0 ? (d == 0 ? 0 : 1) : (d == 2 ? 1 : 0); };
-      std::vector<int> all;
-      for (int p8 = 0; p8 < 8; ++p8) {
-        const int pz = (p8 >> 2) & 1, py = (p8 >> 1) & 1, px = p8 & 1;
-        std::vector<int> src((size_t)Co * Ci * 8 * 8, -1);
-        std::vector<int> fill((size_t)Co * Ci * 8, 0);
-        for (size_t cc = 0; cc < (size_t)Co * Ci; ++cc)
-          for (int dz = 0; dz < 3; ++dz)
-            for (int dy = 0; dy < 3; ++dy)
-              for (int dx = 0; dx < 3; ++dx) {
-                const int e = (emap(pz, dz) * 2 + emap(py, dy)) * 2 + emap(px, dx);
-                int &f = fill[cc * 8 + e];
-                src[(cc * 8 + e) * 8 + f++] = ii[cc * 27 + (dz * 3 + dy) * 3 + dx];
-              }
-        std::vector<int> one = pack_conv_indices(src, 8, Co, Ci, 8, Ci_pad, op.ca.CK, op.NB);
-        all.insert(all.end(), one.begin(), one.end());
-      }
-      if (add_derived(m, const_cast<float *>(op.ca.wfrag), all, 8)) return 1;
+      long long stride = 0;
+      const std::vector<Src8> all = pack_parity_classes(parity_sources(ii, Co, Ci), &stride, [&](const Src8 *s8) {
+        return pack_conv(s8, Co, Ci, 8, Ci_pad, op.ca.CK, op.NB, kNoSrc8);
+      });
+      if (add_derived(m, const_cast<float *>(op.ca.wfrag), all)) return 1;
     } else {
-      if (add_derived(m, const_cast<float *>(op.ca.wfrag), pack_conv_indices(ii, 1, Co, Ci, nt, Ci_pad, op.ca.CK, op.NB), 1)) return 1;
+      if (add_derived(m, const_cast<float *>(op.ca.wfrag), pack_conv(ii.data(), Co, Ci, nt, Ci_pad, op.ca.CK, op.NB, -1), 1)) return 1;
     }
     if (op.d_s2w) {
       // inference-only fused skip conv: keep its packed weights / summed bias in step with the master copy
       const Param &w2 = P(m, op.skip_w);
       const int Ci2 = (int)w2.shape[1];
       const std::vector<int> i2 = ref_index_internal(m, op.skip_w, Co, Ci2, 1);
-      if (add_derived(m, op.d_s2w, pack_conv_indices(i2, 1, Co, Ci2, 1, Ci2, 32, op.NB), 1)) return 1;
+      if (add_derived(m, op.d_s2w, pack_conv(i2.data(), Co, Ci2, 1, Ci2, 32, op.NB, -1), 1)) return 1;
       const int TNf = 32 * op.NB, cpf = (op.ca.Co + TNf - 1) / TNf * TNf;
       std::vector<int> ibf((size_t)cpf * 2, -1);
       for (int i = 0; i < Co; ++i) { ibf[2 * i] = (int)(T->poff[op.bname] + i); ibf[2 * i + 1] = (int)(T->poff[op.skip_b] + i); }
@@ -422,56 +373,15 @@ int train_setup(cm_model *m) {
       if (add_derived_wino(m, op.d_wwino, ii, Co, Ci, Ci_pad)) return 1;
     }
     if (op.qr) {
-      // whole-sample quarter-resolution kernel of the inference plan (pack_qr / pack_qr_skip order)
-      const int ntn = Co / 32, K8 = Ci / 8, ng = 9 * K8;
-      std::vector<int> wq((size_t)ntn * ng * 3 * 64 * 4, -1);
-      size_t o = 0;
-      for (int nt2 = 0; nt2 < ntn; ++nt2)
-        for (int g = 0; g < ng; ++g)
-          for (int dz = 0; dz < 3; ++dz)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int jj = 0; jj < 4; ++jj, ++o) {
-                const int k8 = g / 9, t9 = g % 9, dy = t9 / 3, dx = t9 % 3;
-                const int co = nt2 * 32 + (lane & 31), ci = 8 * k8 + 4 * (lane >> 5) + jj;
-                wq[o] = ii[((size_t)co * Ci + ci) * 27 + (dz * 3 + dy) * 3 + dx];
-              }
-      if (add_derived(m, op.d_wqr, wq, 1)) return 1;
+      // whole-sample quarter-resolution kernel of the inference plan
+      if (add_derived(m, op.d_wqr, pack_qr(ii, Co, Ci), 1)) return 1;
       if (op.d_wqr_skip) {
-        const Param &w2 = P(m, op.skip_w);
-        const int Ci2 = (int)w2.shape[1], ngs = Ci2 / 8;
-        const std::vector<int> i2 = ref_index_internal(m, op.skip_w, Co, Ci2, 1);
-        std::vector<int> ws((size_t)ntn * ngs * 64 * 4, -1);
-        o = 0;
-        for (int nt2 = 0; nt2 < ntn; ++nt2)
-          for (int gs = 0; gs < ngs; ++gs)
-            for (int lane = 0; lane < 64; ++lane)
-              for (int jj = 0; jj < 4; ++jj, ++o)
-                ws[o] = i2[(size_t)(nt2 * 32 + (lane & 31)) * Ci2 + 8 * gs + 4 * (lane >> 5) + jj];
-        if (add_derived(m, op.d_wqr_skip, ws, 1)) return 1;
+        const int Ci2 = (int)P(m, op.skip_w).shape[1];
+        if (add_derived(m, op.d_wqr_skip, pack_qr_skip(ref_index_internal(m, op.skip_w, Co, Ci2, 1).data(), Co, Ci2), 1)) return 1;
       }
     }
-    if (op.first_k) {
-      const int cin = op.first_cin, NS = 27 * cin / 2, hc = cin / 2, ntn = Co / 32;
-      std::vector<int> wp((size_t)ntn * NS * 64, -1);
-      for (int nt2 = 0; nt2 < ntn; ++nt2)
-        for (int t = 0; t < 27; ++t)
-          for (int pp = 0; pp < hc; ++pp)
-            for (int lane = 0; lane < 64; ++lane) {
-              const int co = nt2 * 32 + (lane & 31), ci = hc * (lane >> 5) + pp;
-              if (ci < Ci) wp[((size_t)nt2 * NS + t * hc + pp) * 64 + lane] = ii[((size_t)co * Ci + ci) * 27 + t];
-            }
-      if (add_derived(m, op.d_wfirst, wp, 1)) return 1;
-    }
-    if (op.small_n) {
-      const int nco = op.small_nco, CK = op.ca.CK, nch = Ci_pad / CK;
-      std::vector<int> ws((size_t)nch * 27 * CK * nco, -1);
-      for (int ch = 0; ch < nch; ++ch)
-        for (int t = 0; t < 27; ++t)
-          for (int ci = 0; ci < CK; ++ci)
-            for (int co = 0; co < Co; ++co)
-              if (ch * CK + ci < Ci) ws[(((size_t)ch * 27 + t) * CK + ci) * nco + co] = ii[((size_t)co * Ci + ch * CK + ci) * 27 + t];
-      if (add_derived(m, op.d_wsmall, ws, 1)) return 1;
-    }
+    if (op.first_k && add_derived(m, op.d_wfirst, pack_first(ii.data(), Co, Ci, op.first_cin, -1), 1)) return 1;
+    if (op.small_n && add_derived(m, op.d_wsmall, pack_small(ii.data(), Co, Ci, Ci_pad, op.ca.CK, op.small_nco, -1), 1)) return 1;
     {
       const int TN = 32 * op.NB, co_pad = (op.ca.Co + TN - 1) / TN * TN;
       std::vector<int> ib((size_t)co_pad, -1);
@@ -499,7 +409,7 @@ int train_setup(cm_model *m) {
       a.out_cs = Ci_pad; a.CK = pick_ck(Cy, 0);
       a.nch0 = Cy / a.CK; a.nch1 = 0;
       D.NB = Ci > 32 ? 2 : 1;
-      std::vector<int> pidx = pack_conv_indices(src, 1, Ci, Co, nt, Cy, a.CK, D.NB);
+      const std::vector<int> pidx = pack_conv(src.data(), Ci, Co, nt, Cy, a.CK, D.NB, -1);
       if (dev_alloc(m, (void **)&D.wfrag, pidx.size() * sizeof(float))) return 1;
       if (add_derived(m, D.wfrag, pidx, 1, true)) return 1;
       const int TN = 32 * D.NB, cop = (Ci + TN - 1) / TN * TN;
@@ -529,18 +439,8 @@ int train_setup(cm_model *m) {
       if (op.qr && op.d_wqr_b6 && nt == 27 && Cy == Co && Co % 64 == 0 && Ci % 32 == 0 && Ci == Ci_pad && a.Zo == 2 &&
           a.Yo * a.Xo <= 64 && 8 * (a.Yo + 2) * (a.Xo + 2) <= 64 * 9 && m->precision != CM_PRECISION_F16 && !cm::diag_env("CM_NO_TRAIN_QR")) {
         op.train_qr = true;
-        const int ntn = Ci / 32, K8 = Co / 8, ng = 9 * K8, cw = Co / 8, nsw = (cw + 15) >> 4;
-        std::vector<int> wq((size_t)ntn * ng * 3 * 64 * 4, -1);
-        size_t o = 0;
-        for (int nt2 = 0; nt2 < ntn; ++nt2)
-          for (int g = 0; g < ng; ++g)
-            for (int dz = 0; dz < 3; ++dz)
-              for (int lane = 0; lane < 64; ++lane)
-                for (int jj = 0; jj < 4; ++jj, ++o) {
-                  const int k8 = g / 9, t9 = g % 9, dy = t9 / 3, dx = t9 % 3;
-                  const int cio = nt2 * 32 + (lane & 31), cy = 8 * k8 + 4 * (lane >> 5) + jj;   // dgrad output / input channel
-                  wq[o] = src[((size_t)cio * Co + cy) * 27 + (dz * 3 + dy) * 3 + dx];
-                }
+        const int ntn = Ci / 32, cw = Co / 8, nsw = (cw + 15) >> 4;
+        const std::vector<int> wq = pack_qr(src, Ci, Co);                 // dgrad output channels Ci, input channels Co (= Cy)
         D.wqr_floats = (long long)wq.size();
         if (dev_alloc(m, (void **)&D.wqr, wq.size() * sizeof(float))) return 1;
         if (add_derived(m, D.wqr, wq, 1, true)) return 1;
