@@ -36,6 +36,26 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
+// h2 scale of one sample from its n source values themselves, for the case the slot statistics cannot serve (cm_h2_sample_scale
+// returned 1).  All 256 threads call it (two barriers inside; `scratch`: 4 floats of LDS nothing else uses until it returns).  A maximum
+// below 2^14 fits f16 unscaled, so the statistics' answer stands -- every finite-statistics launch keeps its bits; otherwise the same power
+// of two as cm_h2_sample_scale's, from the true maximum.  Inf in the data: no scaling, the outputs that read it are non-finite.
+__device__ __forceinline__ float ups_h2_scale_from_data(const float *__restrict__ x, unsigned n, float *scratch, int tid) {
+  float bm = 0.f;
+  for (unsigned i = (unsigned)tid; i < n; i += 256u) bm = fmaxf(bm, fabsf(x[i]));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) bm = fmaxf(bm, __shfl_xor(bm, off));
+  if ((tid & 63) == 0) scratch[tid >> 6] = bm;
+  __syncthreads();
+  const float m = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
+  __syncthreads();
+  const unsigned e = (__float_as_uint(m) >> 23) & 255u;
+  if (!(m >= 16384.f) || e == 255u) return 1.0f;
+  int se = 267 - (int)e;                                      // as in cm_h2_sample_scale: m s < 2^14
+  se = se < 32 ? 32 : se;
+  return __uint_as_float((unsigned)se << 23);
+}
+
 // tabH[(p * 2 + pz)][HV]: in-sample source voxel of halo voxel h of tile position p for class p_z, or -1 (zero padding);
 // tabM[p][32 MBW][2]: row m -> halo index of its source voxel at (e = 0, p_y = p_x = 0) | packed global source coordinates
 // (Z << 20 | Y << 10 | X) or -1 (padding row).
@@ -104,7 +124,11 @@ __global__ __launch_bounds__(256, OCC) void conv_ups_kernel(const ConvArgs a, co
   const int mode = (planes && a.bz == a.Zs) ? 1 + pz : 0;
   const int nch = a.C0 >> 5;
   float sa = 1.f;                                  // h2: this sample's activation scale (a power of two)
-  if constexpr (H2) sa = cm_h2_sample_scale(a.gp0, a.gc0, a.gns0, a.C0, b, A, tid, 256);
+  if constexpr (H2) {
+    sa = cm_h2_sample_scale(a.gp0, a.gc0, a.gns0, a.C0, b, A, tid, 256);
+    // 1 is also what non-finite statistics give (M2 overflows once |x - mean| > 1.8e19): they bound nothing, so the range comes from the data
+    if (sa == 1.0f) sa = ups_h2_scale_from_data(a.src0 + (size_t)b * Vs * a.C0, Vs * (unsigned)a.C0, A, tid);
+  }
 
   auto body = [&](auto mode_c) {
   constexpr int MODE = decltype(mode_c)::value;

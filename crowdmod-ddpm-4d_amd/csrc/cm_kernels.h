@@ -158,7 +158,9 @@ __device__ __forceinline__ void cm_chan_combine(float &n, float &mean, float &m2
   const float d = meanb - mean;
   const float f = nb * __builtin_amdgcn_rcpf(nt);
   mean += d * f;
-  m2 += m2b + d * d * n * f;
+  // n == 0 (the first triple of a merge): the cross term is 0 whatever d is.  Written out, because 0 * (d * d) is NaN once
+  // d * d overflows (|mean| > 1.8e19), where the variance itself is still finite or +inf (rstd 0), never NaN.
+  m2 += m2b + (n > 0.f ? d * d * n * f : 0.f);
   n = nt;
 }
 // Consumer prologue, slot form (ConvArgs::gp0): rows[2 (C0 + C1)] of sample `b` from the producers' slot partials.  Called by all

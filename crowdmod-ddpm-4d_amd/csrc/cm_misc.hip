@@ -16,7 +16,9 @@ __device__ __forceinline__ void chan_combine(float &n, float &mean, float &m2, f
   const float d = meanb - mean;
   const float f = nb * __builtin_amdgcn_rcpf(nt);  // hardware reciprocal (1 ulp) instead of an IEEE division
   mean += d * f;
-  m2 += m2b + d * d * n * f;
+  // n == 0 (the first triple of a merge): the cross term is 0 whatever d is.  Written out, because 0 * (d * d) is NaN once
+  // d * d overflows (|mean| > 1.8e19), where the variance itself is still finite or +inf (rstd 0), never NaN.
+  m2 += m2b + (n > 0.f ? d * d * n * f : 0.f);
   n = nt;
 }
 
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void chan_stats_kernel(const float *__restrict
       const float md = s1[i] / n;
       mean[i] = piv[i] + md;
       m2[i] = s2[i] - s1[i] * md;
-      if (m2[i] < 0.f) m2[i] = 0.f;
+      if (!(m2[i] >= 0.f)) m2[i] = s2[i] > 3.0e38f ? s2[i] : 0.f;   // (inf - inf: the squares overflowed, M2 = +inf, not NaN)
     } else { mean[i] = 0.f; m2[i] = 0.f; }
   }
 #pragma unroll

@@ -6,7 +6,10 @@ The training step draws two things on the device (crowdmod-ddpm-4d_amd/csrc/cm_m
     (column, sample_id_base + b, step, 0xD120), key (seed lo, seed hi), keep if u >= p, value 1/(1-p);
   * eps ~ N(0, 1) when the caller passes none: philox_normal (Box-Muller on one Philox draw), counter
     (element >> 1, sample, step, (sample >> 32) ^ 0x5eed), key (seed lo, seed hi); the training step uses
-    the step word 0x40000000 + (number of earlier device draws of this handle).
+    the step word 0x40000000 + (number of earlier device draws of this handle);
+  * the sampling noise, from the same philox_normal: x_T of cm_sample_loop (launch_randn, step word 0x7FFFFFFF) and
+    z_t inside cm_sampler_update (sampler_step_kernel and the tail of conv_fin_kernel; step word t), element index
+    e = ((c H + h) W + w) F + f of the sample in reference layout.
 
 Everything below is written from the definitions (Philox4x32-10: Salmon et al., SC'11; Dropout3d:
 torch.nn.functional.dropout3d) in numpy uint64 / float32 arithmetic, so the tests can restate what the device
@@ -19,7 +22,14 @@ import numpy as np
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 DROPOUT_STREAM = 0xD120
+# The step word (third counter word) of philox_normal has three disjoint users:
+#   [0, MAX_TIMESTEPS)            z_t of the reverse step at timestep t (StepRow.step = t; cm_ddpm_step: t)
+#   [0x40000000, 0x7FFFFFFE]      eps of the training step: EPS_STEP_WORD + the handle's draw counter (mod 2^30)
+#   0x7FFFFFFF                    x_T of cm_sample_loop
+# (a handle's 2^30 - 1-th training draw would reuse x_T's word: out of reach, and under another seed in practice)
 EPS_STEP_WORD = 0x40000000
+XT_STEP_WORD = 0x7FFFFFFF
+MAX_TIMESTEPS = 1000
 _M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -66,28 +76,83 @@ def dropout_masks(seed: int, step: int, sample_id_base: int, B: int, width: int,
     return np.where(u >= pf, keep, np.float32(0.0)).astype(np.float32)
 
 
-def normal(seed: int, step: int, sample_id_base: int, B: int, per: int) -> np.ndarray:
-    """[B, per] N(0, 1) of philox_normal: element e of sample b uses Philox draw (e >> 1) of sample
-    sample_id_base + b; even elements take rad * cos(2 pi u2), odd ones rad * sin(2 pi u2).  Evaluated in
-    float64 from the exact fp32 uniforms and rounded to fp32 once."""
+def uniforms(seed: int, step: int, sample_id_base: int, B: int, elem) -> tuple:
+    """(u1, u2), each [B, len(elem)] fp32: the two uniforms behind element index elem[i] of samples sample_id_base + b.
+    Counter (elem >> 1, sample, step, (sample >> 32) ^ 0x5eed), key (seed lo, seed hi), words 0 and 1 of the draw."""
     k0, k1 = _split_seed(seed)
     sample = np.arange(B, dtype=np.int64) + int(sample_id_base)
-    e = np.arange(per, dtype=np.int64)
+    e = np.asarray(elem, dtype=np.int64)
     hi = ((sample >> 32) ^ 0x5EED).astype(np.uint64)[:, None]
     r0, r1, _, _ = philox4x32_10((e >> 1).astype(np.uint64)[None, :], sample.astype(np.uint64)[:, None],
                                  int(step) & 0xFFFFFFFF, hi, k0, k1)
-    u1 = unit_float(r0).astype(np.float64)
-    ang = (np.float32(6.283185307179586) * unit_float(r1)).astype(np.float64)   # the device's fp32 product
-    rad = np.sqrt(-2.0 * np.log(u1))
+    return unit_float(r0), unit_float(r1)
+
+
+def normal64(seed: int, step: int, sample_id_base: int, B: int, per: int, *, elem=None, swap: bool = False) -> np.ndarray:
+    """[B, per] N(0, 1) of philox_normal in float64, BEFORE the final rounding: position i of sample b is element
+    index e = elem[i] (default i) of sample sample_id_base + b and uses Philox draw (e >> 1); even e take
+    rad * cos(2 pi u2), odd e rad * sin(2 pi u2), rad = sqrt(-2 ln u1).  Evaluated in float64 from the exact fp32
+    uniforms and the device's fp32 product 2 pi u2.  `elem` and `swap` (cos <-> sin) exist for the negative controls
+    of the tests: what a wrong element order or a swapped branch would have drawn."""
+    e = np.arange(per, dtype=np.int64) if elem is None else np.asarray(elem, dtype=np.int64).reshape(per)
+    pairs, inv = np.unique(e >> 1, return_inverse=True)             # one Philox draw serves both elements of a pair
+    u1, u2 = uniforms(seed, step, sample_id_base, B, pairs << 1)
+    ang = (np.float32(6.283185307179586) * u2).astype(np.float64)   # the device's fp32 product
+    rad = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
     odd = (e & 1).astype(bool)[None, :]
-    return np.where(odd, rad * np.sin(ang), rad * np.cos(ang)).astype(np.float32)
+    if swap:
+        odd = ~odd
+    inv = inv.reshape(-1)
+    return np.where(odd, (rad * np.sin(ang))[:, inv], (rad * np.cos(ang))[:, inv])
+
+
+def normal(seed: int, step: int, sample_id_base: int, B: int, per: int) -> np.ndarray:
+    """normal64 rounded to fp32 once."""
+    return normal64(seed, step, sample_id_base, B, per).astype(np.float32)
+
+
+def ref_elem(shape) -> np.ndarray:
+    """Element indices of one sample [C, H, W, F] in reference order: e = ((c H + h) W + w) F + f, i.e. arange."""
+    return np.arange(int(np.prod(shape)), dtype=np.int64)
+
+
+def channels_last_elem(shape) -> np.ndarray:
+    """What a kernel would use as element index had it counted in its internal channels-last order
+    e' = ((f H + h) W + w) C + c -- listed in reference order (negative control)."""
+    C_, H, W, F = (int(v) for v in shape)
+    c, h, w, f = np.meshgrid(np.arange(C_), np.arange(H), np.arange(W), np.arange(F), indexing="ij")
+    return (((f * H + h) * W + w) * C_ + c).reshape(-1).astype(np.int64)
+
+
+def sample_xT(seed: int, sample_id_base: int, shape, **kw) -> np.ndarray:
+    """x_T of cm_sample_loop(d_xT = null) in float64: launch_randn with the step word XT_STEP_WORD; [B, C, H, W, F]."""
+    B, per = int(shape[0]), int(np.prod(shape[1:]))
+    return normal64(seed, XT_STEP_WORD, sample_id_base, B, per, **kw).reshape(shape)
+
+
+def sample_z(seed: int, t: int, sample_id_base: int, shape, **kw) -> np.ndarray:
+    """z_t of the DDPM / DDIM update at timestep t (cm_sampler_update; the step word is t itself) in float64."""
+    B, per = int(shape[0]), int(np.prod(shape[1:]))
+    return normal64(seed, sampler_step_word(t), sample_id_base, B, per, **kw).reshape(shape)
+
+
+def sampler_step_word(t: int) -> int:
+    """Step word of the noise of the reverse step at timestep t, 0 <= t < T <= 1000 (the time-embedding table's rows)."""
+    t = int(t)
+    assert 0 <= t < MAX_TIMESTEPS, t
+    return t
+
+
+def eps_step_word(draw: int) -> int:
+    """Step word of the `draw`-th device eps of a training handle (0 for its first)."""
+    return EPS_STEP_WORD + (int(draw) & 0x3FFFFFFF)
 
 
 def train_eps(seed: int, draw: int, sample_id_base: int, shape) -> np.ndarray:
     """eps of cm_train_step(d_eps = null): the handle's `draw`-th device draw (0 for its first), [B, C, H, W, F]."""
     B = int(shape[0])
     per = int(np.prod(shape[1:]))
-    return normal(seed, EPS_STEP_WORD + (int(draw) & 0x3FFFFFFF), sample_id_base, B, per).reshape(shape)
+    return normal(seed, eps_step_word(draw), sample_id_base, B, per).reshape(shape)
 
 
 def mask_layout(plan):
