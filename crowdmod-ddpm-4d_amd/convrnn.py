@@ -4,7 +4,11 @@ every generative model is compared against.
 
 `Forecaster` keeps the reference's constructor arguments and call convention --
 `forecaster(x_obs[B,4,H,W,P], target_obs[B,4,H,W,F], teacher_forcing=False) -> [B,4,H,W,F]` -- and the `nn.Module`
-surface the driver touches.  All arithmetic runs in libcrowdmod_hip.so (cm_convrnn_*, cm_convrnn.hip); inference only.
+surface the driver touches.  All arithmetic runs in libcrowdmod_hip.so (cm_convrnn_*, cm_convrnn.hip, cm_convrnn_train.hip).
+
+Training (convRNN.py:98-221) is reached through `Forecaster.train_init / train_step / evaluate_loss` and
+`ConvRNN_model._train_one_epoch / fit` (script: train_convrnn.py).  `Forecaster.train()` -- the nn.Module mode switch -- and
+`ConvRNN_model.train(...)` keep refusing: the forecaster has no mode-dependent layer, and the driver's loop is `fit`.
 """
 from __future__ import annotations
 
@@ -17,7 +21,8 @@ import numpy as np
 from . import config as cfgmod, convrnn_spec, native
 from .unet import _is_torch
 
-_REFUSAL = "ConvRNN training (Poisson-KL + masked MSE loss, AMSGrad) is not implemented on this path (inference only)"
+_REFUSAL = ("ConvRNN training (Poisson-KL + masked MSE loss, AMSGrad) is not reached through train(): use "
+            "ConvRNN_model.fit / Forecaster.train_step (train_convrnn.py); the forecaster has no train mode")
 
 
 def _cell_name(cell_class) -> str:
@@ -50,6 +55,8 @@ class Forecaster:
         self._shapes = convrnn_spec.param_shapes(self.cfg)
         self._params: Dict[str, np.ndarray] = convrnn_spec.init_params(self.cfg, seed if seed is not None else 0)
         self._handle = None
+        self._hyper = None      # (lr, beta1, beta2, eps, weight_decay) once train_init has been called
+        self._trained = False   # the native master weights are ahead of self._params
 
     # -- nn.Module surface ---------------------------------------------------------
     def eval(self):
@@ -71,6 +78,8 @@ class Forecaster:
         return list(self._params.values())
 
     def state_dict(self) -> Dict[str, np.ndarray]:
+        if self._trained:
+            self.sync()
         return {k: v.copy() for k, v in self._params.items()}
 
     def load_state_dict(self, state: Dict[str, object], strict: bool = True):
@@ -89,6 +98,7 @@ class Forecaster:
                 if tuple(got[k].shape) != tuple(shp):
                     raise RuntimeError(f"size mismatch for {k}: got {tuple(got[k].shape)}, expected {tuple(shp)}")
                 self._params[k] = got[k]
+        self._trained = False   # the loaded weights replace whatever the native handle trained
         self._release()
         return self
 
@@ -104,6 +114,8 @@ class Forecaster:
 
     def _release(self):
         if self._handle is not None:
+            if self._trained:
+                self.sync()
             native.lib().cm_convrnn_destroy(self._handle)
             self._handle = None
 
@@ -135,6 +147,8 @@ class Forecaster:
                 arr = np.ascontiguousarray(arr, dtype=np.float32)
                 native.check(L.cm_convrnn_set_param(h, name.encode(), arr.ctypes.data, arr.size))
             native.check(L.cm_convrnn_finalize(h))
+            if self._hyper is not None:
+                native.check(L.cm_convrnn_train_init(h, *self._hyper))
         except Exception:
             L.cm_convrnn_destroy(h)
             raise
@@ -176,6 +190,139 @@ class Forecaster:
         native.check(L.cm_convrnn_forecast_host(h, pst.ctypes.data, tgt.ctypes.data, tf, ex, out.ctypes.data, B))
         return out
 
+    # -- training ------------------------------------------------------------------
+    def train_init(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+        """torch.optim.Adam(parameters(), lr, betas, eps, weight_decay, amsgrad=True) of convRNN.py:49-53: fresh optimizer
+        state on the current weights.  The native state is (re)built with the next batch."""
+        self._release()
+        self._hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+        return self
+
+    def _train_handle(self, past, target):
+        B, Cc, H, W, P = (int(v) for v in past.shape)
+        F = int(target.shape[4])
+        if Cc != self.cfg.input_channels or tuple(target.shape[:4]) != (B, Cc, H, W):
+            raise ValueError(f"shape mismatch: past {tuple(past.shape)}, target {tuple(target.shape)}")
+        if self._hyper is None:   # evaluate_loss alone: the tape without an optimizer in use
+            self._hyper = (0.0, 0.9, 0.999, 1e-8, 0.0)
+        if self._trained and ((P, F) != (self.cfg.past_len, self.cfg.future_len) or B > self._native_max_batch):
+            raise ValueError("a Forecaster that has trained keeps its frame counts and max_batch (optimizer state lives in "
+                             "the native handle): build it with max_batch >= the largest batch")
+        self._last_train_B = B
+        return self.ensure(H, W, P, F, B), B
+
+    def _device_pair(self, past, target):
+        """Device addresses of (past, target): torch CUDA tensors as they are, numpy arrays through device buffers."""
+        if _is_torch(past):
+            import torch
+            if not past.is_cuda:
+                raise ValueError("torch inputs must live on the GPU; pass numpy arrays for host staging")
+            pst, tgt = past.contiguous().float(), target.to(device=past.device).contiguous().float()
+            torch.cuda.current_stream(past.device).synchronize()
+            return pst.data_ptr(), tgt.data_ptr(), (pst, tgt)
+        bufs = tuple(native.DeviceBuffer.from_array(np.ascontiguousarray(a, dtype=np.float32), self.device) for a in (past, target))
+        return bufs[0].ptr, bufs[1].ptr, bufs
+
+    def evaluate_loss(self, past, target, teacher_forcing=False, eps: float = 1e-6):
+        """utils/loss.py:15-52 on the device: (rloss, vloss, loss_considering_density, loss_not_considering_density)."""
+        h, B = self._train_handle(past, target)
+        p, t, keep = self._device_pair(past, target)
+        terms = (C.c_double * 4)()
+        native.check(native.lib().cm_convrnn_loss(h, p, t, int(bool(teacher_forcing)), float(eps), terms, B, None))
+        del keep
+        return tuple(float(v) for v in terms)
+
+    def train_step(self, past, target, teacher_forcing=False, eps: float = 1e-6, alpha: float = 1.0, apply_update: bool = True):
+        """One step of convRNN.py:121-128 on rloss + alpha * vloss: forward, loss, backward and (apply_update) the AMSGrad
+        update behind one native call.  Returns the four loss terms of the weights before the update."""
+        if self._hyper is None:
+            raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
+        h, B = self._train_handle(past, target)
+        p, t, keep = self._device_pair(past, target)
+        terms = (C.c_double * 4)()
+        native.check(native.lib().cm_convrnn_train_step(h, p, t, int(bool(teacher_forcing)), float(eps), float(alpha), terms, B,
+                                                        int(bool(apply_update)), None))
+        del keep
+        self._trained = self._trained or bool(apply_update)
+        return tuple(float(v) for v in terms)
+
+    def _need_train(self):
+        if self._handle is None or self._hyper is None:
+            raise RuntimeError("no training step has run on this Forecaster")
+        return self._handle
+
+    def train_forecast(self) -> np.ndarray:
+        """The raw frames [B, 4, H, W, F] of the last train_step / evaluate_loss forward.  Test hook."""
+        h, g = self._need_train(), self.cfg
+        out = np.empty((self._last_train_B, 4, g.rows, g.cols, g.future_len), np.float32)
+        native.check(native.lib().cm_convrnn_train_get_forecast(h, out.ctypes.data, out.size))
+        return out
+
+    def grad(self, name: str) -> np.ndarray:
+        out = np.empty(self._shapes[name], np.float32)
+        native.check(native.lib().cm_convrnn_train_get_grad(self._need_train(), name.encode(), out.ctypes.data, out.size))
+        return out
+
+    def apply_update(self):
+        native.check(native.lib().cm_convrnn_train_apply(self._need_train(), None))
+        self._trained = True
+
+    def set_lr(self, lr: float):
+        self._hyper = (float(lr),) + tuple(self._hyper[1:]) if self._hyper else None
+        native.check(native.lib().cm_convrnn_train_set_lr(self._need_train(), float(lr)))
+
+    def opt_step(self, value: Optional[int] = None) -> int:
+        step = C.c_int32(0 if value is None else int(value))
+        native.check(native.lib().cm_convrnn_train_opt_step(self._need_train(), C.byref(step), int(value is not None)))
+        return int(step.value)
+
+    _OPT_KEYS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
+
+    def opt_state(self) -> dict:
+        """torch.optim.Adam(amsgrad=True).state_dict() of the reference optimizer (convRNN.py:49-53): what save_checkpoint
+        stores under "opt" (utils/utils.py:140-147)."""
+        h, L = self._need_train(), native.lib()
+        step, state = self.opt_step(), {}
+        if step > 0:
+            for i, (name, shp) in enumerate(self._shapes.items()):
+                st = {"step": np.float32(step)}
+                for which, key in enumerate(self._OPT_KEYS):
+                    st[key] = np.empty(shp, np.float32)
+                    native.check(L.cm_convrnn_train_get_opt_state(h, name.encode(), which, st[key].ctypes.data, st[key].size))
+                state[i] = st
+        lr, b1, b2, eps, wd = self._hyper
+        group = {"lr": lr, "betas": (b1, b2), "eps": eps, "weight_decay": wd, "amsgrad": True, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                 "params": list(range(len(self._shapes)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_opt_state(self, opt: dict):
+        """Inverse of opt_state (resume from a checkpoint's "opt" entry); the handle must exist (one step or loss has run)."""
+        h, L = self._need_train(), native.lib()
+        names, step = list(self._shapes), 0
+        for i, st in opt.get("state", {}).items():
+            for which, key in enumerate(self._OPT_KEYS):
+                v = st[key]
+                arr = np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v), dtype=np.float32)
+                native.check(L.cm_convrnn_train_set_opt_state(h, names[int(i)].encode(), which, arr.ctypes.data, arr.size))
+            step = int(float(st["step"]))
+        self.opt_step(step)
+        groups = opt.get("param_groups") or []
+        if groups:
+            self.set_lr(float(groups[0]["lr"]))
+        return self
+
+    def sync(self):
+        """Master weights -> state_dict(); every packed layout is rebuilt from them."""
+        h, L = self._need_train(), native.lib()
+        native.check(L.cm_convrnn_train_sync(h))
+        for name, shp in self._shapes.items():
+            arr = np.empty(shp, np.float32)
+            native.check(L.cm_convrnn_get_param(h, name.encode(), arr.ctypes.data, arr.size))
+            self._params[name] = arr
+        self._trained = False
+        return self
+
     def debug_state(self, level: int, which: int = 0) -> np.ndarray:
         """Hidden state [B, C, h, w] the last call left: level 0 quarter, 1 half, 2 full resolution; which 0 = h, 1 = c
         (ConvLSTM only).  Test hook."""
@@ -196,7 +343,7 @@ class Forecaster:
 
 
 class ConvRNN_model:
-    """ConvRNN_model (convRNN.py:22-316) without the training loop and the matplotlib tail."""
+    """ConvRNN_model (convRNN.py:22-316) without wandb and the matplotlib tail; its training loop is `fit`."""
 
     def __init__(self, cfg, arch, mprops_count=4, output_dir=None, from_fixed_past=False, *, device: int = 0,
                  seed: int = 42):
@@ -213,6 +360,97 @@ class ConvRNN_model:
 
     def train(self, *a, **kw):
         raise NotImplementedError(_REFUSAL)
+
+    # -- training (convRNN.py:49-60, 98-221) ---------------------------------------
+    def _solver(self) -> dict:
+        tr = self.cfg.MODEL.CONVRNN.get("TRAIN", None) or {}
+        sv = tr.get("SOLVER", None) or {}
+        sch = sv.get("SCHEDULER", None) or {}
+        return {"epochs": int(getattr(self, "_epochs_override", None) or tr.get("EPOCHS", 0)), "lr": float(sv.get("LR", 1e-3)),
+                "betas": tuple(float(v) for v in sv.get("BETAS", (0.9, 0.999))), "weight_decay": float(sv.get("WEIGHT_DECAY", 0.0)),
+                "factor": float(sch.get("FACTOR", 0.5)), "patience": int(sch.get("PATIENCE", 10)), "min_lr": float(sch.get("MIN_LR", 0.0))}
+
+    def _ensure_training(self):
+        if getattr(self, "_plateau", None) is None:
+            from .ddpm_model import ReduceLROnPlateau
+            s = self._solver()
+            self._lr = s["lr"]
+            self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
+            self.convRNN.train_init(s["lr"], s["betas"], 1e-8, s["weight_decay"])
+
+    def _loss_eps(self) -> float:
+        mp = self.cfg.get("MACROPROPS", {}) if hasattr(self.cfg, "get") else {}
+        return float(mp.get("EPS", 1e-6)) if hasattr(mp, "get") else 1e-6
+
+    def _train_one_epoch(self, train_data_loader, val_data_loader, epoch, alpha=1):
+        """convRNN.py:98-171: one native call per training batch (forward, loss, backward, AMSGrad), forward + loss per
+        validation batch (never teacher-forced).  Returns the reference's ten values."""
+        self._ensure_training()
+        eps, net = self._loss_eps(), self.convRNN
+        lists = [[] for _ in range(8)]   # train r, v, val r, v, train d, nd, val d, nd
+        means = []
+        for loader, tf, step, (ri, vi, di, ni) in ((train_data_loader, self.teacher_forcing, True, (0, 1, 4, 5)),
+                                                   (val_data_loader, False, False, (2, 3, 6, 7))):
+            total, count = 0.0, 0
+            for past, future in loader:
+                past, future = np.asarray(past, dtype=np.float32), np.asarray(future, dtype=np.float32)
+                if step:
+                    r, v, d, nd = net.train_step(past, future, tf, eps, alpha=float(alpha))
+                else:
+                    r, v, d, nd = net.evaluate_loss(past, future, tf, eps)
+                for k, val in ((ri, r), (vi, v), (di, d), (ni, nd)):
+                    lists[k].append(val)
+                total += r + alpha * v
+                count += 1
+            means.append(total / count if count else float("nan"))   # MeanMetric of no update
+        return (means[0], means[1], *lists)
+
+    def save_checkpoint(self, epoch_tag, path: Optional[str] = None) -> str:
+        """utils/utils.py:140-147: {"opt": optimizer.state_dict(), "model": model.state_dict()}."""
+        from . import checkpoint
+        path = path or self.checkpoint_path(epoch_tag)
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        state = self.convRNN.state_dict()
+        checkpoint.save_checkpoint(state, path, opt_state=self.convRNN.opt_state())
+        return path
+
+    def fit(self, batched_train_data, batched_val_data, *, log=None, save=True) -> dict:
+        """convRNN.py:173-221 without wandb and the plots: epochs of _train_one_epoch, ReduceLROnPlateau stepped with the
+        epoch's train loss, the stop after three consecutive NaN epochs, the best checkpoint under tag "000".  Returns the
+        loss histories."""
+        import logging
+        self._ensure_training()
+        keys = ("train_rloss", "train_vloss", "val_rloss", "val_vloss", "train_dloss", "train_ndloss", "val_dloss", "val_ndloss")
+        hist = {k: [] for k in keys}
+        hist["train_loss"], hist["val_loss"] = [], []
+        best_loss, nan_run = 1e6, 0
+        for epoch in range(1, self._solver()["epochs"] + 1):
+            out = self._train_one_epoch(batched_train_data, batched_val_data, epoch=epoch)
+            epoch_train_loss, epoch_val_loss = out[0], out[1]
+            hist["train_loss"].append(epoch_train_loss)
+            hist["val_loss"].append(epoch_val_loss)
+            for k, v in zip(keys, out[2:]):
+                hist[k].extend(v)
+            if log:
+                log({"train_loss": epoch_train_loss, "val_loss": epoch_val_loss, "epoch": epoch, "lr": self._lr})
+            new_lr = self._plateau.step(epoch_train_loss)
+            if new_lr != self._lr:
+                self._lr = new_lr
+                self.convRNN.set_lr(new_lr)
+            if np.isnan(epoch_train_loss):
+                nan_run += 1
+                logging.warning("Epoch %d: loss is NaN (%d consecutive)", epoch, nan_run)
+                if nan_run >= 3:
+                    logging.error("Loss has been NaN for 3 consecutive epochs; terminating training early.")
+                    break
+            else:
+                nan_run = 0
+            if save and epoch_train_loss < best_loss:
+                best_loss = epoch_train_loss
+                self.save_checkpoint("000")
+        if self.convRNN._trained:
+            self.convRNN.sync()
+        return hist
 
     def checkpoint_path(self, epoch_tag) -> str:
         """utils/utils.py:160-163: the last name field is CELL_CLASS[4:], e.g. ConvRNN_ATC_TE600_PL5_FL3_CE000_GRUCell.pth."""

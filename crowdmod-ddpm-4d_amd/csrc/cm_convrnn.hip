@@ -120,9 +120,11 @@ __global__ __launch_bounds__(256) void crnn_conv_kernel(const CrnnConvArgs a) {
       if (ch >= hid) continue;
       const float *g = Cs + row * CS + 4 * cl;   // i, f, o, g (convLSTMCell.py:62)
       const long long o = pix * hid + ch;
-      const float cn = sigmoidf(g[1]) * a.c[o] + sigmoidf(g[0]) * tanhf(g[3]);
-      a.c[o] = cn;
-      a.y[o] = sigmoidf(g[2]) * tanhf(cn);
+      const float gi = sigmoidf(g[0]), gf = sigmoidf(g[1]), go = sigmoidf(g[2]), gg = tanhf(g[3]);
+      const float cn = gf * a.c[o] + gi * gg, tc = tanhf(cn);
+      (a.cn ? a.cn : a.c)[o] = cn;
+      a.y[o] = go * tc;
+      if (a.t0) { *(float4 *)(a.t0 + pix * a.N + 4 * ch) = make_float4(gi, gf, go, gg); a.t1[o] = tc; }
       continue;
     }
     const int col = n0 + cl;
@@ -133,12 +135,15 @@ __global__ __launch_bounds__(256) void crnn_conv_kernel(const CrnnConvArgs a) {
     } else if (EPI == CRNN_EPI_GRU_GATES) {   // columns [0, hid): reset gate, [hid, 2 hid): update gate
       const int hid = a.N >> 1;
       const float s = sigmoidf(v);
-      if (col < hid) a.y[pix * hid + col] = s * a.hprev[pix * hid + col];
-      else a.u[pix * hid + col - hid] = s;
+      if (col < hid) {
+        a.y[pix * hid + col] = s * a.hprev[pix * hid + col];
+        if (a.t0) a.t0[pix * hid + col] = s;
+      } else a.u[pix * hid + col - hid] = s;
     } else if (EPI == CRNN_EPI_GRU_CAND) {    // convGRUCell.py:64-66
       const long long o = pix * a.N + col;
-      const float uu = a.u[o];
-      a.y[o] = (1.0f - uu) * tanhf(v) + uu * a.hprev[o];
+      const float uu = a.u[o], cand = tanhf(v);
+      a.y[o] = (1.0f - uu) * cand + uu * a.hprev[o];
+      if (a.t0) a.t0[o] = cand;
     } else {                                  // CRNN_EPI_LAST
       a.out[((((long long)eb * a.N + col) * a.Ho + oy) * a.Wo + ox) * a.Ft + a.t] = a.exp_out ? exp03(v, col) : v;
       if (a.win) a.win[(long long)eb * a.win_bs + ((long long)oy * a.Wo + ox) * 8 + col] = exp03(v, col);

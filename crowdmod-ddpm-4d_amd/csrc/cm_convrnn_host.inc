@@ -29,8 +29,10 @@ struct cm_convrnn {
   float *win = nullptr, *act[6] = {}, *scr = nullptr, *u = nullptr, *h[3][2] = {}, *c[3] = {};
   float *st_past = nullptr, *st_tgt = nullptr, *st_out = nullptr;   // staging of the host-buffer entry point
   int cur[3] = {0, 0, 0};
+  struct CrnnTrain *train = nullptr;   // cm_convrnn_train_host.inc
   std::vector<void *> allocs;
 };
+void crnn_free_train(CrnnTrain *t);
 
 namespace {
 
@@ -71,8 +73,8 @@ void crnn_build(cm_convrnn *m) {
 }
 
 // Conv2d weight [N][Cin][3][3] -> rows row(n) of dst [.][9 * Cpad], k = (ky * 3 + kx) * Cpad + c (channels Cin .. Cpad - 1 stay 0)
-template <class F>
-void crnn_pack3(const float *w, int N, int Cin, int Cpad, F row, float *dst) {
+template <class T, class F>
+void crnn_pack3(const T *w, int N, int Cin, int Cpad, F row, T *dst) {
   for (int n = 0; n < N; ++n)
     for (int c = 0; c < Cin; ++c)
       for (int t = 0; t < 9; ++t) dst[(size_t)row(n) * 9 * Cpad + (size_t)t * Cpad + c] = w[((size_t)n * Cin + c) * 9 + t];
@@ -80,8 +82,9 @@ void crnn_pack3(const float *w, int N, int Cin, int Cpad, F row, float *dst) {
 
 // ConvTranspose2d weight [Cin][N][4][4] -> [4 parity classes (py, px)][N][4 * Cin], k = (ty * 2 + tx) * Cin + c: output
 // (2 qy + py, 2 qx + px) reads input (qy + py - ty, qx + px - tx) through weight tap (1 - py + 2 ty, 1 - px + 2 tx)
-std::vector<float> crnn_pack_t4(const float *w, int Cin, int N) {
-  std::vector<float> out((size_t)16 * N * Cin);
+template <class T>
+std::vector<T> crnn_pack_t4(const T *w, int Cin, int N) {
+  std::vector<T> out((size_t)16 * N * Cin);
   for (int cls = 0; cls < 4; ++cls)
     for (int n = 0; n < N; ++n)
       for (int tap = 0; tap < 4; ++tap)
@@ -94,28 +97,35 @@ std::vector<float> crnn_pack_t4(const float *w, int Cin, int N) {
 
 // Packed weights of layer i: `w0` and, for a GRU cell, `w1` (the candidate conv).  GRU gates: rows [0, hid) reset_gate,
 // [hid, 2 hid) update_gate.  LSTM: row 4 ch + gate of the packed matrix is row gate * hid + ch of conv.weight (i, f, o, g).
-void crnn_pack_layer(const cm_convrnn *m, int i, std::vector<float> *w0, std::vector<float> *w1) {
+// T = float packs values (src(j): tensor p0 + j of the layer); T = unsigned packs 1-based indices into the flat master
+// weights, 0 where the packed layout holds a padding zero (cm_convrnn_train_host.inc).
+template <class T, class S>
+void crnn_pack_layer_t(const cm_convrnn *m, int i, S src, std::vector<T> *w0, std::vector<T> *w1) {
   const CrnnLayer &l = m->L[i];
-  const Param *p = &m->params[l.p0];
   w1->clear();
-  if (l.kind == CRNN_UP) { *w0 = crnn_pack_t4(p->host.data(), l.cin, l.cout); return; }
+  if (l.kind == CRNN_UP) { *w0 = crnn_pack_t4<T>(src(0), l.cin, l.cout); return; }
   if (l.kind != CRNN_CELL) {
     const int cpad = (l.cin + 7) / 8 * 8;
-    w0->assign((size_t)l.cout * 9 * cpad, 0.f);
-    crnn_pack3(p->host.data(), l.cout, l.cin, cpad, [](int n) { return n; }, w0->data());
+    w0->assign((size_t)l.cout * 9 * cpad, T(0));
+    crnn_pack3(src(0), l.cout, l.cin, cpad, [](int n) { return n; }, w0->data());
     return;
   }
   const int hid = l.cout, cin = l.cin + hid;
   if (m->cfg.cell == CM_CELL_GRU) {
-    w0->assign((size_t)2 * hid * 9 * cin, 0.f);
-    crnn_pack3(p[0].host.data(), hid, cin, cin, [](int n) { return n; }, w0->data());
-    crnn_pack3(p[1].host.data(), hid, cin, cin, [hid](int n) { return hid + n; }, w0->data());
-    w1->assign((size_t)hid * 9 * cin, 0.f);
-    crnn_pack3(p[2].host.data(), hid, cin, cin, [](int n) { return n; }, w1->data());
+    w0->assign((size_t)2 * hid * 9 * cin, T(0));
+    crnn_pack3(src(0), hid, cin, cin, [](int n) { return n; }, w0->data());
+    crnn_pack3(src(1), hid, cin, cin, [hid](int n) { return hid + n; }, w0->data());
+    w1->assign((size_t)hid * 9 * cin, T(0));
+    crnn_pack3(src(2), hid, cin, cin, [](int n) { return n; }, w1->data());
   } else {
-    w0->assign((size_t)4 * hid * 9 * cin, 0.f);
-    crnn_pack3(p[0].host.data(), 4 * hid, cin, cin, [hid](int n) { return 4 * (n % hid) + n / hid; }, w0->data());
+    w0->assign((size_t)4 * hid * 9 * cin, T(0));
+    crnn_pack3(src(0), 4 * hid, cin, cin, [hid](int n) { return 4 * (n % hid) + n / hid; }, w0->data());
   }
+}
+
+void crnn_pack_layer(const cm_convrnn *m, int i, std::vector<float> *w0, std::vector<float> *w1) {
+  const Param *p = &m->params[m->L[i].p0];
+  crnn_pack_layer_t<float>(m, i, [p](int j) { return p[j].host.data(); }, w0, w1);
 }
 
 int crnn_alloc(cm_convrnn *m, float **p, size_t n) {
@@ -269,6 +279,7 @@ int cm_convrnn_destroy(cm_convrnn *m) {
     for (void *p : m->allocs) hipFree(p);
     if (m->stream) hipStreamDestroy(m->stream);
   }
+  crnn_free_train(m->train);
   delete m;
   return 0;
 }
@@ -421,3 +432,5 @@ int cm_convrnn_cost(const cm_convrnn *m, int32_t B, double *flops, double *bytes
 }
 
 }  // extern "C"
+
+#include "cm_convrnn_train_host.inc"

@@ -39,6 +39,96 @@ void refused(F &&edit, const char *what) {
 
 float wval(int tensor, size_t i) { return (float)((tensor * 7919 + (int)(i % 100003)) % 2003) - 1001.f; }
 
+// The backward weight layouts (cm_convrnn_train_host.inc) against a direct index computation on the state_dict tensors, as
+// values and as the 1-based index tables the device re-packs and reduces through.
+void test_train_packs(const cm_convrnn *m, int cell) {
+  std::vector<size_t> off;
+  size_t total = 0;
+  for (const Param &p : m->params) { off.push_back(total); total += (size_t)p.numel(); }
+  std::vector<unsigned> ids(total);
+  for (size_t k = 0; k < total; ++k) ids[k] = (unsigned)(k + 1);
+  const bool gru = cell == CM_CELL_GRU;
+  std::vector<float> fv[2], bv[2];
+  std::vector<unsigned> fi[2], bi[2];
+  for (int i = 0; i < 13; ++i) {
+    const CrnnLayer &l = m->L[i];
+    const Param *pp = &m->params[l.p0];
+    const size_t *po = &off[l.p0];
+    crnn_pack_train_t<float>(m, i, [&](int j) { return pp[j].host.data(); }, fv, bv);
+    crnn_pack_train_t<unsigned>(m, i, [&](int j) { return ids.data() + po[j]; }, fi, bi);
+    // weight of conv j: output channel n (in the packed row order), input channel c, tap (ky, kx): tensor and flat element
+    auto elem = [&](int j, int n, int c, int ky, int kx, int *tensor, size_t *e) {
+      if (l.kind == CRNN_UP) { *tensor = 0; *e = (((size_t)c * l.cout + n) * 4 + ky) * 4 + kx; return; }
+      const int cin = l.kind == CRNN_CELL ? l.cin + l.cout : l.cin;
+      int t = 0, row = n;
+      if (l.kind == CRNN_CELL && gru) { t = j ? 2 : n / l.cout; row = j ? n : n % l.cout; }
+      if (l.kind == CRNN_CELL && !gru) row = (n % 4) * l.cout + n / 4;
+      *tensor = t; *e = (((size_t)row * cin + c) * 3 + ky) * 3 + kx;
+    };
+    size_t seen = 0;
+    for (int j = 0; j < 2; ++j) {
+      if (bv[j].empty()) continue;
+      EXPECT(bv[j].size() == bi[j].size() && fv[j].size() == fi[j].size());
+      const bool cellk = l.kind == CRNN_CELL;
+      const int N = cellk ? (j ? 1 : gru ? 2 : 4) * l.cout : l.cout, Nr = (N + 7) / 8 * 8;
+      const int cin = cellk ? l.cin + l.cout : l.cin, cpad = (cin + 7) / 8 * 8;
+      std::vector<char> hit(bv[j].size(), 0);
+      auto check = [&](size_t at, int n, int c, int ky, int kx) {
+        int t; size_t e;
+        elem(j, n, c, ky, kx, &t, &e);
+        if (at >= bv[j].size() || hit[at] || bv[j][at] != pp[t].host[e] || bi[j][at] != (unsigned)(po[t] + e + 1)) {
+          fprintf(stderr, "backward pack differs in layer %d conv %d (n %d c %d tap %d %d)\n", i, j, n, c, ky, kx); ++failures; return false;
+        }
+        hit[at] = 1; ++seen;
+        return true;
+      };
+      bool ok = true;
+      if (l.kind == CRNN_UP) {          // [c][(ky * 4 + kx) * N + n]: dy(2 iy - 1 + ky, 2 ix - 1 + kx) meets x(iy, ix) through w[c][n][ky][kx]
+        EXPECT(bv[j].size() == (size_t)cin * 16 * N);
+        for (int c = 0; c < cin && ok; ++c)
+          for (int ky = 0; ky < 4; ++ky)
+            for (int kx = 0; kx < 4; ++kx)
+              for (int n = 0; n < N && ok; ++n) ok = check(((size_t)c * 16 + ky * 4 + kx) * N + n, n, c, ky, kx);
+      } else if (l.kind == CRNN_DOWN) { // input (2 qy + py, ...) = 2 oy + ky - 1 with oy = qy + py - ty: ky = 1 - py + 2 ty
+        EXPECT(bv[j].size() == (size_t)9 * cin * N);
+        size_t base = 0;
+        for (int cls = 0; cls < 4; ++cls) {
+          const int py = cls >> 1, px = cls & 1, nt = (1 + py) * (1 + px);
+          for (int c = 0; c < cin && ok; ++c)
+            for (int ty = 0; ty <= py; ++ty)
+              for (int tx = 0; tx <= px; ++tx)
+                for (int n = 0; n < N && ok; ++n) {
+                  const int ky = 1 - py + 2 * ty, kx = 1 - px + 2 * tx;
+                  EXPECT(2 * (py - ty) + ky - 1 == py && 2 * (px - tx) + kx - 1 == px);   // the tap does reach this parity
+                  ok = check(base + ((size_t)c * nt + ty * (1 + px) + tx) * N + n, n, c, ky, kx);
+                }
+          base += (size_t)nt * cin * N;
+        }
+      } else {                          // [c][(ty * 3 + tx) * Nr + n]: dy(q + t - 1) met x(q) through tap (2 - ty, 2 - tx)
+        EXPECT(bv[j].size() == (size_t)cpad * 9 * Nr);
+        for (int c = 0; c < cin && ok; ++c)
+          for (int ty = 0; ty < 3; ++ty)
+            for (int tx = 0; tx < 3; ++tx)
+              for (int n = 0; n < N && ok; ++n) ok = check(((size_t)c * 9 + ty * 3 + tx) * Nr + n, n, c, 2 - ty, 2 - tx);
+      }
+      if (!ok) return;
+      for (size_t k = 0; k < hit.size(); ++k)
+        if (!hit[k] && (bv[j][k] != 0.f || bi[j][k] != 0)) { fprintf(stderr, "padding of backward pack %d/%d is not zero\n", i, j); ++failures; return; }
+      // the forward index table names the element the forward value came from
+      for (size_t k = 0; k < fv[j].size(); ++k) {
+        const unsigned id = fi[j][k];
+        bool same = id ? false : fv[j][k] == 0.f;
+        for (int t = 0; id && t < 3 && l.p0 + t < (int)m->params.size(); ++t)
+          if (id > po[t] && id <= po[t] + pp[t].host.size()) same = pp[t].host[id - 1 - po[t]] == fv[j][k];
+        if (!same) { fprintf(stderr, "forward index table differs in layer %d conv %d\n", i, j); ++failures; return; }
+      }
+    }
+    size_t numel = 0;
+    for (int t = 0; t < (l.kind == CRNN_CELL && gru ? 3 : 1); ++t) numel += pp[t].host.size();
+    EXPECT(seen == numel);   // every weight exactly once
+  }
+}
+
 void test_handle(int cell) {
   cm_convrnn_config c = base_cfg(cell);
   cm_convrnn *m = nullptr;
@@ -112,6 +202,12 @@ void test_handle(int cell) {
           for (int ch = 0; ch < cin; ++ch)
             if (w1[(size_t)row * 9 * cin + (size_t)t * cin + ch] != p[2].host[((size_t)row * cin + ch) * 9 + t]) { fprintf(stderr, "candidate pack differs in layer %d\n", i); ++failures; return; }
   }
+  test_train_packs(m, cell);
+  EXPECT(cm_convrnn_train_init(m, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f) != 0 && strstr(cm_last_error(), "host-only"));
+  double terms[4];
+  EXPECT(cm_convrnn_loss(m, &one, &one, 0, 1e-6, terms, 1, nullptr) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_train_step(m, &one, &one, 0, 1e-6, 1.0, terms, 1, 1, nullptr) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_train_sync(m) != 0 && cm_convrnn_train_get_grad(m, "x", &one, 1) != 0);
   EXPECT(cm_convrnn_destroy(m) == 0);
 }
 

@@ -508,6 +508,9 @@ struct CrnnConvArgs {
   float *u;                       // GRU_GATES: writes u [..][N/2]; GRU_CAND: reads it
   const float *hprev;             // GRU_GATES / GRU_CAND: h_prev [B][Ho][Wo][hid]
   float *c;                       // LSTM: the cell state [B][Ho][Wo][N/4], updated in place
+  // Training tape (cm_convrnn_train.hip), all null in inference.  cn: LSTM, c' goes here instead of over `c`.
+  // t0: GRU_GATES r; GRU_CAND the candidate; LSTM the activated gates [..][N] (column 4 ch + gate).  t1: LSTM tanh(c').
+  float *cn, *t0, *t1;
   float *out; int Ft, t;          // LAST: result [B][N][Ho][Wo][Ft] (reference layout), frame t
   float *win; long long win_bs;   // LAST: or null; the window frame [Ho][Wo][8] this step frees (exp on channels 0 and 3), sample stride
   int exp_out;                    // LAST: exp on channels 0 and 3 of `out` as well
@@ -517,6 +520,66 @@ hipError_t launch_crnn_conv(const CrnnConvArgs &a, hipStream_t st);
 hipError_t launch_crnn_pack_frames(const float *src, float *win, int B, int H, int W, int L, int nslots, int slot0, hipStream_t st);
 // State [B][h][w][C] (channels-last) into [B][C][h][w].
 hipError_t launch_crnn_state_nchw(const float *src, float *dst, int B, int C, int h, int w, hipStream_t st);
+
+// ConvRNN training (cm_convrnn_train.hip): data gradients and weight gradients as gather-form GEMMs of the forward's tile
+// family, the gate backward, the loss and AMSGrad.  Determinism as in the forward: one writer per element, fixed order.
+// Gather geometries of a source S [B][Hs][Ws][.] seen from row pixel (qy, qx):
+//   S1  3 x 3 taps, S(qy + ty - 1, qx + tx - 1)               G4  4 x 4 taps, S(2 qy - 1 + ty, 2 qx - 1 + tx)
+//   S2  3 x 3 taps, S(2 qy + ty - 1, 2 qx + tx - 1)
+//   P3  four parity classes (py, px) of (1 + py)(1 + px) taps: row (qy, qx) is output pixel (2 qy + py, 2 qx + px) and reads
+//       S(qy + py - ty, qx + px - tx): the data gradient of the 3 x 3 stride-2 conv (data gradient only)
+enum { CRNN_BG_S1 = 0, CRNN_BG_S2 = 1, CRNN_BG_G4 = 2, CRNN_BG_P3 = 3 };
+// Data gradient: D[m][c] = sum_k gather(dy)[m][k] Wd[c][k], k = tap * Cs + n, for c in [0, C0 + C1): columns [0, C0) belong to
+// destination 0 (the layer's input x), [C0, C0 + C1) to destination 1 (the cell's h_prev or r * h_prev).
+struct CrnnDgradArgs {
+  int geo;
+  const float *dy; int Cs, Hs, Ws;   // gradient of the conv's output [B][Hs][Ws][Cs], Cs a multiple of 8
+  const float *Wd;                   // [C0 + C1][taps * Cs]; P3: the four classes one after the other (1, 2, 2, 4 taps)
+  int B, Hd, Wd_, C0, C1;            // destination grid and channel split
+  float *d0; int acc0;               // [B][Hd][Wd_][C0] or null (columns skipped); acc0: += instead of =
+  const float *mask0;                // or null; else the saved LeakyReLU output of d0's tensor: the sum is scaled by its slope
+  float *d1; int acc1;               // [B][Hd][Wd_][C1]
+  const float *gr, *gh; float *gdr;  // GRU candidate conv: d1 += v r, gdr [..][2 C1] column ch = v h_prev r (1 - r)
+  const float *fb_exp; long long fb_bs; int fb_C;   // feedback into d yhat (d0 [B][Hd][Wd_][8], += on columns < fb_C): the window
+                                     // frame fed back [Hd][Wd_][8], sample stride fb_bs; columns 0 and 3 are scaled by it
+};
+hipError_t launch_crnn_dgrad(const CrnnDgradArgs &a, hipStream_t st);
+// Weight gradient partials: part[z][n][k] += sum over rows m of split z of R[m][n] gather(x0 || x1)[m][k], k = tap * (C0 + C1) + c
+// (the packed forward layout of an S1 / S2 conv; for the transposed conv R is its input and the gathered source its output
+// gradient, G4, which gives [cin][16 taps * N]).  Rows are split in `nsplit` ranges of equal length (a multiple of 32).
+struct CrnnWgradArgs {
+  int geo;
+  const float *R; int Nr;            // row matrix [B][Hm][Wm][Nr], Nr a multiple of 8
+  const float *x0, *x1; long long bs0, bs1; int C0, C1, Hs, Ws;
+  int B, Hm, Wm, nsplit;
+  float *part;                       // [nsplit][Nr][taps * (C0 + C1)]
+};
+hipError_t launch_crnn_wgrad(const CrnnWgradArgs &a, hipStream_t st);
+// grad[idx[e] - 1] = sum_z part[z * zstride + e], z ascending, for every e < n with idx[e] != 0
+hipError_t launch_crnn_wgrad_reduce(const float *part, int nsplit, long long zstride, long long n, const unsigned *idx, float *grad,
+                                    hipStream_t st);
+// dst[e] = idx[e] ? master[idx[e] - 1] : 0: every packed weight layout from the master weights
+hipError_t launch_crnn_gather(const float *master, const unsigned *idx, float *dst, long long n, hipStream_t st);
+// GRU gate backward on n = B h w hid elements: from dh' (dcur), u, cand, h_prev: dprev = dcur u; dcand_pre = dcur (1 - u)
+// (1 - cand^2); dru [..][2 hid] column hid + ch = dcur (h_prev - cand) u (1 - u)
+hipError_t launch_crnn_gru_bwd(const float *dcur, const float *u, const float *cand, const float *hprev, float *dprev,
+                               float *dcand, float *dru, long long n, int hid, hipStream_t st);
+// LSTM gate backward: gates [..][4 hid] (column 4 ch + gate: i, f, o, g), c_prev, tanh(c'); dc is updated in place to the
+// gradient of c_prev; dpre [..][4 hid] in the gates' layout; dprev = 0
+hipError_t launch_crnn_lstm_bwd(const float *dcur, const float *gates, const float *cprev, const float *tc, float *dc,
+                                float *dprev, float *dpre, long long n, int hid, hipStream_t st);
+hipError_t launch_crnn_add(float *dst, const float *src, long long n, hipStream_t st);
+// The five sums of utils/loss.py:15-52 over yhat, y [B][4][HW][F] in float64 (fixed-order partials, then one finalise):
+// sums[0..4] = Poisson-KL, masked MSE, occupied count, empty penalty, empty count; terms[0..3] = rloss, vloss,
+// loss_considering_density, loss_not_considering_density.  part: ceil(B HW F / 256) * 5 doubles.
+hipError_t launch_crnn_loss(const float *yhat, const float *y, int B, int HW, int F, double eps, double *part, double *sums,
+                            double *terms, hipStream_t st);
+// d (rloss + alpha vloss) / d yhat into dY [F][B][HW][8] (channels 4-7 zero), from the finalised sums
+hipError_t launch_crnn_loss_grad(const float *yhat, const float *y, int B, int HW, int F, double eps, double alpha,
+                                 const double *sums, float *dY, hipStream_t st);
+// torch.optim.Adam(amsgrad=True) with coupled L2: launch_adam plus vmax = max(vmax, v), sqrt(vmax) in the denominator
+hipError_t launch_amsgrad(float *p, const float *g, float *m, float *v, float *vmax, long long n, float lr, float b1, float b2,
+                          float eps, float wd, int step, hipStream_t st);
 
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.

@@ -156,6 +156,18 @@ SIGNATURES = {
     "cm_convrnn_forecast_host": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "cm_convrnn_debug_state": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "cm_convrnn_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cm_convrnn_train_init": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "cm_convrnn_loss": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.POINTER(C.c_double), C.c_int32, _P]),
+    "cm_convrnn_train_step": (C.c_int, [_P, _P, _P, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int32,
+                                        C.c_int32, _P]),
+    "cm_convrnn_train_apply": (C.c_int, [_P, _P]),
+    "cm_convrnn_train_set_lr": (C.c_int, [_P, C.c_float]),
+    "cm_convrnn_train_get_forecast": (C.c_int, [_P, _P, C.c_int64]),
+    "cm_convrnn_train_get_grad": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "cm_convrnn_train_get_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
+    "cm_convrnn_train_set_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
+    "cm_convrnn_train_opt_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
+    "cm_convrnn_train_sync": (C.c_int, [_P]),
 }
 
 

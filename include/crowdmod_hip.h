@@ -433,6 +433,37 @@ int cm_convrnn_debug_state(cm_convrnn *m, int32_t level, int32_t which, float *h
 /* Algorithmic FLOPs and bytes of one forecast at batch B. */
 int cm_convrnn_cost(const cm_convrnn *m, int32_t B, double *flops, double *bytes);
 
+/* ---- ConvRNN training (convRNN.py:98-171): evaluate_loss (utils/loss.py:15-52), backpropagation through all future_len
+ * steps, torch.optim.Adam(amsgrad=True) with coupled L2.  Exact fp32 products, deterministic (fixed summation order, no
+ * atomics; results do not depend on max_batch).  Every entry point below refuses a host-only handle, and the ones that take
+ * a batch refuse B outside [1, max_batch]; cm_last_error names the reason. */
+/* Master weights, flat gradient, exp_avg, exp_avg_sq, max_exp_avg_sq and the activation tape for max_batch, after
+ * cm_convrnn_finalize.  On an allocation failure cm_last_error reports the bytes requested so far. */
+int cm_convrnn_train_init(cm_convrnn *m, float lr, float beta1, float beta2, float eps, float weight_decay);
+/* Forward and loss only (the validation half): h_terms = rloss, vloss, loss_considering_density,
+ * loss_not_considering_density.  d_past [B,4,H,W,P], d_target [B,4,H,W,F] device buffers; loss_eps = MACROPROPS.EPS. */
+int cm_convrnn_loss(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, double loss_eps,
+                    double h_terms[4], int32_t B, void *stream);
+/* One training step on rloss + alpha * vloss: forward, loss, every gradient and, with apply_update != 0, the AMSGrad
+ * update and the re-pack of the weights.  Nothing synchronises or allocates until the read-back of h_terms (may be NULL:
+ * then the call only enqueues).  Without teacher forcing the fed-back frames carry gradient, as in the reference. */
+int cm_convrnn_train_step(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, double loss_eps,
+                          double alpha, double h_terms[4], int32_t B, int32_t apply_update, void *stream);
+/* The AMSGrad update from the gradients the last step left (advances the optimizer step). */
+int cm_convrnn_train_apply(cm_convrnn *m, void *stream);
+int cm_convrnn_train_set_lr(cm_convrnn *m, float lr);
+/* The raw frames [B,4,H,W,F] of the last training or loss forward (host buffer). */
+int cm_convrnn_train_get_forecast(cm_convrnn *m, float *h_out, int64_t numel);
+/* Gradient of a state_dict tensor, in its reference layout (host buffer). */
+int cm_convrnn_train_get_grad(cm_convrnn *m, const char *name, float *h_data, int64_t numel);
+/* which: 0 exp_avg, 1 exp_avg_sq, 2 max_exp_avg_sq. */
+int cm_convrnn_train_get_opt_state(cm_convrnn *m, const char *name, int32_t which, float *h_data, int64_t numel);
+int cm_convrnn_train_set_opt_state(cm_convrnn *m, const char *name, int32_t which, const float *h_data, int64_t numel);
+/* Reads the optimizer's step count into *step, after setting it from *step when set != 0. */
+int cm_convrnn_train_opt_step(cm_convrnn *m, int32_t *step, int32_t set);
+/* Copies the master weights back to the state_dict (cm_convrnn_get_param) and re-packs every weight layout. */
+int cm_convrnn_train_sync(cm_convrnn *m);
+
 #ifdef __cplusplus
 }
 #endif

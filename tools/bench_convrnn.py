@@ -25,11 +25,12 @@ sys.path.insert(0, ROOT)
 FP32_MFMA_PEAK_TFLOPS = 157.3
 
 
-def torch_forecaster(params, cfg, dev):
-    """The forecaster written with torch.nn.functional on `dev`: returns f(past, target, teacher_forcing) -> [B,4,H,W,Ft]."""
+def torch_forecaster(params, cfg, dev, w=None):
+    """The forecaster written with torch.nn.functional on `dev`: returns f(past, target, teacher_forcing) -> [B,4,H,W,Ft].
+    `w`: the weights as tensors already on `dev` (tools/bench_convrnn_train.py passes its nn.Parameters)."""
     import torch
     import torch.nn.functional as F
-    w = {k: torch.from_numpy(v).to(dev) for k, v in params.items()}
+    w = w if w is not None else {k: torch.from_numpy(v).to(dev) for k, v in params.items()}
     enc, forc = "encoder.encoder_cell_list.", "forecaster_cell_list."
 
     def cell(prefix, x, state):

@@ -60,8 +60,8 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if args.arch == "ConvRNN":
-        raise SystemExit("ConvRNN: training (Poisson-KL + masked MSE loss, AMSGrad) is not implemented on this path; "
-                         "the forecaster runs natively for inference (generate_samples.py, generate_metrics.py)")
+        raise SystemExit("ConvRNN: training through train.py is not implemented on this path; use train_convrnn.py "
+                         "(Poisson-KL + masked MSE loss, AMSGrad, backpropagation through the forecast steps)")
     if args.arch not in ("DDPM-UNet", "FM-UNet", "FM-DiT"):   # FM-DiT: FM_model.train raises NotImplementedError
         raise SystemExit(f"{args.arch}: only the UNet-backbone generators (DDPM-UNet, FM-UNet) are implemented on this path")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
