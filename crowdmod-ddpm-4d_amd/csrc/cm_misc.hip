@@ -632,10 +632,14 @@ __global__ __launch_bounds__(256) void time_mlp_kernel(const float *__restrict__
     h2[o] = silu_f(acc);
   }
   __syncthreads();
+  // The row is added to a conv output of the same channel, and a checkpoint's dense_1 bias can be orders of magnitude above the
+  // products: the dot product is summed on its own and the bias added last, one rounding at the bias's magnitude (as the reference's
+  // F.linear does).  Started from the bias, each of the tx additions rounds there: 3e-3 on a bias of 1e4, six times the final rounding,
+  // which the GroupNorm behind the conv turns into 1e-2 of its block's gradients (tests/test_gpu_gn_stats.py, the offset model).
   for (int o = tid; o < nproj; o += 256) {
-    float acc = bd[o];
+    float acc = 0.f;
     for (int i = 0; i < tx; ++i) acc = fmaf(Wd[(size_t)o * tx + i], h2[i], acc);
-    out[(size_t)row * nproj + o] = acc;
+    out[(size_t)row * nproj + o] = acc + bd[o];
   }
 }
 

@@ -2560,6 +2560,13 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
     snprintf(buf, (size_t)capacity, "other %s %s", op.label.c_str(), pl.ops[index].attn_sample ? "attn_sample_kernel" : "attn_head_kernel");
     return 0;
   }
+  if (op.kind == OP_GNFIN && m->plan.err.empty() && m->plan.ops.size() == m->ops.size() && m->plan.ops[index].fin != FIN_NONE) {
+    // ... "other <label> fin <who> <ns0> <ns1>": who merged this GroupNorm's slots in the last forward, and how many slots per source
+    static const char *const who[] = {"none", "qr", "combine", "wino", "alone"};
+    const OpPlan &p = m->plan.ops[index];
+    snprintf(buf, (size_t)capacity, "other %s fin %s %d %d", op.label.c_str(), who[p.fin], p.ns0, p.ns1);
+    return 0;
+  }
   if (op.kind != OP_CONV) { snprintf(buf, (size_t)capacity, "other %s", op.label.c_str()); return 0; }
   const cm::ConvArgs &a = op.ca;
   const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);

@@ -319,7 +319,10 @@ int cm_debug_conv_flags(int32_t flags);
 int cm_debug_conv_count(const cm_model *m, int32_t *count);
 /* One line of text per op of the plan.  A convolution: "conv <label> ..." (fields: cm_model.cpp).  A fused attention block:
  * "other <label> <kernel>", <kernel> = attn_sample_kernel or attn_head_kernel -- what this handle's inference plan launches for
- * the block at the batch of its last forward (planned again on each call, not a record of a launch).  Anything else: "other <label>". */
+ * the block at the batch of its last forward (planned again on each call, not a record of a launch).  A GroupNorm finalisation, once a
+ * forward has run: "other <label> fin <who> <ns0> <ns1>", <who> = qr | combine | wino | alone -- what merged its slot statistics in the
+ * last forward (the whole-sample quarter-resolution conv, the second pass of a K-split conv / attention block, the Winograd
+ * consumer's prologue, gn_finalize_kernel) and the slots per sample of its one or two sources.  Anything else: "other <label>". */
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity);
 /* Test hook: conv op `index` alone on caller data (no GroupNorm / SiLU / time row / residual / fused skip; bias stays).
  * h_in0 / h_in1: host channels-last [B][Zs][Ys][Xs][C0 / C1]; h_out: host [B][Zo][Yo][Xo][C of the output tensor -- the last
