@@ -9,7 +9,11 @@
 // h_p, w_p); its unpatchify is the scatter with pt = 1), one self-attention over all T_p * N_s tokens per block instead
 // of the spatial / temporal pair, 6 modulation chunks per block instead of 9, and 10 tensors per block instead of 14.
 
+struct cm_dit_train;                       // cm_dit_train_host.inc: the training state of a DiT2D handle (cm_dit_train_init)
+void cm_free_dit_train(cm_dit_train *t);   // (host-side struct only; its device buffers live in cm_model::allocs)
 struct cm_dit_plan {
+  ~cm_dit_plan() { cm_free_dit_train(train); }
+  cm_dit_train *train = nullptr;
   cm_dit_config cfg{};
   bool full = false;           // DiT2D: one full self-attention per block (cm_model_create_dit2d)
   int Ns = 0, Tp = 0, qs = 0, tok = 0, Kp = 0, Nout = 0, ldmod = 0;
@@ -18,6 +22,7 @@ struct cm_dit_plan {
   float *X = nullptr, *QKV = nullptr, *AO = nullptr, *Hm = nullptr;   // [max_batch * tok][D | 3D | D | mlp_hidden]
   float *modtab = nullptr;     // [1000][depth * 9D + 2D]: per block shift1 scale1 gate1 shift2 ... gate3, then the final layer's
                                // (DiT2D: depth * 6D + 2D, shift1 scale1 gate1 shift2 scale2 gate2)
+  float *tab_h1 = nullptr, *tab_e = nullptr, *tab_cs = nullptr;   // scratch of dit_build_tables
   std::vector<const float *> w;  // device copies of the state_dict tensors, in state_dict order
 };
 
@@ -107,16 +112,19 @@ cm::DitGemmArgs dit_gemm_args(int pro, int epi, long long M, int N, int K) {
 
 // Conditioning tables for all 1000 t (DiT4D_V4.py:363, 134-137, 216): e = time_blocks(t), c = SiLU(time_proj(e)); every
 // adaLN_modulation applies SiLU(c) before its Linear.  The table row t holds each block's 9 chunks and the final layer's 2.
-// DiT2D computes the same chain (DiT2D.py:275, 94-97, 117-119) with 6 chunks per block.
+// DiT2D computes the same chain (DiT2D.py:275, 94-97, 117-119) with 6 chunks per block.  Runs again from cm_dit_train_sync, on
+// the buffers of the first call.
 int dit_build_tables(cm_model *m) {
   cm_dit_plan &d = *m->dit;
   const cm_dit_config &c = d.cfg;
   const int D = c.hidden_size, tx = D * c.time_multiple;
-  float *h1 = nullptr, *e = nullptr, *cs = nullptr;
-  if (dev_alloc(m, (void **)&d.modtab, (size_t)TIME_ROWS * d.ldmod * sizeof(float))) return 1;
-  if (dev_alloc(m, (void **)&h1, (size_t)TIME_ROWS * tx * sizeof(float))) return 1;
-  if (dev_alloc(m, (void **)&e, (size_t)TIME_ROWS * tx * sizeof(float))) return 1;
-  if (dev_alloc(m, (void **)&cs, (size_t)TIME_ROWS * D * sizeof(float))) return 1;
+  if (!d.modtab) {
+    if (dev_alloc(m, (void **)&d.modtab, (size_t)TIME_ROWS * d.ldmod * sizeof(float))) return 1;
+    if (dev_alloc(m, (void **)&d.tab_h1, (size_t)TIME_ROWS * tx * sizeof(float))) return 1;
+    if (dev_alloc(m, (void **)&d.tab_e, (size_t)TIME_ROWS * tx * sizeof(float))) return 1;
+    if (dev_alloc(m, (void **)&d.tab_cs, (size_t)TIME_ROWS * D * sizeof(float))) return 1;
+  }
+  float *h1 = d.tab_h1, *e = d.tab_e, *cs = d.tab_cs;
   hipStream_t st = m->stream;
   cm::DitGemmArgs a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_SILU, TIME_ROWS, tx, D);
   a.A = d.w[2]; a.lda = D; a.W = d.w[3]; a.bias = d.w[4]; a.Y = h1; a.ldy = tx;

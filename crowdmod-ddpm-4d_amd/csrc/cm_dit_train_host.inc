@@ -1,0 +1,457 @@
+// Training step of the DiT2D denoiser (arch "FM-DiT"), included at the end of cm_model.cpp.  Mirrors FM_model._train_step
+// (models/flow_matching/flow_matching.py:104-157) below the host driver: u_pred = DiT2D(x_t, t, past) in train mode,
+// loss = mse(u_pred, u_target), backward, torch.optim.Adam with coupled L2.  Kernels: cm_dit_train.hip, cm_dit.hip.
+//
+// Parameters, gradients and both Adam moments are flat buffers in state_dict order (cm_train_state's layout); the forward reads
+// the master weights in place -- the DiT takes the reference layout, so an update leaves nothing to re-pack.  The eval path keeps
+// its own weight copies and conditioning table (cm_dit_plan::w, modtab), which only cm_dit_train_sync refreshes.
+//
+// Tape, per block (allocated for max_batch by cm_dit_train_init): the residual stream entering the block and between its two
+// halves (X cannot be updated in place), QKV, the attention's log-sum-exp and output, the pre-gate output of out_proj, the fc1
+// pre-activation and the dropped fc2 output.  Recomputed in the backward: LayerNorm statistics with the normalised and the
+// modulated rows, dropped GELU(fc1), every dropout mask, the attention probabilities, the patch matrix.
+// The conditioning chain (time MLP, time_proj, both SiLUs, every adaLN_modulation.1) runs on the batch's B rows from the master
+// weights of the step into mod [B][ldmod]; the forward GEMMs address it through an iota "timestep" buffer.
+
+struct cm_dit_train {
+  size_t nfloats = 0;
+  std::vector<size_t> off;       // per state_dict tensor: offset in the flat buffers
+  float *pbuf = nullptr, *gbuf = nullptr, *mbuf = nullptr, *vbuf = nullptr;
+  float lr = 1e-4f, b1 = 0.5f, b2 = 0.999f, eps = 1e-8f, wd = 0.001f, dropout = 0.1f;
+  int step = 0, last_B = 0;
+  long long sample_base = 0;
+  std::vector<float *> Xs, QKV, AO, Yo, H1, Y2, LSE;   // tape: Xs[2 i] enters block i, Xs[2 i + 1] its MLP half
+  float *Hm = nullptr, *G1 = nullptr, *G2 = nullptr, *GH = nullptr, *G3 = nullptr, *XN = nullptr, *Aln = nullptr, *rs = nullptr;
+  float *dX = nullptr, *delta = nullptr, *Pm = nullptr, *dYf = nullptr, *pred = nullptr;
+  float *mod = nullptr, *dmod = nullptr, *emb = nullptr, *h1 = nullptr, *h1s = nullptr, *e = nullptr, *z = nullptr, *c = nullptr;
+  float *sc = nullptr, *dsc = nullptr, *dc = nullptr, *dz = nullptr, *de = nullptr, *dh1s = nullptr, *dh1 = nullptr;
+  long long *iota = nullptr;
+  float *wpart = nullptr;
+  double *cpart = nullptr;       // float64 partials of the bias column sums
+  float *mse_partial = nullptr, *mse_loss = nullptr;
+};
+
+void cm_free_dit_train(cm_dit_train *t) { delete t; }
+
+namespace {
+
+constexpr int DITT_KCHUNK = 256, DITT_MAX_SPLIT = 32;   // rows of one weight-gradient partial; partials per weight gradient
+
+int ditt_check(const cm_model *m, const char *what, bool need_train) {
+  if (!m) return fail("%s: null model handle", what);
+  if (!m->dit) return fail("%s: a UNet handle trains through cm_train_*; this entry point takes FM-DiT (DiT2D) handles only", what);
+  if (!m->dit->full) return fail("%s: DDPM-DiT (DiT4D_V4) training is not implemented; only FM-DiT (DiT2D) handles train", what);
+  if (m->device < 0) return fail("%s: a host-only handle (device -1) cannot train", what);
+  if (!m->finalized) return fail("%s: cm_model_finalize has not been called", what);
+  if (need_train && !m->dit->train) return fail("%s: cm_dit_train_init has not been called", what);
+  return 0;
+}
+
+int ditt_setup(cm_model *m) {
+  cm_dit_plan &d = *m->dit;
+  cm_dit_train *T = d.train;
+  const cm_dit_config &c = d.cfg;
+  const size_t B = (size_t)c.max_batch, rows = B * d.tok, D = (size_t)c.hidden_size, mlp = (size_t)c.mlp_hidden;
+  const size_t tx = D * c.time_multiple, F = sizeof(float);
+  size_t maxw = 0, maxb = 1;
+  for (const Param &p : m->params) {
+    T->off.push_back(T->nfloats); T->nfloats += (size_t)p.numel(); maxw = std::max(maxw, (size_t)p.numel());
+    if (p.shape.size() == 1) maxb = std::max(maxb, (size_t)p.numel());
+  }
+  for (float **b : {&T->pbuf, &T->gbuf, &T->mbuf, &T->vbuf}) {
+    if (dev_alloc(m, (void **)b, T->nfloats * F)) return 1;
+    CM_HIP(hipMemset(*b, 0, T->nfloats * F));
+  }
+  for (size_t i = 0; i < m->params.size(); ++i)
+    CM_HIP(hipMemcpy(T->pbuf + T->off[i], d.w[i], (size_t)m->params[i].numel() * F, hipMemcpyDeviceToDevice));
+  auto alloc = [&](float **p, size_t n) { return dev_alloc(m, (void **)p, n * F); };
+  T->Xs.assign(2 * c.depth + 1, nullptr);
+  for (float *&x : T->Xs) if (alloc(&x, rows * D)) return 1;
+  for (auto *v : {&T->QKV, &T->AO, &T->Yo, &T->H1, &T->Y2, &T->LSE}) v->assign(c.depth, nullptr);
+  for (int i = 0; i < c.depth; ++i) {
+    if (alloc(&T->QKV[i], rows * 3 * D) || alloc(&T->AO[i], rows * D) || alloc(&T->Yo[i], rows * D) || alloc(&T->H1[i], rows * mlp) ||
+        alloc(&T->Y2[i], rows * D) || alloc(&T->LSE[i], rows * c.num_heads))
+      return 1;
+  }
+  if (alloc(&T->Hm, rows * mlp) || alloc(&T->GH, rows * mlp) || alloc(&T->G1, rows * D) || alloc(&T->G2, rows * D) ||
+      alloc(&T->G3, rows * 3 * D) || alloc(&T->XN, rows * D) || alloc(&T->Aln, rows * D) || alloc(&T->rs, rows) ||
+      alloc(&T->dX, rows * D) || alloc(&T->delta, rows * c.num_heads) || alloc(&T->Pm, rows * d.Kp) ||
+      alloc(&T->dYf, rows * d.Nout) || alloc(&T->pred, B * (size_t)m->per_sample()))
+    return 1;
+  if (alloc(&T->mod, B * d.ldmod) || alloc(&T->dmod, B * d.ldmod) || alloc(&T->emb, B * D) || alloc(&T->h1, B * tx) ||
+      alloc(&T->h1s, B * tx) || alloc(&T->e, B * tx) || alloc(&T->z, B * D) || alloc(&T->c, B * D) || alloc(&T->sc, B * D) ||
+      alloc(&T->dsc, B * D) || alloc(&T->dc, B * D) || alloc(&T->dz, B * D) || alloc(&T->de, B * tx) || alloc(&T->dh1s, B * tx) ||
+      alloc(&T->dh1, B * tx))
+    return 1;
+  if (dev_alloc(m, (void **)&T->cpart, (size_t)cm::DITT_COLSUM_SEGS * maxb * sizeof(double))) return 1;
+  if (alloc(&T->wpart, (size_t)DITT_MAX_SPLIT * maxw) || alloc(&T->mse_partial, 64) || alloc(&T->mse_loss, 1)) return 1;
+  std::vector<long long> io(B);
+  std::iota(io.begin(), io.end(), 0LL);
+  if (dev_alloc(m, (void **)&T->iota, B * sizeof(long long))) return 1;
+  CM_HIP(hipMemcpy(T->iota, io.data(), B * sizeof(long long), hipMemcpyHostToDevice));
+  CM_HIP(hipDeviceSynchronize());
+  return 0;
+}
+
+// the conditioning rows of the batch from the master weights: e = time_blocks(t), c = SiLU(time_proj(e)), SiLU(c), every adaLN Linear
+int ditt_conditioning(cm_model *m, int B, hipStream_t st) {
+  const cm_dit_plan &d = *m->dit;
+  cm_dit_train *T = d.train;
+  const cm_dit_config &c = d.cfg;
+  const int D = c.hidden_size, tx = D * c.time_multiple, nch = d.nchunk(), pb = d.per_block();
+  auto W = [&](int i) { return T->pbuf + T->off[i]; };
+  auto lin = [&](const float *A, int K, int wi, float *Y, int N, int ldy) {
+    cm::DitGemmArgs a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, B, N, K);
+    a.A = A; a.lda = K; a.W = W(wi); a.bias = W(wi + 1); a.Y = Y; a.ldy = ldy;
+    return cm::launch_dit_gemm(a, st);
+  };
+  CM_HIP(cm::launch_ditt_gather_rows(W(2), m->tbuf, T->emb, B, D, st));
+  CM_HIP(lin(T->emb, D, 3, T->h1, tx, tx));
+  CM_HIP(cm::launch_ditt_silu(T->h1, T->h1s, nullptr, (long long)B * tx, st));
+  CM_HIP(lin(T->h1s, tx, 5, T->e, tx, tx));
+  CM_HIP(lin(T->e, tx, 7, T->z, D, D));
+  CM_HIP(cm::launch_ditt_silu(T->z, T->c, nullptr, (long long)B * D, st));
+  CM_HIP(cm::launch_ditt_silu(T->c, T->sc, nullptr, (long long)B * D, st));
+  for (int i = 0; i <= c.depth; ++i) {
+    const bool fin = i == c.depth;
+    const int wi = fin ? DIT_HEAD + pb * c.depth + 2 : DIT_HEAD + pb * i + pb - 2;
+    CM_HIP(lin(T->sc, D, wi, T->mod + (size_t)i * nch * D, fin ? 2 * D : nch * D, d.ldmod));
+  }
+  return 0;
+}
+
+// DiT2D.forward in train mode for the first B samples: x8, tbuf -> eps_cl, with the tape
+int ditt_forward(cm_model *m, int B, uint64_t seed, hipStream_t st) {
+  const cm_dit_plan &d = *m->dit;
+  cm_dit_train *T = d.train;
+  const cm_dit_config &c = d.cfg;
+  const int D = c.hidden_size, D3 = 3 * D, mlp = c.mlp_hidden, nq = d.Tp - d.qs, nch = d.nchunk(), pb = d.per_block();
+  const long long M = (long long)B * d.tok;
+  auto W = [&](int i) { return T->pbuf + T->off[i]; };
+  cm::DitGemmArgs base{};
+  base.tok = d.tok; base.tbuf = T->iota; base.mod = T->mod; base.ldmod = d.ldmod;
+  base.L = m->L(); base.Hh = c.rows; base.Ww = c.cols; base.p = c.patch_size; base.pt = 1;
+  base.Ns = d.Ns; base.wpn = c.cols / c.patch_size; base.Cout = c.out_channels;
+  auto gemm = [&](int pro, int epi, long long rows, int N, int K) {
+    cm::DitGemmArgs a = base;
+    a.pro = pro; a.epi = epi; a.M = rows; a.N = N; a.K = K; a.grp = (int)rows;
+    return a;
+  };
+  cm::DitDrop dr{seed, T->sample_base, T->step, 0, T->dropout};
+  cm::DitGemmArgs a = gemm(cm::DIT_PRO_PATCH, cm::DIT_EPI_PATCH, M, D, d.Kp);
+  a.x8 = m->x8; a.W = W(9); a.bias = W(10); a.Y = T->Xs[0]; a.ldy = D; a.spos = W(0); a.tpos = W(1);
+  CM_HIP(cm::launch_dit_gemm(a, st));
+  for (int i = 0; i < c.depth; ++i) {
+    const int w0 = DIT_HEAD + pb * i, mo = i * nch * D;
+    dr.block = i;
+    float *Xin = T->Xs[2 * i], *Xmid = T->Xs[2 * i + 1], *Xout = T->Xs[2 * i + 2];
+    a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
+    a.A = Xin; a.lda = D; a.W = W(w0); a.bias = W(w0 + 1); a.Y = T->QKV[i]; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
+    CM_HIP(cm::launch_dit_gemm(a, st));
+    cm::DitTrAttnArgs at{T->QKV[i], T->AO[i], T->LSE[i], nullptr, nullptr, nullptr, B, d.tok, D, c.num_heads, dr};
+    CM_HIP(cm::launch_ditt_attn_fwd(at, st));
+    a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, M, D, D);
+    a.A = T->AO[i]; a.lda = D; a.W = W(w0 + 2); a.bias = W(w0 + 3); a.Y = T->Yo[i]; a.ldy = D;
+    CM_HIP(cm::launch_dit_gemm(a, st));
+    CM_HIP(cm::launch_ditt_gate(Xin, Xmid, T->Yo[i], nullptr, T->mod, d.ldmod, mo + 2 * D, M, D, d.tok, cm::DITT_SITE_NONE, dr, st));
+    a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, mlp, D);
+    a.A = Xmid; a.lda = D; a.W = W(w0 + 4); a.bias = W(w0 + 5); a.Y = T->H1[i]; a.ldy = mlp; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
+    CM_HIP(cm::launch_dit_gemm(a, st));
+    CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->Hm, M, mlp, d.tok, dr, 0, st));
+    a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, M, D, mlp);
+    a.A = T->Hm; a.lda = mlp; a.W = W(w0 + 6); a.bias = W(w0 + 7); a.Y = T->Y2[i]; a.ldy = D;
+    CM_HIP(cm::launch_dit_gemm(a, st));
+    CM_HIP(cm::launch_ditt_gate(Xmid, Xout, T->Y2[i], nullptr, T->mod, d.ldmod, mo + 5 * D, M, D, d.tok, cm::DITT_SITE_MLP2, dr, st));
+  }
+  const int wf = DIT_HEAD + pb * c.depth;
+  a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_UNPATCH, M, d.Nout, D);
+  a.M = (long long)B * nq * d.Ns; a.grp = nq * d.Ns; a.grp_stride = d.tok; a.grp_off = d.qs * d.Ns;
+  a.A = T->Xs[2 * c.depth]; a.lda = D; a.W = W(wf); a.bias = W(wf + 1); a.Y = m->eps_cl;
+  a.off_shift = c.depth * nch * D; a.off_scale = c.depth * nch * D + D;
+  CM_HIP(cm::launch_dit_gemm(a, st));
+  return 0;
+}
+
+int ditt_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hipStream_t st) {
+  const cm_dit_plan &d = *m->dit;
+  cm_dit_train *T = d.train;
+  const cm_dit_config &c = d.cfg;
+  const int D = c.hidden_size, D3 = 3 * D, mlp = c.mlp_hidden, nq = d.Tp - d.qs, nch = d.nchunk(), pb = d.per_block();
+  const int tx = D * c.time_multiple;
+  const long long M = (long long)B * d.tok, Mf = (long long)B * nq * d.Ns;
+  auto W = [&](int i) { return T->pbuf + T->off[i]; };
+  auto G = [&](int i) { return T->gbuf + T->off[i]; };
+  // dX [rows][Kin] (+)= dY [rows][Nout] W [Nout][Kin]
+  auto gemm_dx = [&](const float *dY, int ldy, const float *Wm, float *dXo, long long rows, int Kin, int Nout, int accum) {
+    cm::DitTrGemmArgs g{dY, Wm, dXo, (int)rows, Kin, Nout, ldy, Kin, Kin, 0, accum, 1, 0, nullptr};
+    return cm::launch_ditt_gemm(g, st);
+  };
+  // dW [Nout][Kin] = dY^T A over `rows` rows, in fixed row ranges
+  auto gemm_dw = [&](const float *dY, int ldy, const float *A, int lda, float *dW, long long rows, int Nout, int Kin) {
+    cm::DitTrGemmArgs g{dY, A, dW, Nout, Kin, rows, ldy, lda, Kin, 1, 0, 1, 0, nullptr};
+    long long ns = (rows + DITT_KCHUNK - 1) / DITT_KCHUNK;
+    if (ns > 1) {
+      ns = std::min<long long>(ns, DITT_MAX_SPLIT);
+      g.nsplit = (int)ns; g.kchunk = ((rows + ns - 1) / ns + 31) / 32 * 32; g.part = T->wpart;
+    }
+    return cm::launch_ditt_gemm(g, st);
+  };
+  auto colsum = [&](const float *U, int ldu, float *out, long long rows, int N) {
+    return cm::launch_ditt_colsum(U, ldu, out, rows, N, T->cpart, st);
+  };
+  cm::DitTrLnArgs ln{};
+  ln.XN = T->XN; ln.A = T->Aln; ln.rs = T->rs; ln.dX = T->dX; ln.mod = T->mod; ln.ldmod = d.ldmod; ln.D = D; ln.tok = d.tok;
+  cm::DitDrop dr{seed, T->sample_base, T->step, 0, T->dropout};
+  CM_HIP(hipMemsetAsync(T->gbuf, 0, T->nfloats * sizeof(float), st));
+  CM_HIP(hipMemsetAsync(T->dX, 0, (size_t)M * D * sizeof(float), st));
+
+  // loss -> final layer (future rows only, compact)
+  cm::DitTrPatchArgs pa{};
+  pa.x8 = m->x8; pa.Pm = T->Pm; pa.pred = T->pred; pa.target = d_target; pa.dYf = T->dYf; pa.dX0 = T->dX;
+  pa.dspos = G(0); pa.dtpos = G(1);
+  pa.B = B; pa.C = c.out_channels; pa.L = m->L(); pa.Hh = c.rows; pa.Ww = c.cols; pa.p = c.patch_size; pa.Ns = d.Ns;
+  pa.wpn = c.cols / c.patch_size; pa.tok = d.tok; pa.qs = d.qs; pa.Kp = d.Kp; pa.Nout = d.Nout; pa.D = D;
+  CM_HIP(cm::launch_ditt_loss_grad(pa, st));
+  const int wf = DIT_HEAD + pb * c.depth, mof = c.depth * nch * D;
+  ln.X = T->Xs[2 * c.depth]; ln.M = Mf; ln.grp = nq * d.Ns; ln.grp_stride = d.tok; ln.grp_off = d.qs * d.Ns;
+  ln.off_shift = mof; ln.off_scale = mof + D; ln.dA = T->G1;
+  CM_HIP(cm::launch_ditt_ln_fwd(ln, st));
+  CM_HIP(gemm_dw(T->dYf, d.Nout, T->Aln, D, G(wf), Mf, d.Nout, D));
+  CM_HIP(colsum(T->dYf, d.Nout, G(wf + 1), Mf, d.Nout));
+  CM_HIP(gemm_dx(T->dYf, d.Nout, W(wf), T->G1, Mf, D, d.Nout, 0));
+  CM_HIP(cm::launch_ditt_segsum(T->G1, D, nullptr, 0, T->dmod + mof, d.ldmod, B, (long long)nq * d.Ns, D, st));
+  CM_HIP(cm::launch_ditt_segsum(T->G1, D, T->XN, D, T->dmod + mof + D, d.ldmod, B, (long long)nq * d.Ns, D, st));
+  CM_HIP(cm::launch_ditt_ln_bwd(ln, st));
+
+  ln.M = M; ln.grp = (int)M; ln.grp_stride = 0; ln.grp_off = 0;
+  for (int i = c.depth - 1; i >= 0; --i) {
+    const int w0 = DIT_HEAD + pb * i, mo = i * nch * D;
+    dr.block = i;
+    // MLP half: x = x_mid + gate2 * drop2(fc2(drop1(gelu(fc1(modulate(LN(x_mid)))))))
+    CM_HIP(cm::launch_ditt_segsum(T->dX, D, T->Y2[i], D, T->dmod + mo + 5 * D, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_gate(nullptr, nullptr, T->G1, T->dX, T->mod, d.ldmod, mo + 5 * D, M, D, d.tok, cm::DITT_SITE_MLP2, dr, st));
+    CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->Hm, M, mlp, d.tok, dr, 0, st));
+    CM_HIP(gemm_dw(T->G1, D, T->Hm, mlp, G(w0 + 6), M, D, mlp));
+    CM_HIP(colsum(T->G1, D, G(w0 + 7), M, D));
+    CM_HIP(gemm_dx(T->G1, D, W(w0 + 6), T->GH, M, mlp, D, 0));
+    CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->GH, M, mlp, d.tok, dr, 1, st));
+    ln.X = T->Xs[2 * i + 1]; ln.off_shift = mo + 3 * D; ln.off_scale = mo + 4 * D; ln.dA = T->G2;
+    CM_HIP(cm::launch_ditt_ln_fwd(ln, st));
+    CM_HIP(gemm_dw(T->GH, mlp, T->Aln, D, G(w0 + 4), M, mlp, D));
+    CM_HIP(colsum(T->GH, mlp, G(w0 + 5), M, mlp));
+    CM_HIP(gemm_dx(T->GH, mlp, W(w0 + 4), T->G2, M, D, mlp, 0));
+    CM_HIP(cm::launch_ditt_segsum(T->G2, D, nullptr, 0, T->dmod + mo + 3 * D, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_segsum(T->G2, D, T->XN, D, T->dmod + mo + 4 * D, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_ln_bwd(ln, st));
+    // attention half: x_mid = x_in + gate1 * out_proj(attention(in_proj(modulate(LN(x_in)))))
+    CM_HIP(cm::launch_ditt_segsum(T->dX, D, T->Yo[i], D, T->dmod + mo + 2 * D, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_gate(nullptr, nullptr, T->G1, T->dX, T->mod, d.ldmod, mo + 2 * D, M, D, d.tok, cm::DITT_SITE_NONE, dr, st));
+    CM_HIP(gemm_dw(T->G1, D, T->AO[i], D, G(w0 + 2), M, D, D));
+    CM_HIP(colsum(T->G1, D, G(w0 + 3), M, D));
+    CM_HIP(gemm_dx(T->G1, D, W(w0 + 2), T->G2, M, D, D, 0));
+    cm::DitTrAttnArgs at{T->QKV[i], T->AO[i], T->LSE[i], T->G2, T->delta, T->G3, B, d.tok, D, c.num_heads, dr};
+    CM_HIP(cm::launch_ditt_attn_delta(at, st));
+    CM_HIP(cm::launch_ditt_attn_bwd(at, st));
+    ln.X = T->Xs[2 * i]; ln.off_shift = mo; ln.off_scale = mo + D; ln.dA = T->G1;
+    CM_HIP(cm::launch_ditt_ln_fwd(ln, st));
+    CM_HIP(gemm_dw(T->G3, D3, T->Aln, D, G(w0), M, D3, D));
+    CM_HIP(colsum(T->G3, D3, G(w0 + 1), M, D3));
+    CM_HIP(gemm_dx(T->G3, D3, W(w0), T->G1, M, D, D3, 0));
+    CM_HIP(cm::launch_ditt_segsum(T->G1, D, nullptr, 0, T->dmod + mo, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_segsum(T->G1, D, T->XN, D, T->dmod + mo + D, d.ldmod, B, d.tok, D, st));
+    CM_HIP(cm::launch_ditt_ln_bwd(ln, st));
+  }
+  // patch embedding and both position embeddings
+  CM_HIP(cm::launch_ditt_patch_gather(pa, st));
+  CM_HIP(gemm_dw(T->dX, D, T->Pm, d.Kp, G(9), M, D, d.Kp));
+  CM_HIP(colsum(T->dX, D, G(10), M, D));
+  CM_HIP(cm::launch_ditt_pos_grad(pa, st));
+  // conditioning chain: d mod [B][ldmod] through every adaLN Linear, the two SiLUs, time_proj and the time MLP
+  for (int i = 0; i <= c.depth; ++i) {
+    const bool fin = i == c.depth;
+    const int wi = fin ? wf + 2 : DIT_HEAD + pb * i + pb - 2, N = fin ? 2 * D : nch * D;
+    const float *dm = T->dmod + (size_t)i * nch * D;
+    CM_HIP(gemm_dw(dm, d.ldmod, T->sc, D, G(wi), B, N, D));
+    CM_HIP(colsum(dm, d.ldmod, G(wi + 1), B, N));
+    CM_HIP(gemm_dx(dm, d.ldmod, W(wi), T->dsc, B, D, N, i > 0));
+  }
+  CM_HIP(cm::launch_ditt_silu(T->c, T->dc, T->dsc, (long long)B * D, st));
+  CM_HIP(cm::launch_ditt_silu(T->z, T->dz, T->dc, (long long)B * D, st));
+  CM_HIP(gemm_dw(T->dz, D, T->e, tx, G(7), B, D, tx));
+  CM_HIP(colsum(T->dz, D, G(8), B, D));
+  CM_HIP(gemm_dx(T->dz, D, W(7), T->de, B, tx, D, 0));
+  CM_HIP(gemm_dw(T->de, tx, T->h1s, tx, G(5), B, tx, tx));
+  CM_HIP(colsum(T->de, tx, G(6), B, tx));
+  CM_HIP(gemm_dx(T->de, tx, W(5), T->dh1s, B, tx, tx, 0));
+  CM_HIP(cm::launch_ditt_silu(T->h1, T->dh1, T->dh1s, (long long)B * tx, st));
+  CM_HIP(gemm_dw(T->dh1, tx, T->emb, D, G(3), B, tx, D));
+  CM_HIP(colsum(T->dh1, tx, G(4), B, tx));
+  return 0;
+}
+
+// torch.optim.Adam over every tensor but the frozen sinusoid table (index 2 of DiT2D's state_dict: nn.Embedding.from_pretrained)
+int ditt_apply(cm_model *m, hipStream_t st) {
+  cm_dit_train *T = m->dit->train;
+  T->step += 1;
+  const size_t lo = T->off[2], hi = T->off[3];
+  CM_HIP(cm::launch_adam(T->pbuf, T->gbuf, T->mbuf, T->vbuf, (long long)lo, T->lr, T->b1, T->b2, T->eps, T->wd, T->step, st));
+  CM_HIP(cm::launch_adam(T->pbuf + hi, T->gbuf + hi, T->mbuf + hi, T->vbuf + hi, (long long)(T->nfloats - hi), T->lr, T->b1, T->b2,
+                         T->eps, T->wd, T->step, st));
+  return 0;
+}
+
+int ditt_find(cm_model *m, const char *what, const char *name, int64_t numel, size_t *off) {
+  if (!name) return fail("%s: null name", what);
+  auto it = m->pindex.find(name);
+  if (it == m->pindex.end()) return fail("%s: unknown parameter %s", what, name);
+  if (numel != m->params[it->second].numel()) return fail("%s: size mismatch for %s", what, name);
+  *off = m->dit->train->off[it->second];
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cm_dit_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay, float dropout_rate) {
+  if (ditt_check(m, "cm_dit_train_init", false)) return 1;
+  if (!(dropout_rate >= 0.f && dropout_rate < 1.f)) return fail("cm_dit_train_init: dropout rate %g outside [0,1)", dropout_rate);
+  const cm_dit_config &c = m->dit->cfg;
+  if (c.num_heads > 64 || c.depth > 8192 || m->dit->tok > 1024)
+    return fail("cm_dit_train_init: the dropout streams address at most 64 heads, 8192 blocks and 1024 tokens per sample");
+  DevGuard g(m->device);
+  if (!m->dit->train) {
+    m->dit->train = new cm_dit_train();
+    if (ditt_setup(m)) {   // no half-built state stays installed (the device buffers it got are cm_model::allocs')
+      cm_free_dit_train(m->dit->train);
+      m->dit->train = nullptr;
+      return 1;
+    }
+  }
+  cm_dit_train *T = m->dit->train;
+  T->lr = lr; T->b1 = beta1; T->b2 = beta2; T->eps = eps; T->wd = weight_decay; T->dropout = dropout_rate;
+  return 0;
+}
+
+int cm_dit_train_set_lr(cm_model *m, float lr) {
+  if (ditt_check(m, "cm_dit_train_set_lr", true)) return 1;
+  m->dit->train->lr = lr;
+  return 0;
+}
+
+int cm_dit_train_set_sample_base(cm_model *m, int64_t sample_id_base) {
+  if (ditt_check(m, "cm_dit_train_set_sample_base", true)) return 1;
+  if (sample_id_base < 0 || sample_id_base + m->cfg.max_batch > 0xffffffffLL)
+    return fail("cm_dit_train_set_sample_base: sample indices must stay in [0, 2^32)");
+  m->dit->train->sample_base = sample_id_base;
+  return 0;
+}
+
+int cm_dit_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const int64_t *d_t, const float *d_target, uint64_t seed,
+                         float *h_loss, int32_t B, int32_t apply_update, void *stream) {
+  if (ditt_check(m, "cm_dit_train_step_xt", true)) return 1;
+  if (B < 1 || B > m->cfg.max_batch) return fail("cm_dit_train_step_xt: batch %d outside [1, max_batch=%d]", B, m->cfg.max_batch);
+  if (!d_xt || !d_past || !d_t || !d_target || !h_loss) return fail("cm_dit_train_step_xt: null argument");
+  DevGuard g(m->device);
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  cm_dit_train *T = m->dit->train;
+  const cm_unet_config &c = m->cfg;
+  CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
+  CM_HIP(cm::launch_assemble_input(d_past, d_xt, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
+  if (ditt_conditioning(m, B, st) || ditt_forward(m, B, seed, st)) return 1;
+  CM_HIP(cm::launch_extract_output(m->eps_cl, 8, T->pred, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st));
+  CM_HIP(cm::launch_mse_loss(T->pred, d_target, (long long)B * m->per_sample(), T->mse_partial, T->mse_loss, st));
+  T->last_B = B;
+  if (ditt_backward(m, d_target, B, seed, st)) return 1;
+  if (apply_update && ditt_apply(m, st)) return 1;
+  CM_HIP(hipMemcpyAsync(h_loss, T->mse_loss, sizeof(float), hipMemcpyDeviceToHost, st));
+  CM_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int cm_dit_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel) {
+  if (ditt_check(m, "cm_dit_train_flat_grads", true)) return 1;
+  if (!d_grads || !numel) return fail("cm_dit_train_flat_grads: null argument");
+  *d_grads = m->dit->train->gbuf;
+  *numel = (int64_t)m->dit->train->nfloats;
+  return 0;
+}
+
+int cm_dit_train_apply(cm_model *m, void *stream) {
+  if (ditt_check(m, "cm_dit_train_apply", true)) return 1;
+  DevGuard g(m->device);
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  if (ditt_apply(m, st)) return 1;
+  CM_HIP(hipStreamSynchronize(st));
+  return 0;
+}
+
+int cm_dit_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel) {
+  size_t off = 0;
+  if (ditt_check(m, "cm_dit_train_get_grad", true)) return 1;
+  if (!h_out) return fail("cm_dit_train_get_grad: null argument");
+  if (ditt_find(m, "cm_dit_train_get_grad", name, numel, &off)) return 1;
+  DevGuard g(m->device);
+  CM_HIP(hipMemcpy(h_out, m->dit->train->gbuf + off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// which: 0 exp_avg, 1 exp_avg_sq, 2 the master weights themselves
+int cm_dit_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel) {
+  size_t off = 0;
+  if (ditt_check(m, "cm_dit_train_get_opt_state", true)) return 1;
+  if (!h_out || which < 0 || which > 2) return fail("cm_dit_train_get_opt_state: bad argument");
+  if (ditt_find(m, "cm_dit_train_get_opt_state", name, numel, &off)) return 1;
+  DevGuard g(m->device);
+  cm_dit_train *T = m->dit->train;
+  const float *src = (which == 0 ? T->mbuf : which == 1 ? T->vbuf : T->pbuf) + off;
+  CM_HIP(hipMemcpy(h_out, src, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int cm_dit_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel) {
+  size_t off = 0;
+  if (ditt_check(m, "cm_dit_train_set_opt_state", true)) return 1;
+  if (!h_in || which < 0 || which > 1) return fail("cm_dit_train_set_opt_state: bad argument");
+  if (ditt_find(m, "cm_dit_train_set_opt_state", name, numel, &off)) return 1;
+  DevGuard g(m->device);
+  cm_dit_train *T = m->dit->train;
+  CM_HIP(hipMemcpy((which == 0 ? T->mbuf : T->vbuf) + off, h_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int cm_dit_train_opt_step(cm_model *m, int32_t *step, int32_t set) {
+  if (ditt_check(m, "cm_dit_train_opt_step", true)) return 1;
+  if (!step) return fail("cm_dit_train_opt_step: null argument");
+  if (set) m->dit->train->step = *step; else *step = m->dit->train->step;
+  return 0;
+}
+
+// The master weights into the handle's state_dict and into the eval path's weight copies, and the 1000-row conditioning table
+// rebuilt from them: until this call the eval forward computes what it computed before training.
+int cm_dit_train_sync(cm_model *m) {
+  if (ditt_check(m, "cm_dit_train_sync", true)) return 1;
+  DevGuard g(m->device);
+  cm_dit_plan &d = *m->dit;
+  cm_dit_train *T = d.train;
+  CM_HIP(hipDeviceSynchronize());
+  for (size_t i = 0; i < m->params.size(); ++i) {
+    const size_t bytes = (size_t)m->params[i].numel() * sizeof(float);
+    CM_HIP(hipMemcpy(m->params[i].host.data(), T->pbuf + T->off[i], bytes, hipMemcpyDeviceToHost));
+    CM_HIP(hipMemcpy(const_cast<float *>(d.w[i]), T->pbuf + T->off[i], bytes, hipMemcpyDeviceToDevice));
+  }
+  return dit_build_tables(m);
+}
+
+int cm_dit_train_get_pred(cm_model *m, float *h_out, int64_t numel) {
+  if (ditt_check(m, "cm_dit_train_get_pred", true)) return 1;
+  cm_dit_train *T = m->dit->train;
+  if (!h_out) return fail("cm_dit_train_get_pred: null argument");
+  if (T->last_B < 1) return fail("cm_dit_train_get_pred: no training step has run");
+  if (numel != (int64_t)T->last_B * m->per_sample()) return fail("cm_dit_train_get_pred: %lld elements, the last step predicted %lld", (long long)numel, (long long)T->last_B * m->per_sample());
+  DevGuard g(m->device);
+  CM_HIP(hipMemcpy(h_out, T->pred, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // extern "C"

@@ -494,6 +494,69 @@ hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st);
 // DiT2D: one self-attention over all T_p * N_s tokens of a sample (any count), on the fp32 matrix instruction
 hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st);
 
+// DiT2D training step (cm_dit_train.hip; host plan: cm_dit_train_host.inc).
+// Dropout site of a mask value; with (seed, optimizer step, global sample, block, head, row, column) it addresses one Philox word.
+enum { DITT_SITE_ATTN = 0, DITT_SITE_MLP1 = 1, DITT_SITE_MLP2 = 2, DITT_SITE_NONE = -1 };
+struct DitDrop {
+  unsigned long long seed;
+  long long sample_base;          // global index of the batch's sample 0
+  int step, block;                // optimizer step; DiT block
+  float p;                        // rate; 0: every mask value is exactly 1
+};
+// C[m][n] (+)= sum_k A(m, k) B[k * ldb + n] on v_mfma_f32_32x32x2_f32; A(m, k) = ta ? A[k * lda + m] : A[m * lda + k].
+// nsplit > 1: k is cut into nsplit fixed ranges of kchunk (a multiple of 32) whose partial products go to part[z][M][N] and are
+// summed in ascending z by one more launch.
+struct DitTrGemmArgs {
+  const float *A, *B; float *C;
+  int M, N; long long K;
+  int lda, ldb, ldc, ta, accum;
+  int nsplit; long long kchunk; float *part;
+};
+hipError_t launch_ditt_gemm(const DitTrGemmArgs &a, hipStream_t st);
+// out[seg * ldo + col] = sum over the seg_rows rows of segment seg of U[r][col] * (V ? V[r][col] : 1), float64 accumulation
+hipError_t launch_ditt_segsum(const float *U, int ldu, const float *V, int ldv, float *out, int ldo, int nseg, long long seg_rows,
+                              int N, hipStream_t st);
+// out[col] = sum over all rows of U[r][col]: as one segment up to DITT_COLSUM_ROWS rows, else as at most DITT_COLSUM_SEGS fixed row
+// ranges whose float64 partials (part [DITT_COLSUM_SEGS][N]) are added in ascending order
+constexpr int DITT_COLSUM_ROWS = 256, DITT_COLSUM_SEGS = 64;
+hipError_t launch_ditt_colsum(const float *U, int ldu, float *out, long long rows, int N, double *part, hipStream_t st);
+// LayerNorm (no affine, eps 1e-6) + modulate of logical rows r -> token row (r / grp) * grp_stride + grp_off + r % grp, compact outputs
+struct DitTrLnArgs {
+  const float *X; float *XN, *A, *rs;        // token rows [.][D]; normalised rows, modulated rows [M][D], rstd [M]
+  const float *dA; float *dX;                 // backward: gradient of the modulated rows [M][D]; residual-stream gradient (+=)
+  const float *mod; int ldmod, off_shift, off_scale;   // conditioning rows [B][ldmod]
+  long long M; int D, tok, grp, grp_stride, grp_off;
+};
+hipError_t launch_ditt_ln_fwd(const DitTrLnArgs &a, hipStream_t st);
+hipError_t launch_ditt_ln_bwd(const DitTrLnArgs &a, hipStream_t st);
+// Hm = mask1 * gelu(H1); backward in place: dH *= mask1 * gelu'(H1)
+hipError_t launch_ditt_gelu_drop(const float *H1, float *Hm, long long rows, int N, int tok, DitDrop dr, int bwd, hipStream_t st);
+// forward: Yd = mask * Y (in place when site != NONE), Xout = Xin + gate[b] * Yd; backward (Xin null): Y = gate[b] * dX * mask
+hipError_t launch_ditt_gate(const float *Xin, float *Xout, float *Y, const float *dX, const float *mod, int ldmod, int off_gate,
+                            long long rows, int D, int tok, int site, DitDrop dr, hipStream_t st);
+hipError_t launch_ditt_silu(const float *x, float *y, const float *dy, long long n, hipStream_t st);   // dy null: y = silu(x); else y = dy * silu'(x)
+hipError_t launch_ditt_gather_rows(const float *table, const long long *t, float *out, int B, int D, hipStream_t st);
+struct DitTrPatchArgs {
+  const float *x8; float *Pm;                  // [B][L][H][W][8] -> patches [rows][Kp]
+  const float *pred, *target; float *dYf;      // [B,C,H,W,F] -> loss gradient of the final linear's rows [B * F * Ns][Nout]
+  const float *dX0; float *dspos, *dtpos;      // gradient of the embedded tokens -> position-embedding gradients
+  int B, C, L, Hh, Ww, p, Ns, wpn, tok, qs, Kp, Nout, D;
+};
+hipError_t launch_ditt_patch_gather(const DitTrPatchArgs &a, hipStream_t st);
+hipError_t launch_ditt_loss_grad(const DitTrPatchArgs &a, hipStream_t st);
+hipError_t launch_ditt_pos_grad(const DitTrPatchArgs &a, hipStream_t st);
+// Train-mode attention of DiT2D: the forward keeps the log-sum-exp per (sample, head, query) and drops probabilities; the backward
+// recomputes P = exp(s - lse) in two passes (dQ per query tile, dK / dV per key tile); the masks are drawn in all three.
+struct DitTrAttnArgs {
+  const float *qkv; float *out, *lse;          // [B][S][3E]; [B][S][E]; [B][heads][S]
+  const float *dout; float *delta, *dqkv;      // gradient of out; sum_d dout * out per (sample, head, query); [B][S][3E]
+  int B, S, E, heads;
+  DitDrop dr;
+};
+hipError_t launch_ditt_attn_fwd(const DitTrAttnArgs &a, hipStream_t st);
+hipError_t launch_ditt_attn_delta(const DitTrAttnArgs &a, hipStream_t st);
+hipError_t launch_ditt_attn_bwd(const DitTrAttnArgs &a, hipStream_t st);
+
 // ConvRNN forecaster (cm_convrnn.hip): one implicit-GEMM 2-D convolution with fused epilogues, and the frame packer.
 enum { CRNN_GEO_S1 = 0, CRNN_GEO_S2 = 1, CRNN_GEO_T4 = 2 };   // 3x3 stride 1 pad 1; 3x3 stride 2 pad 1; transposed 4x4 stride 2 pad 1
 enum { CRNN_EPI_LEAKY = 0, CRNN_EPI_GRU_GATES = 1, CRNN_EPI_GRU_CAND = 2, CRNN_EPI_LSTM = 3, CRNN_EPI_LAST = 4 };

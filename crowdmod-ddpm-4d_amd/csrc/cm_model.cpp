@@ -2860,4 +2860,5 @@ int cm_model_class_flops(const cm_model *m, int32_t B, double flops[8]) {
 }  // extern "C"
 
 #include "cm_train_host.inc"
+#include "cm_dit_train_host.inc"
 #include "cm_convrnn_host.inc"

@@ -4,7 +4,8 @@
 Same constructor arguments and call convention as the reference --
 `denoiser(future[B,C,H,W,F], t[B] int64, past[B,C,H,W,P]) -> [B,C,H,W,F]` -- and the `nn.Module` surface the DDPM
 driver touches (`eval/to/state_dict/load_state_dict`, `ensure` like `UNet.ensure`).  All arithmetic runs in
-libcrowdmod_hip.so (cm_model_create_dit / cm_model_create_dit2d, cm_dit.hip); inference only.
+libcrowdmod_hip.so (cm_model_create_dit / cm_model_create_dit2d, cm_dit.hip).  DiT4D_V4 is inference only; DiT2D also
+trains, through the `fit_*` family (cm_dit_train_*, cm_dit_train.hip) -- `train()` / `train_init()` keep raising on both.
 """
 from __future__ import annotations
 
@@ -237,3 +238,158 @@ class DiT2D(DiT4D_V4):
             self._release()
             self.cfg = dataclasses.replace(self.cfg, past_len=int(past_len), future_len=int(future_len))
         return super().ensure(rows, cols, past_len, future_len, batch)
+
+    # -- training (cm_dit_train_*) -------------------------------------------------
+    def _fit_handle(self):
+        if self._handle is None or not getattr(self, "_fit", False):
+            raise RuntimeError("DiT2D.fit_init has not been called (or the handle was re-created since)")
+        return self._handle
+
+    def _release(self):
+        """Destroying the handle of a model that is training would silently drop the unsynced master weights, both
+        Adam moments and the step counter: refuse, unless `fit_end` (or the destructor) asked for it."""
+        if getattr(self, "_fit", False) and not getattr(self, "_fit_closing", False):
+            raise RuntimeError("DiT2D: this call would re-create the native handle (a larger batch than fit_init "
+                               "allocated, other frame counts, load_state_dict or another device) while it holds "
+                               "training state; call sync() and fit_end() first, then fit_init again")
+        super()._release()
+        self._fit = False
+
+    def load_state_dict(self, state, strict: bool = True):
+        if getattr(self, "_fit", False):
+            self._release()          # raises, before any tensor is replaced
+        return super().load_state_dict(state, strict)
+
+    def fit_end(self):
+        """Give up the training state (call `sync` first to keep the weights); the handle may be re-created again."""
+        self._fit = False
+        return self
+
+    def __del__(self):
+        self._fit_closing = True
+        super().__del__()
+
+    def fit_init(self, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None, batch=None):
+        """Allocate the training state (master weights, gradients, Adam moments, the tape) on the native handle, for
+        batches of at most `batch` (default max_batch) samples.  torch.optim.Adam(lr, betas, eps, weight_decay);
+        dropout_rate defaults to the constructor's."""
+        g = self.cfg
+        p = g.dropout_rate if dropout_rate is None else float(dropout_rate)
+        h = self.ensure(g.grid_rows, g.grid_cols, g.past_len, g.future_len, int(batch or self.max_batch))
+        native.check(native.lib().cm_dit_train_init(h, float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                    float(weight_decay), p))
+        self._fit = True
+        return self
+
+    def set_lr(self, lr: float):
+        native.check(native.lib().cm_dit_train_set_lr(self._fit_handle(), float(lr)))
+
+    def fit_step_xt(self, xt, t, past, target, seed: int = 0, apply_update: bool = True, sample_base: int = 0) -> float:
+        """One training step: u = DiT2D(xt, t, past) in train mode, loss = mse(u, target), backward, Adam when
+        `apply_update`.  numpy arrays (host staging) or torch CUDA tensors; returns the loss."""
+        L, h = native.lib(), self._fit_handle()
+        B = int(xt.shape[0])
+        if B > self._native_max_batch:
+            raise ValueError(f"batch {B} exceeds the {self._native_max_batch} samples fit_init allocated")
+        native.check(L.cm_dit_train_set_sample_base(h, int(sample_base)))
+        loss = C.c_float()
+        if _is_torch(xt):
+            import torch
+            a = [v.contiguous().float() for v in (xt, past, target)]
+            tt = t.to(device=xt.device, dtype=torch.long).contiguous()
+            torch.cuda.current_stream(xt.device).synchronize()
+            native.check(L.cm_dit_train_step_xt(h, a[0].data_ptr(), a[1].data_ptr(), tt.data_ptr(), a[2].data_ptr(),
+                                                int(seed), C.byref(loss), B, int(bool(apply_update)), None))
+            return float(loss.value)
+        bufs = [native.DeviceBuffer.from_array(np.ascontiguousarray(v, dtype=np.float32), self.device)
+                for v in (xt, past, target)]
+        tb = native.DeviceBuffer.from_array(
+            np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,))), self.device)
+        try:
+            native.check(L.cm_dit_train_step_xt(h, bufs[0].ptr, bufs[1].ptr, tb.ptr, bufs[2].ptr, int(seed),
+                                                C.byref(loss), B, int(bool(apply_update)), None))
+        finally:
+            for b in bufs + [tb]:
+                b.free()
+        return float(loss.value)
+
+    def _tensor(self, fn, name, *extra):
+        out = np.empty(self._shapes[name], dtype=np.float32)
+        native.check(fn(self._fit_handle(), name.encode(), *extra, out.ctypes.data, out.size))
+        return out
+
+    def grad(self, name: str) -> np.ndarray:
+        """Gradient of one state_dict tensor after the last step."""
+        return self._tensor(native.lib().cm_dit_train_get_grad, name)
+
+    def opt_state(self, name: str, which: int) -> np.ndarray:
+        """0 exp_avg, 1 exp_avg_sq, 2 the master weights (what the next step reads; `sync` publishes them)."""
+        return self._tensor(native.lib().cm_dit_train_get_opt_state, name, int(which))
+
+    def set_opt_state(self, name: str, which: int, value):
+        v = np.ascontiguousarray(value, dtype=np.float32).reshape(self._shapes[name])
+        native.check(native.lib().cm_dit_train_set_opt_state(self._fit_handle(), name.encode(), int(which),
+                                                             v.ctypes.data, v.size))
+
+    def opt_step(self, set_to: Optional[int] = None) -> int:
+        s = C.c_int32(0 if set_to is None else int(set_to))
+        native.check(native.lib().cm_dit_train_opt_step(self._fit_handle(), C.byref(s), int(set_to is not None)))
+        return int(s.value)
+
+    def flat_grads(self):
+        """(device address, element count) of the flat fp32 gradient buffer in state_dict order (the all-reduce
+        operand of data-parallel training: step(apply_update=False), all-reduce, apply_update())."""
+        p, n = C.c_void_p(), C.c_int64()
+        native.check(native.lib().cm_dit_train_flat_grads(self._fit_handle(), C.byref(p), C.byref(n)))
+        return p.value, int(n.value)
+
+    def apply_update(self):
+        native.check(native.lib().cm_dit_train_apply(self._fit_handle(), None))
+
+    def train_pred(self, B: int) -> np.ndarray:
+        """Train-mode prediction [B, C, H, W, F] of the last step."""
+        g = self.cfg
+        out = np.empty((int(B), g.output_channels, g.grid_rows, g.grid_cols, g.future_len), dtype=np.float32)
+        native.check(native.lib().cm_dit_train_get_pred(self._fit_handle(), out.ctypes.data, out.size))
+        return out
+
+    def sync(self):
+        """Publish the trained weights: state_dict(), the eval forward and the sampling loops see them from here on."""
+        L, h = native.lib(), self._fit_handle()
+        native.check(L.cm_dit_train_sync(h))
+        for name, shp in self._shapes.items():
+            buf = np.empty(shp, dtype=np.float32)
+            native.check(L.cm_model_get_param(h, name.encode(), buf.ctypes.data, buf.size))
+            self._params[name] = buf
+        return self
+
+    sync_trained = sync   # the name the shared epoch loop (DDPM_model.train / save_checkpoint) calls
+
+    def trainable_names(self):
+        return list(self._shapes)
+
+    def optimizer_state_dict(self, lr: float, betas, eps: float, weight_decay: float):
+        """torch.optim.Adam.state_dict() of the reference optimizer (flow_matching.py:27-30) over
+        u_predictor.parameters(): what a checkpoint stores under "opt".  The frozen sinusoid table is a parameter
+        without state."""
+        names = self.trainable_names()
+        step, state = self.opt_step(), {}
+        if step > 0:
+            for i, name in enumerate(names):
+                if name != self._TABLE:
+                    state[i] = {"step": np.float32(step), "exp_avg": self.opt_state(name, 0),
+                                "exp_avg_sq": self.opt_state(name, 1)}
+        group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps),
+                 "weight_decay": float(weight_decay), "amsgrad": False, "maximize": False, "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                 "params": list(range(len(names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, opt: dict):
+        """Inverse of optimizer_state_dict (resume from a checkpoint's "opt" entry)."""
+        names, step = self.trainable_names(), 0
+        for i, st in opt.get("state", {}).items():
+            for which, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
+                self.set_opt_state(names[int(i)], which, np.asarray(st[key]))
+            step = int(np.asarray(st["step"]).reshape(-1)[0])
+        self.opt_step(step)

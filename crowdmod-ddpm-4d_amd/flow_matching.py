@@ -1,13 +1,13 @@
 """Host-side mirror of the reference's flow-matching driver
 (/root/reference/models/flow_matching/flow_matching.py:14-250, archs "FM-UNet" and "FM-DiT").
 
-The velocity predictor is the same native UNet, or the native DiT2D (dit.py; sampling only); sampling is the Euler integrator
+The velocity predictor is the same native UNet, or the native DiT2D (dit.py; it trains through `fit`); sampling is the Euler integrator
     x <- x + (1/N) u(x, idx_i, past),  t_i = linspace(0,1,N)[i],  idx_i = clamp(t_i * TIME_MAX_POS).long()
 run as ONE device-resident loop (cm_sample_loop with CM_SAMPLER_FM_EULER); the reference maps the
 "Heun" integrator name to the Euler routine as well (flow_matching.py:44-47), and so does this class.
 Training draws x0 ~ N(0,1), t ~ U(0,1), builds (x_t, u_target) with the Linear or Conic path on the
 host (two axpys on [B,C,H,W,F]) and runs the native train-mode forward + MSE + backward + Adam step
-(cm_train_step_xt)."""
+(cm_train_step_xt; for the DiT2D of "FM-DiT": cm_dit_train_step_xt, through `FM_model.fit`)."""
 from __future__ import annotations
 
 import os
@@ -89,9 +89,14 @@ class FM_model(DDPM_model):
             tv = tb.reshape(-1, 1, 1, 1, 1)
             xt, u_target = w_fn(np.asarray(x0b, dtype=np.float32), x1, tv)
             t_idx = (tb * np.float32(self.time_max_pos)).astype(np.int64)   # (t * time_max_pos).long(): truncation
-            loss = self.denoiser.train_step_xt(xt.astype(np.float32), past, t_idx, u_target.astype(np.float32),
-                                               drop_masks=drop_masks, seed=self.seed + self._fm_calls,
-                                               apply_update=grad_sync is None)
+            if self.arch == "FM-DiT":   # the DiT2D draws its masks on the device only: (seed, step, global sample index)
+                loss = self.denoiser.fit_step_xt(xt.astype(np.float32), t_idx, past, u_target.astype(np.float32),
+                                                 seed=self.seed + self._fm_calls, apply_update=grad_sync is None,
+                                                 sample_base=self.dp_rank * B)
+            else:
+                loss = self.denoiser.train_step_xt(xt.astype(np.float32), past, t_idx, u_target.astype(np.float32),
+                                                   drop_masks=drop_masks, seed=self.seed + self._fm_calls,
+                                                   apply_update=grad_sync is None)
             if grad_sync is not None:
                 grad_sync(self.denoiser)
                 self.denoiser.apply_update()
@@ -115,11 +120,44 @@ class FM_model(DDPM_model):
 
     def train(self, batched_train_data, baseline_ckpt=None, *, log=None, grad_sync=None, save=True, loss_sync=None):
         if self.arch == "FM-DiT":
-            raise NotImplementedError(f"training {self.arch} is not implemented on this path (sampling only)")
+            raise NotImplementedError(f"training {self.arch} through train() is not implemented on this path; use "
+                                      "FM_model.fit / train_fm_dit.py (DiT2D backward, dropout from the device Philox "
+                                      "stream, Adam)")
         keep = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
         self._keep_override = keep
         return super().train(batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save,
                              loss_sync=loss_sync)
+
+    def _refuse_training(self):
+        if not getattr(self, "_fitting", False):
+            super()._refuse_training()
+
+    def _ensure_training(self, past, future):
+        if self.arch != "FM-DiT":
+            return super()._ensure_training(past, future)
+        from .ddpm_model import ReduceLROnPlateau
+        net = self.denoiser
+        B, _, H, W, F = future.shape
+        if not getattr(net, "_fit", False):
+            s = self._solver()
+            net.ensure(H, W, int(past.shape[4]), F, max(B, net.max_batch))
+            net.fit_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], dropout_rate=self.res.dit.dropout_rate)
+            self._lr = s["lr"]
+            self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
+
+    def fit(self, batched_train_data, baseline_ckpt=None, *, log=None, grad_sync=None, save=True, loss_sync=None):
+        """Train the DiT2D of arch "FM-DiT" (flow_matching.py:104-201): the epoch loop of `train` -- the same w_fn and
+        time truncation, grad_sync / loss_sync hooks, ReduceLROnPlateau, NaN stop, CHECKPOINTS_TO_KEEP, checkpoint
+        name and {"opt", "model"} file -- stepping through cm_dit_train_*.  Returns the epoch losses."""
+        if self.arch != "FM-DiT":
+            raise NotImplementedError(f"FM_model.fit trains FM-DiT only; {self.arch} goes through train()")
+        self._keep_override = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
+        self._fitting = True
+        try:
+            return DDPM_model.train(self, batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save,
+                                    loss_sync=loss_sync)
+        finally:
+            self._fitting = False
 
     # -- sampling entry (flow_matching.py:250-292) ------------------------------------------
     def sampling(self, batched_test_data, plotType=None, model_fullname=None, plotMprop=None, plotPast=None,

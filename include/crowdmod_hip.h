@@ -389,6 +389,40 @@ int cm_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel
  * returns them) and refresh the eval-mode time-embedding table. */
 int cm_train_sync(cm_model *m);
 
+/* ---- FM-DiT training: replaces FM_model._train_step + optimizer.step() for arch "FM-DiT" ----
+ * (models/flow_matching/flow_matching.py:104-157, models/backbones/DiT2D.py in train mode; torch.optim.Adam with
+ * coupled L2.)  A family of its own: cm_train_* keep refusing DiT handles.  Only a finalized DiT2D handle on a device
+ * trains; a UNet handle, a DDPM-DiT (DiT4D_V4) handle and a host-only handle are refused by name.  fp32 throughout,
+ * head dim 64, at most 1024 tokens per sample, 64 heads; single GPU plus the flat-gradient protocol below.
+ * cm_dit_train_init allocates the master weights, gradients and Adam moments (flat, state_dict order) and the tape
+ * of the train-mode forward for max_batch samples; dropout_rate is DiT2D's DROPOUT_RATE (attention probabilities,
+ * after GELU, after fc2), in [0, 1). */
+int cm_dit_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      float dropout_rate);
+int cm_dit_train_set_lr(cm_model *m, float lr);
+/* Global index of this rank's sample 0: the dropout masks are a function of (seed, optimizer step, GLOBAL sample
+ * index, block, site, head, row, column), so a sample's masks do not depend on its batch.  Indices stay below 2^32. */
+int cm_dit_train_set_sample_base(cm_model *m, int64_t sample_id_base);
+/* One step on device buffers: u_hat = DiT2D(d_xt, d_t, d_past) in train mode (masks from the device Philox stream
+ * keyed by `seed`); *h_loss = mse(u_hat, d_target); backward; if apply_update != 0: Adam.  Synchronous. */
+int cm_dit_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const int64_t *d_t,
+                         const float *d_target, uint64_t seed, float *h_loss, int32_t B, int32_t apply_update,
+                         void *stream);
+/* Data-parallel use: step(apply_update=0) on every rank, all-reduce(mean) the flat buffer, cm_dit_train_apply. */
+int cm_dit_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel);
+int cm_dit_train_apply(cm_model *m, void *stream);
+int cm_dit_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel);
+/* which = 0 exp_avg, 1 exp_avg_sq, 2 (get only) the master weights; cm_dit_train_opt_step reads (set=0) or writes
+ * (set=1) the step counter. */
+int cm_dit_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel);
+int cm_dit_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel);
+int cm_dit_train_opt_step(cm_model *m, int32_t *step, int32_t set);
+/* Copy the master weights into the handle's state_dict and the eval path's weights, and rebuild the eval path's
+ * 1000-row conditioning table from them.  Until this call the eval forward computes what it did before training. */
+int cm_dit_train_sync(cm_model *m);
+/* The train-mode prediction [B,C,H,W,F] of the last step (host buffer). */
+int cm_dit_train_get_pred(cm_model *m, float *h_out, int64_t numel);
+
 /* ---- ConvRNN forecaster: replaces Forecaster(...) (models/convRNN/forecaster.py) and
  * ConvRNN_model._generate_convRNN (models/convRNN/convRNN.py:223-231) -----------------------------------
  * The deterministic ConvGRU / ConvLSTM encoder-forecaster baseline of arch "ConvRNN".  It has no timestep and no
