@@ -119,8 +119,10 @@ __global__ __launch_bounds__(512, 2) void conv_qr_kernel(const QrArgs a) {
     const int q = tid & (QP - 1), hv0 = tid >> a.qshift, hvstep = 512 >> a.qshift;
     const bool qok = q < Q;
     const int c = 4 * q;
-    const bool from0 = c < a.C0;
-    const float *sp = from0 ? a.src0 + (size_t)b * V * a.C0 + c : a.src1 + (size_t)b * V * a.C1 + (c - a.C0);
+    // (lanes beyond the last quad -- Q is not a power of two -- load like quad 0 and store nothing: their own channel offset is past
+    //  both sources, and with a single source src1 is null: 48 -> 64 channels faulted here)
+    const bool from0 = c < a.C0 || !qok;
+    const float *sp = from0 ? a.src0 + (size_t)b * V * a.C0 + (qok ? c : 0) : a.src1 + (size_t)b * V * a.C1 + (c - a.C0);
     const int Cs = from0 ? a.C0 : a.C1;
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
     if (a.gamma && qok) {

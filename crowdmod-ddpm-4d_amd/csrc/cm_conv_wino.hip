@@ -551,12 +551,20 @@ __global__ __launch_bounds__(256 * NBW, OCC) void conv_wino_kernel(const ConvArg
 //   WHOLE  8 x 2 x 2 tile on a grid that it divides, Co a multiple of 32: every wave owns all 32 rows x 32 channels, row -> voxel
 //          is linear in the tile origin -- no output-offset table, no row masks, per-lane base + uniform strides for the stores,
 //          the residual loads and the skip conv's rows
-// Same arithmetic in the same order in every form: results are bit-identical to FM = 0 (tests/test_gpu_wino_forms.py).
+//   AHEAD  (h2 ONE forms) the halo loads run one whole chunk period ahead, in a two-slot register buffer.  The memory counter retires
+//          in order: halo loads issued just BEFORE a matrix phase are older than that phase's ring refills, so the first wait on a
+//          refill (step RD6 of the phase, 0.12 us later) waits for the whole HBM burst -- in every chunk, whatever the ring depth.  Here
+//          the loads of chunk ch + 2 go out AFTER the last refill of chunk ch's phase: every refill waited on before step RD6 of the
+//          next phase is older than they are, and they have step A + step B + two barriers + RD6 steps to land.  In a SKIP instantiation
+//          the fused skip conv's operand chunks are double-buffered the same way (a ONE form holds no next tile's halo in its epilogue).
+// Same arithmetic in the same order in every form: results are bit-identical to FM = 0 (tests/test_gpu_wino_forms.py,
+// tests/test_gpu_wino_prefetch.py).
 template <int BZ, int PY, int PX, bool F16, int NBW, bool SKIP, int B6 = 0, int FM = 0>   // B6: 0 off, 1 six bf16 cross terms, 2 three (relaxed plan), 3 three f16 cross terms (h2)
 __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArgs a, const int *__restrict__ tabA,
                                                                   const int *__restrict__ tabO, int G) {
   constexpr bool ONE = (FM & WINO_FORM_ONE) != 0, PLAIN = (FM & WINO_FORM_PLAIN) != 0, OWNGN = (FM & WINO_FORM_OWNGN) != 0;
-  constexpr bool WHOLE = (FM & WINO_FORM_WHOLE) != 0;
+  constexpr bool WHOLE = (FM & WINO_FORM_WHOLE) != 0, AHEAD = (FM & WINO_FORM_AHEAD) != 0;
+  static_assert(!AHEAD || (ONE && PLAIN && B6 == 3), "the halo-ahead order is a variant of the h2 one-sample forms");
   static_assert(!WHOLE || (BZ == 8 && PY == 2 && PX == 2 && NBW == 1), "the whole-tile form is the full-resolution tile's");
   static_assert(!OWNGN || PLAIN, "own GroupNorm is a variant of the plain activation form");
   constexpr int NT = 256 * NBW;
@@ -671,8 +679,12 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
   // (read once per workgroup after the table has landed, below)
 
   // ---- loads of (sample b, chunk ch): halo voxels of the thread's step-A slots + the GroupNorm rows of its channel quad
-  f32x4 ald[RK], scn = {1.f, 1.f, 1.f, 1.f}, shn = {0.f, 0.f, 0.f, 0.f};
-  auto issue = [&](int b, int ch) {
+  // (AHEAD: two slots, chunk ch in slot ch & 1; the slot is a constant at every use -- the chunk loop below is unrolled by two)
+  constexpr int NSL = AHEAD ? 2 : 1;
+  f32x4 ald[NSL][RK], scn[NSL], shn[NSL];
+#pragma unroll
+  for (int s = 0; s < NSL; ++s) { scn[s] = f32x4{1.f, 1.f, 1.f, 1.f}; shn[s] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  auto issue = [&](const int SL, int b, int ch) {
     const bool s0 = ch < n0;
     const int Cn = s0 ? a.C0 : a.C1;
     const float *base = (s0 ? a.src0 + ch * CS : a.src1 + (ch - n0) * CS) + (size_t)b * Vs * Cn;      // wave-uniform
@@ -681,15 +693,15 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
     for (int k = 0; k < RK; ++k) {
       unsigned vo = (unsigned)asoff[k];
       asm volatile("" : "+v"(vo));               // keep ONE copy of the offsets live (no hoisted per-source products)
-      ald[k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (__umul24(vo, cb) + aq16));
+      ald[SL][k] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (__umul24(vo, cb) + aq16));
     }
     if (PLAIN ? !OWNGN : a.gn != nullptr) {
       const float *gp = a.gn + (size_t)b * 2 * Ctot + (s0 ? ch * CS : a.C0 + (ch - n0) * CS);              // wave-uniform
-      scn = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp) + aq16);
-      shn = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp + Ctot) + aq16);
+      scn[SL] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp) + aq16);
+      shn[SL] = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(gp + Ctot) + aq16);
     }
   };
-  issue(g0, 0);
+  issue(0, g0, 0);
   if constexpr (!WHOLE) __syncthreads();         // outoff visible
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   // this lane's output rows of the epilogue: reg -> row (reg & 3) + 8 (reg >> 2) + 4 hh of sub-block `wave` (re-read per tile:
@@ -728,9 +740,28 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[x][i] = 0.f;
 
-    for (int ch = 0; ch < nchunks; ++ch) {
+    if constexpr (AHEAD) {
+      // chunk 1 goes out once chunk 0 has landed, at the head of chunk 0's step A: the cover every later chunk gets.  (The explicit
+      // use makes slot 0 complete on every path into the loop: left to the first step A, the wait the compiler derives for the loop
+      // head would name the youngest load in flight around the back edge -- the halo loads that have just been issued.)
+#pragma unroll
+      for (int k = 0; k < RK; ++k) asm volatile("" : "+v"(ald[0][k]));
+      if constexpr (!OWNGN) asm volatile("" : "+v"(scn[0]), "+v"(shn[0]));
+      if (nchunks > 1) issue(NSL - 1, b, 1);
+      asm volatile("" ::: "memory");
+    }
+    // AHEAD: the loop runs over PAIRS of chunks (slot = ch & 1 is then a constant at every use), an odd last chunk follows as pass 1.
+    // The pair loop has one exit and nothing between the loads and the next step A but straight code: a chunk skipped inside the
+    // loop would leave a path from freshly issued loads back to the loop head, and the wait derived for the head would name them.
+    const int npair = AHEAD ? (nchunks & ~1) : nchunks;
+#pragma unroll
+    for (int pass = 0; pass < NSL; ++pass)
+    for (int ch0 = pass ? npair : 0; ch0 < (pass ? nchunks : npair); ch0 += NSL)
+#pragma unroll
+    for (int SL = 0; SL < NSL - pass; ++SL) {
+      const int ch = ch0 + SL;
       // ---- step A: this chunk's halo voxels -> activated image R ------------------------------------------
-      f32x4 sc1 = scn, sh1 = shn;
+      f32x4 sc1 = scn[SL], sh1 = shn[SL];
       if (own_gn) {
         const int cb0 = (ch < n0 ? ch * CS : a.C0 + (ch - n0) * CS) + 4 * aq;
         sc1 = *reinterpret_cast<const f32x4 *>(GNL + cb0);
@@ -745,7 +776,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #pragma unroll
         for (int k = 0; k < RK; ++k) {
           const int v = (tid >> 2) + (NT / 4) * k + RV0;
-          f32x4 w = ald[k] * sc1 + sh1;
+          f32x4 w = ald[SL][k] * sc1 + sh1;
           w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]);
           if (!((aok >> k) & 1u)) w = f32x4{0.f, 0.f, 0.f, 0.f};
           if (v >= RV0 && v < RV0 + RVC) *reinterpret_cast<f32x4 *>(R + (v - RV0) * RS_ + 4 * aq) = w;
@@ -754,7 +785,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #pragma unroll
         for (int k = 0; k < RK; ++k) {
           const int v = (tid >> 2) + (NT / 4) * k + RV0;
-          f32x4 w = ald[k];
+          f32x4 w = ald[SL][k];
           if (norm) {
             w = w * sc1 + sh1;
             if (a.silu) { w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]); }
@@ -828,9 +859,12 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       }
       __syncthreads();
       // ---- next chunk's loads (possibly the next sample's first chunk): in flight under this matrix phase -----
+      // (AHEAD: chunk ch + 1 is already in flight or landed; chunk ch + 2 goes out behind the last ring refill of this phase)
 #if !(CM_WINO_ABL & 2)
-      if (ch + 1 < nchunks) issue(b, ch + 1);
-      else if (more_b) issue(b + G, 0);
+      if constexpr (!AHEAD) {
+        if (ch + 1 < nchunks) issue(0, b, ch + 1);
+        else if (more_b) issue(0, b + G, 0);
+      }
 #endif
       // ---- matrix phase: NG groups (z tap [, 8-channel half]) x 4 components, A fragments one group ahead -------
       auto aread = [&](int g, f32x4 (&af)[4]) {
@@ -884,6 +918,14 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
           }
           asm volatile("" ::: "memory");
         }
+#if !(CM_WINO_ABL & 2)
+        if constexpr (AHEAD) {
+          // the slot step A of this chunk has emptied takes chunk ch + 2: younger than every refill of this phase (the fences keep
+          // the loads between the last refill and the barrier of the next step A); the last two chunks issue nothing
+          if (pass == 0 && ch + 2 < nchunks) issue(SL, b, ch + 2);
+          asm volatile("" ::: "memory");
+        }
+#endif
       } else {
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -921,7 +963,10 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #define CM_WINO_SKIP_EARLY 0   // (measured: no gain -- 31.9 vs 32.8, 70.4 vs 69.7 us per layer, step 1.169 vs 1.166 ms)
 #endif
     constexpr bool SKIP_EARLY = SKIP && B6 == 3 && CM_WINO_SKIP_EARLY;
-    f32x4 ska[4], skw[4];
+    // AHEAD (a ONE form: no next tile's halo is held here): two operand slots, chunk c2 + 1 requested before the matrix instructions
+    // of chunk c2, chunk 0 above the exchange barriers
+    constexpr bool SKIP2 = SKIP && AHEAD;
+    f32x4 ska[4], skw[4], skb[SKIP2 ? 4 : 1], skx[SKIP2 ? 4 : 1];
     int svox = 0;
     if constexpr (SKIP) {
       if constexpr (WHOLE) {                     // row r = 4 z + 2 py + px of sub-block (wave >> 1, wave & 1)
@@ -932,6 +977,10 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       }
       // h2 (24 registers lighter than the six-term form): the skip conv's first operand chunk travels under the output transform
       if constexpr (SKIP_EARLY) wino_skip_load1(a, nt, n2a, n2, 0, svox, lane, ska, skw);
+      if constexpr (SKIP2 && !SKIP_EARLY) {
+        if (n2 > 0) wino_skip_load1(a, nt, n2a, n2, 0, svox, lane, ska, skw);
+        asm volatile("" ::: "memory");
+      }
     }
     if constexpr ((CM_WINO_ABL & 16) != 0) {      // (ablation: no epilogue; one store keeps the accumulators alive)
       if (t0[0] + t1[0] == 12345.f) a.out[0] = t0[1];
@@ -964,11 +1013,28 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
     }
     if constexpr (B6 == 3) v = v * a.h2_oscale;   // (h2 fragments hold w * 2^k; the skip conv below adds to the unscaled sums)
     if constexpr (SKIP) {
-      // operands one 32-channel chunk at a time (double buffering them was the register peak of the kernel and spilled into the
-      // chunk loop: 37 registers even in the h2 form); h2: the FIRST chunk was requested above the output transform
+      if constexpr (SKIP2) {
+        // same accumulation order c2 = 0, 1, 2 ...; each wait names one slot with exactly one younger request in flight (a
+        // conditional request in front of a shared wait would make it a wait for everything)
+        if (n2 > 0)
+          for (int c2 = 0;; c2 += 2) {
+            if (c2 + 1 >= n2) { wino_skip_mfma1(ska, skw, v); break; }
+            wino_skip_load1(a, nt, n2a, n2, c2 + 1, svox, lane, skb, skx);
+            asm volatile("" ::: "memory");
+            wino_skip_mfma1(ska, skw, v);
+            if (c2 + 2 >= n2) { wino_skip_mfma1(skb, skx, v); break; }
+            wino_skip_load1(a, nt, n2a, n2, c2 + 2, svox, lane, ska, skw);
+            asm volatile("" ::: "memory");
+            wino_skip_mfma1(skb, skx, v);
+          }
+      } else {
+      // without AHEAD: operands one 32-channel chunk at a time (in a form that holds the next tile's halo here, double buffering them
+      // was the register peak of the kernel and spilled into the chunk loop: 37 registers even in the h2 form); SKIP_EARLY: the FIRST
+      // chunk was requested above the output transform
       for (int c2 = 0; c2 < n2; ++c2) {
         if (!(SKIP_EARLY && c2 == 0)) wino_skip_load1(a, nt, n2a, n2, c2, svox, lane, ska, skw);
         wino_skip_mfma1(ska, skw, v);
+      }
       }
     }
     // bias, time-embedding row, residual, channels-last store, GroupNorm statistics (slot format of gn_finalize)
@@ -1293,6 +1359,8 @@ bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn) {
 // sample lanes (B > G), a full-resolution grid the tile does not divide, the six-term / relaxed / f16 / fp32 operand forms, and every
 // diagnostic run (a.dbg != 0: the CM_CONV_DBG / cm_debug_conv_flags switches; bit 1 << 20 selects nothing else and is the
 // documented way to force the generic kernel for an A/B or a bit-identity check).
+// The launcher adds AHEAD (halo loads a chunk period ahead, skip operands double-buffered) to every specialised form unless
+// CM_NO_WINO_AHEAD is set under CM_DIAG: the same forms in the one-ahead order, for A/B runs.
 int conv_wino_form(const ConvArgs &a, int G) {
   if (a.dbg != 0 || a.f16 != 4) return 0;
   if (G < a.B || a.pm || !a.silu) return 0;
@@ -1307,10 +1375,11 @@ int conv_wino_form(const ConvArgs &a, int G) {
   return WINO_FORM_ONE | WINO_FORM_PLAIN | (own ? WINO_FORM_OWNGN : 0);
 }
 
-static std::atomic<long long> wino_form_launches[16];
+static std::atomic<long long> wino_form_launches[16], wino_ahead_launches;
 void conv_wino_form_counts(long long counts[16], bool reset) {
   for (int i = 0; i < 16; ++i) counts[i] = reset ? wino_form_launches[i].exchange(0) : wino_form_launches[i].load();
 }
+long long conv_wino_ahead_count(bool reset) { return reset ? wino_ahead_launches.exchange(0) : wino_ahead_launches.load(); }
 
 hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   ConvArgs a = a_in;
@@ -1343,11 +1412,15 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
     hipError_t et = wino_tabs_get(a, 256 * nbw, &tb);
     if (et != hipSuccess) return et;
     const dim3 gridp((unsigned)G, (unsigned)ntp, (unsigned)nz);
-    const int fm = nbw == conv_wino_nbw(a.bz, a.Co) ? conv_wino_form(a, G) : 0;
-    wino_form_launches[fm & 15].fetch_add(1, std::memory_order_relaxed);
+    static const bool no_ahead = cm::diag_env("CM_NO_WINO_AHEAD") != nullptr;
+    const int fm0 = nbw == conv_wino_nbw(a.bz, a.Co) ? conv_wino_form(a, G) : 0;
+    const int fm = fm0 && !no_ahead ? fm0 | WINO_FORM_AHEAD : fm0;
+    int fm_run = 0;   // the form of the instantiation the dispatch below really takes (a form without one runs the generic kernel: counted as 0)
 #define CM_WINO_PGO1(KERNEL, THREADS)                                                               \
   {                                                                                                 \
     CM_WINO_ATTR(KERNEL)                                                                            \
+    wino_form_launches[fm_run & 15].fetch_add(1, std::memory_order_relaxed);                        \
+    if (fm_run & WINO_FORM_AHEAD) wino_ahead_launches.fetch_add(1, std::memory_order_relaxed);      \
     hipLaunchKernelGGL(KERNEL, gridp, dim3(THREADS), ldsp, st, a, tb.tA, tb.tO, G);                 \
     return hipGetLastError();                                                                       \
   }
@@ -1358,6 +1431,7 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   }
 #define CM_WINO_PGOFM(Z, PY_, PX_, NB, THREADS, FM_)                                                \
     if (h2 && fm == (FM_)) {                                                                        \
+      fm_run = (FM_);                                                                               \
       if (a.s2w) CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, true, 3, (FM_)>), THREADS) \
       CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, false, 3, (FM_)>), THREADS)          \
     }
@@ -1382,6 +1456,8 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
         if (nbw == 2 && b6) {                                                                       \
           CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN)                         \
           CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN)       \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_AHEAD)       \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN | WINO_FORM_AHEAD) \
           CM_WINO_PGO6(z, py, px, 512)                                                              \
         }                                                                                           \
         if (nbw == 2 && f16) CM_WINO_PGO(z, py, px, true, 2, 512)                                   \
@@ -1391,6 +1467,7 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
       if constexpr (z == 8 && py == 2 && px == 2) {                                                 \
         if (b6) {                                                                                   \
           CM_WINO_PGOFM(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE)       \
+          CM_WINO_PGOFM(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE | WINO_FORM_AHEAD) \
           CM_WINO_PGO61(z, py, px, 256)                                                             \
         }                                                                                           \
         CM_WINO_PGO(z, py, px, false, 1, 256)                                                       \

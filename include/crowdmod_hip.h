@@ -342,6 +342,9 @@ int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, fl
  * counts[f] = the instantiation compiled for form f (bits: 1 one sample per workgroup, 2 plain GroupNorm + SiLU load, 4 GroupNorm
  * finalised from slot partials, 8 whole full-resolution tiles). */
 int cm_debug_wino_form_counts(int64_t counts[16], int32_t reset);
+/* ... and how many of those launches ran the halo-ahead order of the specialised forms (halo loads a chunk period ahead of the
+ * weight ring, skip-conv operands double-buffered); the form index above does not carry that bit. */
+int cm_debug_wino_ahead_count(int64_t *launches, int32_t reset);
 int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32_t by, int32_t bx,
                        int32_t B, int32_t iters, float *us);
 
