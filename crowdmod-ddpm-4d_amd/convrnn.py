@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import config as cfgmod, convrnn_spec, native
+from . import config as cfgmod, convrnn_spec, native, optim_state
 from .unet import _is_torch
 
 _REFUSAL = ("ConvRNN training (Poisson-KL + masked MSE loss, AMSGrad) is not reached through train(): use "
@@ -276,37 +276,27 @@ class Forecaster:
         native.check(native.lib().cm_convrnn_train_opt_step(self._need_train(), C.byref(step), int(value is not None)))
         return int(step.value)
 
-    _OPT_KEYS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
-
     def opt_state(self) -> dict:
         """torch.optim.Adam(amsgrad=True).state_dict() of the reference optimizer (convRNN.py:49-53): what save_checkpoint
         stores under "opt" (utils/utils.py:140-147)."""
         h, L = self._need_train(), native.lib()
-        step, state = self.opt_step(), {}
-        if step > 0:
-            for i, (name, shp) in enumerate(self._shapes.items()):
-                st = {"step": np.float32(step)}
-                for which, key in enumerate(self._OPT_KEYS):
-                    st[key] = np.empty(shp, np.float32)
-                    native.check(L.cm_convrnn_train_get_opt_state(h, name.encode(), which, st[key].ctypes.data, st[key].size))
-                state[i] = st
+
+        def get(name, which):
+            out = np.empty(self._shapes[name], np.float32)
+            native.check(L.cm_convrnn_train_get_opt_state(h, name.encode(), which, out.ctypes.data, out.size))
+            return out
+
         lr, b1, b2, eps, wd = self._hyper
-        group = {"lr": lr, "betas": (b1, b2), "eps": eps, "weight_decay": wd, "amsgrad": True, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(self._shapes)))}
-        return {"state": state, "param_groups": [group]}
+        return optim_state.dump(self._shapes, (), optim_state.AMSGRAD_KEYS, lr, (b1, b2), eps, wd, get, self.opt_step())
 
     def load_opt_state(self, opt: dict):
         """Inverse of opt_state (resume from a checkpoint's "opt" entry); the handle must exist (one step or loss has run)."""
         h, L = self._need_train(), native.lib()
-        names, step = list(self._shapes), 0
-        for i, st in opt.get("state", {}).items():
-            for which, key in enumerate(self._OPT_KEYS):
-                v = st[key]
-                arr = np.ascontiguousarray(v.detach().cpu().numpy() if _is_torch(v) else np.asarray(v), dtype=np.float32)
-                native.check(L.cm_convrnn_train_set_opt_state(h, names[int(i)].encode(), which, arr.ctypes.data, arr.size))
-            step = int(float(st["step"]))
-        self.opt_step(step)
+
+        def put(name, which, arr):
+            native.check(L.cm_convrnn_train_set_opt_state(h, name.encode(), which, arr.ctypes.data, arr.size))
+
+        self.opt_step(optim_state.load(opt, self._shapes, optim_state.AMSGRAD_KEYS, put))
         groups = opt.get("param_groups") or []
         if groups:
             self.set_lr(float(groups[0]["lr"]))

@@ -42,9 +42,9 @@ float wval(int tensor, size_t i) { return (float)((tensor * 7919 + (int)(i % 100
 // The backward weight layouts (cm_convrnn_train_host.inc) against a direct index computation on the state_dict tensors, as
 // values and as the 1-based index tables the device re-packs and reduces through.
 void test_train_packs(const cm_convrnn *m, int cell) {
-  std::vector<size_t> off;
-  size_t total = 0;
-  for (const Param &p : m->params) { off.push_back(total); total += (size_t)p.numel(); }
+  const OptLayout lay = opt_layout(m->params, {});   // as cm_convrnn_train_init lays the store out
+  const std::vector<size_t> &off = lay.off;
+  const size_t total = lay.nfloats;
   std::vector<unsigned> ids(total);
   for (size_t k = 0; k < total; ++k) ids[k] = (unsigned)(k + 1);
   const bool gru = cell == CM_CELL_GRU;

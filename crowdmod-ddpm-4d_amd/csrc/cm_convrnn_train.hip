@@ -10,7 +10,7 @@
 //                      channels, K = pixels of all samples, split in ranges; a workgroup ADDS its tile to the partial of its
 //                      range (one writer per element; the applications of a weight are launches in stream order), and
 //                      crnn_wgrad_reduce_kernel sums the ranges in order into the reference layout.
-//   gate backward, loss (float64 partials, fixed-order finalise), d loss / d yhat, AMSGrad: elementwise.
+//   gate backward, loss (float64 partials, fixed-order finalise), d loss / d yhat: elementwise (the AMSGrad update is cm_train.hip's launch_adam).
 // Every global address is guarded: rows by the pixel count, columns by the channel count, taps by the source grid.
 #include "cm_kernels.h"
 
@@ -301,21 +301,6 @@ __global__ __launch_bounds__(256) void crnn_loss_grad_kernel(const float *yhat, 
   d[1] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__global__ void amsgrad_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-                               float *__restrict__ vmax, long long n, float lr, float b1, float b2, float eps, float wd, float bc1,
-                               float bc2) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float gg = g[i] + wd * p[i];
-  const float mm = b1 * m[i] + (1.0f - b1) * gg;
-  const float vv = b2 * v[i] + (1.0f - b2) * gg * gg;
-  const float vx = fmaxf(vmax[i], vv);
-  m[i] = mm;
-  v[i] = vv;
-  vmax[i] = vx;
-  p[i] -= (lr / bc1) * mm / (sqrtf(vx) / sqrtf(bc2) + eps);
-}
-
 inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -403,14 +388,6 @@ hipError_t launch_crnn_loss_grad(const float *yhat, const float *y, int B, int H
   const long long n = (long long)B * HW * F;
   if (n <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(crnn_loss_grad_kernel, dim3(blocks_of(n)), dim3(256), 0, st, yhat, y, n, B, HW, F, eps, alpha, sums, dY);
-  return hipGetLastError();
-}
-
-hipError_t launch_amsgrad(float *p, const float *g, float *m, float *v, float *vmax, long long n, float lr, float b1, float b2, float eps,
-                          float wd, int step, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
-  hipLaunchKernelGGL(amsgrad_kernel, dim3(blocks_of(n)), dim3(256), 0, st, p, g, m, v, vmax, n, lr, b1, b2, eps, wd, bc1, bc2);
   return hipGetLastError();
 }
 

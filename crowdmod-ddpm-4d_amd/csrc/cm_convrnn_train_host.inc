@@ -26,11 +26,7 @@ struct CrnnTConv {
 };
 
 struct CrnnTrain {
-  float lr = 0, b1 = 0, b2 = 0, eps = 0, wd = 0;
-  int step = 0;
-  size_t nfloats = 0;
-  std::vector<size_t> off;   // flat offset of every state_dict tensor
-  float *master = nullptr, *grad = nullptr, *ea = nullptr, *eas = nullptr, *vmax = nullptr;
+  OptStore opt;              // cm_opt_store.inc: no frozen tensor, with vmax (AMSGrad)
   CrnnTConv cv[13][2];
   float *tp[13][4] = {};     // tape buffers of a layer (see above)
   float *H[3] = {}, *Ct[3] = {};
@@ -122,8 +118,8 @@ int crnn_train_repack(cm_convrnn *m, hipStream_t st) {
     for (int j = 0; j < 2; ++j) {
       const CrnnTConv &v = T->cv[i][j];
       if (!v.nf) continue;
-      CM_HIP(cm::launch_crnn_gather(T->master, v.fidx, *v.fw, (long long)v.nf, st));
-      CM_HIP(cm::launch_crnn_gather(T->master, v.bidx, v.bw, (long long)v.nb, st));
+      CM_HIP(cm::launch_crnn_gather(T->opt.p, v.fidx, *v.fw, (long long)v.nf, st));
+      CM_HIP(cm::launch_crnn_gather(T->opt.p, v.bidx, v.bw, (long long)v.nb, st));
     }
   return 0;
 }
@@ -340,16 +336,9 @@ int crnn_train_backward(const CrnnTapeRun &R, int tf) {
       if (!v.nf) continue;
       const bool up = L[i].kind == CRNN_UP;
       CM_HIP(cm::launch_crnn_wgrad_reduce(v.part, crnn_nsplit((long long)B * R.pix[v.level_m]), (long long)v.npart, (long long)(up ? v.nb : v.nf),
-                                          up ? v.bidx : v.fidx, T->grad, st));
+                                          up ? v.bidx : v.fidx, T->opt.g, st));
     }
   return 0;
-}
-
-int crnn_train_apply(cm_convrnn *m, hipStream_t st) {
-  CrnnTrain *T = m->train;
-  T->step += 1;
-  CM_HIP(cm::launch_amsgrad(T->master, T->grad, T->ea, T->eas, T->vmax, (long long)T->nfloats, T->lr, T->b1, T->b2, T->eps, T->wd, T->step, st));
-  return crnn_train_repack(m, st);
 }
 
 // forward (+ loss) (+ backward) (+ update); the four terms come back after one synchronisation at the end
@@ -364,7 +353,7 @@ int crnn_train_run(cm_convrnn *m, const float *d_past, const float *d_target, in
   if (backward) {
     CM_HIP(cm::launch_crnn_loss_grad(T->yhat, d_target, B, HW, c.future_len, loss_eps, alpha, T->lsums, T->dY, st));
     if (crnn_train_backward(R, tf)) return 1;
-    if (apply_update && crnn_train_apply(m, st)) return 1;
+    if (apply_update && (T->opt.apply(st) || crnn_train_repack(m, st))) return 1;
   }
   if (h_terms) {
     CM_HIP(hipMemcpyAsync(h_terms, T->lterms, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -373,10 +362,9 @@ int crnn_train_run(cm_convrnn *m, const float *d_past, const float *d_target, in
   return 0;
 }
 
-int crnn_train_tensor(const cm_convrnn *m, const char *name, size_t *off, int64_t *numel) {
-  for (size_t i = 0; i < m->params.size(); ++i)
-    if (m->params[i].name == name) { *off = m->train->off[i]; *numel = m->params[i].numel(); return 0; }
-  return fail("unknown ConvRNN parameter '%s'", name);
+int crnn_opt_buffer(OptStore &S, int which, float **buf) {
+  *buf = which == 0 ? S.m : which == 1 ? S.v : which == 2 ? S.vmax : nullptr;
+  return *buf ? 0 : fail("optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq, 2 = max_exp_avg_sq", which);
 }
 
 }  // namespace
@@ -393,9 +381,9 @@ int cm_convrnn_train_init(cm_convrnn *m, float lr, float beta1, float beta2, flo
   DevGuard g(m->device);
   const cm_convrnn_config &c = m->cfg;
   auto T = std::make_unique<CrnnTrain>();
-  T->lr = lr; T->b1 = beta1; T->b2 = beta2; T->eps = eps; T->wd = weight_decay;
-  for (const Param &p : m->params) { T->off.push_back(T->nfloats); T->nfloats += (size_t)p.numel(); }
-  if (T->nfloats >= 0xffffffffULL) return fail("cm_convrnn_train_init: %zu weights exceed the 32-bit index tables", T->nfloats);
+  T->opt.hyper(lr, beta1, beta2, eps, weight_decay);
+  const size_t nfloats = opt_layout(m->params, {}).nfloats;
+  if (nfloats >= 0xffffffffULL) return fail("cm_convrnn_train_init: %zu weights exceed the 32-bit index tables", nfloats);
   size_t bytes = 0;
   auto alloc = [&](float **p, size_t n) {
     n = std::max<size_t>(n, 8);
@@ -406,24 +394,20 @@ int cm_convrnn_train_init(cm_convrnn *m, float lr, float beta1, float beta2, flo
     m->allocs.push_back(*p);
     return 0;
   };
-  for (float **p : {&T->master, &T->grad, &T->ea, &T->eas, &T->vmax})
-    if (alloc(p, T->nfloats)) return 1;
-  for (float *p : {T->grad, T->ea, T->eas, T->vmax}) CM_HIP(hipMemset(p, 0, T->nfloats * sizeof(float)));
-  for (size_t i = 0; i < m->params.size(); ++i)
-    CM_HIP(hipMemcpy(T->master + T->off[i], m->params[i].host.data(), m->params[i].host.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (T->opt.init(m->params, {}, true, alloc)) return 1;
 
   const size_t MB = (size_t)c.max_batch;
   const bool gru = c.cell == CM_CELL_GRU;
   size_t pix[3];
   for (int l = 0; l < 3; ++l) pix[l] = (size_t)m->lh[l] * m->lw[l];
-  std::vector<unsigned> ids(T->nfloats);
+  std::vector<unsigned> ids(nfloats);
   for (size_t k = 0; k < ids.size(); ++k) ids[k] = (unsigned)(k + 1);
   std::vector<unsigned> fi[2], bi[2];
   std::vector<float> fv[2], bv[2];
   for (int i = 0; i < 13; ++i) {
     const CrnnLayer &l = m->L[i];
     const Param *pp = &m->params[l.p0];
-    const size_t *po = &T->off[l.p0];
+    const size_t *po = &T->opt.off[l.p0];
     crnn_pack_train_t<unsigned>(m, i, [&](int j) { return ids.data() + po[j]; }, fi, bi);
     crnn_pack_train_t<float>(m, i, [&](int j) { return pp[j].host.data(); }, fv, bv);
     for (int j = 0; j < 2; ++j) {
@@ -496,13 +480,14 @@ int cm_convrnn_train_step(cm_convrnn *m, const float *d_past, const float *d_tar
 int cm_convrnn_train_apply(cm_convrnn *m, void *stream) {
   if (crnn_train_ready(m, 1, true)) return 1;
   DevGuard g(m->device);
-  return crnn_train_apply(m, stream ? (hipStream_t)stream : m->stream);
+  hipStream_t st = stream ? (hipStream_t)stream : m->stream;
+  return m->train->opt.apply(st) || crnn_train_repack(m, st);
 }
 
 int cm_convrnn_train_set_lr(cm_convrnn *m, float lr) {
   if (crnn_train_ready(m, 1, true)) return 1;
   if (!(lr >= 0.f)) return fail("lr must be >= 0");
-  m->train->lr = lr;
+  m->train->opt.lr = lr;
   return 0;
 }
 
@@ -521,64 +506,33 @@ int cm_convrnn_train_get_forecast(cm_convrnn *m, float *h_out, int64_t numel) {
 
 int cm_convrnn_train_get_grad(cm_convrnn *m, const char *name, float *h_data, int64_t numel) {
   if (crnn_train_ready(m, 1, true)) return 1;
-  if (!name || !h_data) return fail("null argument");
-  size_t off; int64_t n;
-  if (crnn_train_tensor(m, name, &off, &n)) return 1;
-  if (numel != n) return fail("parameter '%s' has %lld elements, got %lld", name, (long long)n, (long long)numel);
   DevGuard g(m->device);
-  CM_HIP(hipDeviceSynchronize());
-  CM_HIP(hipMemcpy(h_data, m->train->grad + off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  return m->train->opt.copy_out(m->params, m->train->opt.g, name, numel, h_data);
 }
 
-static float *crnn_opt_buffer(CrnnTrain *T, int which) { return which == 0 ? T->ea : which == 1 ? T->eas : which == 2 ? T->vmax : nullptr; }
-
 int cm_convrnn_train_get_opt_state(cm_convrnn *m, const char *name, int32_t which, float *h_data, int64_t numel) {
-  if (crnn_train_ready(m, 1, true)) return 1;
-  if (!name || !h_data) return fail("null argument");
-  float *buf = crnn_opt_buffer(m->train, which);
-  if (!buf) return fail("optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq, 2 = max_exp_avg_sq", which);
-  size_t off; int64_t n;
-  if (crnn_train_tensor(m, name, &off, &n)) return 1;
-  if (numel != n) return fail("parameter '%s' has %lld elements, got %lld", name, (long long)n, (long long)numel);
+  float *buf = nullptr;
+  if (crnn_train_ready(m, 1, true) || crnn_opt_buffer(m->train->opt, which, &buf)) return 1;
   DevGuard g(m->device);
-  CM_HIP(hipDeviceSynchronize());
-  CM_HIP(hipMemcpy(h_data, buf + off, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  return m->train->opt.copy_out(m->params, buf, name, numel, h_data);
 }
 
 int cm_convrnn_train_set_opt_state(cm_convrnn *m, const char *name, int32_t which, const float *h_data, int64_t numel) {
-  if (crnn_train_ready(m, 1, true)) return 1;
-  if (!name || !h_data) return fail("null argument");
-  float *buf = crnn_opt_buffer(m->train, which);
-  if (!buf) return fail("optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq, 2 = max_exp_avg_sq", which);
-  size_t off; int64_t n;
-  if (crnn_train_tensor(m, name, &off, &n)) return 1;
-  if (numel != n) return fail("parameter '%s' has %lld elements, got %lld", name, (long long)n, (long long)numel);
+  float *buf = nullptr;
+  if (crnn_train_ready(m, 1, true) || crnn_opt_buffer(m->train->opt, which, &buf)) return 1;
   DevGuard g(m->device);
-  CM_HIP(hipDeviceSynchronize());
-  CM_HIP(hipMemcpy(buf + off, h_data, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
+  return m->train->opt.copy_in(m->params, buf, name, numel, h_data);
 }
 
 int cm_convrnn_train_opt_step(cm_convrnn *m, int32_t *step, int32_t set) {
   if (crnn_train_ready(m, 1, true)) return 1;
-  if (!step) return fail("null argument");
-  if (set) {
-    if (*step < 0) return fail("optimizer step must be >= 0");
-    m->train->step = *step;
-  }
-  *step = m->train->step;
-  return 0;
+  return m->train->opt.opt_step(step, set);
 }
 
 int cm_convrnn_train_sync(cm_convrnn *m) {
   if (crnn_train_ready(m, 1, true)) return 1;
   DevGuard g(m->device);
-  CrnnTrain *T = m->train;
-  CM_HIP(hipDeviceSynchronize());
-  for (size_t i = 0; i < m->params.size(); ++i)
-    CM_HIP(hipMemcpy(m->params[i].host.data(), T->master + T->off[i], m->params[i].host.size() * sizeof(float), hipMemcpyDeviceToHost));
+  if (m->train->opt.pull_masters(m->params)) return 1;
   if (crnn_train_repack(m, m->stream)) return 1;
   CM_HIP(hipStreamSynchronize(m->stream));
   return 0;

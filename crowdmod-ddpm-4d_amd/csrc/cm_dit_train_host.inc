@@ -2,9 +2,10 @@
 // (models/flow_matching/flow_matching.py:104-157) below the host driver: u_pred = DiT2D(x_t, t, past) in train mode,
 // loss = mse(u_pred, u_target), backward, torch.optim.Adam with coupled L2.  Kernels: cm_dit_train.hip, cm_dit.hip.
 //
-// Parameters, gradients and both Adam moments are flat buffers in state_dict order (cm_train_state's layout); the forward reads
-// the master weights in place -- the DiT takes the reference layout, so an update leaves nothing to re-pack.  The eval path keeps
-// its own weight copies and conditioning table (cm_dit_plan::w, modtab), which only cm_dit_train_sync refreshes.
+// Parameters, gradients and both Adam moments live in an OptStore (cm_opt_store.inc) whose frozen tensor is the sinusoid table
+// (index 2 of the state_dict); the forward reads the master weights in place -- the DiT takes the reference layout, so an update
+// leaves nothing to re-pack.  The eval path keeps its own weight copies and conditioning table (cm_dit_plan::w, modtab), which
+// only cm_dit_train_sync refreshes.
 //
 // Tape, per block (allocated for max_batch by cm_dit_train_init): the residual stream entering the block and between its two
 // halves (X cannot be updated in place), QKV, the attention's log-sum-exp and output, the pre-gate output of out_proj, the fc1
@@ -14,11 +15,9 @@
 // weights of the step into mod [B][ldmod]; the forward GEMMs address it through an iota "timestep" buffer.
 
 struct cm_dit_train {
-  size_t nfloats = 0;
-  std::vector<size_t> off;       // per state_dict tensor: offset in the flat buffers
-  float *pbuf = nullptr, *gbuf = nullptr, *mbuf = nullptr, *vbuf = nullptr;
-  float lr = 1e-4f, b1 = 0.5f, b2 = 0.999f, eps = 1e-8f, wd = 0.001f, dropout = 0.1f;
-  int step = 0, last_B = 0;
+  OptStore opt;
+  float dropout = 0.1f;
+  int last_B = 0;
   long long sample_base = 0;
   std::vector<float *> Xs, QKV, AO, Yo, H1, Y2, LSE;   // tape: Xs[2 i] enters block i, Xs[2 i + 1] its MLP half
   float *Hm = nullptr, *G1 = nullptr, *G2 = nullptr, *GH = nullptr, *G3 = nullptr, *XN = nullptr, *Aln = nullptr, *rs = nullptr;
@@ -55,16 +54,11 @@ int ditt_setup(cm_model *m) {
   const size_t tx = D * c.time_multiple, F = sizeof(float);
   size_t maxw = 0, maxb = 1;
   for (const Param &p : m->params) {
-    T->off.push_back(T->nfloats); T->nfloats += (size_t)p.numel(); maxw = std::max(maxw, (size_t)p.numel());
+    maxw = std::max(maxw, (size_t)p.numel());
     if (p.shape.size() == 1) maxb = std::max(maxb, (size_t)p.numel());
   }
-  for (float **b : {&T->pbuf, &T->gbuf, &T->mbuf, &T->vbuf}) {
-    if (dev_alloc(m, (void **)b, T->nfloats * F)) return 1;
-    CM_HIP(hipMemset(*b, 0, T->nfloats * F));
-  }
-  for (size_t i = 0; i < m->params.size(); ++i)
-    CM_HIP(hipMemcpy(T->pbuf + T->off[i], d.w[i], (size_t)m->params[i].numel() * F, hipMemcpyDeviceToDevice));
   auto alloc = [&](float **p, size_t n) { return dev_alloc(m, (void **)p, n * F); };
+  if (T->opt.init(m->params, {2}, false, alloc, d.w.data())) return 1;
   T->Xs.assign(2 * c.depth + 1, nullptr);
   for (float *&x : T->Xs) if (alloc(&x, rows * D)) return 1;
   for (auto *v : {&T->QKV, &T->AO, &T->Yo, &T->H1, &T->Y2, &T->LSE}) v->assign(c.depth, nullptr);
@@ -99,7 +93,7 @@ int ditt_conditioning(cm_model *m, int B, hipStream_t st) {
   cm_dit_train *T = d.train;
   const cm_dit_config &c = d.cfg;
   const int D = c.hidden_size, tx = D * c.time_multiple, nch = d.nchunk(), pb = d.per_block();
-  auto W = [&](int i) { return T->pbuf + T->off[i]; };
+  auto W = [&](int i) { return T->opt.p + T->opt.off[i]; };
   auto lin = [&](const float *A, int K, int wi, float *Y, int N, int ldy) {
     cm::DitGemmArgs a = dit_gemm_args(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, B, N, K);
     a.A = A; a.lda = K; a.W = W(wi); a.bias = W(wi + 1); a.Y = Y; a.ldy = ldy;
@@ -127,7 +121,7 @@ int ditt_forward(cm_model *m, int B, uint64_t seed, hipStream_t st) {
   const cm_dit_config &c = d.cfg;
   const int D = c.hidden_size, D3 = 3 * D, mlp = c.mlp_hidden, nq = d.Tp - d.qs, nch = d.nchunk(), pb = d.per_block();
   const long long M = (long long)B * d.tok;
-  auto W = [&](int i) { return T->pbuf + T->off[i]; };
+  auto W = [&](int i) { return T->opt.p + T->opt.off[i]; };
   cm::DitGemmArgs base{};
   base.tok = d.tok; base.tbuf = T->iota; base.mod = T->mod; base.ldmod = d.ldmod;
   base.L = m->L(); base.Hh = c.rows; base.Ww = c.cols; base.p = c.patch_size; base.pt = 1;
@@ -137,7 +131,7 @@ int ditt_forward(cm_model *m, int B, uint64_t seed, hipStream_t st) {
     a.pro = pro; a.epi = epi; a.M = rows; a.N = N; a.K = K; a.grp = (int)rows;
     return a;
   };
-  cm::DitDrop dr{seed, T->sample_base, T->step, 0, T->dropout};
+  cm::DitDrop dr{seed, T->sample_base, T->opt.step, 0, T->dropout};
   cm::DitGemmArgs a = gemm(cm::DIT_PRO_PATCH, cm::DIT_EPI_PATCH, M, D, d.Kp);
   a.x8 = m->x8; a.W = W(9); a.bias = W(10); a.Y = T->Xs[0]; a.ldy = D; a.spos = W(0); a.tpos = W(1);
   CM_HIP(cm::launch_dit_gemm(a, st));
@@ -179,8 +173,8 @@ int ditt_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hipS
   const int D = c.hidden_size, D3 = 3 * D, mlp = c.mlp_hidden, nq = d.Tp - d.qs, nch = d.nchunk(), pb = d.per_block();
   const int tx = D * c.time_multiple;
   const long long M = (long long)B * d.tok, Mf = (long long)B * nq * d.Ns;
-  auto W = [&](int i) { return T->pbuf + T->off[i]; };
-  auto G = [&](int i) { return T->gbuf + T->off[i]; };
+  auto W = [&](int i) { return T->opt.p + T->opt.off[i]; };
+  auto G = [&](int i) { return T->opt.g + T->opt.off[i]; };
   // dX [rows][Kin] (+)= dY [rows][Nout] W [Nout][Kin]
   auto gemm_dx = [&](const float *dY, int ldy, const float *Wm, float *dXo, long long rows, int Kin, int Nout, int accum) {
     cm::DitTrGemmArgs g{dY, Wm, dXo, (int)rows, Kin, Nout, ldy, Kin, Kin, 0, accum, 1, 0, nullptr};
@@ -201,8 +195,8 @@ int ditt_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hipS
   };
   cm::DitTrLnArgs ln{};
   ln.XN = T->XN; ln.A = T->Aln; ln.rs = T->rs; ln.dX = T->dX; ln.mod = T->mod; ln.ldmod = d.ldmod; ln.D = D; ln.tok = d.tok;
-  cm::DitDrop dr{seed, T->sample_base, T->step, 0, T->dropout};
-  CM_HIP(hipMemsetAsync(T->gbuf, 0, T->nfloats * sizeof(float), st));
+  cm::DitDrop dr{seed, T->sample_base, T->opt.step, 0, T->dropout};
+  CM_HIP(hipMemsetAsync(T->opt.g, 0, T->opt.nfloats * sizeof(float), st));
   CM_HIP(hipMemsetAsync(T->dX, 0, (size_t)M * D * sizeof(float), st));
 
   // loss -> final layer (future rows only, compact)
@@ -289,26 +283,6 @@ int ditt_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hipS
   return 0;
 }
 
-// torch.optim.Adam over every tensor but the frozen sinusoid table (index 2 of DiT2D's state_dict: nn.Embedding.from_pretrained)
-int ditt_apply(cm_model *m, hipStream_t st) {
-  cm_dit_train *T = m->dit->train;
-  T->step += 1;
-  const size_t lo = T->off[2], hi = T->off[3];
-  CM_HIP(cm::launch_adam(T->pbuf, T->gbuf, T->mbuf, T->vbuf, (long long)lo, T->lr, T->b1, T->b2, T->eps, T->wd, T->step, st));
-  CM_HIP(cm::launch_adam(T->pbuf + hi, T->gbuf + hi, T->mbuf + hi, T->vbuf + hi, (long long)(T->nfloats - hi), T->lr, T->b1, T->b2,
-                         T->eps, T->wd, T->step, st));
-  return 0;
-}
-
-int ditt_find(cm_model *m, const char *what, const char *name, int64_t numel, size_t *off) {
-  if (!name) return fail("%s: null name", what);
-  auto it = m->pindex.find(name);
-  if (it == m->pindex.end()) return fail("%s: unknown parameter %s", what, name);
-  if (numel != m->params[it->second].numel()) return fail("%s: size mismatch for %s", what, name);
-  *off = m->dit->train->off[it->second];
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -328,14 +302,14 @@ int cm_dit_train_init(cm_model *m, float lr, float beta1, float beta2, float eps
       return 1;
     }
   }
-  cm_dit_train *T = m->dit->train;
-  T->lr = lr; T->b1 = beta1; T->b2 = beta2; T->eps = eps; T->wd = weight_decay; T->dropout = dropout_rate;
+  m->dit->train->opt.hyper(lr, beta1, beta2, eps, weight_decay);
+  m->dit->train->dropout = dropout_rate;
   return 0;
 }
 
 int cm_dit_train_set_lr(cm_model *m, float lr) {
   if (ditt_check(m, "cm_dit_train_set_lr", true)) return 1;
-  m->dit->train->lr = lr;
+  m->dit->train->opt.lr = lr;
   return 0;
 }
 
@@ -363,7 +337,7 @@ int cm_dit_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, co
   CM_HIP(cm::launch_mse_loss(T->pred, d_target, (long long)B * m->per_sample(), T->mse_partial, T->mse_loss, st));
   T->last_B = B;
   if (ditt_backward(m, d_target, B, seed, st)) return 1;
-  if (apply_update && ditt_apply(m, st)) return 1;
+  if (apply_update && T->opt.apply(st)) return 1;
   CM_HIP(hipMemcpyAsync(h_loss, T->mse_loss, sizeof(float), hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
   return 0;
@@ -371,60 +345,44 @@ int cm_dit_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, co
 
 int cm_dit_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel) {
   if (ditt_check(m, "cm_dit_train_flat_grads", true)) return 1;
-  if (!d_grads || !numel) return fail("cm_dit_train_flat_grads: null argument");
-  *d_grads = m->dit->train->gbuf;
-  *numel = (int64_t)m->dit->train->nfloats;
-  return 0;
+  return m->dit->train->opt.flat_grads(d_grads, numel);
 }
 
 int cm_dit_train_apply(cm_model *m, void *stream) {
   if (ditt_check(m, "cm_dit_train_apply", true)) return 1;
   DevGuard g(m->device);
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  if (ditt_apply(m, st)) return 1;
+  if (m->dit->train->opt.apply(st)) return 1;
   CM_HIP(hipStreamSynchronize(st));
   return 0;
 }
 
 int cm_dit_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel) {
-  size_t off = 0;
   if (ditt_check(m, "cm_dit_train_get_grad", true)) return 1;
-  if (!h_out) return fail("cm_dit_train_get_grad: null argument");
-  if (ditt_find(m, "cm_dit_train_get_grad", name, numel, &off)) return 1;
   DevGuard g(m->device);
-  CM_HIP(hipMemcpy(h_out, m->dit->train->gbuf + off, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  return m->dit->train->opt.copy_out(m->params, m->dit->train->opt.g, name, numel, h_out);
 }
 
-// which: 0 exp_avg, 1 exp_avg_sq, 2 the master weights themselves
+// which: 0 exp_avg, 1 exp_avg_sq, and on get only 2 the master weights themselves
 int cm_dit_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel) {
-  size_t off = 0;
   if (ditt_check(m, "cm_dit_train_get_opt_state", true)) return 1;
-  if (!h_out || which < 0 || which > 2) return fail("cm_dit_train_get_opt_state: bad argument");
-  if (ditt_find(m, "cm_dit_train_get_opt_state", name, numel, &off)) return 1;
+  if (which < 0 || which > 2) return fail("cm_dit_train_get_opt_state: optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq, 2 = master weights", which);
   DevGuard g(m->device);
-  cm_dit_train *T = m->dit->train;
-  const float *src = (which == 0 ? T->mbuf : which == 1 ? T->vbuf : T->pbuf) + off;
-  CM_HIP(hipMemcpy(h_out, src, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  OptStore &S = m->dit->train->opt;
+  return S.copy_out(m->params, which == 0 ? S.m : which == 1 ? S.v : S.p, name, numel, h_out);
 }
 
 int cm_dit_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel) {
-  size_t off = 0;
   if (ditt_check(m, "cm_dit_train_set_opt_state", true)) return 1;
-  if (!h_in || which < 0 || which > 1) return fail("cm_dit_train_set_opt_state: bad argument");
-  if (ditt_find(m, "cm_dit_train_set_opt_state", name, numel, &off)) return 1;
+  if (which < 0 || which > 1) return fail("cm_dit_train_set_opt_state: optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq", which);
   DevGuard g(m->device);
-  cm_dit_train *T = m->dit->train;
-  CM_HIP(hipMemcpy((which == 0 ? T->mbuf : T->vbuf) + off, h_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
+  OptStore &S = m->dit->train->opt;
+  return S.copy_in(m->params, which ? S.v : S.m, name, numel, h_in);
 }
 
 int cm_dit_train_opt_step(cm_model *m, int32_t *step, int32_t set) {
   if (ditt_check(m, "cm_dit_train_opt_step", true)) return 1;
-  if (!step) return fail("cm_dit_train_opt_step: null argument");
-  if (set) m->dit->train->step = *step; else *step = m->dit->train->step;
-  return 0;
+  return m->dit->train->opt.opt_step(step, set);
 }
 
 // The master weights into the handle's state_dict and into the eval path's weight copies, and the 1000-row conditioning table
@@ -434,12 +392,9 @@ int cm_dit_train_sync(cm_model *m) {
   DevGuard g(m->device);
   cm_dit_plan &d = *m->dit;
   cm_dit_train *T = d.train;
-  CM_HIP(hipDeviceSynchronize());
-  for (size_t i = 0; i < m->params.size(); ++i) {
-    const size_t bytes = (size_t)m->params[i].numel() * sizeof(float);
-    CM_HIP(hipMemcpy(m->params[i].host.data(), T->pbuf + T->off[i], bytes, hipMemcpyDeviceToHost));
-    CM_HIP(hipMemcpy(const_cast<float *>(d.w[i]), T->pbuf + T->off[i], bytes, hipMemcpyDeviceToDevice));
-  }
+  if (T->opt.pull_masters(m->params)) return 1;
+  for (size_t i = 0; i < m->params.size(); ++i)
+    CM_HIP(hipMemcpy(const_cast<float *>(d.w[i]), T->opt.p + T->opt.off[i], (size_t)m->params[i].numel() * sizeof(float), hipMemcpyDeviceToDevice));
   return dit_build_tables(m);
 }
 

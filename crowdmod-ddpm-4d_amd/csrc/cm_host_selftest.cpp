@@ -1154,9 +1154,50 @@ void test_misc_errors() {
   EXPECT(linspace_f32(0.f, 1.f, 10, 0) == 0.f && linspace_f32(0.f, 1.f, 10, 9) == 1.f && linspace_f32(3.f, 5.f, 1, 0) == 3.f);
 }
 
+// The optimizer store's layout (cm_opt_store.inc): offsets are the prefix sums of the tensor sizes, the trainable ranges the
+// complement of the frozen tensors, never an empty one; and the store's refusals that need no device.
+void test_opt_store() {
+  using Ranges = std::vector<std::pair<size_t, size_t>>;
+  auto params = [](std::vector<std::vector<int64_t>> shapes) {
+    std::vector<Param> ps;
+    for (auto &s : shapes) { Param p; p.name = "t" + std::to_string(ps.size()); p.shape = s; ps.push_back(p); }
+    return ps;
+  };
+  for (const auto &ps : {params({{5}, {3, 2}, {7}, {2, 1, 2}}), params({{1000, 16}, {16, 3, 3, 3}, {16}, {1}, {9}}), params({{3}, {1}, {4}, {1}})}) {
+    std::vector<size_t> off;
+    size_t n = 0;
+    for (const Param &p : ps) { off.push_back(n); n += (size_t)p.numel(); }
+    const int last = (int)ps.size() - 1;
+    const OptLayout a = opt_layout(ps, {0}), b = opt_layout(ps, {2}), c = opt_layout(ps, {});
+    EXPECT(a.off == off && b.off == off && c.off == off && a.nfloats == n && b.nfloats == n && c.nfloats == n);
+    EXPECT((a.ranges == Ranges{{off[1], n}} && b.ranges == Ranges{{0, off[2]}, {off[3], n}} && c.ranges == Ranges{{0, n}}));
+    EXPECT((opt_layout(ps, {last}).ranges == Ranges{{0, off[last]}}));            // a frozen last tensor: no empty tail
+    EXPECT((opt_layout(ps, {1, 2}).ranges == Ranges{{0, off[1]}, {off[3], n}}));  // adjacent frozen tensors: nothing between them
+    OptStore S;
+    static_cast<OptLayout &>(S) = b;
+    size_t o = ~(size_t)0;
+    EXPECT(S.find(ps, "t2", ps[2].numel(), &o) == 0 && o == off[2]);
+    EXPECT(S.find(ps, "t9", 1, &o) != 0 && strstr(cm_last_error(), "unknown parameter t9"));
+    EXPECT(S.find(ps, "t2", ps[2].numel() + 1, &o) != 0 && strstr(cm_last_error(), "size mismatch for t2") && o == off[2]);
+    int32_t s = 4, neg = -1;
+    EXPECT(S.opt_step(&s, 1) == 0 && s == 4 && S.step == 4);
+    EXPECT(S.opt_step(&neg, 1) != 0 && strstr(cm_last_error(), "must be >= 0") && S.step == 4 && neg == -1);
+    EXPECT(S.opt_step(&neg, 0) == 0 && neg == 4 && S.opt_step(nullptr, 0) != 0);
+  }
+  // the UNet family's accessors take which 0 and 1 only, and say so before they look at the handle
+  float x = 0.f;
+  for (int which : {-1, 2, 3}) {
+    EXPECT(cm_train_get_opt_state(nullptr, "first.bias", which, &x, 1) != 0 && strstr(cm_last_error(), "0 = exp_avg, 1 = exp_avg_sq"));
+    EXPECT(cm_train_set_opt_state(nullptr, "first.bias", which, &x, 1) != 0 && strstr(cm_last_error(), "0 = exp_avg, 1 = exp_avg_sq"));
+  }
+  EXPECT(cm_train_get_opt_state(nullptr, "first.bias", 1, &x, 1) != 0 && strstr(cm_last_error(), "bad argument"));
+  printf("test_opt_store ok\n");
+}
+
 }  // namespace
 
 int main() {
+  test_opt_store();
   test_schedule();
   test_plan_and_params();
   test_packers();

@@ -588,7 +588,7 @@ hipError_t launch_crnn_pack_frames(const float *src, float *win, int B, int H, i
 hipError_t launch_crnn_state_nchw(const float *src, float *dst, int B, int C, int h, int w, hipStream_t st);
 
 // ConvRNN training (cm_convrnn_train.hip): data gradients and weight gradients as gather-form GEMMs of the forward's tile
-// family, the gate backward, the loss and AMSGrad.  Determinism as in the forward: one writer per element, fixed order.
+// family, the gate backward and the loss (the AMSGrad update is launch_adam).  Determinism as in the forward: one writer per element, fixed order.
 // Gather geometries of a source S [B][Hs][Ws][.] seen from row pixel (qy, qx):
 //   S1  3 x 3 taps, S(qy + ty - 1, qx + tx - 1)               G4  4 x 4 taps, S(2 qy - 1 + ty, 2 qx - 1 + tx)
 //   S2  3 x 3 taps, S(2 qy + ty - 1, 2 qx + tx - 1)
@@ -643,9 +643,6 @@ hipError_t launch_crnn_loss(const float *yhat, const float *y, int B, int HW, in
 // d (rloss + alpha vloss) / d yhat into dY [F][B][HW][8] (channels 4-7 zero), from the finalised sums
 hipError_t launch_crnn_loss_grad(const float *yhat, const float *y, int B, int HW, int F, double eps, double alpha,
                                  const double *sums, float *dY, hipStream_t st);
-// torch.optim.Adam(amsgrad=True) with coupled L2: launch_adam plus vmax = max(vmax, v), sqrt(vmax) in the denominator
-hipError_t launch_amsgrad(float *p, const float *g, float *m, float *v, float *vmax, long long n, float lr, float b1, float b2,
-                          float eps, float wd, int step, hipStream_t st);
 
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.
@@ -879,7 +876,8 @@ struct TimeBwdArgs {
   float *dW1, *db1, *dW2, *db2, *dWd, *dbd;
 };
 hipError_t launch_time_bwd(const TimeBwdArgs &a, hipStream_t st);
-hipError_t launch_adam(float *p, const float *g, float *m, float *v, long long n, float lr, float b1, float b2,
+// torch.optim.Adam with coupled L2 over n elements; with vmax, Adam(amsgrad=True): vmax = max(vmax, v), sqrt(vmax) in the denominator
+hipError_t launch_adam(float *p, const float *g, float *m, float *v, float *vmax, long long n, float lr, float b1, float b2,
                        float eps, float wd, int step, hipStream_t st);
 // Winograd-transformed weights (cm_conv_wino.hip layout, pack_wino) re-derived from the master parameters after an optimizer
 // step: element (n tile, chunk, xi_y, z tap, k half, xi_x, lane, jj) = sum_{dy,dx} G[xi_y][dy] G[xi_x][dx] W[idx27[(co, ci)][dz, dy, dx]].

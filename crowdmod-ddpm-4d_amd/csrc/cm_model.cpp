@@ -2866,6 +2866,7 @@ int cm_model_class_flops(const cm_model *m, int32_t B, double flops[8]) {
 
 }  // extern "C"
 
+#include "cm_opt_store.inc"
 #include "cm_train_host.inc"
 #include "cm_dit_train_host.inc"
 #include "cm_convrnn_host.inc"

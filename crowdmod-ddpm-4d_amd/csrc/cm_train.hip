@@ -1549,26 +1549,30 @@ hipError_t launch_time_bwd(const TimeBwdArgs &a, hipStream_t st) {
 }
 
 // --------------------------------------------------------------------------------
-// Adam with coupled L2 (torch.optim.Adam(weight_decay=wd), ddpm.py:53-56), elementwise.
+// Adam with coupled L2 (torch.optim.Adam(weight_decay=wd), ddpm.py:53-56), elementwise; AMS (amsgrad=True): sqrt(max(vmax, v)) below.
 // --------------------------------------------------------------------------------
+template <bool AMS>
 __global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                            float *__restrict__ v, long long n, float lr, float b1, float b2, float eps, float wd,
-                            float bc1, float bc2) {
+                            float *__restrict__ v, float *__restrict__ vmax, long long n, float lr, float b1, float b2,
+                            float eps, float wd, float bc1, float bc2) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float gg = g[i] + wd * p[i];
   const float mm = b1 * m[i] + (1.0f - b1) * gg;
   const float vv = b2 * v[i] + (1.0f - b2) * gg * gg;
+  const float vx = AMS ? fmaxf(vmax[i], vv) : vv;
   m[i] = mm;
   v[i] = vv;
-  p[i] -= (lr / bc1) * mm / (sqrtf(vv) / sqrtf(bc2) + eps);
+  if constexpr (AMS) vmax[i] = vx;
+  p[i] -= (lr / bc1) * mm / (sqrtf(vx) / sqrtf(bc2) + eps);
 }
 
-hipError_t launch_adam(float *p, const float *g, float *m, float *v, long long n, float lr, float b1, float b2,
+hipError_t launch_adam(float *p, const float *g, float *m, float *v, float *vmax, long long n, float lr, float b1, float b2,
                        float eps, float wd, int step, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
   const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps,
-                     wd, bc1, bc2);
+  hipLaunchKernelGGL(vmax ? adam_kernel<true> : adam_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, g, m, v,
+                     vmax, n, lr, b1, b2, eps, wd, bc1, bc2);
   return hipGetLastError();
 }
 

@@ -14,15 +14,11 @@
 
 struct cm_train_state {
   std::set<const Act *> gset;  // backward pass: tensors whose gradient buffer has received a contribution
-  // flat parameter storage in state_dict order: master weights, gradients, Adam moments
-  size_t nfloats = 0;
-  std::map<std::string, size_t> poff;
-  float *pbuf = nullptr, *gbuf = nullptr, *mbuf = nullptr, *vbuf = nullptr;
-  float lr = 5e-5f, b1 = 0.5f, b2 = 0.999f, eps = 1e-8f, wd = 0.003f;
+  // master weights, gradients, Adam moments; frozen: the sinusoid table, first tensor of the state_dict (requires_grad False, embeddings.py:24)
+  OptStore opt;
   float dropout = 0.1f;  // nn.Dropout3d(p) of the ResnetBlocks (layers.py:42), cfg DROPOUT_RATE
-  int step = 0;
   hipEvent_t ev_dy = nullptr, ev_wdone = nullptr;   // backward: weight-gradient launches run on a second stream (see backward_ops)
-  // derived device tensors refreshed from pbuf after every optimizer step
+  // derived device tensors refreshed from the master weights (opt.p) after every optimizer step
   struct Derived { float *dst; int *d_idx; int nk; long long n; bool bwd_only; };
   std::vector<Derived> derived;
   cm::PackJob *d_jobs = nullptr;   // the same list as one device-side job table
@@ -91,17 +87,22 @@ void cm_free_train_state(cm_train_state *t) {
 
 namespace {
 
-float *grad_of(cm_model *m, const std::string &name) { return m->train->gbuf + m->train->poff.at(name); }
+size_t off_of(cm_model *m, const std::string &name) { return m->train->opt.off[m->pindex.at(name)]; }   // offset in the flat buffers
+float *grad_of(cm_model *m, const std::string &name) { return m->train->opt.g + off_of(m, name); }
 
-// positions in the flat parameter buffer (pbuf) of a conv weight's elements, in the internal tap order [Co][Ci][t]: the layouts of
-// cm_pack.h, fed with these instead of the values, give the index maps of the device re-pack
+// positions in the flat parameter buffer (opt.p) of a tensor's elements, in state_dict order
+std::vector<int> flat_index(cm_model *m, const std::string &name) {
+  std::vector<int> v((size_t)P(m, name).numel());
+  std::iota(v.begin(), v.end(), (int)off_of(m, name));
+  return v;
+}
+// ... of a conv weight's elements, in the internal tap order [Co][Ci][t]: the layouts of cm_pack.h, fed with these instead of the
+// values, give the index maps of the device re-pack
 std::vector<int> ref_index_internal(cm_model *m, const std::string &wname, int Co, int Ci, int ntaps) {
-  std::vector<int> ref((size_t)Co * Ci * ntaps);
-  std::iota(ref.begin(), ref.end(), (int)m->train->poff.at(wname));
-  return to_internal_taps(ref.data(), Co, Ci, ntaps);
+  return to_internal_taps(flat_index(m, wname).data(), Co, Ci, ntaps);
 }
 
-// a device tensor re-derived from pbuf after every optimizer step: element i = sum over its nk indices (-1: none) of pbuf[index]
+// a device tensor re-derived from opt.p after every optimizer step: element i = sum over its nk indices (-1: none) of opt.p[index]
 int add_derived(cm_model *m, float *dst, const int *idx, size_t count, int nk, bool bwd_only = false) {
   cm_train_state::Derived d;
   d.dst = dst; d.nk = nk; d.n = (long long)(count / nk); d.bwd_only = bwd_only;
@@ -159,7 +160,7 @@ int refresh_h2(cm_model *m) {
   auto fetch = [&](const std::string &name, std::vector<float> *out) -> int {
     const Param &pr = P(m, name);
     out->resize((size_t)pr.numel());
-    CM_HIP(hipMemcpy(out->data(), T->pbuf + T->poff[name], out->size() * sizeof(float), hipMemcpyDeviceToHost));
+    CM_HIP(hipMemcpy(out->data(), T->opt.p + off_of(m, name), out->size() * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   };
   std::vector<float> w, gam, bet, frag;
@@ -185,7 +186,7 @@ int refresh_h2(cm_model *m) {
     float *dst = kind == H2_WINO ? op.d_wwino_h2 : kind == H2_QR ? op.d_wqr_h2 : op.d_wups_h2;
     const float ws = h2_pack(op, kind, w.data(), &frag);
     if (!(ws > 0.f)) { op.h2_off = true; continue; }
-    if (kind == H2_FIN) CM_HIP(cm::launch_fin_pack(T->pbuf + T->poff[op.wname], op.d_wfin_h2, op.ca.Co, 2, m->stream, ws));
+    if (kind == H2_FIN) CM_HIP(cm::launch_fin_pack(T->opt.p + off_of(m, op.wname), op.d_wfin_h2, op.ca.Co, 2, m->stream, ws));
     else CM_HIP(hipMemcpy(dst, frag.data(), frag.size() * sizeof(float), hipMemcpyHostToDevice));
     op.h2_oscale = 1.f / ws;
   }
@@ -217,7 +218,7 @@ int repack_all(cm_model *m, hipStream_t st) {
     T->pack_total = total;
     T->pack_blocks = (long long)b2j.size();
   }
-  CM_HIP(cm::launch_gather_pack_jobs(T->pbuf, T->d_jobs, T->d_blk2job, T->pack_blocks, st));
+  CM_HIP(cm::launch_gather_pack_jobs(T->opt.p, T->d_jobs, T->d_blk2job, T->pack_blocks, st));
   if (!T->d_wjobs && !T->derived_wino.empty()) {
     std::vector<cm::WinoPackJob> jobs;
     std::vector<int> b2j;
@@ -233,7 +234,7 @@ int repack_all(cm_model *m, hipStream_t st) {
     CM_HIP(hipMemcpy(T->d_wblk2job, b2j.data(), b2j.size() * sizeof(int), hipMemcpyHostToDevice));
     T->wpack_blocks = (long long)b2j.size();
   }
-  CM_HIP(cm::launch_wino_pack_jobs(T->pbuf, T->d_wjobs, T->d_wblk2job, T->wpack_blocks, st));
+  CM_HIP(cm::launch_wino_pack_jobs(T->opt.p, T->d_wjobs, T->d_wblk2job, T->wpack_blocks, st));
   // the split fragments of the inference forward follow the fp32 fragments just re-derived above
   for (Op &op : m->ops) {
     if (op.kind != OP_CONV) continue;
@@ -241,7 +242,7 @@ int repack_all(cm_model *m, hipStream_t st) {
       CM_HIP(cm::launch_ups_b6_repack(op.ca.wfrag, op.ca.wpar_stride, op.d_wups_b6, op.wups_b6_stride, op.ca.Co, op.ca.C0, op.NB, st));
     if (op.d_wwino_b6) CM_HIP(cm::launch_wino_b6_repack(op.d_wwino, op.d_wwino_b6, op.wwino_floats, st));
     if (op.d_wqr_b6) CM_HIP(cm::launch_qr_b6_repack(op.d_wqr, op.d_wqr_b6, op.wqr_floats, op.ca.C0 + op.ca.C1, st));
-    if (op.d_wfin) CM_HIP(cm::launch_fin_pack(T->pbuf + T->poff[op.wname], op.d_wfin, op.ca.Co, 0, st));   // the last conv's column-packed fragments
+    if (op.d_wfin) CM_HIP(cm::launch_fin_pack(T->opt.p + off_of(m, op.wname), op.d_wfin, op.ca.Co, 0, st));   // the last conv's column-packed fragments
   }
   for (auto &D : T->dg) {
     if (D.wwino_b6) CM_HIP(cm::launch_wino_b6_repack(D.wwino, D.wwino_b6, D.wwino_floats, st));
@@ -254,16 +255,7 @@ int train_setup(cm_model *m) {
   cm_train_state *T = m->train;
   const cm_unet_config &c = m->cfg;
   const size_t B = (size_t)c.max_batch;
-  // ---- flat parameter buffers ----
-  size_t off = 0;
-  for (auto &p : m->params) { T->poff[p.name] = off; off += (size_t)p.numel(); }
-  T->nfloats = off;
-  for (float **b : {&T->pbuf, &T->gbuf, &T->mbuf, &T->vbuf}) {
-    if (dev_alloc(m, (void **)b, off * sizeof(float))) return 1;
-    CM_HIP(hipMemset(*b, 0, off * sizeof(float)));
-  }
-  for (auto &p : m->params)
-    CM_HIP(hipMemcpy(T->pbuf + T->poff[p.name], p.host.data(), (size_t)p.numel() * sizeof(float), hipMemcpyHostToDevice));
+  if (T->opt.init(m->params, {0}, false, [&](float **p, size_t n) { return dev_alloc(m, (void **)p, n * sizeof(float)); })) return 1;
 
   // ---- activation gradients, GroupNorm mean/rstd, maximal channel count ----
   int Cmax = 8;
@@ -326,21 +318,13 @@ int train_setup(cm_model *m) {
   for (size_t oi = 0; oi < m->ops.size(); ++oi) {
     Op &op = m->ops[oi];
     if (op.kind == OP_GNFIN) {
-      const size_t ng = P(m, op.gname).host.size();
-      std::vector<int> ig(ng), ib(ng);
-      for (size_t i = 0; i < ng; ++i) { ig[i] = (int)(T->poff[op.gname] + i); ib[i] = (int)(T->poff[op.bename] + i); }
-      if (add_derived(m, const_cast<float *>(op.gamma), ig, 1)) return 1;
-      if (add_derived(m, const_cast<float *>(op.beta), ib, 1)) return 1;
+      if (add_derived(m, const_cast<float *>(op.gamma), flat_index(m, op.gname), 1)) return 1;
+      if (add_derived(m, const_cast<float *>(op.beta), flat_index(m, op.bename), 1)) return 1;
       continue;
     }
     if (op.kind == OP_ATTNBLK) {
       // reference-layout weight copies of the fused attention block follow the master weights too
-      for (auto nw : {std::make_pair(op.win_name, op.d_win), std::make_pair(op.wout_name, op.d_wout)}) {
-        const size_t k = P(m, nw.first).host.size();
-        std::vector<int> v(k);
-        for (size_t i = 0; i < k; ++i) v[i] = (int)(T->poff[nw.first] + i);
-        if (add_derived(m, nw.second, v, 1)) return 1;
-      }
+      if (add_derived(m, op.d_win, flat_index(m, op.win_name), 1) || add_derived(m, op.d_wout, flat_index(m, op.wout_name), 1)) return 1;
       continue;
     }
     if (op.kind != OP_CONV) continue;
@@ -366,7 +350,7 @@ int train_setup(cm_model *m) {
       if (add_derived(m, op.d_s2w, pack_conv(i2.data(), Co, Ci2, 1, Ci2, 32, op.NB, -1), 1)) return 1;
       const int TNf = 32 * op.NB, cpf = (op.ca.Co + TNf - 1) / TNf * TNf;
       std::vector<int> ibf((size_t)cpf * 2, -1);
-      for (int i = 0; i < Co; ++i) { ibf[2 * i] = (int)(T->poff[op.bname] + i); ibf[2 * i + 1] = (int)(T->poff[op.skip_b] + i); }
+      for (int i = 0; i < Co; ++i) { ibf[2 * i] = (int)(off_of(m, op.bname) + i); ibf[2 * i + 1] = (int)(off_of(m, op.skip_b) + i); }
       if (add_derived(m, op.d_bias_fused, ibf, 2)) return 1;
     }
     if (op.wino) {
@@ -385,7 +369,7 @@ int train_setup(cm_model *m) {
     {
       const int TN = 32 * op.NB, co_pad = (op.ca.Co + TN - 1) / TN * TN;
       std::vector<int> ib((size_t)co_pad, -1);
-      for (int i = 0; i < Co; ++i) ib[i] = (int)(T->poff[op.bname] + i);
+      for (int i = 0; i < Co; ++i) ib[i] = (int)(off_of(m, op.bname) + i);
       if (add_derived(m, const_cast<float *>(op.ca.bias), ib, 1)) return 1;
     }
     // ---- data gradient: dA[.., Ctot_in] = conv(dY, W'),  W'[ci][co][t'] = W[co][ci][flip t'] ----
@@ -484,21 +468,15 @@ int train_setup(cm_model *m) {
   }
   // time-embedding MLP copies
   {
-    auto map1 = [&](const std::string &n) {
-      const size_t k = P(m, n).host.size();
-      std::vector<int> v(k);
-      for (size_t i = 0; i < k; ++i) v[i] = (int)(T->poff[n] + i);
-      return v;
-    };
-    if (add_derived(m, m->d_time[1], map1("time_embeddings.time_blocks.1.weight"), 1)) return 1;
-    if (add_derived(m, m->d_time[2], map1("time_embeddings.time_blocks.1.bias"), 1)) return 1;
-    if (add_derived(m, m->d_time[3], map1("time_embeddings.time_blocks.3.weight"), 1)) return 1;
-    if (add_derived(m, m->d_time[4], map1("time_embeddings.time_blocks.3.bias"), 1)) return 1;
+    if (add_derived(m, m->d_time[1], flat_index(m, "time_embeddings.time_blocks.1.weight"), 1)) return 1;
+    if (add_derived(m, m->d_time[2], flat_index(m, "time_embeddings.time_blocks.1.bias"), 1)) return 1;
+    if (add_derived(m, m->d_time[3], flat_index(m, "time_embeddings.time_blocks.3.weight"), 1)) return 1;
+    if (add_derived(m, m->d_time[4], flat_index(m, "time_embeddings.time_blocks.3.bias"), 1)) return 1;
     std::vector<int> wd, bd;
     auto visit = [&](const BlockDesc &b) {
       if (b.kind != 0) return;
-      for (int v : map1(b.prefix + ".dense_1.weight")) wd.push_back(v);
-      for (int v : map1(b.prefix + ".dense_1.bias")) bd.push_back(v);
+      for (int v : flat_index(m, b.prefix + ".dense_1.weight")) wd.push_back(v);
+      for (int v : flat_index(m, b.prefix + ".dense_1.bias")) bd.push_back(v);
     };
     for (auto &b : m->enc) visit(b);
     for (auto &b : m->bott) visit(b);
@@ -811,17 +789,6 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
   return 0;
 }
 
-int apply_adam(cm_model *m, hipStream_t st) {
-  cm_train_state *T = m->train;
-  T->step += 1;
-  // the sinusoid table (first tensor of the state_dict) is frozen: nn.Embedding.from_pretrained
-  // leaves requires_grad False (embeddings.py:24), so Adam never touches it
-  const size_t skip = (size_t)m->params[0].numel();
-  CM_HIP(cm::launch_adam(T->pbuf + skip, T->gbuf + skip, T->mbuf + skip, T->vbuf + skip, (long long)(T->nfloats - skip),
-                         T->lr, T->b1, T->b2, T->eps, T->wd, T->step, st));
-  return repack_all(m, st);
-}
-
 }  // namespace
 
 extern "C" {
@@ -838,8 +805,8 @@ int cm_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, fl
     m->train = new cm_train_state();
     if (train_setup(m)) return 1;
   }
-  cm_train_state *T = m->train;
-  T->lr = lr; T->b1 = beta1; T->b2 = beta2; T->eps = eps; T->wd = weight_decay; T->dropout = dropout_rate;
+  m->train->opt.hyper(lr, beta1, beta2, eps, weight_decay);
+  m->train->dropout = dropout_rate;
   return 0;
 }
 
@@ -852,7 +819,7 @@ int cm_train_set_sample_base(cm_model *m, int64_t sample_id_base) {
 
 int cm_train_set_lr(cm_model *m, float lr) {
   if (!m || !m->train) return fail("cm_train_init has not been called");
-  m->train->lr = lr;
+  m->train->opt.lr = lr;
   return 0;
 }
 
@@ -867,7 +834,7 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
   if (d_dropmask)
     CM_HIP(hipMemcpyAsync(m->dropmask, d_dropmask, (size_t)B * m->nproj * sizeof(float), hipMemcpyDeviceToDevice, st));
   else
-    CM_HIP(cm::launch_dropout_mask(m->dropmask, B, m->nproj, T->dropout, seed, T->sample_base, T->step, st));
+    CM_HIP(cm::launch_dropout_mask(m->dropmask, B, m->nproj, T->dropout, seed, T->sample_base, T->opt.step, st));
   CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
   CM_HIP(cm::launch_time_mlp(m->d_time[0], m->d_time[1], m->d_time[2], m->d_time[3], m->d_time[4], m->d_time[5], m->d_time[6],
                              c.base_channels, c.base_channels * c.time_multiple, m->nproj, B, nullptr, T->train_temb,
@@ -887,7 +854,7 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
   }
   if (!rc) rc = backward_ops(m, B, st);
   if (rc) return 1;
-  if (apply_update && apply_adam(m, st)) return 1;
+  if (apply_update && (T->opt.apply(st) || repack_all(m, st))) return 1;
   CM_HIP(hipMemcpyAsync(h_loss, m->mse_loss, sizeof(float), hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
   return 0;
@@ -929,57 +896,46 @@ int cm_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const 
 }
 
 int cm_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel) {
-  if (!m || !m->train || !name || !h_out) return fail("bad argument");
-  auto it = m->train->poff.find(name);
-  if (it == m->train->poff.end()) return fail("unknown parameter %s", name);
-  const Param &p = m->params[m->pindex.at(name)];
-  if (numel != p.numel()) return fail("size mismatch for %s", name);
+  if (!m || !m->train) return fail("bad argument");
   DevGuard g(m->device);
-  CM_HIP(hipMemcpy(h_out, m->train->gbuf + it->second, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  return m->train->opt.copy_out(m->params, m->train->opt.g, name, numel, h_out);
 }
 
 // Adam state of one tensor (torch.optim.Adam state_dict layout: 'exp_avg', 'exp_avg_sq'; 'step' from
-// cm_train_opt_step) -- what utils/utils.py:140-147 stores under "opt".  which: 0 exp_avg, 1 exp_avg_sq.
+// cm_train_opt_step) -- what utils/utils.py:140-147 stores under "opt".  which: 0 exp_avg, 1 exp_avg_sq, nothing else.
+static int train_which(const char *what, int32_t which) {
+  return which == 0 || which == 1 ? 0 : fail("%s: optimizer state %d: 0 = exp_avg, 1 = exp_avg_sq", what, which);
+}
 int cm_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel) {
-  if (!m || !m->train || !name || !h_out) return fail("bad argument");
-  auto it = m->train->poff.find(name);
-  if (it == m->train->poff.end()) return fail("unknown parameter %s", name);
-  if (numel != m->params[m->pindex.at(name)].numel()) return fail("size mismatch for %s", name);
+  if (train_which("cm_train_get_opt_state", which)) return 1;
+  if (!m || !m->train) return fail("bad argument");
   DevGuard g(m->device);
-  const float *src = (which == 0 ? m->train->mbuf : m->train->vbuf) + it->second;
-  CM_HIP(hipMemcpy(h_out, src, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost));
-  return 0;
+  OptStore &S = m->train->opt;
+  return S.copy_out(m->params, which ? S.v : S.m, name, numel, h_out);
 }
 int cm_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel) {
-  if (!m || !m->train || !name || !h_in) return fail("bad argument");
-  auto it = m->train->poff.find(name);
-  if (it == m->train->poff.end()) return fail("unknown parameter %s", name);
-  if (numel != m->params[m->pindex.at(name)].numel()) return fail("size mismatch for %s", name);
+  if (train_which("cm_train_set_opt_state", which)) return 1;
+  if (!m || !m->train) return fail("bad argument");
   DevGuard g(m->device);
-  float *dst = (which == 0 ? m->train->mbuf : m->train->vbuf) + it->second;
-  CM_HIP(hipMemcpy(dst, h_in, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
+  OptStore &S = m->train->opt;
+  return S.copy_in(m->params, which ? S.v : S.m, name, numel, h_in);
 }
 int cm_train_opt_step(cm_model *m, int32_t *step, int32_t set) {
-  if (!m || !m->train || !step) return fail("bad argument");
-  if (set) m->train->step = *step; else *step = m->train->step;
-  return 0;
+  if (!m || !m->train) return fail("bad argument");
+  return m->train->opt.opt_step(step, set);
 }
 
 // Data-parallel training: the flat gradient buffer (state_dict order, fp32) for an all-reduce between
 // cm_train_step(apply_update=0) and cm_train_apply.
 int cm_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel) {
-  if (!m || !m->train || !d_grads || !numel) return fail("bad argument");
-  *d_grads = m->train->gbuf;
-  *numel = (int64_t)m->train->nfloats;
-  return 0;
+  if (!m || !m->train) return fail("bad argument");
+  return m->train->opt.flat_grads(d_grads, numel);
 }
 int cm_train_apply(cm_model *m, void *stream) {
   if (!m || !m->train) return fail("cm_train_init has not been called");
   DevGuard g(m->device);
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-  if (apply_adam(m, st)) return 1;
+  if (m->train->opt.apply(st) || repack_all(m, st)) return 1;
   CM_HIP(hipStreamSynchronize(st));
   return 0;
 }
@@ -989,9 +945,7 @@ int cm_train_apply(cm_model *m, void *stream) {
 int cm_train_sync(cm_model *m) {
   if (!m || !m->train) return fail("cm_train_init has not been called");
   DevGuard g(m->device);
-  cm_train_state *T = m->train;
-  for (auto &p : m->params)
-    CM_HIP(hipMemcpy(p.host.data(), T->pbuf + T->poff[p.name], (size_t)p.numel() * sizeof(float), hipMemcpyDeviceToHost));
+  if (m->train->opt.pull_masters(m->params)) return 1;
   const cm_unet_config &c = m->cfg;
   CM_HIP(cm::launch_time_mlp(m->d_time[0], m->d_time[1], m->d_time[2], m->d_time[3], m->d_time[4], m->d_time[5], m->d_time[6],
                              c.base_channels, c.base_channels * c.time_multiple, m->nproj, TIME_ROWS, nullptr,

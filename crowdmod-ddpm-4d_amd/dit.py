@@ -14,7 +14,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import dit2d_spec, dit_spec, native
+from . import dit2d_spec, dit_spec, native, optim_state
 from .unet import _is_torch
 
 
@@ -372,24 +372,9 @@ class DiT2D(DiT4D_V4):
         """torch.optim.Adam.state_dict() of the reference optimizer (flow_matching.py:27-30) over
         u_predictor.parameters(): what a checkpoint stores under "opt".  The frozen sinusoid table is a parameter
         without state."""
-        names = self.trainable_names()
-        step, state = self.opt_step(), {}
-        if step > 0:
-            for i, name in enumerate(names):
-                if name != self._TABLE:
-                    state[i] = {"step": np.float32(step), "exp_avg": self.opt_state(name, 0),
-                                "exp_avg_sq": self.opt_state(name, 1)}
-        group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps),
-                 "weight_decay": float(weight_decay), "amsgrad": False, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group]}
+        return optim_state.dump(self.trainable_names(), (self._TABLE,), optim_state.ADAM_KEYS, lr, betas, eps, weight_decay,
+                                self.opt_state, self.opt_step())
 
     def load_optimizer_state_dict(self, opt: dict):
         """Inverse of optimizer_state_dict (resume from a checkpoint's "opt" entry)."""
-        names, step = self.trainable_names(), 0
-        for i, st in opt.get("state", {}).items():
-            for which, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
-                self.set_opt_state(names[int(i)], which, np.asarray(st[key]))
-            step = int(np.asarray(st["step"]).reshape(-1)[0])
-        self.opt_step(step)
+        self.opt_step(optim_state.load(opt, self.trainable_names(), optim_state.ADAM_KEYS, self.set_opt_state))

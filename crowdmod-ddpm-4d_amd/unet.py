@@ -15,7 +15,7 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from . import native, spec
+from . import native, optim_state, spec
 
 
 def _is_torch(x) -> bool:
@@ -356,34 +356,23 @@ class UNet:
         step = C.c_int32()
         native.check(L.cm_train_opt_step(self._handle, C.byref(step), 0))
         names = self.trainable_names()
-        state = {}
-        if step.value > 0:
-            for i, name in enumerate(names):
-                if i == 0:
-                    continue  # requires_grad=False: the optimizer never created state for it
-                shp = self._params[name].shape
-                m1, m2 = np.empty(shp, np.float32), np.empty(shp, np.float32)
-                native.check(L.cm_train_get_opt_state(self._handle, name.encode(), 0, m1.ctypes.data, m1.size))
-                native.check(L.cm_train_get_opt_state(self._handle, name.encode(), 1, m2.ctypes.data, m2.size))
-                state[i] = {"step": np.float32(step.value), "exp_avg": m1, "exp_avg_sq": m2}
-        group = {"lr": float(lr), "betas": (float(betas[0]), float(betas[1])), "eps": float(eps),
-                 "weight_decay": float(weight_decay), "amsgrad": False, "maximize": False, "foreach": None,
-                 "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group]}
+
+        def get(name, which):
+            out = np.empty(self._params[name].shape, np.float32)
+            native.check(L.cm_train_get_opt_state(self._handle, name.encode(), which, out.ctypes.data, out.size))
+            return out
+
+        # names[0], the sinusoid table, has requires_grad=False: the optimizer never created state for it
+        return optim_state.dump(names, names[:1], optim_state.ADAM_KEYS, lr, betas, eps, weight_decay, get, step.value)
 
     def load_optimizer_state_dict(self, opt: dict):
         """Inverse of optimizer_state_dict (resume from a checkpoint's "opt" entry)."""
         L = native.lib()
-        names = self.trainable_names()
-        step = 0
-        for i, st in opt.get("state", {}).items():
-            name = names[int(i)]
-            for which, key in ((0, "exp_avg"), (1, "exp_avg_sq")):
-                arr = np.ascontiguousarray(np.asarray(st[key]), dtype=np.float32)
-                native.check(L.cm_train_set_opt_state(self._handle, name.encode(), which, arr.ctypes.data, arr.size))
-            step = max(step, int(np.asarray(st["step"]).reshape(-1)[0]))
-        cs = C.c_int32(step)
+
+        def put(name, which, arr):
+            native.check(L.cm_train_set_opt_state(self._handle, name.encode(), which, arr.ctypes.data, arr.size))
+
+        cs = C.c_int32(optim_state.load(opt, self.trainable_names(), optim_state.ADAM_KEYS, put))
         native.check(L.cm_train_opt_step(self._handle, C.byref(cs), 1))
 
     def sync_trained(self):

@@ -375,8 +375,10 @@ int cm_train_step(cm_model *m, const cm_schedule *s, const float *d_future, cons
  * buffer from cm_train_flat_grads, then cm_train_apply (Adam + re-pack). */
 int cm_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel);
 int cm_train_apply(cm_model *m, void *stream);
-/* Adam state for the "opt" entry of a checkpoint (utils/utils.py:140-147): which = 0 exp_avg,
- * 1 exp_avg_sq; cm_train_opt_step reads (set=0) or writes (set=1) the step counter. */
+/* Adam state for the "opt" entry of a checkpoint (utils/utils.py:140-147): which = 0 exp_avg, 1 exp_avg_sq; any other
+ * value is refused.  The three families' accessors share these rules: a copy-out (gradient, optimizer state) waits for
+ * the device first; *_opt_step reads the step counter into *step, after setting it from *step when set != 0; a negative
+ * step is refused and changes nothing. */
 int cm_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel);
 int cm_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel);
 int cm_train_opt_step(cm_model *m, int32_t *step, int32_t set);
@@ -415,8 +417,8 @@ int cm_dit_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, co
 int cm_dit_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel);
 int cm_dit_train_apply(cm_model *m, void *stream);
 int cm_dit_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel);
-/* which = 0 exp_avg, 1 exp_avg_sq, 2 (get only) the master weights; cm_dit_train_opt_step reads (set=0) or writes
- * (set=1) the step counter. */
+/* which = 0 exp_avg, 1 exp_avg_sq, 2 (get only) the master weights, anything else is refused; the step counter as in
+ * cm_train_opt_step. */
 int cm_dit_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel);
 int cm_dit_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel);
 int cm_dit_train_opt_step(cm_model *m, int32_t *step, int32_t set);
@@ -496,10 +498,10 @@ int cm_convrnn_train_set_lr(cm_convrnn *m, float lr);
 int cm_convrnn_train_get_forecast(cm_convrnn *m, float *h_out, int64_t numel);
 /* Gradient of a state_dict tensor, in its reference layout (host buffer). */
 int cm_convrnn_train_get_grad(cm_convrnn *m, const char *name, float *h_data, int64_t numel);
-/* which: 0 exp_avg, 1 exp_avg_sq, 2 max_exp_avg_sq. */
+/* which: 0 exp_avg, 1 exp_avg_sq, 2 max_exp_avg_sq, anything else is refused. */
 int cm_convrnn_train_get_opt_state(cm_convrnn *m, const char *name, int32_t which, float *h_data, int64_t numel);
 int cm_convrnn_train_set_opt_state(cm_convrnn *m, const char *name, int32_t which, const float *h_data, int64_t numel);
-/* Reads the optimizer's step count into *step, after setting it from *step when set != 0. */
+/* Reads the optimizer's step count into *step, after setting it from *step when set != 0 (a negative step is refused). */
 int cm_convrnn_train_opt_step(cm_convrnn *m, int32_t *step, int32_t set);
 /* Copies the master weights back to the state_dict (cm_convrnn_get_param) and re-packs every weight layout. */
 int cm_convrnn_train_sync(cm_convrnn *m);

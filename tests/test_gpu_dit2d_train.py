@@ -330,6 +330,18 @@ def test_refusals():
         native.check(L.cm_dit_train_step_xt(net._handle, 1, 1, 1, 1, 0, C.byref(loss), 3, 0, None))
     with pytest.raises(native.NativeError, match="dropout rate"):
         native.check(L.cm_dit_train_init(net._handle, LR, 0.5, 0.999, EPS, WD, 1.0))
+    # the optimizer store's rules: a negative step is refused and changes nothing; `which` 0, 1 and (get only) 2
+    assert net.opt_step(3) == 3
+    with pytest.raises(native.NativeError, match="step must be >= 0"):
+        net.opt_step(-1)
+    assert net.opt_step() == 3 and net.opt_step(0) == 0
+    k = "patch_embed.proj.bias"
+    for which in (-1, 3):
+        with pytest.raises(native.NativeError, match="optimizer state"):
+            net.opt_state(k, which)
+    for which in (-1, 2):
+        with pytest.raises(native.NativeError, match="optimizer state"):
+            net.set_opt_state(k, which, params[k])
     with pytest.raises(RuntimeError, match="training state"):      # a larger eval batch would re-create the handle
         net(np.concatenate([xt, xt]), np.concatenate([t, t]), np.concatenate([past, past]))
     assert net(xt[:2], t[:2], past[:2]).shape == xt[:2].shape      # within the allocation the eval path is open

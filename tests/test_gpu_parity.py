@@ -585,6 +585,20 @@ def test_abi_rejects_bad_arguments_loudly():
         native.check(L.cm_train_apply(h, None))
     with pytest.raises(ValueError):
         net(fut[:, :2], np.array([1, 2]), past)                   # channel mismatch is caught before the call
+    # the optimizer accessors: `which` is 0 or 1 and nothing else; a negative step is refused and changes nothing
+    net.train_init(lr=5e-5, betas=(0.5, 0.999), weight_decay=0.003)
+    buf, step = np.zeros(8, np.float32), C.c_int32(5)
+    for fn in (L.cm_train_get_opt_state, L.cm_train_set_opt_state):
+        for which in (-1, 2):
+            with pytest.raises(native.NativeError, match="0 = exp_avg, 1 = exp_avg_sq"):
+                native.check(fn(h, b"first.bias", which, buf.ctypes.data, 8))
+        native.check(fn(h, b"first.bias", 1, buf.ctypes.data, 8))
+    native.check(L.cm_train_opt_step(h, C.byref(step), 1))
+    step.value = -1
+    with pytest.raises(native.NativeError, match="step must be >= 0"):
+        native.check(L.cm_train_opt_step(h, C.byref(step), 1))
+    native.check(L.cm_train_opt_step(h, C.byref(step), 0))
+    assert step.value == 5
 
 
 @pytest.mark.gpu
