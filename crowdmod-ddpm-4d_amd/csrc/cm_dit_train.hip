@@ -11,7 +11,8 @@
 //   Philox4x32-10, key (seed lo, seed hi), counter (column >> 2, sample, step, 0x80000000 | site << 29 | block << 16 | head << 10 | row),
 //   word (column & 3) -> u = unit_float(word); keep iff u >= p, value 1 / (1 - p) in fp32.
 // site 0: attention probabilities (row = query, column = key); 1: after GELU (row = token, column = hidden unit, head 0);
-// 2: after fc2 (row = token, column = channel, head 0).  Bit 31 of the fourth counter word keeps these draws apart from the
+// 2: after fc2 (row = token, column = channel, head 0); 3: the temporal attention of DiT4D_V4 (cm_dit4d_train.hip), whose spatial
+// attention runs the kernels below per (sample, slot) group and draws at the group's place in its sample (DitDrop::gps).  Bit 31 of the fourth counter word keeps these draws apart from the
 // Dropout3d masks (0xD120) and from philox_normal ((sample >> 32) ^ 0x5eed < 2^31).
 #include "cm_kernels.h"
 
@@ -30,19 +31,6 @@ constexpr int GB = 64, GK = 32, GS = GK + 1;
 __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-__device__ __forceinline__ void drop4(const DitDrop &dr, long long sample, int site, int head, int row, int col4, float out[4]) {
-  if (dr.p == 0.f) { out[0] = out[1] = out[2] = out[3] = 1.f; return; }
-  unsigned r[4];
-  const unsigned w3 = 0x80000000u | ((unsigned)site << 29) | ((unsigned)dr.block << 16) | ((unsigned)head << 10) | (unsigned)row;
-  philox4x32_10((unsigned)col4, (unsigned)sample, (unsigned)dr.step, w3, (unsigned)dr.seed, (unsigned)(dr.seed >> 32), r);
-  const float keep = 1.0f / (1.0f - dr.p);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float u = ((float)(r[i] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    out[i] = u >= dr.p ? keep : 0.f;
-  }
 }
 
 __device__ __forceinline__ int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
@@ -114,16 +102,17 @@ __global__ __launch_bounds__(256) void ditt_gemm_reduce_kernel(const DitTrGemmAr
 
 // ---- segment column sums -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ditt_segsum_kernel(const float *__restrict__ U, int ldu, const float *__restrict__ V, int ldv,
-                                                          float *__restrict__ out, int ldo, long long seg_rows, int N) {
+                                                          float *__restrict__ out, int ldo, long long seg_rows, int N,
+                                                          long long useg, long long vseg) {
   __shared__ double sh[8][32];
   const int tid = threadIdx.x, cl = tid & 31, j = tid >> 5;
   const int col = blockIdx.x * 32 + cl;
-  const long long seg = blockIdx.y, r0 = seg * seg_rows;
+  const long long seg = blockIdx.y, u0 = seg * useg, v0 = seg * vseg;
   double s = 0.0;
   if (col < N)
     for (long long r = j; r < seg_rows; r += 8) {
-      const double u = U[(r0 + r) * ldu + col];
-      s += V ? u * (double)V[(r0 + r) * ldv + col] : u;
+      const double u = U[(u0 + r) * ldu + col];
+      s += V ? u * (double)V[(v0 + r) * ldv + col] : u;
     }
   sh[j][cl] = s;
   __syncthreads();
@@ -218,7 +207,7 @@ __global__ __launch_bounds__(256) void ditt_gelu_drop_kernel(const float *__rest
   const long long r = i / n4;
   const int c4 = (int)(i % n4);
   float mk[4];
-  drop4(dr, dr.sample_base + r / tok, DITT_SITE_MLP1, 0, (int)(r % tok), c4, mk);
+  ditt_drop4(dr, dr.sample_base + r / tok, DITT_SITE_MLP1, 0, (int)(r % tok), c4, mk);
   const float4 h = *(const float4 *)(H1 + r * N + 4 * c4);
   const float hv[4] = {h.x, h.y, h.z, h.w};
   float4 *dst = (float4 *)(Hm + r * N + 4 * c4);
@@ -243,7 +232,7 @@ __global__ __launch_bounds__(256) void ditt_gate_kernel(const float *__restrict_
   const long long r = i / n4, b = r / tok;
   const int c4 = (int)(i % n4);
   float mk[4] = {1.f, 1.f, 1.f, 1.f};
-  if (site != DITT_SITE_NONE) drop4(dr, dr.sample_base + b, site, 0, (int)(r % tok), c4, mk);
+  if (site != DITT_SITE_NONE) ditt_drop4(dr, dr.sample_base + b, site, 0, (int)(r % tok), c4, mk);
   const float4 g = *(const float4 *)(mod + b * ldmod + off_gate + 4 * c4);
   float4 *yp = (float4 *)(Y + r * D + 4 * c4);
   if (Xin) {
@@ -273,25 +262,29 @@ __global__ __launch_bounds__(256) void ditt_gather_rows_kernel(const float *__re
   out[i] = table[t[i / D] * D + i % D];
 }
 
-// patches of the forward's gather prologue (pt = 1): k = (c p + ih) p + iw of token (frame, h_p, w_p)
+// patches of the forward's gather prologue: k = ((c pt + it) p + ih) p + iw of token (slot, h_p, w_p), frame slot * pt + it
 __global__ __launch_bounds__(256) void ditt_patch_gather_kernel(const DitTrPatchArgs a) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x, rows = (long long)a.B * a.tok;
   if (i >= rows * a.Kp) return;
   const long long pr = i / a.Kp, b = pr / a.tok;
   const int k = (int)(i % a.Kp), p = a.p;
-  const int iw = k % p, ih = (k / p) % p, c = k / (p * p);
+  const int iw = k % p, ih = (k / p) % p, it = (k / (p * p)) % a.pt, c = k / (p * p * a.pt);
   const int s = (int)(pr % a.tok), tp = s / a.Ns, hw = s % a.Ns, hp = hw / a.wpn, wp = hw % a.wpn;
-  a.Pm[i] = a.x8[((((b * a.L) + tp) * a.Hh + hp * p + ih) * a.Ww + wp * p + iw) * 8 + c];
+  a.Pm[i] = a.x8[((((b * a.L) + tp * a.pt + it) * a.Hh + hp * p + ih) * a.Ww + wp * p + iw) * 8 + c];
 }
 
-// d loss / d (final linear output) through the unpatchify gather: 2 (pred - target) / N at the voxel the feature lands on
+// d loss / d (final linear output) through the unpatchify gather: 2 (pred - target) / N at the voxel the feature lands on.
+// Feature ((it C + c) p + ih) p + iw of future slot f is frame (qs + f) pt + it; a frame < P of the first future slot carries no
+// loss: exactly 0.
 __global__ __launch_bounds__(256) void ditt_loss_grad_kernel(const DitTrPatchArgs a) {
-  const int F = a.L - a.qs, p = a.p;
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, rows = (long long)a.B * F * a.Ns;
+  const int nq = a.tok / a.Ns - a.qs, F = a.L - a.P, p = a.p;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, rows = (long long)a.B * nq * a.Ns;
   if (i >= rows * a.Nout) return;
-  const long long rc = i / a.Nout, b = rc / ((long long)F * a.Ns);
-  const int col = (int)(i % a.Nout), rem = (int)(rc % ((long long)F * a.Ns)), f = rem / a.Ns, hw = rem % a.Ns;
-  const int iw = col % p, ih = (col / p) % p, c = col / (p * p), hp = hw / a.wpn, wp = hw % a.wpn;
+  const long long rc = i / a.Nout, b = rc / ((long long)nq * a.Ns);
+  const int col = (int)(i % a.Nout), rem = (int)(rc % ((long long)nq * a.Ns)), sl = rem / a.Ns, hw = rem % a.Ns;
+  const int iw = col % p, ih = (col / p) % p, c = (col / (p * p)) % a.C, it = col / (p * p * a.C);
+  const int hp = hw / a.wpn, wp = hw % a.wpn, f = (a.qs + sl) * a.pt + it - a.P;
+  if (f < 0) { a.dYf[i] = 0.f; return; }
   const long long e = ((((b * a.C + c) * a.Hh + hp * p + ih) * a.Ww + wp * p + iw) * F + f);
   const double n = (double)a.B * a.C * a.Hh * a.Ww * F;
   a.dYf[i] = (float)(((double)a.pred[e] - (double)a.target[e]) * (2.0 / n));
@@ -379,7 +372,7 @@ __global__ __launch_bounds__(64) void ditt_attn_fwd_kernel(const DitTrAttnArgs a
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float mk[4];
-      drop4(a.dr, a.dr.sample_base + b, DITT_SITE_ATTN, h, qc, (k0 + 8 * g + 4 * hf) >> 2, mk);
+      ditt_drop4(a.dr, a.dr.sample_base + b / a.dr.gps, DITT_SITE_ATTN, h, (int)(b % a.dr.gps) * S + qc, (k0 + 8 * g + 4 * hf) >> 2, mk);
 #pragma unroll
       for (int e = 0; e < 4; ++e) s[4 * g + e] *= mk[e];
     }
@@ -456,7 +449,7 @@ __global__ __launch_bounds__(64) void ditt_attn_dq_kernel(const DitTrAttnArgs a)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       float mk[4];
-      drop4(a.dr, a.dr.sample_base + b, DITT_SITE_ATTN, h, qc, (k0 + 8 * g + 4 * hf) >> 2, mk);
+      ditt_drop4(a.dr, a.dr.sample_base + b / a.dr.gps, DITT_SITE_ATTN, h, (int)(b % a.dr.gps) * S + qc, (k0 + 8 * g + 4 * hf) >> 2, mk);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int r = 4 * g + e;
@@ -521,7 +514,7 @@ __global__ __launch_bounds__(64) void ditt_attn_dkv_kernel(const DitTrAttnArgs a
       t0[r] = qp[0]; t1[r] = qp[32];
       u0[r] = dp[0]; u1[r] = dp[32];
       float mk[4];
-      drop4(a.dr, a.dr.sample_base + b, DITT_SITE_ATTN, h, qrc, key >> 2, mk);
+      ditt_drop4(a.dr, a.dr.sample_base + b / a.dr.gps, DITT_SITE_ATTN, h, (int)(b % a.dr.gps) * S + qrc, key >> 2, mk);
       const float mv = mk[key & 3];
       const float p = qr < S ? expf(s[r] - lseb[qrc]) : 0.f;   // tail queries contribute exactly 0
       pa[r] = p * mv;
@@ -566,8 +559,14 @@ hipError_t launch_ditt_gemm(const DitTrGemmArgs &a, hipStream_t st) {
 hipError_t launch_ditt_segsum(const float *U, int ldu, const float *V, int ldv, float *out, int ldo, int nseg, long long seg_rows,
                               int N, hipStream_t st) {
   if (nseg <= 0 || N <= 0) return hipSuccess;
+  return launch_ditt_segsum_rows(U, ldu, seg_rows, V, ldv, seg_rows, out, ldo, nseg, seg_rows, N, st);
+}
+
+hipError_t launch_ditt_segsum_rows(const float *U, int ldu, long long useg, const float *V, int ldv, long long vseg, float *out,
+                                   int ldo, int nseg, long long seg_rows, int N, hipStream_t st) {
+  if (nseg <= 0 || N <= 0) return hipSuccess;
   hipLaunchKernelGGL(ditt_segsum_kernel, dim3((unsigned)((N + 31) / 32), (unsigned)nseg), dim3(256), 0, st, U, ldu, V, ldv, out, ldo,
-                     seg_rows, N);
+                     seg_rows, N, useg, vseg);
   return hipGetLastError();
 }
 
@@ -619,12 +618,14 @@ hipError_t launch_ditt_gather_rows(const float *table, const long long *t, float
 }
 
 hipError_t launch_ditt_patch_gather(const DitTrPatchArgs &a, hipStream_t st) {
+  if (a.pt < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ditt_patch_gather_kernel, dim3(blocks_of((long long)a.B * a.tok * a.Kp)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
 hipError_t launch_ditt_loss_grad(const DitTrPatchArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(ditt_loss_grad_kernel, dim3(blocks_of((long long)a.B * (a.L - a.qs) * a.Ns * a.Nout)), dim3(256), 0, st, a);
+  if (a.pt < 1 || a.P < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ditt_loss_grad_kernel, dim3(blocks_of((long long)a.B * (a.tok / a.Ns - a.qs) * a.Ns * a.Nout)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -635,7 +636,7 @@ hipError_t launch_ditt_pos_grad(const DitTrPatchArgs &a, hipStream_t st) {
 
 namespace {
 bool attn_ok(const DitTrAttnArgs &a) {
-  return a.S >= 1 && a.S <= 1024 && a.E == 64 * a.heads && a.heads <= 64 && a.dr.block >= 0 && a.dr.block < 8192 &&
+  return a.S >= 1 && a.dr.gps >= 1 && (long long)a.dr.gps * a.S <= 1024 && a.E == 64 * a.heads && a.heads <= 64 && a.dr.block >= 0 && a.dr.block < 8192 &&
          (long long)a.B * a.heads * ((a.S + 31) / 32) <= 0x7fffffffLL;
 }
 }  // namespace

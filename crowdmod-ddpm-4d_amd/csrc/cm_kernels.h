@@ -499,12 +499,14 @@ hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st);
 
 // DiT2D training step (cm_dit_train.hip; host plan: cm_dit_train_host.inc).
 // Dropout site of a mask value; with (seed, optimizer step, global sample, block, head, row, column) it addresses one Philox word.
-enum { DITT_SITE_ATTN = 0, DITT_SITE_MLP1 = 1, DITT_SITE_MLP2 = 2, DITT_SITE_NONE = -1 };
+enum { DITT_SITE_ATTN = 0, DITT_SITE_MLP1 = 1, DITT_SITE_MLP2 = 2, DITT_SITE_TATTN = 3, DITT_SITE_NONE = -1 };
 struct DitDrop {
   unsigned long long seed;
   long long sample_base;          // global index of the batch's sample 0
   int step, block;                // optimizer step; DiT block
   float p;                        // rate; 0: every mask value is exactly 1
+  int gps;                        // attention groups per sample: group g of ditt_attn_* draws as sample g / gps, row (g % gps) * S + query
+                                  // (1: DiT2D, the group is the sample; T_p: the spatial attention of DiT4D_V4)
 };
 // C[m][n] (+)= sum_k A(m, k) B[k * ldb + n] on v_mfma_f32_32x32x2_f32; A(m, k) = ta ? A[k * lda + m] : A[m * lda + k].
 // nsplit > 1: k is cut into nsplit fixed ranges of kchunk (a multiple of 32) whose partial products go to part[z][M][N] and are
@@ -544,6 +546,7 @@ struct DitTrPatchArgs {
   const float *pred, *target; float *dYf;      // [B,C,H,W,F] -> loss gradient of the final linear's rows [B * F * Ns][Nout]
   const float *dX0; float *dspos, *dtpos;      // gradient of the embedded tokens -> position-embedding gradients
   int B, C, L, Hh, Ww, p, Ns, wpn, tok, qs, Kp, Nout, D;
+  int pt, P;                                   // frames per temporal slot (DiT2D: 1); past frames (the loss reaches frames >= P)
 };
 hipError_t launch_ditt_patch_gather(const DitTrPatchArgs &a, hipStream_t st);
 hipError_t launch_ditt_loss_grad(const DitTrPatchArgs &a, hipStream_t st);
@@ -559,6 +562,26 @@ struct DitTrAttnArgs {
 hipError_t launch_ditt_attn_fwd(const DitTrAttnArgs &a, hipStream_t st);
 hipError_t launch_ditt_attn_delta(const DitTrAttnArgs &a, hipStream_t st);
 hipError_t launch_ditt_attn_bwd(const DitTrAttnArgs &a, hipStream_t st);
+
+// DiT4D_V4 training step (cm_dit4d_train.hip; host plan: cm_dit4d_train_host.inc): what its block structure adds to the above.
+// Temporal cross-attention in train mode, one wave per (sample, patch, head): keys / values the T_p <= 8 slots of the patch,
+// queries the slots >= qs; dropout site DITT_SITE_TATTN (row = query token, column = key slot).  The backward writes the whole
+// [B * tok][3E] gradient of the in-projection, the zeros of the Q third of the past slots included.
+struct DitTrTAttnArgs {
+  const float *qkv; float *out, *lse;          // [B][T_p * N_s][3E]; compact [B][(T_p - qs) * N_s][E]; [B][N_s][heads][T_p - qs]
+  const float *dout; float *dqkv;              // gradient of out (compact); [B][T_p * N_s][3E]  (the backward reads lse, not out)
+  int B, Tp, Ns, qs, E, heads;
+  DitDrop dr;
+};
+hipError_t launch_ditt4_tattn_fwd(const DitTrTAttnArgs &a, hipStream_t st);
+hipError_t launch_ditt4_tattn_bwd(const DitTrTAttnArgs &a, hipStream_t st);
+// Gated residual on the rows >= row0 of each sample, Yc compact [B][tok - row0][D].  Forward (Xin set): Xout = Xin on rows < row0,
+// Xin + gate[b] * Yc on the others.  Backward (Xin null): Gc = gate[b] * dX of the rows >= row0, compact.
+hipError_t launch_ditt4_gate_rows(const float *Xin, float *Xout, const float *Yc, float *Gc, const float *dX, const float *mod,
+                                  int ldmod, int off_gate, int B, int tok, int row0, int D, hipStream_t st);
+// launch_ditt_segsum with the segments of U and V at their own row strides (useg, vseg >= seg_rows)
+hipError_t launch_ditt_segsum_rows(const float *U, int ldu, long long useg, const float *V, int ldv, long long vseg, float *out,
+                                   int ldo, int nseg, long long seg_rows, int N, hipStream_t st);
 
 // ConvRNN forecaster (cm_convrnn.hip): one implicit-GEMM 2-D convolution with fused epilogues, and the frame packer.
 enum { CRNN_GEO_S1 = 0, CRNN_GEO_S2 = 1, CRNN_GEO_T4 = 2 };   // 3x3 stride 1 pad 1; 3x3 stride 2 pad 1; transposed 4x4 stride 2 pad 1
@@ -700,6 +723,21 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, long lon
   const float rad = sqrtf(-2.0f * __logf(u1));
   const float ang = 6.283185307179586f * u2;
   return (elem & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
+}
+
+// One quad of dropout mask values of the DiT training steps (cm_dit_train.hip): counter (col4, sample, step, tag | site | block |
+// head | row), keep iff unit_float(word) >= p, value 1 / (1 - p).
+__device__ __forceinline__ void ditt_drop4(const DitDrop &dr, long long sample, int site, int head, int row, int col4, float out[4]) {
+  if (dr.p == 0.f) { out[0] = out[1] = out[2] = out[3] = 1.f; return; }
+  unsigned r[4];
+  const unsigned w3 = 0x80000000u | ((unsigned)site << 29) | ((unsigned)dr.block << 16) | ((unsigned)head << 10) | (unsigned)row;
+  philox4x32_10((unsigned)col4, (unsigned)sample, (unsigned)dr.step, w3, (unsigned)dr.seed, (unsigned)(dr.seed >> 32), r);
+  const float keep = 1.0f / (1.0f - dr.p);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float u = ((float)(r[i] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    out[i] = u >= dr.p ? keep : 0.f;
+  }
 }
 
 // The reverse-process update, ONE definition for sampler_step_kernel and for the tail of the UNet's last conv (conv_fin_kernel,

@@ -231,6 +231,10 @@ class DDPM_model:
 
     # -- training (ddpm.py:123-202) ---------------------------------------------------
     def _refuse_training(self):
+        if self.arch == "DDPM-DiT":
+            raise NotImplementedError(f"training {self.arch} through train() is not implemented on this path; use "
+                                      "ddpm_dit_train.DDPM_DiT_model.fit / train_ddpm_dit.py (DiT4D_V4 backward, dropout "
+                                      "from the device Philox stream, Adam)")
         if self.arch != "DDPM-UNet":
             raise NotImplementedError(f"training {self.arch} is not implemented on this path (sampling only)")
 

@@ -158,6 +158,19 @@ SIGNATURES = {
     "cm_dit_train_opt_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "cm_dit_train_sync": (C.c_int, [_P]),
     "cm_dit_train_get_pred": (C.c_int, [_P, _P, C.c_int64]),
+    "cm_dit4d_train_init": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "cm_dit4d_train_set_lr": (C.c_int, [_P, C.c_float]),
+    "cm_dit4d_train_set_sample_base": (C.c_int, [_P, C.c_int64]),
+    "cm_dit4d_train_step_xt": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),
+    "cm_dit4d_train_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),
+    "cm_dit4d_train_flat_grads": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "cm_dit4d_train_apply": (C.c_int, [_P, _P]),
+    "cm_dit4d_train_get_grad": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    "cm_dit4d_train_get_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
+    "cm_dit4d_train_set_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
+    "cm_dit4d_train_opt_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
+    "cm_dit4d_train_sync": (C.c_int, [_P]),
+    "cm_dit4d_train_get_pred": (C.c_int, [_P, _P, C.c_int64]),
     "cm_convrnn_create": (C.c_int, [C.POINTER(cm_convrnn_config), C.POINTER(_P)]),
     "cm_convrnn_destroy": (C.c_int, [_P]),
     "cm_convrnn_num_params": (C.c_int, [_P, C.POINTER(C.c_int32)]),

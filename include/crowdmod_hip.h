@@ -428,6 +428,38 @@ int cm_dit_train_sync(cm_model *m);
 /* The train-mode prediction [B,C,H,W,F] of the last step (host buffer). */
 int cm_dit_train_get_pred(cm_model *m, float *h_out, int64_t numel);
 
+/* ---- DDPM-DiT training: DDPM_model._train_step (models/diffusion/ddpm.py:111-154) on the DiT4D_V4 denoiser --------------
+ * (t ~ U{0..T-1}; (x_t, eps) = q_sample(future, t); eps_hat = DiT4D_V4(x_t, t, past) in train mode; loss = mse(eps_hat,
+ * eps); backward; torch.optim.Adam with coupled L2.  The reference runs the forward under fp16 autocast; this path is
+ * fp32 throughout.)  The sibling of cm_dit_train_*, entry for entry; only a finalized DiT4D_V4 handle on a device
+ * trains: a UNet handle, an FM-DiT (DiT2D) handle and a host-only handle are refused by name.  Head dim 64, at most 64
+ * heads.  dropout_rate is DiT4D_V4's DROPOUT_RATE (both attentions' probabilities, after GELU, after fc2), in [0, 1);
+ * the masks are a function of (seed, optimizer step, GLOBAL sample index, block, site, head, row, column). */
+int cm_dit4d_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay,
+                        float dropout_rate);
+int cm_dit4d_train_set_lr(cm_model *m, float lr);
+int cm_dit4d_train_set_sample_base(cm_model *m, int64_t sample_id_base);
+/* One step on device buffers with the caller's noised input and regression target; *h_loss = mse(eps_hat, d_target);
+ * backward; if apply_update != 0: Adam.  Synchronous. */
+int cm_dit4d_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const int64_t *d_t,
+                           const float *d_target, uint64_t seed, float *h_loss, int32_t B, int32_t apply_update,
+                           void *stream);
+/* cm_train_step's shape: x_t = sqrt_alpha_bar[t] * d_future + sqrt_one_minus_alpha_bar[t] * eps, target eps.
+ * d_eps == NULL draws eps ~ N(0,1) from the device Philox stream (seed, draw, global sample), as cm_train_step does. */
+int cm_dit4d_train_step(cm_model *m, const cm_schedule *s, const float *d_future, const float *d_past,
+                        const int64_t *d_t, const float *d_eps, uint64_t seed, float *h_loss, int32_t B,
+                        int32_t apply_update, void *stream);
+int cm_dit4d_train_flat_grads(cm_model *m, void **d_grads, int64_t *numel);
+int cm_dit4d_train_apply(cm_model *m, void *stream);
+int cm_dit4d_train_get_grad(cm_model *m, const char *name, float *h_out, int64_t numel);
+/* which = 0 exp_avg, 1 exp_avg_sq, 2 (get only) the master weights */
+int cm_dit4d_train_get_opt_state(cm_model *m, const char *name, int32_t which, float *h_out, int64_t numel);
+int cm_dit4d_train_set_opt_state(cm_model *m, const char *name, int32_t which, const float *h_in, int64_t numel);
+int cm_dit4d_train_opt_step(cm_model *m, int32_t *step, int32_t set);
+/* Until this call the eval forward and the sampling loops compute what they computed before training. */
+int cm_dit4d_train_sync(cm_model *m);
+int cm_dit4d_train_get_pred(cm_model *m, float *h_out, int64_t numel);
+
 /* ---- ConvRNN forecaster: replaces Forecaster(...) (models/convRNN/forecaster.py) and
  * ConvRNN_model._generate_convRNN (models/convRNN/convRNN.py:223-231) -----------------------------------
  * The deterministic ConvGRU / ConvLSTM encoder-forecaster baseline of arch "ConvRNN".  It has no timestep and no

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Training entry point with the reference's command line (train.py:75-82 of the reference).
+"""Training entry point of arch DDPM-DiT, with the command line of train.py (train.py:75-82 of the reference).
 
-Every batch is ONE native call on the MI355X (cm_train_step): q-sample with device-drawn noise,
-train-mode UNet forward (Dropout3d), MSE, backward, Adam with coupled L2, weight re-pack.  The host
-keeps what the reference's loop keeps on the host: epoch bookkeeping, ReduceLROnPlateau, NaN early
-stop, checkpoints in the reference's {"opt", "model"} torch-zip format and file naming.
+Every batch is ONE native call on the MI355X (cm_dit4d_train_step): eps from the device Philox stream, q_sample,
+train-mode DiT4D_V4 forward with a tape and dropout drawn from the same stream, MSE against eps, the backward of every
+stage, Adam with coupled L2.  The host keeps what the reference's loop keeps on the host (DDPM_DiT_model.fit): t, epoch
+bookkeeping, ReduceLROnPlateau, NaN early stop, checkpoints in the reference's {"opt", "model"} torch-zip format and
+file naming.
 
 Data: `--data-npy` takes sequences [N, C>=3, ROWS, COLS, T] (the reference's in-memory format,
 utils/dataset.py:119) cut into sliding past/future windows; without it a synthetic set ~ N(0,1) of
@@ -48,10 +49,10 @@ def make_loader(past, future, batch_size, seed, rank=0, world=1):
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Train a crowd-macroprops DDPM-UNet (MI355X-native path).")
+    ap = argparse.ArgumentParser(description="Train a crowd-macroprops DDPM-DiT (MI355X-native path).")
     ap.add_argument('--config-yml-file', type=str, default='config/ATC.yml')
     ap.add_argument('--configList-yml-file', type=str, default=None)
-    ap.add_argument('--arch', type=str, default='DDPM-UNet')
+    ap.add_argument('--arch', type=str, default='DDPM-DiT')
     ap.add_argument('--baseline-ckpt', type=str, default=None, help='Baseline model path')
     ap.add_argument('--data-npy', type=str, default=None, help='training sequences [N,C,ROWS,COLS,T] (.npy)')
     ap.add_argument('--synthetic-samples', type=int, default=1024)
@@ -59,33 +60,24 @@ def main():
     ap.add_argument('--device', type=int, default=None)
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
-    if args.arch == "ConvRNN":
-        raise SystemExit("ConvRNN: training through train.py is not implemented on this path; use train_convrnn.py "
-                         "(Poisson-KL + masked MSE loss, AMSGrad, backpropagation through the forecast steps)")
-    if args.arch == "FM-DiT":
-        raise SystemExit("FM-DiT: training through train.py is not implemented on this path; use train_fm_dit.py "
-                         "(DiT2D backward, dropout from the device Philox stream, Adam: FM_model.fit)")
-    if args.arch == "DDPM-DiT":
-        raise SystemExit("DDPM-DiT: training through train.py is not implemented on this path; use train_ddpm_dit.py "
-                         "(DiT4D_V4 backward, dropout from the device Philox stream, Adam: DDPM_DiT_model.fit)")
-    if args.arch not in ("DDPM-UNet", "FM-UNet"):
-        raise SystemExit(f"{args.arch}: only the UNet-backbone generators (DDPM-UNet, FM-UNet) are implemented on this path")
+    if args.arch != "DDPM-DiT":
+        raise SystemExit(f"{args.arch}: train_ddpm_dit.py trains DDPM-DiT only; the UNet-backbone generators go through "
+                         "train.py, FM-DiT through train_fm_dit.py and ConvRNN through train_convrnn.py")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", 0))
 
-    from crowdmod_ddpm_4d_amd.ddpm_model import DDPM_model
-    from crowdmod_ddpm_4d_amd.flow_matching import FM_model
+    from crowdmod_ddpm_4d_amd.ddpm_dit_train import DDPM_DiT_model
     from generate_samples import windows
     cfg = cfgmod.getYamlConfig(args.config_yml_file, args.configList_yml_file)
     res = cfgmod.resolve(cfg, args.arch)
     if args.epochs is not None and res.train is not None:
         res.train["EPOCHS"] = int(args.epochs)
     mprops = 3  # train.py:61 of the reference
-    model = (FM_model if args.arch.startswith("FM-") else DDPM_model)(cfg, args.arch, mprops, device=device)
+    model = DDPM_DiT_model(cfg, args.arch, mprops, device=device)
     if args.epochs is not None:
         model.res = res
     nparams = sum(int(np.prod(v.shape)) for k, v in model.denoiser.state_dict().items()
-                  if k != "time_embeddings.time_blocks.0.weight")
+                  if k != "dif_time_embeddings.time_blocks.0.weight")
     logging.info("Total trainable parameters at denoiser:%d", nparams)
     if args.data_npy:
         seq = np.load(args.data_npy).astype(np.float32)
@@ -117,7 +109,7 @@ def main():
             logf.write(json.dumps(rec) + "\n")
             logf.flush()
 
-    model.train(loader, args.baseline_ckpt, log=log, grad_sync=grad_sync, save=(rank == 0), loss_sync=loss_sync)
+    model.fit(loader, args.baseline_ckpt, log=log, grad_sync=grad_sync, save=(rank == 0), loss_sync=loss_sync)
     logging.info("Trained model %s saved in %s", args.arch, save_dir)
 
 

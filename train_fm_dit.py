@@ -62,7 +62,7 @@ def main():
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if args.arch != "FM-DiT":
         raise SystemExit(f"{args.arch}: train_fm_dit.py trains FM-DiT only; the UNet-backbone generators go through train.py, "
-                         "ConvRNN through train_convrnn.py, and DDPM-DiT (DiT4D_V4) training is not implemented on this path")
+                         "ConvRNN through train_convrnn.py and DDPM-DiT through train_ddpm_dit.py")
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", 0))
 
