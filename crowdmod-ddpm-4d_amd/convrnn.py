@@ -9,6 +9,10 @@ surface the driver touches.  All arithmetic runs in libcrowdmod_hip.so (cm_convr
 Training (convRNN.py:98-221) is reached through `Forecaster.train_init / train_step / evaluate_loss` and
 `ConvRNN_model._train_one_epoch / fit` (script: train_convrnn.py).  `Forecaster.train()` -- the nn.Module mode switch -- and
 `ConvRNN_model.train(...)` keep refusing: the forecaster has no mode-dependent layer, and the driver's loop is `fit`.
+
+Data parallel: the loss divides by counts over the whole batch, so the step is cut at that reduction --
+`Forecaster.train_forward` (six float64 sums), a SUM over ranks, `train_backward` with the totals, a SUM of the flat gradients
+(`flat_grads`), `apply_update` -- behind `train_step / fit(..., sums_sync=, grad_sync=)` with the hooks of distributed.py.
 """
 from __future__ import annotations
 
@@ -232,11 +236,27 @@ class Forecaster:
         del keep
         return tuple(float(v) for v in terms)
 
-    def train_step(self, past, target, teacher_forcing=False, eps: float = 1e-6, alpha: float = 1.0, apply_update: bool = True):
+    def train_step(self, past, target, teacher_forcing=False, eps: float = 1e-6, alpha: float = 1.0, apply_update: bool = True,
+                   *, sums_sync=None, grad_sync=None):
         """One step of convRNN.py:121-128 on rloss + alpha * vloss: forward, loss, backward and (apply_update) the AMSGrad
-        update behind one native call.  Returns the four loss terms of the weights before the update."""
+        update behind one native call.  Returns the four loss terms of the weights before the update.
+
+        With `sums_sync` or `grad_sync` (data-parallel training) the step is cut where the loss reduces over the batch:
+        train_forward, `sums_sync(six sums) -> six global sums`, train_backward with them, `grad_sync(self)` on the flat
+        gradient (a SUM over ranks: each rank's gradient is its share of the global objective's), apply_update.  The terms
+        returned are those of the global batch, identical on every rank."""
         if self._hyper is None:
             raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
+        if sums_sync is not None or grad_sync is not None:
+            sums = self.train_forward(past, target, teacher_forcing)
+            if sums_sync is not None:
+                sums = sums_sync(sums)
+            terms = self.train_backward(sums, eps, alpha)
+            if grad_sync is not None:
+                grad_sync(self)
+            if apply_update:
+                self.apply_update()
+            return terms
         h, B = self._train_handle(past, target)
         p, t, keep = self._device_pair(past, target)
         terms = (C.c_double * 4)()
@@ -245,6 +265,54 @@ class Forecaster:
         del keep
         self._trained = self._trained or bool(apply_update)
         return tuple(float(v) for v in terms)
+
+    # -- the step cut at the loss's reduction over the batch (data-parallel training) ---------------------------------
+    def _forward_sums(self, entry, past, target, teacher_forcing) -> np.ndarray:
+        h, B = self._train_handle(past, target)
+        p, t, keep = self._device_pair(past, target)
+        sums = (C.c_double * 6)()
+        native.check(getattr(native.lib(), entry)(h, p, t, int(bool(teacher_forcing)), B, None, sums))
+        del keep    # the call has synchronised and keeps its own copy of the target frames
+        return np.array(sums[:], dtype=np.float64)
+
+    def train_forward(self, past, target, teacher_forcing=False) -> np.ndarray:
+        """First half of a split step: the forward with its activations kept.  Returns np.float64[6]: the Poisson-KL sum,
+        occupied MSE sum, occupied count, empty penalty sum, empty count of THIS batch, and its element count B*H*W*F."""
+        if self._hyper is None:
+            raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
+        return self._forward_sums("cm_convrnn_train_forward", past, target, teacher_forcing)
+
+    def loss_sums(self, past, target, teacher_forcing=False) -> np.ndarray:
+        """The validation half: forward and the six sums; `terms_from_sums` of their total over ranks is the loss."""
+        return self._forward_sums("cm_convrnn_loss_sums", past, target, teacher_forcing)
+
+    def train_backward(self, global_sums, eps: float = 1e-6, alpha: float = 1.0):
+        """Second half: every gradient of rloss + alpha * vloss over this batch with the denominators of `global_sums` (the
+        six sums added over all ranks; the own sums give train_step(apply_update=False) bit for bit).  No update.  Returns
+        the four loss terms of the global sums."""
+        g = np.ascontiguousarray(global_sums, dtype=np.float64)
+        if g.shape != (6,):
+            raise ValueError(f"global_sums must hold six numbers, got shape {g.shape}")
+        terms = (C.c_double * 4)()
+        native.check(native.lib().cm_convrnn_train_backward(self._need_train(), g.ctypes.data_as(C.POINTER(C.c_double)), float(eps),
+                                                            float(alpha), terms, None))
+        return tuple(float(v) for v in terms)
+
+    @staticmethod
+    def terms_from_sums(sums, eps: float = 1e-6):
+        """utils/loss.py:44-50 from six (global) sums, on the host, by the expressions the device evaluates."""
+        g = np.ascontiguousarray(sums, dtype=np.float64)
+        if g.shape != (6,):
+            raise ValueError(f"sums must hold six numbers, got shape {g.shape}")
+        terms = (C.c_double * 4)()
+        native.check(native.lib().cm_convrnn_loss_terms_from_sums(g.ctypes.data_as(C.POINTER(C.c_double)), float(eps), terms))
+        return tuple(float(v) for v in terms)
+
+    def flat_grads(self):
+        """(device pointer, numel) of the flat fp32 gradient in state_dict order: what distributed.GradAverager reduces."""
+        ptr, n = C.c_void_p(), C.c_int64()
+        native.check(native.lib().cm_convrnn_train_flat_grads(self._need_train(), C.byref(ptr), C.byref(n)))
+        return int(ptr.value), int(n.value)
 
     def _need_train(self):
         if self._handle is None or self._hyper is None:
@@ -372,11 +440,33 @@ class ConvRNN_model:
         mp = self.cfg.get("MACROPROPS", {}) if hasattr(self.cfg, "get") else {}
         return float(mp.get("EPS", 1e-6)) if hasattr(mp, "get") else 1e-6
 
-    def _train_one_epoch(self, train_data_loader, val_data_loader, epoch, alpha=1):
+    @staticmethod
+    def _check_rank_batches(sums_sync, train_data_loader, val_data_loader):
+        """Data-parallel training runs one collective per batch: every rank must bring the same number of batches.  The
+        counts are compared through the sums hook itself (n and n^2 summed over ranks: W * sum n^2 == (sum n)^2 only when
+        all n are equal), so every rank sees the same totals and refuses together instead of hanging in a collective."""
+        try:
+            nt, nv = len(train_data_loader), len(val_data_loader)
+        except TypeError:
+            raise TypeError("data-parallel ConvRNN training needs loaders with len(): the batch counts are compared over "
+                            "the ranks before the first collective") from None
+        tot = np.asarray(sums_sync(np.array([1.0, nt, nt * nt, nv, nv * nv, 0.0])), dtype=np.float64)
+        if tot[0] * tot[2] != tot[1] ** 2 or tot[0] * tot[4] != tot[3] ** 2:
+            raise ValueError(f"data-parallel ConvRNN training: the ranks bring different numbers of batches (this rank: "
+                             f"{nt} training, {nv} validation; over {int(tot[0])} ranks: {int(tot[1])} and {int(tot[3])}); "
+                             f"every rank must see the same number, each batch with at least one sample")
+
+    def _train_one_epoch(self, train_data_loader, val_data_loader, epoch, alpha=1, *, sums_sync=None, grad_sync=None):
         """convRNN.py:98-171: one native call per training batch (forward, loss, backward, AMSGrad), forward + loss per
-        validation batch (never teacher-forced).  Returns the reference's ten values."""
+        validation batch (never teacher-forced).  Returns the reference's ten values.
+
+        With `sums_sync` / `grad_sync` (data parallel) a training batch is the split step and a validation batch is
+        loss_sums, the hook, terms_from_sums: every term is that of the global batch and identical on every rank."""
         self._ensure_training()
         eps, net = self._loss_eps(), self.convRNN
+        split = sums_sync is not None or grad_sync is not None
+        if sums_sync is not None:
+            self._check_rank_batches(sums_sync, train_data_loader, val_data_loader)
         lists = [[] for _ in range(8)]   # train r, v, val r, v, train d, nd, val d, nd
         means = []
         for loader, tf, step, (ri, vi, di, ni) in ((train_data_loader, self.teacher_forcing, True, (0, 1, 4, 5)),
@@ -384,7 +474,17 @@ class ConvRNN_model:
             total, count = 0.0, 0
             for past, future in loader:
                 past, future = np.asarray(past, dtype=np.float32), np.asarray(future, dtype=np.float32)
-                if step:
+                if split and past.shape[0] < 1:
+                    # an empty batch cannot skip its collectives: its NaN sums make every rank refuse together
+                    if sums_sync is not None:
+                        sums_sync(np.full(6, np.nan))
+                    raise ValueError("data-parallel ConvRNN training: a batch without samples on this rank")
+                if split and step:
+                    r, v, d, nd = net.train_step(past, future, tf, eps, alpha=float(alpha), sums_sync=sums_sync, grad_sync=grad_sync)
+                elif split:
+                    sums = net.loss_sums(past, future, tf)
+                    r, v, d, nd = net.terms_from_sums(sums_sync(sums) if sums_sync is not None else sums, eps)
+                elif step:
                     r, v, d, nd = net.train_step(past, future, tf, eps, alpha=float(alpha))
                 else:
                     r, v, d, nd = net.evaluate_loss(past, future, tf, eps)
@@ -404,10 +504,15 @@ class ConvRNN_model:
         checkpoint.save_checkpoint(state, path, opt_state=self.convRNN.opt_state())
         return path
 
-    def fit(self, batched_train_data, batched_val_data, *, log=None, save=True) -> dict:
+    def fit(self, batched_train_data, batched_val_data, *, log=None, save=True, sums_sync=None, grad_sync=None) -> dict:
         """convRNN.py:173-221 without wandb and the plots: epochs of _train_one_epoch, ReduceLROnPlateau stepped with the
         epoch's train loss, the stop after three consecutive NaN epochs, the best checkpoint under tag "000".  Returns the
-        loss histories."""
+        loss histories.
+
+        Data parallel: `sums_sync` (distributed.sum_over_ranks) and `grad_sync` (distributed.GradAverager(average=False)).
+        Every loss is then that of the global batch and identical on every rank, so the scheduler, the NaN stop and the
+        best-checkpoint rule need no further sync; pass save=True on one rank only.  Every rank must bring the same number
+        of batches (refused otherwise, on all ranks together)."""
         import logging
         self._ensure_training()
         keys = ("train_rloss", "train_vloss", "val_rloss", "val_vloss", "train_dloss", "train_ndloss", "val_dloss", "val_ndloss")
@@ -415,7 +520,7 @@ class ConvRNN_model:
         hist["train_loss"], hist["val_loss"] = [], []
         best_loss, nan_run = 1e6, 0
         for epoch in range(1, self._solver()["epochs"] + 1):
-            out = self._train_one_epoch(batched_train_data, batched_val_data, epoch=epoch)
+            out = self._train_one_epoch(batched_train_data, batched_val_data, epoch=epoch, sums_sync=sums_sync, grad_sync=grad_sync)
             epoch_train_loss, epoch_val_loss = out[0], out[1]
             hist["train_loss"].append(epoch_train_loss)
             hist["val_loss"].append(epoch_val_loss)

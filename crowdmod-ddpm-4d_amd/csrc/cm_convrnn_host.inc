@@ -30,6 +30,7 @@ struct cm_convrnn {
   float *st_past = nullptr, *st_tgt = nullptr, *st_out = nullptr;   // staging of the host-buffer entry point
   int cur[3] = {0, 0, 0};
   struct CrnnTrain *train = nullptr;   // cm_convrnn_train_host.inc
+  bool tape_ready = false;             // a cm_convrnn_train_forward is waiting for its backward; any other run clears it
   std::vector<void *> allocs;
 };
 void crnn_free_train(CrnnTrain *t);
@@ -181,6 +182,7 @@ int crnn_run(cm_convrnn *m, const float *d_past, const float *d_target, int tf, 
   const cm_convrnn_config &c = m->cfg;
   const int H = c.rows, W = c.cols, P = c.past_len, Ft = c.future_len, nslots = P + Ft;
   const long long HW = (long long)H * W, win_bs = (long long)nslots * HW * 8;
+  m->tape_ready = false;          // the window is rewritten
   for (int l = 0; l < 3; ++l) {   // _init_hidden: zero states at the start of every call (forecaster.py:99)
     const size_t n = (size_t)B * m->lh[l] * m->lw[l] * m->hid[l] * sizeof(float);
     CM_HIP(hipMemsetAsync(m->h[l][0], 0, n, st));

@@ -208,6 +208,18 @@ void test_handle(int cell) {
   EXPECT(cm_convrnn_loss(m, &one, &one, 0, 1e-6, terms, 1, nullptr) != 0 && strstr(cm_last_error(), "host-only"));
   EXPECT(cm_convrnn_train_step(m, &one, &one, 0, 1e-6, 1.0, terms, 1, 1, nullptr) != 0 && strstr(cm_last_error(), "host-only"));
   EXPECT(cm_convrnn_train_sync(m) != 0 && cm_convrnn_train_get_grad(m, "x", &one, 1) != 0);
+  // the split step
+  double sums[6] = {1.5, 2.0, 1.0, 3.0, 2.0, 3.0};
+  float *gp = nullptr;
+  int64_t gn = 0;
+  EXPECT(cm_convrnn_train_forward(m, &one, &one, 0, 1, nullptr, sums) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_loss_sums(m, &one, &one, 0, 1, nullptr, sums) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_train_backward(m, sums, 1e-6, 1.0, terms, nullptr) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_train_flat_grads(m, &gp, &gn) != 0 && strstr(cm_last_error(), "host-only"));
+  EXPECT(cm_convrnn_loss_terms_from_sums(sums, 0.0, terms) == 0 && terms[0] == 0.5 && terms[2] == 2.0 && terms[3] == 1.5 && terms[1] == 3.5);
+  EXPECT(cm_convrnn_loss_terms_from_sums(nullptr, 0.0, terms) != 0);
+  sums[5] = 0;
+  EXPECT(cm_convrnn_loss_terms_from_sums(sums, 0.0, terms) != 0 && strstr(cm_last_error(), "element count"));
   EXPECT(cm_convrnn_destroy(m) == 0);
 }
 

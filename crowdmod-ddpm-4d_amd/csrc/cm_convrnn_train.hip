@@ -234,8 +234,6 @@ __device__ __forceinline__ double clamp_exp(float v, bool *pass) {
   *pass = e >= 1e-8 && e <= 20.0;
   return e < 1e-8 ? 1e-8 : e > 20.0 ? 20.0 : e;
 }
-// count + eps as the reference forms it: its masks are float32, so the denominator is rounded to fp32
-__device__ __forceinline__ double loss_den(double count, double eps) { return (double)((float)count + (float)eps); }
 __device__ __forceinline__ double clamp_gt(float v) { return v < 1e-8f ? (double)1e-8f : v > 20.f ? 20.0 : (double)v; }
 
 __global__ __launch_bounds__(256) void crnn_loss_partial_kernel(const float *yhat, const float *y, long long n, int HW, int F, double *part) {
@@ -270,14 +268,15 @@ __global__ void crnn_loss_final_kernel(const double *part, int nblocks, double n
     s[threadIdx.x] = sums[threadIdx.x] = t;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const double lcd = s[1] / loss_den(s[2], eps), lncd = s[3] / loss_den(s[4], eps);
-    terms[0] = s[0] / n; terms[1] = lcd + lncd; terms[2] = lcd; terms[3] = lncd;
-  }
+  if (threadIdx.x == 0 && terms) crnn_loss_terms(s, n, eps, terms);
+}
+
+__global__ void crnn_loss_terms_kernel(const double *sums6, double eps, double *terms) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) crnn_loss_terms(sums6, sums6[5], eps, terms);
 }
 
 __global__ __launch_bounds__(256) void crnn_loss_grad_kernel(const float *yhat, const float *y, long long n, int B, int HW, int F, double eps,
-                                                             double alpha, const double *sums, float *dY) {
+                                                             double alpha, const double *sums, double n_den, float *dY) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const long long per = (long long)HW * F, b = i / per, rem = i % per, o = b * 4 * per + rem;
@@ -286,13 +285,13 @@ __global__ __launch_bounds__(256) void crnn_loss_grad_kernel(const float *yhat, 
   const double rho_hat = clamp_exp(yhat[o], &pr), rho_gt = clamp_gt(y[o]);
   const double var_hat = clamp_exp(yhat[o + 3 * per], &pv), var_gt = clamp_gt(y[o + 3 * per]);
   const double m1 = yhat[o + per], m2 = yhat[o + 2 * per];
-  const double g0 = pr ? (1.0 - rho_gt / rho_hat) / (double)n * rho_hat : 0.0;
+  const double g0 = pr ? (1.0 - rho_gt / rho_hat) / n_den * rho_hat : 0.0;
   double g1, g2, g3;
   if (rho_gt >= 1.0) {
-    const double w = alpha / loss_den(sums[2], eps);
+    const double w = alpha / crnn_loss_den(sums[2], eps);
     g1 = 2.0 * (m1 - (double)y[o + per]) * w; g2 = 2.0 * (m2 - (double)y[o + 2 * per]) * w; g3 = 4.0 * (var_hat - var_gt) * w;
   } else {
-    const double w = alpha / loss_den(sums[4], eps);
+    const double w = alpha / crnn_loss_den(sums[4], eps);
     g1 = 2.0 * m1 * w; g2 = 2.0 * m2 * w; g3 = 2.0 * var_hat * w;
   }
   g3 = pv ? g3 * var_hat : 0.0;
@@ -383,11 +382,16 @@ hipError_t launch_crnn_loss(const float *yhat, const float *y, int B, int HW, in
   return hipGetLastError();
 }
 
+hipError_t launch_crnn_loss_terms(const double *sums6, double eps, double *terms, hipStream_t st) {
+  hipLaunchKernelGGL(crnn_loss_terms_kernel, dim3(1), dim3(64), 0, st, sums6, eps, terms);
+  return hipGetLastError();
+}
+
 hipError_t launch_crnn_loss_grad(const float *yhat, const float *y, int B, int HW, int F, double eps, double alpha, const double *sums,
-                                 float *dY, hipStream_t st) {
+                                 double n_den, float *dY, hipStream_t st) {
   const long long n = (long long)B * HW * F;
-  if (n <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(crnn_loss_grad_kernel, dim3(blocks_of(n)), dim3(256), 0, st, yhat, y, n, B, HW, F, eps, alpha, sums, dY);
+  if (n <= 0 || !(n_den >= (double)n)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(crnn_loss_grad_kernel, dim3(blocks_of(n)), dim3(256), 0, st, yhat, y, n, B, HW, F, eps, alpha, sums, n_den, dY);
   return hipGetLastError();
 }
 

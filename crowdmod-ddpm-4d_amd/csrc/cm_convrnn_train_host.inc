@@ -35,6 +35,12 @@ struct CrnnTrain {
   double *lpart = nullptr, *lsums = nullptr, *lterms = nullptr;
   int dcur[3] = {0, 0, 0};
   int lastB = 0;
+  // The split (data-parallel) step.  cm_convrnn_train_forward keeps its target frames in ytgt and its forcing mode in
+  // split_tf; cm_convrnn_train_backward uploads the global sums from hsums (which outlives the call) to gsums.
+  // m->tape_ready says that the tape, the window and ytgt are those of such a forward, with nothing run since.
+  float *ytgt = nullptr;
+  double *gsums = nullptr, hsums[6] = {};
+  int split_tf = 0;
 };
 
 void crnn_free_train(CrnnTrain *t) { delete t; }
@@ -341,20 +347,66 @@ int crnn_train_backward(const CrnnTapeRun &R, int tf) {
   return 0;
 }
 
+CrnnTapeRun crnn_tape_of(cm_convrnn *m, int B, hipStream_t st) {
+  return CrnnTapeRun{m, m->train, B, st, {(long long)m->lh[0] * m->lw[0], (long long)m->lh[1] * m->lw[1], (long long)m->lh[2] * m->lw[2]}};
+}
+
 // forward (+ loss) (+ backward) (+ update); the four terms come back after one synchronisation at the end
 int crnn_train_run(cm_convrnn *m, const float *d_past, const float *d_target, int tf, double loss_eps, double alpha, int backward,
                    int apply_update, double h_terms[4], int B, hipStream_t st) {
   CrnnTrain *T = m->train;
   const cm_convrnn_config &c = m->cfg;
-  CrnnTapeRun R{m, T, B, st, {(long long)m->lh[0] * m->lw[0], (long long)m->lh[1] * m->lw[1], (long long)m->lh[2] * m->lw[2]}};
+  CrnnTapeRun R = crnn_tape_of(m, B, st);
+  m->tape_ready = false;
   if (crnn_tape_forward(R, d_past, d_target, tf)) return 1;
   const int HW = c.rows * c.cols;
   CM_HIP(cm::launch_crnn_loss(T->yhat, d_target, B, HW, c.future_len, loss_eps, T->lpart, T->lsums, T->lterms, st));
   if (backward) {
-    CM_HIP(cm::launch_crnn_loss_grad(T->yhat, d_target, B, HW, c.future_len, loss_eps, alpha, T->lsums, T->dY, st));
+    CM_HIP(cm::launch_crnn_loss_grad(T->yhat, d_target, B, HW, c.future_len, loss_eps, alpha, T->lsums,
+                                     (double)((long long)B * HW * c.future_len), T->dY, st));
     if (crnn_train_backward(R, tf)) return 1;
     if (apply_update && (T->opt.apply(st) || crnn_train_repack(m, st))) return 1;
   }
+  if (h_terms) {
+    CM_HIP(hipMemcpyAsync(h_terms, T->lterms, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    CM_HIP(hipStreamSynchronize(st));
+  }
+  return 0;
+}
+
+// The first half of a split step, and its validation form: the tape forward and the loss sums.  h_sums[0..4] are the five
+// sums of this call's samples, h_sums[5] their element count B HW F, after one synchronisation.  With `keep` the target
+// frames are copied to the handle and the tape is marked as waiting for crnn_split_backward.
+int crnn_forward_sums(cm_convrnn *m, const float *d_past, const float *d_target, int tf, bool keep, double h_sums[6], int B, hipStream_t st) {
+  CrnnTrain *T = m->train;
+  const cm_convrnn_config &c = m->cfg;
+  const int HW = c.rows * c.cols;
+  const long long n = (long long)B * HW * c.future_len;
+  m->tape_ready = false;
+  if (crnn_tape_forward(crnn_tape_of(m, B, st), d_past, d_target, tf)) return 1;
+  CM_HIP(cm::launch_crnn_loss(T->yhat, d_target, B, HW, c.future_len, 0.0, T->lpart, T->lsums, nullptr, st));
+  if (keep) CM_HIP(hipMemcpyAsync(T->ytgt, d_target, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  CM_HIP(hipMemcpyAsync(h_sums, T->lsums, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
+  CM_HIP(hipStreamSynchronize(st));
+  h_sums[5] = (double)n;
+  T->split_tf = tf;
+  m->tape_ready = keep;
+  return 0;
+}
+
+// The second half: the four terms and d loss / d yhat from the GLOBAL sums (this rank's elements, the denominators of all
+// ranks), then the backward over the tape crnn_forward_sums left.  The gradient is this rank's share of the global
+// objective's: the shares are summed over ranks, not averaged.
+int crnn_split_backward(cm_convrnn *m, const double g[6], double loss_eps, double alpha, double h_terms[4], hipStream_t st) {
+  CrnnTrain *T = m->train;
+  const cm_convrnn_config &c = m->cfg;
+  const int B = T->lastB, HW = c.rows * c.cols;
+  m->tape_ready = false;
+  std::copy(g, g + 6, T->hsums);
+  CM_HIP(hipMemcpyAsync(T->gsums, T->hsums, 6 * sizeof(double), hipMemcpyHostToDevice, st));
+  CM_HIP(cm::launch_crnn_loss_terms(T->gsums, loss_eps, T->lterms, st));
+  CM_HIP(cm::launch_crnn_loss_grad(T->yhat, T->ytgt, B, HW, c.future_len, loss_eps, alpha, T->gsums, g[5], T->dY, st));
+  if (crnn_train_backward(crnn_tape_of(m, B, st), T->split_tf)) return 1;
   if (h_terms) {
     CM_HIP(hipMemcpyAsync(h_terms, T->lterms, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     CM_HIP(hipStreamSynchronize(st));
@@ -456,6 +508,7 @@ int cm_convrnn_train_init(cm_convrnn *m, float lr, float beta1, float beta2, flo
   if (alloc(&T->yhat, MB * 4 * HW * Ft) || alloc(&T->dY, Ft * MB * HW * 8)) return 1;
   const size_t nblk = (MB * HW * Ft + 255) / 256;
   if (alloc((float **)&T->lpart, 2 * 5 * nblk) || alloc((float **)&T->lsums, 2 * 5) || alloc((float **)&T->lterms, 2 * 4)) return 1;
+  if (alloc(&T->ytgt, MB * 4 * HW * Ft) || alloc((float **)&T->gsums, 2 * 6)) return 1;
   m->train = T.release();
   return 0;
 }
@@ -477,8 +530,51 @@ int cm_convrnn_train_step(cm_convrnn *m, const float *d_past, const float *d_tar
                         stream ? (hipStream_t)stream : m->stream);
 }
 
+int cm_convrnn_train_forward(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, int32_t B, void *stream,
+                             double h_sums[6]) {
+  if (crnn_train_ready(m, B, true)) return 1;
+  if (!d_past || !d_target || !h_sums) return fail("null argument");
+  DevGuard g(m->device);
+  return crnn_forward_sums(m, d_past, d_target, teacher_forcing != 0, true, h_sums, B, stream ? (hipStream_t)stream : m->stream);
+}
+
+int cm_convrnn_loss_sums(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, int32_t B, void *stream,
+                         double h_sums[6]) {
+  if (crnn_train_ready(m, B, true)) return 1;
+  if (!d_past || !d_target || !h_sums) return fail("null argument");
+  DevGuard g(m->device);
+  return crnn_forward_sums(m, d_past, d_target, teacher_forcing != 0, false, h_sums, B, stream ? (hipStream_t)stream : m->stream);
+}
+
+int cm_convrnn_train_backward(cm_convrnn *m, const double h_global_sums[6], double loss_eps, double alpha, double h_terms[4], void *stream) {
+  if (crnn_train_ready(m, 1, true)) return 1;
+  if (!h_global_sums) return fail("null argument");
+  if (!m->tape_ready)
+    return fail("cm_convrnn_train_backward: no cm_convrnn_train_forward is waiting on this handle (it must come directly before)");
+  const double own = (double)m->train->lastB * m->cfg.rows * m->cfg.cols * m->cfg.future_len;
+  // the three counts are sums of ones: never NaN, whatever the loss sums are (a diverged run keeps its NaN terms)
+  if (!(h_global_sums[2] >= 0) || !(h_global_sums[4] >= 0) || !(h_global_sums[5] >= own) || std::isinf(h_global_sums[5]))
+    return fail("cm_convrnn_train_backward: global counts (%g occupied, %g empty, %g elements) cannot contain this handle's %g elements",
+                h_global_sums[2], h_global_sums[4], h_global_sums[5], own);
+  DevGuard g(m->device);
+  return crnn_split_backward(m, h_global_sums, loss_eps, alpha, h_terms, stream ? (hipStream_t)stream : m->stream);
+}
+
+int cm_convrnn_train_flat_grads(cm_convrnn *m, float **d_ptr, int64_t *numel) {
+  if (crnn_train_ready(m, 1, true)) return 1;
+  return m->train->opt.flat_grads((void **)d_ptr, numel);
+}
+
+int cm_convrnn_loss_terms_from_sums(const double sums[6], double eps, double terms[4]) {
+  if (!sums || !terms) return fail("null argument");
+  if (!(sums[5] >= 1)) return fail("cm_convrnn_loss_terms_from_sums: element count %g < 1", sums[5]);
+  cm::crnn_loss_terms(sums, sums[5], eps, terms);
+  return 0;
+}
+
 int cm_convrnn_train_apply(cm_convrnn *m, void *stream) {
   if (crnn_train_ready(m, 1, true)) return 1;
+  m->tape_ready = false;   // the tape is of the weights before the update
   DevGuard g(m->device);
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   return m->train->opt.apply(st) || crnn_train_repack(m, st);

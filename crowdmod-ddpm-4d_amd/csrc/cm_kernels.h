@@ -661,11 +661,24 @@ hipError_t launch_crnn_add(float *dst, const float *src, long long n, hipStream_
 // The five sums of utils/loss.py:15-52 over yhat, y [B][4][HW][F] in float64 (fixed-order partials, then one finalise):
 // sums[0..4] = Poisson-KL, masked MSE, occupied count, empty penalty, empty count; terms[0..3] = rloss, vloss,
 // loss_considering_density, loss_not_considering_density.  part: ceil(B HW F / 256) * 5 doubles.
+// terms null: the sums alone (the first half of a data-parallel step; eps is not read).
 hipError_t launch_crnn_loss(const float *yhat, const float *y, int B, int HW, int F, double eps, double *part, double *sums,
                             double *terms, hipStream_t st);
-// d (rloss + alpha vloss) / d yhat into dY [F][B][HW][8] (channels 4-7 zero), from the finalised sums
+// count + eps as the reference forms it: its masks are float32, so the denominator is rounded to fp32
+__host__ __device__ inline double crnn_loss_den(double count, double eps) { return (double)((float)count + (float)eps); }
+// The four terms of utils/loss.py:44-50 from the five sums and the element count n: the one definition behind the finalise
+// kernel, the terms kernel of the split step and cm_convrnn_loss_terms_from_sums on the host.
+__host__ __device__ inline void crnn_loss_terms(const double *s, double n, double eps, double *terms) {
+  const double lcd = s[1] / crnn_loss_den(s[2], eps), lncd = s[3] / crnn_loss_den(s[4], eps);
+  terms[0] = s[0] / n; terms[1] = lcd + lncd; terms[2] = lcd; terms[3] = lncd;
+}
+// terms[0..3] from sums[0..4] and the element count sums[5], all on the device (one thread)
+hipError_t launch_crnn_loss_terms(const double *sums6, double eps, double *terms, hipStream_t st);
+// d (rloss + alpha vloss) / d yhat into dY [F][B][HW][8] (channels 4-7 zero) over this call's B HW F elements, from the
+// finalised sums: sums[2], sums[4] are the occupied and empty counts and n_den the element count of the Poisson mean -- the
+// call's own (the fused step) or the totals over every rank of a data-parallel step.
 hipError_t launch_crnn_loss_grad(const float *yhat, const float *y, int B, int HW, int F, double eps, double alpha,
-                                 const double *sums, float *dY, hipStream_t st);
+                                 const double *sums, double n_den, float *dY, hipStream_t st);
 
 // Per-step scalars of the sampling loop as a device table, so that one captured graph of a step can be
 // replayed for every step: the step kernels read row tab[*kctr]; step_begin advances the counter.

@@ -85,6 +85,22 @@ def mean_over_ranks(value: float, group=None) -> float:
     return float(t.item()) / dist.get_world_size(group)
 
 
+def sum_over_ranks(values, group=None) -> np.ndarray:
+    """Element-wise fp64 SUM of a small host vector over the ranks, identical on every rank: the six loss sums of a
+    ConvRNN step (48 bytes), whose loss divides by counts over the global batch.  Device choice as mean_over_ranks."""
+    import torch
+    import torch.distributed as dist
+    v = np.array(values, dtype=np.float64).reshape(-1)
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return v
+    dev = "cpu"
+    if dist.get_backend(group) == "nccl":
+        dev = torch.device("cuda", torch.cuda.current_device())
+    t = torch.from_numpy(v).to(dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy()
+
+
 class _DevView:
     """Zero-copy torch view of a raw device allocation through __cuda_array_interface__."""
 
@@ -95,10 +111,14 @@ class _DevView:
 class GradAverager:
     """grad <- mean over ranks of grad, in place on the library's flat gradient buffer (28.9 MB fp32 for
     the ATC model: ONE all-reduce per step, no bucketing needed at this size).  With the nccl backend the
-    buffer is wrapped zero-copy and reduced by RCCL; with gloo it is staged through the host."""
+    buffer is wrapped zero-copy and reduced by RCCL; with gloo it is staged through the host.
 
-    def __init__(self, group=None):
+    average=False leaves the SUM: the ConvRNN's split step (Forecaster.train_backward) normalises each rank's gradient by
+    the global loss counts, so the ranks' gradients are shares of one objective and add up to its gradient."""
+
+    def __init__(self, group=None, average: bool = True):
         self.group = group
+        self.average = bool(average)
         self._view = None
         self._key = None
 
@@ -115,12 +135,14 @@ class GradAverager:
                 self._view = torch.as_tensor(_DevView(ptr, n), device=f"cuda:{net.device}")
                 self._key = (ptr, n)
             dist.all_reduce(self._view, op=dist.ReduceOp.SUM, group=self.group)
-            self._view.div_(world)
+            if self.average:
+                self._view.div_(world)
             torch.cuda.current_stream(self._view.device).synchronize()
         else:
             host = np.empty(n, dtype=np.float32)
             native.check(native.lib().cm_memcpy_d2h(net.device, host.ctypes.data, ptr, host.nbytes))
             t = torch.from_numpy(host)
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-            t.div_(world)
+            if self.average:
+                t.div_(world)
             native.check(native.lib().cm_memcpy_h2d(net.device, ptr, host.ctypes.data, host.nbytes))

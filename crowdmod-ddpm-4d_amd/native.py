@@ -194,6 +194,11 @@ SIGNATURES = {
     "cm_convrnn_train_set_opt_state": (C.c_int, [_P, C.c_char_p, C.c_int32, _P, C.c_int64]),
     "cm_convrnn_train_opt_step": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32]),
     "cm_convrnn_train_sync": (C.c_int, [_P]),
+    "cm_convrnn_train_forward": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
+    "cm_convrnn_train_backward": (C.c_int, [_P, C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_double), _P]),
+    "cm_convrnn_train_flat_grads": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "cm_convrnn_loss_sums": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_double)]),
+    "cm_convrnn_loss_terms_from_sums": (C.c_int, [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double)]),
 }
 
 

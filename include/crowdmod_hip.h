@@ -538,6 +538,31 @@ int cm_convrnn_train_opt_step(cm_convrnn *m, int32_t *step, int32_t set);
 /* Copies the master weights back to the state_dict (cm_convrnn_get_param) and re-packs every weight layout. */
 int cm_convrnn_train_sync(cm_convrnn *m);
 
+/* ---- The training step cut where the loss has its reduction over the whole batch (data-parallel training).  The loss
+ * divides by counts over ALL samples of a step, so N ranks cannot each run cm_convrnn_train_step and average: each runs
+ * cm_convrnn_train_forward, the six sums are added over the ranks, each runs cm_convrnn_train_backward with the totals, the
+ * flat gradients (each rank's share of the global objective's gradient) are added over the ranks, and each runs
+ * cm_convrnn_train_apply.  Fed its own sums, the pair equals cm_convrnn_train_step(apply_update = 0) bit for bit.
+ * sums[0..4] = Poisson-KL sum, occupied MSE sum, occupied count, empty penalty sum, empty count; sums[5] = B*H*W*F. */
+/* The forward with its activations kept, and the six sums of this call's samples after one synchronisation.  The target
+ * frames are copied: neither device buffer is read after the call returns. */
+int cm_convrnn_train_forward(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, int32_t B,
+                             void *stream, double h_sums[6]);
+/* h_terms (may be NULL: then the call only enqueues) = the four loss terms of the global sums; every gradient of
+ * rloss + alpha * vloss with the global denominators, over this handle's samples; no update.  Refused unless a
+ * cm_convrnn_train_forward on this handle came directly before: any other forward, step, loss or update in between, on
+ * the training or the forecasting side, invalidates it.  The three counts must be numbers >= 0, with sums[5] >= this handle's own element count. */
+int cm_convrnn_train_backward(cm_convrnn *m, const double h_global_sums[6], double loss_eps, double alpha, double h_terms[4],
+                              void *stream);
+/* The flat fp32 gradient buffer on the device, in state_dict order (the optimizer store's layout): what a data-parallel
+ * run reduces in place before cm_convrnn_train_apply.  The coupled L2 term is not in it: the update adds it. */
+int cm_convrnn_train_flat_grads(cm_convrnn *m, float **d_ptr, int64_t *numel);
+/* The validation half: forward and the six sums, no tape kept for a backward. */
+int cm_convrnn_loss_sums(cm_convrnn *m, const float *d_past, const float *d_target, int32_t teacher_forcing, int32_t B,
+                         void *stream, double h_sums[6]);
+/* Host only, no handle: the four loss terms of six (global) sums, by the expressions the device evaluates. */
+int cm_convrnn_loss_terms_from_sums(const double sums[6], double eps, double terms[4]);
+
 #ifdef __cplusplus
 }
 #endif

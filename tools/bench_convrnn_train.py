@@ -8,7 +8,11 @@ forcing on, synthetic weights, device buffers.  Each path: `--warmup` steps, the
 `--steps` steps.  Prints one JSON line per cell: ms per step of both paths, their ratio, and the loss both report for the
 first step (same weights, same batch).
 
-    python tools/bench_convrnn_train.py [--batch 64] [--cells gru lstm] [--steps 20] [--warmup 3] [--no-torch]
+`--split` adds the data-parallel form of the step in the same process, after the fused one: cm_convrnn_train_forward (one
+host synchronisation for the six loss sums), cm_convrnn_train_backward fed those sums back, cm_convrnn_train_apply.  No
+collective runs: the figure is what cutting the step costs on one GPU.
+
+    python tools/bench_convrnn_train.py [--batch 64] [--cells gru lstm] [--steps 20] [--warmup 3] [--no-torch] [--split]
 """
 import argparse
 import json
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-torch", action="store_true", help="time the native path only (profiling runs)")
+    ap.add_argument("--split", action="store_true", help="also time the split (data-parallel) step fed its own sums")
     a = ap.parse_args()
     import torch
     from bench_convrnn import torch_forecaster
@@ -94,6 +99,16 @@ def main():
         ms = timed(native_step, a.steps)
         doc = {"cell": cell, "batch": B, "steps": a.steps, "warmup": a.warmup, "teacher_forcing": True, "native_ms_per_step": ms,
                "native_samples_per_s": B / (ms * 1e-3), "native_first_loss": first[0] + first[1]}
+        if a.split:
+            import ctypes as C
+            sums = (C.c_double * 6)()
+
+            def split_step():   # the forward synchronises for the sums; backward (h_terms NULL) and the update only enqueue
+                native.check(L.cm_convrnn_train_forward(h, d_past.data_ptr(), d_tgt.data_ptr(), 1, B, stream.cuda_stream, sums))
+                native.check(L.cm_convrnn_train_backward(h, sums, EPS, 1.0, None, stream.cuda_stream))
+                native.check(L.cm_convrnn_train_apply(h, stream.cuda_stream))
+            sms = timed(split_step, a.steps)
+            doc.update({"split_ms_per_step": sms, "split_over_fused": sms / ms})
         if not a.no_torch:
             w = {k: torch.nn.Parameter(torch.from_numpy(v).to(dev)) for k, v in params.items()}
             tnet = torch_forecaster(params, cfg, dev, w)
