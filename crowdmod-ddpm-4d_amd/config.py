@@ -146,6 +146,17 @@ def resolve_convrnn(cfg) -> ConvRNNKeys:
                        tuple(int(v) for v in req("FORC_KERNELS")), int(train.get("EPOCHS", 0)))
 
 
+def train_autocast(train) -> bool:
+    """MODEL.<DDPM|FM>.UNET.TRAIN.AUTOCAST of a resolved TRAIN node (Resolved.train): the UNet's training step on f16
+    matrix-core operands in its Winograd layers (the reference's torch.amp.autocast, ddpm.py:116-120).  Absent = False."""
+    if train is None or not hasattr(train, "get"):
+        return False
+    v = train.get("AUTOCAST", False)
+    if not isinstance(v, (bool, int)) or v not in (0, 1, False, True):
+        raise ValueError(f"TRAIN.AUTOCAST must be a bool, not {v!r}")
+    return bool(v)
+
+
 def _first(*vals, default=None):
     for v in vals:
         if v is not None:

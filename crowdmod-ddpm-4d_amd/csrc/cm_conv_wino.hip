@@ -1723,6 +1723,224 @@ __global__ __launch_bounds__(512, 2) void wgrad_wino_kernel(const ConvArgs a, co
     }
 }
 
+// f16-operand form (autocast training step, cm_train_set_autocast): the same contraction on v_mfma_f32_32x32x16_f16 -- 16 patch
+// rows per instruction, fp32 accumulators, the same partials.  V = B^T d B is staged exactly as above and rounded to f16 where the
+// forward's f16 form rounds its transformed input (the LDS write), dM = A dY A^T is formed in fp32 and rounded once.
+// The contraction index k enumerates (output plane zr, patch pr) as k = zr * NPP + pr with NPP = 4 (8 x 2 x 2 tile) or 16 (the
+// two-plane tiles, patches NP .. 15 zero), so that a z tap is the constant offset dz * NPP and a lane's 8 operand elements
+// k = 16 s + 8 hh + j are CONTIGUOUS halves of the transposed image Vt[xi][ci][zi * NPP + patch] (8-byte aligned: two ds_read_b64).
+// Lines are padded by 4 halves: 22 / 34 dwords per (xi, ci) line, the 32 ci lanes of a read fall on 32 different bank pairs.
+template <int BZ, int PY, int PX>
+__global__ __launch_bounds__(512) void wgrad_wino_f16_kernel(const ConvArgs a, const float *__restrict__ dy, int dy_cs,
+                                                             float *__restrict__ part, int G) {
+  constexpr int NP = PY * PX, ROWS = BZ * NP, HZ = BZ + 2;
+  constexpr int NPP = NP == 4 ? 4 : 16;
+  static_assert(NP <= NPP && BZ * NPP == 32 && ROWS <= 32, "32 contraction indices per tile");
+  constexpr int LS = HZ * NPP + 4;                 // halves per (xi, ci) line
+  constexpr int NIT = HZ * NP * 8;
+  static_assert(NIT <= 512, "one staging round of the 512 threads");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  _Float16 *Vt = reinterpret_cast<_Float16 *>(lds);   // [16][32 ci][LS]
+  float *Yt = lds + 16 * 32 * LS / 2;              // [32 k][32 co][4 = (a, b)]
+  constexpr bool TWO = BZ == 8 && CM_WGRAD_TWO;
+  constexpr int RYH = 2 * PY + 2, RXH = 2 * PX + 2, RVX = HZ * RYH * RXH, RSX = 36;
+  float *R = Yt + 32 * 32 * 4;                     // [RVX][RSX] (TWO only)
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = w8 & 3, xh = w8 >> 2;
+  const int r = lane & 31, hh = lane >> 5;
+  const int g = blockIdx.x, cb = blockIdx.y, kb = blockIdx.z;
+  const int Ctot = a.C0 + a.C1;
+  const int ci0 = kb * 32;
+  const int pyt = a.Yo >> 1, pxt = a.Xo >> 1;
+  const int ntile = a.B * a.ntz * a.nty * a.ntx;
+  const float cy0 = wave == 3 ? 0.f : 1.f, cy1 = wave == 0 ? 0.f : (wave == 1 ? 1.f : -1.f);
+
+  f32x16 acc[3][2];
+#pragma unroll
+  for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[dz][x][i] = 0.f;
+  // the padding slots of a line (patches NP .. NPP - 1, the 4 trailing halves) are never written: zero the image once
+  for (int i = tid; i < 16 * 32 * LS / 2; i += 512) lds[i] = 0.f;
+
+  for (int tile = g; tile < ntile; tile += G) {
+    int tt = tile;
+    const int tx = tt % a.ntx; tt /= a.ntx;
+    const int ty = tt % a.nty; tt /= a.nty;
+    const int tz = tt % a.ntz;
+    const int b = tt / a.ntz;
+    const int py0 = min(ty * PY, pyt - PY), px0 = min(tx * PX, pxt - PX);
+    const int z0 = tz * BZ, y0 = 2 * py0, x0 = 2 * px0;
+    __syncthreads();                               // previous tile's operands have been read (first tile: the image is zeroed)
+    if constexpr (TWO) {
+      constexpr int RK = (RVX * 8 + 511) / 512;
+      const int quad = tid & 7;
+      const int c = ci0 + 4 * quad;
+      const bool cok = c < Ctot;
+      const bool from0 = c < a.C0;
+      const float *sp = from0 ? a.src0 + c : a.src1 + (c - a.C0);
+      const int Cs = from0 ? a.C0 : a.C1;
+      f32x4 sc1 = {1.f, 1.f, 1.f, 1.f}, sh1 = {0.f, 0.f, 0.f, 0.f}, pm1 = {1.f, 1.f, 1.f, 1.f};
+      const int cc = cok ? c : 0;
+      if (a.gn) {
+        const float *gp = a.gn + (size_t)b * 2 * Ctot + cc;
+        sc1 = *reinterpret_cast<const f32x4 *>(gp);
+        sh1 = *reinterpret_cast<const f32x4 *>(gp + Ctot);
+      }
+      if (a.pm) pm1 = *reinterpret_cast<const f32x4 *>(a.pm + (size_t)b * a.pm_stride + cc);
+      f32x4 ld[RK];
+      unsigned okm = 0;
+#pragma unroll
+      for (int k = 0; k < RK; ++k) {
+        const int v = (tid >> 3) + 64 * k;
+        const int zi = v / (RYH * RXH), rem = v - zi * (RYH * RXH), ry = rem / RXH, rx = rem - ry * RXH;
+        const int cz = z0 - 1 + zi, cyy = y0 - 1 + ry, cxx = x0 - 1 + rx;
+        const bool ok = v < RVX && cok && cz >= 0 && cz < a.Zs && cyy >= 0 && cyy < a.Ys && cxx >= 0 && cxx < a.Xs;
+        const int off = ok ? ((b * a.Zs + cz) * a.Ys + cyy) * a.Xs + cxx : 0;
+        ld[k] = *reinterpret_cast<const f32x4 *>(sp + (size_t)off * Cs);
+        okm |= (ok ? 1u : 0u) << k;
+      }
+#pragma unroll
+      for (int k = 0; k < RK; ++k) {
+        const int v = (tid >> 3) + 64 * k;
+        f32x4 w = ld[k];
+        if (a.gn) {
+          w = w * sc1 + sh1;
+          if (a.silu) { w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]); }
+        }
+        if (a.pm) w = w * pm1;
+        if (!((okm >> k) & 1u)) w = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (v < RVX) *reinterpret_cast<f32x4 *>(R + (size_t)v * RSX + 4 * quad) = w;
+      }
+      __syncthreads();
+    }
+    // ---- V = B^T d B of the conv's actual input, as the forward stages it; rounded to f16 at the LDS write ----
+    {
+      const bool stager = tid < NIT;
+      const int itc = stager ? tid : 0;
+      const int quad = itc & 7, patch = (itc >> 3) % NP, zi = itc / (8 * NP);
+      const int py = patch / PX, px = patch % PX;
+      const int c = ci0 + 4 * quad;
+      f32x4 d[16];
+      if constexpr (TWO) {
+        const float *rb = R + (size_t)((zi * RYH + 2 * py) * RXH + 2 * px) * RSX + 4 * quad;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) d[i * 4 + j] = *reinterpret_cast<const f32x4 *>(rb + (size_t)(i * RXH + j) * RSX);
+      } else {
+        const bool from0 = c < a.C0;
+        const float *sp = from0 ? a.src0 + c : a.src1 + (c - a.C0);
+        const int Cs = from0 ? a.C0 : a.C1;
+        const int cz = z0 - 1 + zi;
+        const bool zok = stager && c < Ctot && cz >= 0 && cz < a.Zs;
+        unsigned okmask = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int cyy = y0 + 2 * py - 1 + i, cxx = x0 + 2 * px - 1 + j;
+            const bool ok = zok && cyy >= 0 && cyy < a.Ys && cxx >= 0 && cxx < a.Xs;
+            const int off = ok ? ((b * a.Zs + cz) * a.Ys + cyy) * a.Xs + cxx : 0;
+            d[i * 4 + j] = *reinterpret_cast<const f32x4 *>(sp + (size_t)off * Cs);
+            okmask |= (ok ? 1u : 0u) << (i * 4 + j);
+          }
+        f32x4 sc1 = {1.f, 1.f, 1.f, 1.f}, sh1 = {0.f, 0.f, 0.f, 0.f}, pm1 = {1.f, 1.f, 1.f, 1.f};
+        const int cc = c < Ctot ? c : 0;
+        if (a.gn) {
+          const float *gp = a.gn + (size_t)b * 2 * Ctot + cc;
+          sc1 = *reinterpret_cast<const f32x4 *>(gp);
+          sh1 = *reinterpret_cast<const f32x4 *>(gp + Ctot);
+        }
+        if (a.pm) pm1 = *reinterpret_cast<const f32x4 *>(a.pm + (size_t)b * a.pm_stride + cc);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          f32x4 w = d[k];
+          if (a.gn) {
+            w = w * sc1 + sh1;
+            if (a.silu) { w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]); }
+          }
+          if (a.pm) w = w * pm1;
+          d[k] = ((okmask >> k) & 1u) ? w : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 e0 = d[i * 4 + 0], e1 = d[i * 4 + 1], e2 = d[i * 4 + 2], e3 = d[i * 4 + 3];
+        d[i * 4 + 0] = pk_sub(e0, e2); d[i * 4 + 1] = e1 + e2; d[i * 4 + 2] = pk_sub(e2, e1); d[i * 4 + 3] = pk_sub(e1, e3);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 e0 = d[0 * 4 + j], e1 = d[1 * 4 + j], e2 = d[2 * 4 + j], e3 = d[3 * 4 + j];
+        d[0 * 4 + j] = pk_sub(e0, e2); d[1 * 4 + j] = e1 + e2; d[2 * 4 + j] = pk_sub(e2, e1); d[3 * 4 + j] = pk_sub(e1, e3);
+      }
+      if (stager) {
+        _Float16 *vw = Vt + (size_t)(4 * quad) * LS + zi * NPP + patch;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+#pragma unroll
+          for (int c4 = 0; c4 < 4; ++c4) vw[((size_t)k * 32 + c4) * LS] = (_Float16)d[k][c4];
+      }
+    }
+    // ---- raw dY patches by contraction index: Yt[k][co][(a, b)]; padding indices and rows this tile does not own are zero ----
+    if (tid < 256) {
+      const int kk = tid >> 3, q = tid & 7;
+      const int zr = kk / NPP, pr = kk % NPP, py = pr / PX, px = pr % PX;
+      const bool own = pr < NP && py0 + py >= ty * PY && px0 + px >= tx * PX;
+      const int co = cb * 32 + 4 * q;
+      f32x4 yv[4];
+#pragma unroll
+      for (int ab = 0; ab < 4; ++ab) {
+        const int oz = z0 + zr, oy = y0 + 2 * py + (ab >> 1), ox = x0 + 2 * px + (ab & 1);
+        const bool ok = own && oz < a.Zo && oy < a.Yo && ox < a.Xo && co < a.Co;
+        const int off = ok ? ((b * a.Zo + oz) * a.Yo + oy) * a.Xo + ox : 0;
+        yv[ab] = *reinterpret_cast<const f32x4 *>(dy + (size_t)off * dy_cs + (co < a.Co ? co : 0));
+        if (!ok) yv[ab] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4)
+        *reinterpret_cast<f32x4 *>(Yt + ((size_t)kk * 32 + 4 * q + c4) * 4) = f32x4{yv[0][c4], yv[1][c4], yv[2][c4], yv[3][c4]};
+    }
+    __syncthreads();
+    // ---- matrix phase: 2 k steps x (2 components x 3 z taps) -----------------------------------------------
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      f16x8 b0, b1;                                // dM of this wave's two components at k = 16 s + 8 hh + j, column co = r
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 yv = *reinterpret_cast<const f32x4 *>(Yt + ((size_t)(16 * s + 8 * hh + j) * 32 + r) * 4);
+        const float t0 = cy0 * yv[0] + cy1 * yv[2], t1 = cy0 * yv[1] + cy1 * yv[3];
+        b0[j] = (_Float16)(xh ? t0 - t1 : t0);
+        b1[j] = (_Float16)(xh ? -t1 : t0 + t1);
+      }
+#pragma unroll
+      for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+          const _Float16 *ap = Vt + ((size_t)(wave * 4 + 2 * xh + x) * 32 + r) * LS + dz * NPP + 16 * s + 8 * hh;
+          const f16x4 lo = *reinterpret_cast<const f16x4 *>(ap), hi = *reinterpret_cast<const f16x4 *>(ap + 4);
+          const f16x8 av = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          acc[dz][x] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, x ? b1 : b0, acc[dz][x], 0, 0, 0);
+        }
+    }
+  }
+  // ---- partials: part[g][cb][kb][dz][xi][ci][co] ----------------------------------------------------------
+#pragma unroll
+  for (int dz = 0; dz < 3; ++dz)
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+      float *p = part + (((((size_t)g * gridDim.y + cb) * gridDim.z + kb) * 3 + dz) * 16 + wave * 4 + 2 * xh + x) * 1024;
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const int ci = (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+        p[ci * 32 + r] = acc[dz][x][reg];
+      }
+    }
+}
+
 // dW[co][ci][kH][kW][kL] (reference layout) = sum_g G^T dU G of the partials (fixed order)
 __global__ __launch_bounds__(256) void wgrad_wino_reduce_kernel(const float *__restrict__ part, int G, int ncb, int nkb, int Co, int Ci,
                                                                 float *__restrict__ dW) {
@@ -1802,6 +2020,36 @@ hipError_t launch_wgrad_wino(const ConvArgs &a, const float *dy, int dy_cs, floa
       attr_set[dev & 63] = true;                                                                            \
     }                                                                                                       \
     hipLaunchKernelGGL((wgrad_wino_kernel<z, py, px>), dim3(G, ncb, nkb), dim3(512), lds, st, a, dy, dy_cs, part, G); \
+    return hipGetLastError();                                                                               \
+  }
+  CM_WINO_TILES(X)
+#undef X
+  return hipErrorInvalidValue;
+}
+
+// f16 image: 16 x 32 lines of (bz + 2) * NPP + 4 halves (45 KB at full, 70 KB at half resolution; the fp32 image is 80 / 123 KB)
+size_t wgrad_wino_f16_lds(int bz, int by, int bx) {
+  const size_t npp = (by / 2) * (bx / 2) == 4 ? 4 : 16;
+  const size_t r = (bz == 8 && CM_WGRAD_TWO) ? (size_t)(bz + 2) * (by + 2) * (bx + 2) * 36 : 0;
+  return (size_t)16 * 32 * ((bz + 2) * npp + 4) * 2 + (32 * 32 * 4 + r) * sizeof(float);
+}
+
+hipError_t launch_wgrad_wino_f16(const ConvArgs &a, const float *dy, int dy_cs, float *part, int G, int ncb, int nkb, hipStream_t st) {
+  if (!conv_wino_tile_ok(a.bz, a.by, a.bx) || a.stride != 1 || a.par || a.ups || (a.C0 % 4) || (a.C1 % 4) || G < 1) return hipErrorInvalidValue;
+  const size_t lds = wgrad_wino_f16_lds(a.bz, a.by, a.bx);
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+#define X(z, py, px)                                                                                        \
+  if (a.bz == z && a.by == 2 * py && a.bx == 2 * px) {                                                      \
+    static bool attr_set[64] = {false};                                                                     \
+    int dev = 0;                                                                                            \
+    (void)hipGetDevice(&dev);                                                                               \
+    if (!attr_set[dev & 63]) {                                                                              \
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_wino_f16_kernel<z, py, px>),  \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);           \
+      if (e != hipSuccess) return e;                                                                        \
+      attr_set[dev & 63] = true;                                                                            \
+    }                                                                                                       \
+    hipLaunchKernelGGL((wgrad_wino_f16_kernel<z, py, px>), dim3(G, ncb, nkb), dim3(512), lds, st, a, dy, dy_cs, part, G); \
     return hipGetLastError();                                                                               \
   }
   CM_WINO_TILES(X)

@@ -311,6 +311,8 @@ bool conv_wino_b6_ok(int bz, int by, int bx, int Co, int Zo);
 hipError_t launch_wino_b6_repack(const float *wwino, float *w6, long long n_floats, hipStream_t st);
 // Weight gradient in the Winograd domain (same tiles): partials part[G][ncb][nkb][3][16][32 ci][32 co], then G^T dU G
 hipError_t launch_wgrad_wino(const ConvArgs &a, const float *dy, int dy_cs, float *part, int G, int ncb, int nkb, hipStream_t st);
+// ... on f16 operands (autocast training): V and dM rounded to f16, v_mfma_f32_32x32x16_f16, the same partials
+hipError_t launch_wgrad_wino_f16(const ConvArgs &a, const float *dy, int dy_cs, float *part, int G, int ncb, int nkb, hipStream_t st);
 hipError_t launch_wgrad_wino_reduce(const float *part, int G, int ncb, int nkb, int Co, int Ci, float *dW, hipStream_t st);
 // tile (bz, by, bx) the Winograd kernel would use for an output grid, or false if none of its shapes fits
 bool conv_wino_pick(int Zo, int Yo, int Xo, int *bz, int *by, int *bx);
@@ -914,7 +916,8 @@ hipError_t launch_upsample2(const float *x, float *y, int B, int Z, int Y, int X
 hipError_t launch_sumpool2(const float *y, float *x, int B, int Z, int Y, int X, int C, int accumulate, hipStream_t st);
 hipError_t launch_zero_stuff2(const float *y, float *u, int B, int Z, int Y, int X, int C, hipStream_t st);
 hipError_t launch_mse_grad(const float *pred, const float *target, float *g, int B, int C, int H, int W, int P, int F,
-                           hipStream_t st);
+                           hipStream_t st, float scale = 1.f);   // scale: loss scale 2^k of an autocast step
+hipError_t launch_scale_inplace(float *g, long long n, float s, hipStream_t st);
 // `big`: global scratch of attn_bwd_scratch_floats() floats when the S x S matrices exceed LDS (0 floats = not needed)
 size_t attn_bwd_scratch_floats(int B, int S, int E, int heads);
 hipError_t launch_attn_bwd(const float *qkv, const float *dO, float *dqkv, int B, int S, int E, int heads, float *big, hipStream_t st);
@@ -937,6 +940,8 @@ hipError_t launch_adam(float *p, const float *g, float *m, float *v, float *vmax
 // packed element (48 elements per pair and z tap triple): ~20x less traffic than the generic gather.
 struct WinoPackJob { float *dst; const int *idx27; int Co, Ci, Ci_pad, pad; long long n; long long blk0; };
 hipError_t launch_wino_pack_jobs(const float *W, const WinoPackJob *jobs, const int *blk2job, long long nblocks, hipStream_t st);
+// its f16 sibling (autocast training): the same jobs with dst = the f16 fragments (pack_wino_f16 order), the same fp32 sums rounded once
+hipError_t launch_wino_pack_jobs_f16(const float *W, const WinoPackJob *jobs, const int *blk2job, long long nblocks, hipStream_t st);
 
 struct PackJob { float *dst; const int *idx; const float *coef; long long start; int nk; int pad; long long n; long long blk0; };   // coef: optional weights of the nk terms; n elements from workgroup blk0 on
 // blk2job[workgroup] = job index (each job owns ceil(n / 256) consecutive workgroups: no per-element search)

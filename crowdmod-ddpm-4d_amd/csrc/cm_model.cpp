@@ -111,6 +111,7 @@ struct Op {
                             //   sets it from the layer shape; resolve_conv withdraws it when the tile does not fit; final after finalize
   float *d_wwino = nullptr;
   float *d_wwino16 = nullptr;   // the same weights as f16 operands (reduced-precision plan, cm_model_set_precision)
+  float *d_wwino16t = nullptr;  // ... of a default-plan handle that trains under autocast (cm_train_set_autocast): re-packed after every update
   float *d_wwino_b6 = nullptr;  // fp32 plan, inference forward, two-tile layers: exact bf16 x 3 split of d_wwino (pack_wino_b6)
   long long wwino_floats = 0;   // element count of d_wwino
   float *d_wfrag16 = nullptr;   // f16 fragments of a parity-form upsample conv (reduced-precision plan)
@@ -189,7 +190,7 @@ enum ConvForm { FORM_FP32 = 0, FORM_F16 = 1, FORM_B6 = 2, FORM_B3 = 3, FORM_H2 =
 struct ConvRoute { ConvKernel kernel; ConvForm form; };
 
 // The plan of one forward (plan_forward).  B: the batch of ONE enqueue (a lane's share); only conv_wino_p_taken under the f16 plan reads it
-struct FwdCtx { int precision = CM_PRECISION_F32; bool train_fwd = false, h2_stale = false; int B = 1; };
+struct FwdCtx { int precision = CM_PRECISION_F32; bool train_fwd = false, h2_stale = false; int B = 1; bool autocast = false; };   // autocast: the training forward of a handle in cm_train_set_autocast mode 1
 // Who turns the slot statistics behind an OP_GNFIN into scale / shift rows, in order of precedence: its whole-sample quarter-resolution
 // consumer; the second pass of the K-split conv / attention block that produces g0; its Winograd consumer (few slots); its own launch
 enum FinBy { FIN_NONE, FIN_QR, FIN_COMBINE, FIN_WINO, FIN_ALONE };
@@ -255,6 +256,7 @@ struct cm_model {
   float *train_temb = nullptr;  // [B][nproj], row b
   long long *train_iota = nullptr;
   bool use_train_temb = false;
+  bool train_autocast = false;   // cm_train_set_autocast mode 1: the training forward's Winograd layers on f16 operands (FwdCtx::autocast)
   float *mse_partial = nullptr, *mse_loss = nullptr;
   float *ks_scratch = nullptr;  // raw partial outputs of K-split convs [S][B][V][Co]
   size_t ks_scratch_floats = 0;
@@ -1102,7 +1104,7 @@ int h16_mask(const Op &op, bool train_fwd) {
 
 // Pure function of the resolved op and the context: no device pointer is dereferenced (fragment pointers count as present /
 // absent), no stream, no model.  (plan_conv withdraws the upsample conv's h2 form where no earlier op writes its source's slot statistics.)
-ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale) {
+ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale, bool autocast = false) {
   static const bool no_train_qr = cm::diag_env("CM_NO_TRAIN_QR") != nullptr, no_train_b6 = cm::diag_env("CM_NO_TRAIN_B6") != nullptr;
   const bool infer = !train_fwd;
   // the six-term fragments serve the training forward as well (exact splits, fp32 accumulate; they follow every optimizer step);
@@ -1127,6 +1129,8 @@ ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale)
   if (op.ups && (op.d_wups16 || !(op.d_wfrag16 && infer)))
     return {CONV_UPS, form(op.d_wups16, six_ok ? op.d_wups_b6 : nullptr, op.d_wups_h2)};
   if (op.wino && op.f16d && infer) return {CONV_F16D, FORM_F16};
+  // autocast training forward: the layers that train on the Winograd route take its f16-operand form (fp32 activations, fp32 accumulation)
+  if (op.wino && train_fwd && autocast && op.d_wwino16t) return {CONV_WINO, FORM_F16};
   if (op.wino)
     return {CONV_WINO, form(op.d_wwino16, (op.d_wwino_b6 && six_ok && cm::conv_wino_b6_ok(g.bz, g.by, g.bx, g.Co, g.Zo)) ? op.d_wwino_b6 : nullptr, op.d_wwino_h2)};
   if (op.first_k) return {CONV_FIRST, FORM_FP32};
@@ -1222,7 +1226,7 @@ int plan_h16(cm_model *m) {
 // The conv part of a plan entry: the op's route in `ctx` and the slot count of the statistics it writes, that of the kernel family that
 // runs.  `src_slots`: slots an earlier op writes for the source tensor (the upsample conv's h2 form reads them), 0 = none.  Returns an error text or "".
 std::string plan_conv(const Op &op, const FwdCtx &ctx, int src_slots, OpPlan *p) {
-  ConvRoute r = conv_route(op, ctx.precision, ctx.train_fwd, ctx.h2_stale);
+  ConvRoute r = conv_route(op, ctx.precision, ctx.train_fwd, ctx.h2_stale, ctx.autocast);
   if (r.kernel == CONV_UPS && r.form == FORM_H2 && src_slots <= 0) {
     Op plain = op; plain.d_wups_h2 = nullptr;
     r = conv_route(plain, ctx.precision, ctx.train_fwd, ctx.h2_stale);
@@ -1495,7 +1499,7 @@ int run_conv(const cm_model *m, const Op &op, const FwdPlan &plan, const OpPlan 
       break;
     case CONV_WINO: {
       const bool f16 = route.form == FORM_F16;
-      ca.wfrag = f16 ? op.d_wwino16 : route.form == FORM_H2 ? op.d_wwino_h2 : route.form == FORM_FP32 ? op.d_wwino : op.d_wwino_b6;
+      ca.wfrag = f16 ? (train ? op.d_wwino16t : op.d_wwino16) : route.form == FORM_H2 ? op.d_wwino_h2 : route.form == FORM_FP32 ? op.d_wwino : op.d_wwino_b6;
       if (!f16) ca.f16 = route.form;
       if (route.form == FORM_H2) ca.h2_oscale = op.h2_oscale;
       // FIN_WINO: the GroupNorm of the input from the producers' slot partials, merged in the kernel's prologue
@@ -1689,7 +1693,7 @@ int check_ready(cm_model *m, int B) {
 
 // Entry points plan on the calling thread, before anything is enqueued; their own plan goes into cm_model::plan, which nothing else writes.
 int make_plan(const cm_model *m, bool train_fwd, int B, FwdPlan *plan) {
-  *plan = plan_forward(m->ops, FwdCtx{m->precision, train_fwd, m->h2_stale, B});
+  *plan = plan_forward(m->ops, FwdCtx{m->precision, train_fwd, m->h2_stale, B, train_fwd && m->train_autocast});
   return plan->err.empty() ? 0 : fail("%s", plan->err.c_str());
 }
 
@@ -2786,15 +2790,19 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
 // `b16`, when given, receives the part of those FLOPs that is issued as 16-bit-operand matrix instructions, in ISSUED FLOPs:
 // a six-term layer (fp32 products from exact three-way bf16 splits) issues six v_mfma_f32_32x32x16_bf16 products per
 // fp32-equivalent product, an f16-plan layer one; `flops` then keeps the part issued as fp32 matrix instructions.
-static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], double *b16) {
+// `train_f16`, when given, switches to the TRAINING forward in the handle's current mode (cm_train_set_autocast) and receives the
+// executed FLOPs of the convs on f16 operands; `flops` then holds all executed FLOPs.
+static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], double *b16, double *train_f16 = nullptr) {
   CM_NOT_DIT(m, "the exec / issue FLOP split");
   if (!m || !m->finalized || !flops) return fail("model not finalized");
   for (int i = 0; i < 8; ++i) flops[i] = 0;
   if (b16) for (int i = 0; i < 8; ++i) b16[i] = 0;
+  if (train_f16) for (int i = 0; i < 8; ++i) train_f16[i] = 0;
+  const bool train = train_f16 != nullptr;
   // the two projections of an attention block that the plan runs as one whole-sample launch: h2 form, three 16-bit products
   // (the generic conv ops stand in for them here; q k^T and P v stay on the fp32 instruction, counted with OP_ATTN)
   std::vector<char> h2_attn(m->ops.size(), 0);
-  {
+  if (!train) {
     const FwdPlan pl = plan_forward(m->ops, FwdCtx{m->precision, false, m->h2_stale, B});
     for (size_t i = 0; i < m->ops.size(); ++i)
       if (m->ops[i].kind == OP_ATTNBLK && pl.ops[i].attn_sample) h2_attn[m->ops[i].ab_qkv] = h2_attn[m->ops[i].ab_outc] = 1;
@@ -2802,8 +2810,9 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
   for (const Op &op : m->ops) {
     if (op.kind == OP_ATTN) { flops[op.cls] += 4.0 * op.S * (double)op.S * op.E * B; continue; }
     if (op.kind != OP_CONV) continue;
-    // the inference route (the upsample convs' source statistics assumed present)
-    const ConvRoute r = conv_route(op, m->precision, false, m->h2_stale);
+    // the inference route (the upsample convs' source statistics assumed present); `train`: the training forward's, where the
+    // stand-alone skip convs run and the handle's autocast mode decides the Winograd layers' form
+    const ConvRoute r = conv_route(op, m->precision, train, m->h2_stale, train && m->train_autocast);
     // 0: fp32 matrix instructions; 1: f16 operands; 6: six-term bf16 products; 3: h2 / relaxed (three cross terms)
     double mult16 = r.form == FORM_F16 ? 1.0 : r.form == FORM_B6 ? 6.0 : r.form == FORM_FP32 ? 0.0 : 3.0;
     const cm::ConvArgs &a = op.ca;
@@ -2840,6 +2849,7 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
         if (cm::conv_zsplit_variant(a, op.MB, op.NB)) f *= a.par ? 6.0 / 8.0 : 18.0 / 27.0;
     }
     if (h2_attn[&op - m->ops.data()]) mult16 = 3.0;
+    if (train) { flops[op.cls] += f * B; if (r.form == FORM_F16) train_f16[op.cls] += f * B; continue; }
     if (b16 && mult16 > 0.0) b16[op.cls] += mult16 * f * B;
     else flops[op.cls] += f * B;
   }
@@ -2847,6 +2857,11 @@ static int exec_flops_split(const cm_model *m, int32_t B, double flops[8], doubl
 }
 
 int cm_model_exec_flops(const cm_model *m, int32_t B, double flops[8]) { return exec_flops_split(m, B, flops, nullptr); }
+
+int cm_train_exec_flops(const cm_model *m, int32_t B, double flops[8], double f16[8]) {
+  if (!f16) return fail("null output");
+  return exec_flops_split(m, B, flops, nullptr, f16);
+}
 
 int cm_model_issue_flops(const cm_model *m, int32_t B, double f32[8], double b16[8]) {
   if (!b16) return fail("null output");

@@ -1322,9 +1322,9 @@ hipError_t launch_zero_stuff2(const float *y, float *u, int B, int Z, int Y, int
 
 // d(loss)/d(eps_hat) of mean((eps_hat - eps)^2) written into the channels-last gradient of the
 // final conv output [B][L][H][W][8]: zero for the past frames (unet.py:166 slices them away)
-// and for the padding channels.
+// and for the padding channels.  `scale`: the loss scale 2^k of an autocast step (1 otherwise: the same bits as without it).
 __global__ void mse_grad_kernel(const float *__restrict__ pred, const float *__restrict__ target,
-                                float *__restrict__ g, int B, int C, int H, int W, int P, int F) {
+                                float *__restrict__ g, int B, int C, int H, int W, int P, int F, float scale) {
   const int L = P + F;
   const long long total = (long long)B * L * H * W * 8;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -1338,16 +1338,16 @@ __global__ void mse_grad_kernel(const float *__restrict__ pred, const float *__r
   float v = 0.f;
   if (c < C && l >= P) {
     const size_t ref = ((((size_t)b * C + c) * H + hh) * W + w) * F + (l - P);
-    v = 2.0f * (pred[ref] - target[ref]) / (float)((long long)B * C * H * W * F);
+    v = 2.0f * (pred[ref] - target[ref]) / (float)((long long)B * C * H * W * F) * scale;
   }
   g[i] = v;
 }
 
 hipError_t launch_mse_grad(const float *pred, const float *target, float *g, int B, int C, int H, int W, int P, int F,
-                           hipStream_t st) {
+                           hipStream_t st, float scale) {
   const long long total = (long long)B * (P + F) * H * W * 8;
   hipLaunchKernelGGL(mse_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, pred, target, g, B, C,
-                     H, W, P, F);
+                     H, W, P, F, scale);
   return hipGetLastError();
 }
 
@@ -1636,6 +1636,61 @@ __global__ void wino_pack_jobs_kernel(const float *__restrict__ W, const WinoPac
         }
       base[((size_t)xy * 24 + (dz * 2 + k8) * 4 + xx) * 64 * 4] = s;
     }
+}
+
+// f16 sibling of wino_pack_jobs_kernel (autocast training step): the same thread -> (co, ci, z tap) map and the same fp32 sums,
+// each rounded to f16 once and stored in pack_wino_f16 order [n tile][chunk][xi_y][dz][xi_x][lane = 32 hh + co % 32][8 halves],
+// ci = chunk * 16 + 8 hh + j.  jb.dst is the f16 buffer (half the floats of the fp32 one); padded channels are written as zeros.
+__global__ void wino_pack_jobs_f16_kernel(const float *__restrict__ W, const WinoPackJob *__restrict__ jobs, const int *__restrict__ blk2job) {
+  const WinoPackJob jb = jobs[blk2job[blockIdx.x]];
+  const long long t = ((long long)blockIdx.x - jb.blk0) * 256 + threadIdx.x;
+  if (t >= jb.n) return;
+  const int nch = jb.Ci_pad / 16;
+  const int ci = (int)(t % jb.Ci_pad);
+  const int dz = (int)((t / jb.Ci_pad) % 3);
+  const int co = (int)(t / ((long long)jb.Ci_pad * 3));
+  float g[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) g[k] = 0.f;
+  if (co < jb.Co && ci < jb.Ci) {
+    const int *ip = jb.idx27 + ((size_t)co * jb.Ci + ci) * 27 + dz * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { const int j = ip[k]; g[k] = j >= 0 ? W[j] : 0.f; }
+  }
+  const int nt = co >> 5, r = co & 31, chunk = ci >> 4, hh = (ci >> 3) & 1, j8 = ci & 7;
+  _Float16 *base = reinterpret_cast<_Float16 *>(jb.dst) + ((((size_t)nt * nch + chunk) * 4) * 3 * 4 * 64 + hh * 32 + r) * 8 + j8;
+  const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
+#pragma unroll
+  for (int xy = 0; xy < 4; ++xy)
+#pragma unroll
+    for (int xx = 0; xx < 4; ++xx) {
+      float s = 0.f;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const float c = G[xy][dy] * G[xx][dx];
+          if (c != 0.f) s += c * g[dy * 3 + dx];
+        }
+      base[(((size_t)xy * 3 + dz) * 4 + xx) * 64 * 8] = (_Float16)s;
+    }
+}
+
+hipError_t launch_wino_pack_jobs_f16(const float *W, const WinoPackJob *jobs, const int *blk2job, long long nblocks, hipStream_t st) {
+  if (nblocks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(wino_pack_jobs_f16_kernel, dim3((unsigned)nblocks), dim3(256), 0, st, W, jobs, blk2job);
+  return hipGetLastError();
+}
+
+// g[i] *= s: the loss scale of an autocast step taken out of the flat gradient buffer (s = 2^-k: exact)
+__global__ void scale_inplace_kernel(float *__restrict__ g, long long n, float s) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) g[i] *= s;
+}
+hipError_t launch_scale_inplace(float *g, long long n, float s, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(scale_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g, n, s);
+  return hipGetLastError();
 }
 
 hipError_t launch_wino_pack_jobs(const float *W, const WinoPackJob *jobs, const int *blk2job, long long nblocks, hipStream_t st) {

@@ -11,6 +11,11 @@
 // GroupNorm/SiLU backward kernels (or a plain accumulate when T is the identity).
 // Stride-2 convs take the zero-stuffed dY, upsample convs go through the materialised
 // upsampled tensor (wgrad) and a 2x2x2 sum-pool (dgrad).
+//
+// Autocast (cm_train_set_autocast; the reference wraps this step in torch.amp.autocast, ddpm.py:116-120): the layers on the
+// Winograd route run forward, data gradient and weight gradient on f16 operands with fp32 accumulation (the f16 form of the
+// forward kernel, wgrad_wino_f16_kernel), the loss gradient is multiplied by 2^k and the flat gradient buffer by 2^-k at the
+// end of the pass; everything else, and every launch of a handle that never switches it on, is unchanged.
 
 struct cm_train_state {
   std::set<const Act *> gset;  // backward pass: tensors whose gradient buffer has received a contribution
@@ -27,6 +32,7 @@ struct cm_train_state {
   struct DerivedWino { float *dst; int *d_idx27; int Co, Ci, Ci_pad; long long n; };
   std::vector<DerivedWino> derived_wino;
   cm::WinoPackJob *d_wjobs = nullptr; int *d_wblk2job = nullptr; long long wpack_blocks = 0;
+  cm::WinoPackJob *d_wjobs16 = nullptr;   // autocast: the same jobs writing the f16 fragments (wino_pack_jobs_f16_kernel; same workgroup map)
   int njobs = 0;
   long long pack_total = 0;
   // per conv op: data-gradient launch
@@ -40,6 +46,7 @@ struct cm_train_state {
     float *wwino = nullptr;
     float *wwino_b6 = nullptr;  // six-term bf16 split of wwino (pack_wino_b6 order), re-derived after every optimizer step
     long long wwino_floats = 0;
+    float *wwino16 = nullptr;   // autocast: f16 sibling of wwino_b6 (pack_wino_f16 order), allocated when mode 1 is first set
     // two-plane grids: the data gradient on the whole-sample kernel conv_qr2 in its six-term form (no normalisation: `raw`)
     bool qr = false;
     float *wqr = nullptr, *wqr_b6 = nullptr;
@@ -75,6 +82,11 @@ struct cm_train_state {
   long long draws = 0;
   long long sample_base = 0;     // global index of this rank's sample 0 (data-parallel training)
   int Cmax = 0;
+  // autocast (cm_train_set_autocast): f16 operands in the Winograd layers' three passes, loss gradient scaled by 2^ls_k
+  int autocast = 0, ls_req = -1;   // mode; requested scale exponent (< 0: automatic)
+  int ls_k = 0;                    // exponent of the step in flight (0 in fp32 mode: scale 1, no unscale launch)
+  int ls_last_B = 0;               // batch of the last autocast step (cm_train_get_autocast)
+  bool ac_ready = false;           // the f16 fragments (Op::d_wwino16t, Dgrad::wwino16) exist
 };
 
 void cm_free_train_state(cm_train_state *t) {
@@ -195,6 +207,25 @@ int refresh_h2(cm_model *m) {
   return 0;
 }
 
+// autocast: the f16 fragments of the Winograd layers' forward and data gradient from the master weights, one job-table launch
+int repack_f16(cm_model *m, hipStream_t st) {
+  cm_train_state *T = m->train;
+  if (!T->ac_ready) return 0;
+  CM_HIP(cm::launch_wino_pack_jobs_f16(T->opt.p, T->d_wjobs16, T->d_wblk2job, T->wpack_blocks, st));
+  return 0;
+}
+
+// the loss-scale exponent of a step at batch B: the requested one, or the largest k with 2^k <= B*C*H*W*F (loss gradient O(1))
+int autocast_scale_log2(const cm_model *m, int B) {
+  const cm_train_state *T = m->train;
+  if (T->ls_req >= 0) return T->ls_req;
+  const cm_unet_config &c = m->cfg;
+  const long long N = (long long)B * c.out_channels * c.rows * c.cols * c.future_len;
+  int k = 0;
+  while (k < 24 && (2LL << k) <= N) ++k;
+  return k;
+}
+
 int repack_all(cm_model *m, hipStream_t st) {
   cm_train_state *T = m->train;
   m->h2_stale = true;                               // (the h2 fragments follow lazily: refresh_h2)
@@ -248,7 +279,7 @@ int repack_all(cm_model *m, hipStream_t st) {
     if (D.wwino_b6) CM_HIP(cm::launch_wino_b6_repack(D.wwino, D.wwino_b6, D.wwino_floats, st));
     if (D.qr) CM_HIP(cm::launch_qr_b6_repack(D.wqr, D.wqr_b6, D.wqr_floats, D.ca.C0, st));
   }
-  return 0;
+  return T->autocast ? repack_f16(m, st) : 0;
 }
 
 int train_setup(cm_model *m) {
@@ -590,7 +621,8 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
       if (G < 1) return fail("wgrad partial buffer too small");
       const Param &w = P(m, op.wname);
-      CM_HIP(cm::launch_wgrad_wino(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
+      if (T->autocast) CM_HIP(cm::launch_wgrad_wino_f16(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
+      else CM_HIP(cm::launch_wgrad_wino(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
       CM_HIP(cm::launch_wgrad_wino_reduce(T->wpart, G, ncb, nkb, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
     } else if (op.ref_taps == 27 && op.ca.stride == 1 && !op.ca.par && !op.ca.ups && op.pm_off < 0 && !cm::diag_env("CM_NO_WGRAD_PACK") &&
                ((Co == 32 && !op.in1 && op.in0->C == 8 && !op.ca.gn) || (Co <= 4 && op.ca.C0 + op.ca.C1 == 32 && !op.in1))) {
@@ -704,8 +736,10 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       CM_HIP(cm::launch_conv_qr(q, st));
     } else if (D.wino) {
       da.wfrag = D.wwino;
-      if (D.wwino_b6) { da.wfrag = D.wwino_b6; da.f16 = 2; }
-      CM_HIP(cm::launch_conv_wino(da, false, st));
+      const bool f16 = T->autocast && D.wwino16;
+      if (f16) da.wfrag = D.wwino16;
+      else if (D.wwino_b6) { da.wfrag = D.wwino_b6; da.f16 = 2; }
+      CM_HIP(cm::launch_conv_wino(da, f16, st));
     } else {
       CM_HIP(cm::launch_conv(da, D.MB, D.NB, st));
     }
@@ -786,6 +820,9 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
     CM_HIP(hipStreamSynchronize(st));
   }
   CM_HIP(cm::launch_copy_jobs(T->d_cp_jobs, T->n_cp_jobs, T->cp_max, st));
+  // autocast: every gradient above carries the loss scale 2^k exactly (fp32 tensors); take it out once, so that the readers of the
+  // flat buffer (cm_train_get_grad, the all-reduce, Adam, checkpoints) see unscaled gradients
+  if (T->ls_k > 0) CM_HIP(cm::launch_scale_inplace(T->opt.g, (long long)T->opt.nfloats, ldexpf(1.f, -T->ls_k), st));
   return 0;
 }
 
@@ -817,6 +854,64 @@ int cm_train_set_sample_base(cm_model *m, int64_t sample_id_base) {
   return 0;
 }
 
+int cm_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2) {
+  CM_NOT_DIT(m, "cm_train_set_autocast");
+  if (!m) return fail("cm_train_set_autocast: null handle");
+  if (mode != 0 && mode != 1) return fail("cm_train_set_autocast: mode %d: 0 = fp32 step, 1 = autocast", (int)mode);
+  if (loss_scale_log2 > 24) return fail("cm_train_set_autocast: loss_scale_log2 %d above 24", (int)loss_scale_log2);
+  if (!m->train) return fail("cm_train_set_autocast: cm_train_init has not been called");
+  cm_train_state *T = m->train;
+  DevGuard g(m->device);
+  if (mode == 1) {
+    if (!T->ac_ready) {
+      // f16 siblings of the fp32 Winograd fragments: half their bytes, allocated once
+      for (Op &op : m->ops)
+        if (op.kind == OP_CONV && op.wino && op.d_wwino && op.wwino_floats > 0 &&
+            dev_alloc(m, (void **)&op.d_wwino16t, (size_t)op.wwino_floats / 2 * sizeof(float))) return 1;
+      for (auto &D : T->dg)
+        if (D.wino && D.wwino && dev_alloc(m, (void **)&D.wwino16, (size_t)D.wwino_floats / 2 * sizeof(float))) return 1;
+      // the job table of wino_pack_jobs_kernel with the f16 buffers as destinations: same order, same workgroup -> job map
+      // (a model without Winograd layers -- narrow widths, odd grids -- has no such table and nothing to re-pack)
+      if (!T->derived_wino.empty() && (!T->d_wjobs || !T->d_wblk2job)) return fail("cm_train_set_autocast: the Winograd re-pack table has not been built");
+      std::map<const float *, float *> to16;
+      for (Op &op : m->ops) if (op.d_wwino16t) to16[op.d_wwino] = op.d_wwino16t;
+      for (auto &D : T->dg) if (D.wwino16) to16[D.wwino] = D.wwino16;
+      std::vector<cm::WinoPackJob> jobs;
+      long long blk = 0;
+      for (auto &d : T->derived_wino) {
+        cm::WinoPackJob j{};
+        if (!to16.count(d.dst)) return fail("cm_train_set_autocast: a Winograd fragment set has no f16 sibling");
+        j.dst = to16[d.dst]; j.idx27 = d.d_idx27; j.Co = d.Co; j.Ci = d.Ci; j.Ci_pad = d.Ci_pad; j.n = d.n; j.blk0 = blk;
+        blk += (d.n + 255) / 256;
+        jobs.push_back(j);
+      }
+      if (blk != T->wpack_blocks) return fail("cm_train_set_autocast: re-pack tables disagree");
+      if (!jobs.empty()) {
+        if (dev_alloc(m, (void **)&T->d_wjobs16, jobs.size() * sizeof(cm::WinoPackJob))) return 1;
+        CM_HIP(hipMemcpy(T->d_wjobs16, jobs.data(), jobs.size() * sizeof(cm::WinoPackJob), hipMemcpyHostToDevice));
+      }
+      T->ac_ready = true;
+    }
+    // (the fp32 fragments are current: cm_train_init and every update re-derive them; the f16 ones only while the mode is on)
+    if (repack_f16(m, m->stream)) return 1;
+    CM_HIP(hipStreamSynchronize(m->stream));
+  }
+  T->autocast = mode; T->ls_req = mode ? (int)loss_scale_log2 : -1;
+  if (!mode) T->ls_k = 0;
+  m->train_autocast = mode == 1;
+  return 0;
+}
+
+int cm_train_get_autocast(const cm_model *m, int32_t *mode, int32_t *loss_scale_log2) {
+  CM_NOT_DIT(m, "cm_train_get_autocast");
+  if (!m || !mode || !loss_scale_log2) return fail("cm_train_get_autocast: null argument");
+  if (!m->train) return fail("cm_train_get_autocast: cm_train_init has not been called");
+  const cm_train_state *T = m->train;
+  *mode = T->autocast;
+  *loss_scale_log2 = T->autocast ? autocast_scale_log2(m, T->ls_last_B > 0 ? T->ls_last_B : m->cfg.max_batch) : 0;
+  return 0;
+}
+
 int cm_train_set_lr(cm_model *m, float lr) {
   if (!m || !m->train) return fail("cm_train_init has not been called");
   m->train->opt.lr = lr;
@@ -831,6 +926,8 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
   const cm_unet_config &c = m->cfg;
   const long long per = (long long)m->per_sample();
   if (make_plan(m, true, B, &m->plan)) return 1;
+  T->ls_k = T->autocast ? autocast_scale_log2(m, B) : 0;
+  if (T->autocast) T->ls_last_B = B;
   if (d_dropmask)
     CM_HIP(hipMemcpyAsync(m->dropmask, d_dropmask, (size_t)B * m->nproj * sizeof(float), hipMemcpyDeviceToDevice, st));
   else
@@ -849,7 +946,7 @@ static int train_step_core(cm_model *m, const float *d_xt, const float *d_past, 
   }
   if (!rc) {
     hipError_t e = cm::launch_mse_loss(T->pred, d_target, (long long)B * per, m->mse_partial, m->mse_loss, st);
-    if (e == hipSuccess) e = cm::launch_mse_grad(T->pred, d_target, m->act_by_name.at("final")->g, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st);
+    if (e == hipSuccess) e = cm::launch_mse_grad(T->pred, d_target, m->act_by_name.at("final")->g, B, c.out_channels, c.rows, c.cols, c.past_len, c.future_len, st, ldexpf(1.f, T->ls_k));
     if (e != hipSuccess) rc = fail("loss kernels failed");
   }
   if (!rc) rc = backward_ops(m, B, st);

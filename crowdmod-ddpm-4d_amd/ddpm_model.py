@@ -258,7 +258,15 @@ class DDPM_model:
             net.set_sample_base(self.dp_rank * B)
         if not getattr(net, "_train_ready", False):
             s = self._solver()
-            net.train_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"])
+            # TRAIN.AUTOCAST (absent: False), or the caller's override (train.py --autocast)
+            over = getattr(self, "autocast_override", None)
+            autocast = cfgmod.train_autocast(self.res.train) if over is None else bool(over)
+            net.train_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], autocast=autocast)
+            if autocast:
+                import logging
+                # (automatic scale: the largest 2^k <= B*C*H*W*F of THIS batch -- the handle reports it for max_batch until a step has run)
+                logging.info("UNet training step under autocast: f16 operands in the Winograd layers, loss scale 2^%d at batch %d",
+                             min(24, int(future.size).bit_length() - 1), B)
             self._lr = s["lr"]
             self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
 

@@ -129,6 +129,8 @@ class FM_model(DDPM_model):
                              loss_sync=loss_sync)
 
     def _refuse_training(self):
+        if self.arch == "FM-UNet":      # the UNet backbone trains through train() (cm_train_step_xt), like DDPM-UNet
+            return
         if not getattr(self, "_fitting", False):
             super()._refuse_training()
 

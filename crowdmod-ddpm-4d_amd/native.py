@@ -121,6 +121,7 @@ SIGNATURES = {
     "cm_model_cost": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cm_model_class_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
     "cm_model_exec_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double)]),
+    "cm_train_exec_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cm_model_issue_flops": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cm_frame_metrics": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "cm_mass_preservation_grad": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
@@ -136,6 +137,8 @@ SIGNATURES = {
                                      C.POINTER(C.c_float)]),
     "cm_train_init": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "cm_train_set_lr": (C.c_int, [_P, C.c_float]),
+    "cm_train_set_autocast": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "cm_train_get_autocast": (C.c_int, [_P, _P, _P]),
     "cm_train_set_sample_base": (C.c_int, [_P, C.c_int64]),
     "cm_train_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),
     "cm_train_step_xt": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),

@@ -168,7 +168,9 @@ class UNet:
             # the handle this one replaces was training: continue from its optimizer state
             opt, hp = carry
             self._carry_opt = None
-            self.train_init(lr=hp["lr"], betas=hp["betas"], eps=hp["eps"], weight_decay=hp["weight_decay"])
+            on, k = getattr(self, "_autocast", (False, -1))
+            self.train_init(lr=hp["lr"], betas=hp["betas"], eps=hp["eps"], weight_decay=hp["weight_decay"], autocast=on,
+                            loss_scale_log2=k)
             self.load_optimizer_state_dict(opt)
         return h
 
@@ -247,8 +249,10 @@ class UNet:
         return dout.download(fut.shape)
 
     # -- training step (ddpm.py:111-121,142-144) -------------------------------------
-    def train_init(self, lr=5e-5, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.003):
-        """Device-side optimizer state: torch.optim.Adam(lr, betas, weight_decay) of ddpm.py:53-56."""
+    def train_init(self, lr=5e-5, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.003, autocast=False, loss_scale_log2=-1):
+        """Device-side optimizer state: torch.optim.Adam(lr, betas, weight_decay) of ddpm.py:53-56.
+        autocast: True = the training step of the reference's torch.amp.autocast (ddpm.py:116-120), see set_autocast;
+        False (default) = the fp32 step."""
         if self._handle is None:
             raise RuntimeError("call ensure() (or run a forward) before train_init()")
         native.check(native.lib().cm_train_init(self._handle, float(lr), float(betas[0]), float(betas[1]), float(eps),
@@ -258,6 +262,28 @@ class UNet:
                                "weight_decay": float(weight_decay)}
         if getattr(self, "_sample_base", 0):
             native.check(native.lib().cm_train_set_sample_base(self._handle, int(self._sample_base)))
+        self._autocast = (bool(autocast), int(loss_scale_log2) if autocast else -1)
+        native.check(native.lib().cm_train_set_autocast(self._handle, 1 if autocast else 0, self._autocast[1]))
+
+    def set_autocast(self, on: bool, loss_scale_log2: int = -1):
+        """Training step under autocast: f16 matrix-core operands with fp32 accumulation in the stride-1 3x3x3 layers of the
+        Winograd route (training forward, data gradient, weight gradient); everything else, the gradients and Adam stay
+        fp32.  The loss gradient is scaled by 2^loss_scale_log2 inside the step (< 0: automatic, the largest power of two
+        <= B*C*H*W*F) and the gradients are unscaled before anything reads them.  Governs train_step, train_step_xt and
+        forward_train; the eval forward and the sampling loop are untouched."""
+        if not getattr(self, "_train_ready", False):
+            raise RuntimeError("train_init() has not been called")
+        native.check(native.lib().cm_train_set_autocast(self._handle, 1 if on else 0, int(loss_scale_log2)))
+        self._autocast = (bool(on), int(loss_scale_log2) if on else -1)
+
+    @property
+    def autocast(self):
+        """(mode, loss_scale_log2 in force) of the training step; (False, 0) before train_init."""
+        if not getattr(self, "_train_ready", False) or self._handle is None:
+            return (False, 0)
+        mode, k = C.c_int32(), C.c_int32()
+        native.check(native.lib().cm_train_get_autocast(self._handle, C.byref(mode), C.byref(k)))
+        return (bool(mode.value), int(k.value))
 
     def set_lr(self, lr: float):
         native.check(native.lib().cm_train_set_lr(self._handle, float(lr)))
@@ -421,6 +447,31 @@ class UNet:
         fl = (C.c_double * 8)()
         native.check(native.lib().cm_model_exec_flops(self._handle, B, fl))
         return float(sum(fl))
+
+    def train_exec_flops(self, B: int):
+        """(all, on f16 operands): matrix-core FLOPs the TRAINING forward executes at batch B in the current mode
+        (cm_train_exec_flops: the accounting of exec_flops on the training routes; the second figure is 0 without autocast)."""
+        fl, f16 = (C.c_double * 8)(), (C.c_double * 8)()
+        native.check(native.lib().cm_train_exec_flops(self._handle, B, fl, f16))
+        return float(sum(fl)), float(sum(f16))
+
+    def winograd_weights(self):
+        """Weight names of the stride-1 3x3x3 convs on the Winograd route -- the layers autocast moves to f16 operands.
+        The one reader of cm_debug_conv_info's "conv <label = weight name> <taps> ... <wino>" line outside the debug tests."""
+        L, h = native.lib(), self._handle
+        cnt = C.c_int32()
+        native.check(L.cm_debug_conv_count(h, C.byref(cnt)))
+        buf = C.create_string_buffer(512)
+        out = []
+        for i in range(cnt.value):
+            native.check(L.cm_debug_conv_info(h, i, buf, len(buf)))
+            f = buf.value.decode().split()
+            if f[0] == "conv":
+                if len(f) < 21:
+                    raise RuntimeError(f"cm_debug_conv_info: unexpected line {buf.value!r}")
+                if int(f[2]) == 27 and int(f[20]) == 1:
+                    out.append(f[1])
+        return out
 
     def conv3_issue_flops(self, B: int):
         """(fp32-instruction FLOPs, 16-bit-operand-instruction FLOPs) the 3x3x3 convolutions ISSUE on the matrix cores: a

@@ -288,6 +288,9 @@ int cm_model_class_flops(const cm_model *m, int32_t B, double flops[8]);
 /* Matrix-core FLOPs the plan EXECUTES per class (parity-form upsample convs: 8 of 27 taps; Winograd F(2x2,3x3)
  * layers: 16 multiplies per 2x2 outputs and z tap instead of 36) -- the hardware-utilisation side of the roofline. */
 int cm_model_exec_flops(const cm_model *m, int32_t B, double flops[8]);
+/* The same accounting for the TRAINING forward in the handle's current mode (cm_train_set_autocast): flops = all executed
+ * matrix-core FLOPs per kernel class, f16 = the part of the convolutions that runs on f16 operands (0 with the mode off). */
+int cm_train_exec_flops(const cm_model *m, int32_t B, double flops[8], double f16[8]);
 /* The same FLOPs by the matrix instruction that issues them: `f32` = issued as fp32 instructions (v_mfma_f32_32x32x2_f32),
  * `b16` = ISSUED FLOPs of 16-bit-operand instructions (v_mfma_f32_32x32x16_{bf16,f16}): a six-term layer -- fp32 products
  * from exact three-way bf16 splits -- issues six of them per fp32-equivalent product, an f16-plan layer one.  The time the
@@ -352,10 +355,22 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
  * (models/diffusion/ddpm.py:111-121,142-144; optimizer built at ddpm.py:53-56:
  * torch.optim.Adam(lr, betas, weight_decay) -- L2 coupled into the gradient.)
  * cm_train_init allocates master weights / gradients / Adam moments on the device
- * (state_dict order) and the backward workspace; call once after cm_model_finalize. */
+ * (state_dict order) and the backward workspace; call once after cm_model_finalize.
+ * The step runs in fp32 unless cm_train_set_autocast switches its Winograd layers to f16 operands (below). */
 int cm_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float dropout_rate /* cfg DROPOUT_RATE: nn.Dropout3d(p), layers.py:42 */);
 int cm_train_set_lr(cm_model *m, float lr);
+/* The reference trains this UNet under torch.amp.autocast("cuda") without a GradScaler (ddpm.py:116-120).
+ * 0 = fp32 step (default, today's launches), 1 = autocast: f16 matrix-core operands with fp32 accumulation in the
+ * stride-1 3x3x3 layers of the Winograd route -- training forward, data gradient and weight gradient; activations,
+ * gradients, GroupNorm, attention and Adam stay fp32.  The loss gradient is multiplied by 2^k and the flat gradient
+ * buffer by 2^-k at the end of the backward, so every reader of the gradients sees unscaled numbers.
+ * loss_scale_log2 < 0 = automatic: the largest k with 2^k <= B*C*H*W*F of the step (a function of B alone).
+ * Call after cm_train_init, between steps.  Governs cm_train_step, cm_train_step_xt and cm_unet_forward_train;
+ * cm_unet_forward and cm_sample_loop are untouched. */
+int cm_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2);
+/* *loss_scale_log2: the exponent in force (automatic: for the batch of the last step, max_batch before the first). */
+int cm_train_get_autocast(const cm_model *m, int32_t *mode, int32_t *loss_scale_log2);
 /* Data-parallel training: global index of this rank's sample 0 (rank * per-rank batch).  The device
  * Philox streams of eps and of the Dropout3d masks are addressed by (seed, step, GLOBAL sample index), so
  * ranks draw different noise and a job's samples draw the same numbers however it is sharded.  Default 0. */

@@ -57,6 +57,8 @@ def main():
     ap.add_argument('--synthetic-samples', type=int, default=1024)
     ap.add_argument('--epochs', type=int, default=None, help='override TRAIN.EPOCHS')
     ap.add_argument('--device', type=int, default=None)
+    ap.add_argument('--autocast', action='store_true',
+                    help='train the UNet under autocast (f16 operands in the Winograd layers): overrides TRAIN.AUTOCAST')
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if args.arch == "ConvRNN":
@@ -84,6 +86,8 @@ def main():
     model = (FM_model if args.arch.startswith("FM-") else DDPM_model)(cfg, args.arch, mprops, device=device)
     if args.epochs is not None:
         model.res = res
+    if args.autocast:
+        model.autocast_override = True
     nparams = sum(int(np.prod(v.shape)) for k, v in model.denoiser.state_dict().items()
                   if k != "time_embeddings.time_blocks.0.weight")
     logging.info("Total trainable parameters at denoiser:%d", nparams)
