@@ -5,6 +5,9 @@ every generative model is compared against.
 `Forecaster` keeps the reference's constructor arguments and call convention --
 `forecaster(x_obs[B,4,H,W,P], target_obs[B,4,H,W,F], teacher_forcing=False) -> [B,4,H,W,F]` -- and the `nn.Module`
 surface the driver touches.  All arithmetic runs in libcrowdmod_hip.so (cm_convrnn_*, cm_convrnn.hip, cm_convrnn_train.hip).
+The state surface, the handle's creation, the staging of inputs and the trainer accessors are `NativeModule`'s
+(native_module.py), shared with the UNet and DiT wrappers; here are the frame counts the handle follows, the loss-term
+steps, and the optimizer that a re-created handle starts afresh.
 
 Training (convRNN.py:98-221) is reached through `Forecaster.train_init / train_step / evaluate_loss` and
 `ConvRNN_model._train_one_epoch / fit` (script: train_convrnn.py).  `Forecaster.train()` -- the nn.Module mode switch -- and
@@ -23,7 +26,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import config as cfgmod, convrnn_spec, native, optim_state
-from .unet import _is_torch
+from .native_module import NativeModule
 
 _REFUSAL = ("ConvRNN training (Poisson-KL + masked MSE loss, AMSGrad) is not reached through train(): use "
             "ConvRNN_model.fit / Forecaster.train_step (train_convrnn.py); the forecaster has no train mode")
@@ -36,7 +39,12 @@ def _cell_name(cell_class) -> str:
     return name
 
 
-class Forecaster:
+class Forecaster(NativeModule):
+    _NAME = "Forecaster"
+    _CREATE = "cm_convrnn_create"
+    _MODEL = "cm_convrnn"
+    _FAMILY = "cm_convrnn_train"
+
     def __init__(self, input_size, input_channels, enc_hidden_channels, forc_hidden_channels, enc_kernels, forc_kernels,
                  device=0, cell_class="ConvGRUCell", bias=False, *, past_len: int = 5, future_len: int = 3,
                  max_batch: int = 64, seed: Optional[int] = 42):
@@ -51,32 +59,15 @@ class Forecaster:
                                               tuple(int(v) for v in forc_hidden_channels),
                                               tuple(int(v) for v in enc_kernels), tuple(int(v) for v in forc_kernels),
                                               _cell_name(cell_class), int(past_len), int(future_len))
-        self.input_channels = self.cfg.input_channels
-        self.device = device if isinstance(device, int) else 0
-        self.max_batch = int(max_batch)
-        self._native_max_batch = 0
-        self.training = False
-        self._shapes = convrnn_spec.param_shapes(self.cfg)
-        self._params: Dict[str, np.ndarray] = convrnn_spec.init_params(self.cfg, seed if seed is not None else 0)
-        self._handle = None
+        self._init_state(convrnn_spec, device if isinstance(device, int) else 0, max_batch, seed)
         self._hyper = None      # (lr, beta1, beta2, eps, weight_decay) once train_init has been called
         self._trained = False   # the native master weights are ahead of self._params
 
     # -- nn.Module surface ---------------------------------------------------------
-    def eval(self):
-        self.training = False
-        return self
-
     def train(self, mode: bool = True):
         if mode:
             raise NotImplementedError(_REFUSAL)
         return self.eval()
-
-    def to(self, device=None):
-        if isinstance(device, int) and device != self.device:
-            self._release()
-            self.device = device
-        return self
 
     def parameters(self):
         return list(self._params.values())
@@ -84,27 +75,11 @@ class Forecaster:
     def state_dict(self) -> Dict[str, np.ndarray]:
         if self._trained:
             self.sync()
-        return {k: v.copy() for k, v in self._params.items()}
+        return super().state_dict()
 
-    def load_state_dict(self, state: Dict[str, object], strict: bool = True):
-        got = {}
-        for k, v in state.items():
-            if _is_torch(v):
-                v = v.detach().cpu().numpy()
-            got[k] = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-        missing = [k for k in self._shapes if k not in got]
-        unexpected = [k for k in got if k not in self._shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for Forecaster: missing keys {missing}, "
-                               f"unexpected keys {unexpected}")
-        for k, shp in self._shapes.items():
-            if k in got:
-                if tuple(got[k].shape) != tuple(shp):
-                    raise RuntimeError(f"size mismatch for {k}: got {tuple(got[k].shape)}, expected {tuple(shp)}")
-                self._params[k] = got[k]
+    def _release_for_load(self):
         self._trained = False   # the loaded weights replace whatever the native handle trained
         self._release()
-        return self
 
     # -- native handle -------------------------------------------------------------
     def native_config(self, max_batch: int, device: int) -> native.cm_convrnn_config:
@@ -117,11 +92,9 @@ class Forecaster:
         return c
 
     def _release(self):
-        if self._handle is not None:
-            if self._trained:
-                self.sync()
-            native.lib().cm_convrnn_destroy(self._handle)
-            self._handle = None
+        if self._handle is not None and self._trained:
+            self.sync()
+        self._destroy()
 
     def __del__(self):
         try:
@@ -142,27 +115,13 @@ class Forecaster:
             return self._handle
         self._release()
         self.max_batch = max(self.max_batch, batch)
-        L = native.lib()
-        c = self.native_config(self.max_batch, self.device)
-        h = C.c_void_p()
-        native.check(L.cm_convrnn_create(C.byref(c), C.byref(h)))
-        try:
-            for name, arr in self._params.items():
-                arr = np.ascontiguousarray(arr, dtype=np.float32)
-                native.check(L.cm_convrnn_set_param(h, name.encode(), arr.ctypes.data, arr.size))
-            native.check(L.cm_convrnn_finalize(h))
-            if self._hyper is not None:
-                native.check(L.cm_convrnn_train_init(h, *self._hyper))
-        except Exception:
-            L.cm_convrnn_destroy(h)
-            raise
-        self._handle, self._native_max_batch = h, self.max_batch
-        return h
+        return self._create_handle()
+
+    def _after_finalize(self, h):
+        if self._hyper is not None:     # the optimizer of train_init lives in the handle: fresh state on the new one
+            native.check(self._fn("init")(h, *self._hyper))
 
     # -- forward -------------------------------------------------------------------
-    def __call__(self, x_obs, target_obs, teacher_forcing=False, hidden_state=None, *, exp_output: bool = False):
-        return self.forward(x_obs, target_obs, teacher_forcing, hidden_state, exp_output=exp_output)
-
     def forward(self, x_obs, target_obs, teacher_forcing=False, hidden_state=None, *, exp_output: bool = False):
         """Forecaster.forward (forecaster.py:89-176), eval mode; `exp_output` adds the exp on channels 0 and 3 of
         ConvRNN_model._generate_convRNN.  numpy in -> numpy out (host staging); torch CUDA tensors in -> torch CUDA tensor
@@ -170,29 +129,13 @@ class Forecaster:
         frames fed back."""
         if hidden_state is not None:
             raise NotImplementedError("Stateful mode not implemented.")   # forecaster.py:96-97
-        L = native.lib()
         B, Cc, H, W, P = (int(v) for v in x_obs.shape)
         F = int(target_obs.shape[4])
         if Cc != self.cfg.input_channels or tuple(target_obs.shape[:4]) != (B, Cc, H, W):
             raise ValueError(f"shape mismatch: x_obs {tuple(x_obs.shape)}, target_obs {tuple(target_obs.shape)}")
         h = self.ensure(H, W, P, F, B)
-        tf, ex = int(bool(teacher_forcing)), int(bool(exp_output))
-        if _is_torch(x_obs):
-            import torch
-            if not x_obs.is_cuda:
-                raise ValueError("torch inputs must live on the GPU; pass numpy arrays for host staging")
-            pst = x_obs.contiguous().float()
-            tgt = target_obs.to(device=x_obs.device).contiguous().float()
-            out = torch.empty_like(tgt)
-            torch.cuda.current_stream(x_obs.device).synchronize()
-            native.check(L.cm_convrnn_forecast(h, pst.data_ptr(), tgt.data_ptr(), tf, ex, out.data_ptr(), B, None))
-            native.check(L.cm_device_synchronize(self.device))
-            return out
-        pst = np.ascontiguousarray(x_obs, dtype=np.float32)
-        tgt = np.ascontiguousarray(target_obs, dtype=np.float32)
-        out = np.empty_like(tgt)
-        native.check(L.cm_convrnn_forecast_host(h, pst.ctypes.data, tgt.ctypes.data, tf, ex, out.ctypes.data, B))
-        return out
+        return self._eval_forward(h, "cm_convrnn_forecast", [(x_obs, np.float32), (target_obs, np.float32)], target_obs, B,
+                                  int(bool(teacher_forcing)), int(bool(exp_output)))
 
     # -- training ------------------------------------------------------------------
     def train_init(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
@@ -202,7 +145,7 @@ class Forecaster:
         self._hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
         return self
 
-    def _train_handle(self, past, target):
+    def _step_handle(self, past, target):
         B, Cc, H, W, P = (int(v) for v in past.shape)
         F = int(target.shape[4])
         if Cc != self.cfg.input_channels or tuple(target.shape[:4]) != (B, Cc, H, W):
@@ -215,25 +158,17 @@ class Forecaster:
         self._last_train_B = B
         return self.ensure(H, W, P, F, B), B
 
-    def _device_pair(self, past, target):
-        """Device addresses of (past, target): torch CUDA tensors as they are, numpy arrays through device buffers."""
-        if _is_torch(past):
-            import torch
-            if not past.is_cuda:
-                raise ValueError("torch inputs must live on the GPU; pass numpy arrays for host staging")
-            pst, tgt = past.contiguous().float(), target.to(device=past.device).contiguous().float()
-            torch.cuda.current_stream(past.device).synchronize()
-            return pst.data_ptr(), tgt.data_ptr(), (pst, tgt)
-        bufs = tuple(native.DeviceBuffer.from_array(np.ascontiguousarray(a, dtype=np.float32), self.device) for a in (past, target))
-        return bufs[0].ptr, bufs[1].ptr, bufs
+    def _pair(self, past, target):
+        """Device addresses of (past, target) for the block: torch CUDA tensors as they are, numpy arrays through device
+        buffers (every call made on them has synchronised and keeps its own copy of the target frames)."""
+        return self._staged([(past, np.float32), (target, np.float32)])
 
     def evaluate_loss(self, past, target, teacher_forcing=False, eps: float = 1e-6):
         """utils/loss.py:15-52 on the device: (rloss, vloss, loss_considering_density, loss_not_considering_density)."""
-        h, B = self._train_handle(past, target)
-        p, t, keep = self._device_pair(past, target)
+        h, B = self._step_handle(past, target)
         terms = (C.c_double * 4)()
-        native.check(native.lib().cm_convrnn_loss(h, p, t, int(bool(teacher_forcing)), float(eps), terms, B, None))
-        del keep
+        with self._pair(past, target) as (p, t):
+            native.check(native.lib().cm_convrnn_loss(h, p, t, int(bool(teacher_forcing)), float(eps), terms, B, None))
         return tuple(float(v) for v in terms)
 
     def train_step(self, past, target, teacher_forcing=False, eps: float = 1e-6, alpha: float = 1.0, apply_update: bool = True,
@@ -257,22 +192,20 @@ class Forecaster:
             if apply_update:
                 self.apply_update()
             return terms
-        h, B = self._train_handle(past, target)
-        p, t, keep = self._device_pair(past, target)
+        h, B = self._step_handle(past, target)
         terms = (C.c_double * 4)()
-        native.check(native.lib().cm_convrnn_train_step(h, p, t, int(bool(teacher_forcing)), float(eps), float(alpha), terms, B,
-                                                        int(bool(apply_update)), None))
-        del keep
+        with self._pair(past, target) as (p, t):
+            native.check(self._fn("step")(h, p, t, int(bool(teacher_forcing)), float(eps), float(alpha), terms, B,
+                                          int(bool(apply_update)), None))
         self._trained = self._trained or bool(apply_update)
         return tuple(float(v) for v in terms)
 
     # -- the step cut at the loss's reduction over the batch (data-parallel training) ---------------------------------
     def _forward_sums(self, entry, past, target, teacher_forcing) -> np.ndarray:
-        h, B = self._train_handle(past, target)
-        p, t, keep = self._device_pair(past, target)
+        h, B = self._step_handle(past, target)
         sums = (C.c_double * 6)()
-        native.check(getattr(native.lib(), entry)(h, p, t, int(bool(teacher_forcing)), B, None, sums))
-        del keep    # the call has synchronised and keeps its own copy of the target frames
+        with self._pair(past, target) as (p, t):
+            native.check(entry(h, p, t, int(bool(teacher_forcing)), B, None, sums))
         return np.array(sums[:], dtype=np.float64)
 
     def train_forward(self, past, target, teacher_forcing=False) -> np.ndarray:
@@ -280,11 +213,11 @@ class Forecaster:
         occupied MSE sum, occupied count, empty penalty sum, empty count of THIS batch, and its element count B*H*W*F."""
         if self._hyper is None:
             raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
-        return self._forward_sums("cm_convrnn_train_forward", past, target, teacher_forcing)
+        return self._forward_sums(self._fn("forward"), past, target, teacher_forcing)
 
     def loss_sums(self, past, target, teacher_forcing=False) -> np.ndarray:
         """The validation half: forward and the six sums; `terms_from_sums` of their total over ranks is the loss."""
-        return self._forward_sums("cm_convrnn_loss_sums", past, target, teacher_forcing)
+        return self._forward_sums(native.lib().cm_convrnn_loss_sums, past, target, teacher_forcing)
 
     def train_backward(self, global_sums, eps: float = 1e-6, alpha: float = 1.0):
         """Second half: every gradient of rloss + alpha * vloss over this batch with the denominators of `global_sums` (the
@@ -294,8 +227,8 @@ class Forecaster:
         if g.shape != (6,):
             raise ValueError(f"global_sums must hold six numbers, got shape {g.shape}")
         terms = (C.c_double * 4)()
-        native.check(native.lib().cm_convrnn_train_backward(self._need_train(), g.ctypes.data_as(C.POINTER(C.c_double)), float(eps),
-                                                            float(alpha), terms, None))
+        native.check(self._fn("backward")(self._train_handle(), g.ctypes.data_as(C.POINTER(C.c_double)), float(eps),
+                                          float(alpha), terms, None))
         return tuple(float(v) for v in terms)
 
     @staticmethod
@@ -308,63 +241,39 @@ class Forecaster:
         native.check(native.lib().cm_convrnn_loss_terms_from_sums(g.ctypes.data_as(C.POINTER(C.c_double)), float(eps), terms))
         return tuple(float(v) for v in terms)
 
-    def flat_grads(self):
-        """(device pointer, numel) of the flat fp32 gradient in state_dict order: what distributed.GradAverager reduces."""
-        ptr, n = C.c_void_p(), C.c_int64()
-        native.check(native.lib().cm_convrnn_train_flat_grads(self._need_train(), C.byref(ptr), C.byref(n)))
-        return int(ptr.value), int(n.value)
-
-    def _need_train(self):
+    def _train_handle(self):
         if self._handle is None or self._hyper is None:
             raise RuntimeError("no training step has run on this Forecaster")
         return self._handle
 
     def train_forecast(self) -> np.ndarray:
         """The raw frames [B, 4, H, W, F] of the last train_step / evaluate_loss forward.  Test hook."""
-        h, g = self._need_train(), self.cfg
+        h, g = self._train_handle(), self.cfg
         out = np.empty((self._last_train_B, 4, g.rows, g.cols, g.future_len), np.float32)
-        native.check(native.lib().cm_convrnn_train_get_forecast(h, out.ctypes.data, out.size))
-        return out
-
-    def grad(self, name: str) -> np.ndarray:
-        out = np.empty(self._shapes[name], np.float32)
-        native.check(native.lib().cm_convrnn_train_get_grad(self._need_train(), name.encode(), out.ctypes.data, out.size))
+        native.check(self._fn("get_forecast")(h, out.ctypes.data, out.size))
         return out
 
     def apply_update(self):
-        native.check(native.lib().cm_convrnn_train_apply(self._need_train(), None))
+        super().apply_update()
         self._trained = True
 
     def set_lr(self, lr: float):
         self._hyper = (float(lr),) + tuple(self._hyper[1:]) if self._hyper else None
-        native.check(native.lib().cm_convrnn_train_set_lr(self._need_train(), float(lr)))
+        super().set_lr(lr)
 
     def opt_step(self, value: Optional[int] = None) -> int:
-        step = C.c_int32(0 if value is None else int(value))
-        native.check(native.lib().cm_convrnn_train_opt_step(self._need_train(), C.byref(step), int(value is not None)))
-        return int(step.value)
+        return super().opt_step(value)
 
     def opt_state(self) -> dict:
         """torch.optim.Adam(amsgrad=True).state_dict() of the reference optimizer (convRNN.py:49-53): what save_checkpoint
         stores under "opt" (utils/utils.py:140-147)."""
-        h, L = self._need_train(), native.lib()
-
-        def get(name, which):
-            out = np.empty(self._shapes[name], np.float32)
-            native.check(L.cm_convrnn_train_get_opt_state(h, name.encode(), which, out.ctypes.data, out.size))
-            return out
-
+        self._train_handle()
         lr, b1, b2, eps, wd = self._hyper
-        return optim_state.dump(self._shapes, (), optim_state.AMSGRAD_KEYS, lr, (b1, b2), eps, wd, get, self.opt_step())
+        return self._dump_opt((), optim_state.AMSGRAD_KEYS, lr, (b1, b2), eps, wd)
 
     def load_opt_state(self, opt: dict):
         """Inverse of opt_state (resume from a checkpoint's "opt" entry); the handle must exist (one step or loss has run)."""
-        h, L = self._need_train(), native.lib()
-
-        def put(name, which, arr):
-            native.check(L.cm_convrnn_train_set_opt_state(h, name.encode(), which, arr.ctypes.data, arr.size))
-
-        self.opt_step(optim_state.load(opt, self._shapes, optim_state.AMSGRAD_KEYS, put))
+        self._load_opt(opt, optim_state.AMSGRAD_KEYS)
         groups = opt.get("param_groups") or []
         if groups:
             self.set_lr(float(groups[0]["lr"]))
@@ -372,12 +281,7 @@ class Forecaster:
 
     def sync(self):
         """Master weights -> state_dict(); every packed layout is rebuilt from them."""
-        h, L = self._need_train(), native.lib()
-        native.check(L.cm_convrnn_train_sync(h))
-        for name, shp in self._shapes.items():
-            arr = np.empty(shp, np.float32)
-            native.check(L.cm_convrnn_get_param(h, name.encode(), arr.ctypes.data, arr.size))
-            self._params[name] = arr
+        self._pull_trained()
         self._trained = False
         return self
 

@@ -21,7 +21,8 @@ import numpy as np
 from . import config as cfgmod
 from . import native
 from .diffusion import DDPM
-from .unet import UNet, _is_torch
+from .native_module import _is_torch
+from .unet import UNet
 
 
 class ReduceLROnPlateau:
@@ -270,13 +271,36 @@ class DDPM_model:
             self._lr = s["lr"]
             self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
 
+    def _ensure_dit_training(self, past, future):
+        """`_ensure_training` of the drivers whose denoiser trains through the fit_* family (DDPM_DiT_model, FM_model on
+        "FM-DiT"): the training state is allocated once, for the largest batch."""
+        net = self.denoiser
+        B, _, H, W, F = future.shape
+        if not getattr(net, "_fit", False):
+            s = self._solver()
+            net.ensure(H, W, int(past.shape[4]), F, max(B, net.max_batch))
+            net.fit_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], dropout_rate=self.res.dit.dropout_rate)
+            self._lr = s["lr"]
+            self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
+
+    def _draw_t(self, forward_sampler: DDPM, rng: np.random.Generator, B: int):
+        """(t ~ U{0..T-1} of one batch, the seed of what the device draws for it)."""
+        t = rng.integers(0, forward_sampler.timesteps, size=(B,)).astype(np.int64)
+        self._train_calls = getattr(self, "_train_calls", 0) + 1
+        return t, self.seed + self._train_calls
+
+    def _train_batch(self, forward_sampler: DDPM, past, future, rng: np.random.Generator, apply_update: bool) -> float:
+        """The denoiser's step on one batch (ddpm.py:111-121,142-144): q-sample with device-drawn noise, train-mode
+        forward, MSE, backward and -- `apply_update` -- Adam behind one native call.  Returns the loss.  What a driver of
+        another denoiser or objective overrides."""
+        t, seed = self._draw_t(forward_sampler, rng, future.shape[0])
+        return self.denoiser.train_step(forward_sampler._handle, future, past, t, None, seed=seed, apply_update=apply_update)
+
     def _train_one_epoch(self, forward_sampler: DDPM, loader, epoch, *, rng: Optional[np.random.Generator] = None,
-                         grad_sync=None):
-        """ddpm.py:123-154: for every (past, future) batch: t ~ U{0..T-1}, q-sample with device-drawn
-        noise, train-mode forward, MSE, backward, Adam -- one native call per batch.  `grad_sync`, when
+                         grad_sync=None, **step_kw):
+        """ddpm.py:123-154: every (past, future) batch through `_train_batch` (`step_kw` goes to it).  `grad_sync`, when
         given, is called between backward and update (data-parallel gradient averaging).
         Returns the mean batch loss (MeanMetric)."""
-        self._refuse_training()
         # one stream of timesteps per (seed, epoch, rank): replicas must not train on identical draws
         rng = rng or np.random.default_rng([self.seed + epoch, self.dp_rank] if self.dp_world > 1 else self.seed + epoch)
         total, count = 0.0, 0
@@ -284,14 +308,8 @@ class DDPM_model:
             past = np.ascontiguousarray(past, dtype=np.float32)
             future = np.ascontiguousarray(future, dtype=np.float32)
             self._ensure_training(past, future)
-            t = rng.integers(0, forward_sampler.timesteps, size=(future.shape[0],)).astype(np.int64)
-            self._train_calls = getattr(self, "_train_calls", 0) + 1
-            if grad_sync is None:
-                loss = self.denoiser.train_step(forward_sampler._handle, future, past, t, None,
-                                                seed=self.seed + self._train_calls, apply_update=True)
-            else:
-                loss = self.denoiser.train_step(forward_sampler._handle, future, past, t, None,
-                                                seed=self.seed + self._train_calls, apply_update=False)
+            loss = self._train_batch(forward_sampler, past, future, rng, grad_sync is None, **step_kw)
+            if grad_sync is not None:
                 grad_sync(self.denoiser)
                 self.denoiser.apply_update()
             total += loss
@@ -327,6 +345,10 @@ class DDPM_model:
         checkpoint decisions are identical on every rank (a rank that stopped alone would leave the others
         blocked in the gradient all-reduce)."""
         self._refuse_training()
+        return self._run_epochs(batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save, loss_sync=loss_sync)
+
+    def _run_epochs(self, batched_train_data, baseline_ckpt, *, log, grad_sync, save, loss_sync):
+        """The epoch loop of `train`, behind its admission check (and behind that of a subclass's `fit`)."""
         import logging
         forward_sampler = DDPM(timesteps=max(2, self.res.timesteps), scale=self.res.scale, device=self.device)
         if baseline_ckpt is not None:

@@ -6,20 +6,22 @@ Same constructor arguments and call convention as the reference --
 driver touches (`eval/to/state_dict/load_state_dict`, `ensure` like `UNet.ensure`).  All arithmetic runs in
 libcrowdmod_hip.so (cm_model_create_dit / cm_model_create_dit2d, cm_dit.hip).  Both train through the `fit_*` family
 (DiT4D_V4: cm_dit4d_train_*, cm_dit4d_train.hip; DiT2D: cm_dit_train_*, cm_dit_train.hip) -- `train()` / `train_init()`
-keep raising on both.
+keep raising on both.  The state surface, the handle's creation, the staging of inputs and the trainer accessors are
+`NativeModule`'s (native_module.py), shared with the UNet and ConvRNN wrappers; here are the geometry the handle is bound
+to, the refusal to re-create a handle that holds training state, and the `fit_*` steps.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Optional
 
 import numpy as np
 
 from . import dit2d_spec, dit_spec, native, optim_state
-from .unet import _is_torch
+from .native_module import NativeModule
 
 
-class DiT4D_V4:
+class DiT4D_V4(NativeModule):
     _NAME = "DiT4D_V4"
     _SPEC = dit_spec
     _CREATE = "cm_model_create_dit"
@@ -30,32 +32,21 @@ class DiT4D_V4:
                  t_patch_size=2, patch_size=4, hidden_size=256, depth=6, num_heads=4, mlp_ratio=4.0, dropout_rate=0.1,
                  time_multiple=4, total_time_steps=1000, condition="Past", T_max=32, *, device: int = 0,
                  max_batch: int = 64, seed: Optional[int] = 42):
-        if condition != "Past":
-            raise NotImplementedError("only condition='Past' (the configuration every reference config uses)")
-        if int(total_time_steps) != 1000:
-            raise NotImplementedError("total_time_steps other than 1000 (the reference never sets it)")
+        self._check_ctor(condition, total_time_steps)
         self.cfg = dit_spec.DiTConfig(int(input_channels), int(output_channels), int(grid_rows), int(grid_cols),
                                       int(past_len), int(future_len), int(t_patch_size), int(patch_size),
                                       int(hidden_size), int(depth), int(num_heads), float(mlp_ratio),
                                       float(dropout_rate), int(time_multiple), condition, int(T_max))
-        self.input_channels = self.cfg.input_channels
-        self.condition = condition
-        self.device = int(device)
-        self.max_batch = int(max_batch)
-        self._native_max_batch = 0
-        self.training = False
-        self._init_state(seed)
+        self._init_state(self._SPEC, device, max_batch, seed)
 
-    def _init_state(self, seed):
-        self._shapes = self._SPEC.param_shapes(self.cfg)
-        self._params: Dict[str, np.ndarray] = self._SPEC.init_params(self.cfg, seed if seed is not None else 0)
-        self._handle = None
+    def _check_ctor(self, condition, total_time_steps):
+        if condition != "Past":
+            raise NotImplementedError("only condition='Past' (the configuration every reference config uses)")
+        if int(total_time_steps) != 1000:
+            raise NotImplementedError("total_time_steps other than 1000 (the reference never sets it)")
+        self.condition = condition
 
     # -- nn.Module surface ---------------------------------------------------------
-    def eval(self):
-        self.training = False
-        return self
-
     def train(self, mode: bool = True):
         if mode:
             raise NotImplementedError(f"{self._NAME}.train(): the nn.Module training mode is not implemented on this path; "
@@ -66,38 +57,8 @@ class DiT4D_V4:
         raise NotImplementedError(f"{self._NAME}.train_init is the UNet's entry; {self._NAME} trains through the fit_* family "
                                   "(fit_init, fit_step_xt, ...)")
 
-    def to(self, device=None):
-        if isinstance(device, int) and device != self.device:
-            self._release()
-            self.device = device
-        return self
-
     def parameters(self):
         return [v for k, v in self._params.items() if k != self._TABLE]
-
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {k: v.copy() for k, v in self._params.items()}
-
-    def load_state_dict(self, state: Dict[str, object], strict: bool = True):
-        if getattr(self, "_fit", False):
-            self._release()          # raises, before any tensor is replaced
-        got = {}
-        for k, v in state.items():
-            if _is_torch(v):
-                v = v.detach().cpu().numpy()
-            got[k] = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-        missing = [k for k in self._shapes if k not in got]
-        unexpected = [k for k in got if k not in self._shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for {self._NAME}: missing keys {missing}, "
-                               f"unexpected keys {unexpected}")
-        for k, shp in self._shapes.items():
-            if k in got:
-                if tuple(got[k].shape) != tuple(shp):
-                    raise RuntimeError(f"size mismatch for {k}: got {tuple(got[k].shape)}, expected {tuple(shp)}")
-                self._params[k] = got[k]
-        self._release()
-        return self
 
     # -- native handle -------------------------------------------------------------
     def native_config(self, max_batch: int, device: int) -> native.cm_dit_config:
@@ -111,14 +72,13 @@ class DiT4D_V4:
 
     def _release(self):
         """Destroying the handle of a model that is training would silently drop the unsynced master weights, both
-        Adam moments and the step counter: refuse, unless `fit_end` (or the destructor) asked for it."""
+        Adam moments and the step counter: refuse, unless `fit_end` (or the destructor) asked for it.  load_state_dict
+        comes here before it replaces any tensor."""
         if getattr(self, "_fit", False) and not getattr(self, "_fit_closing", False):
             raise RuntimeError(f"{self._NAME}: this call would re-create the native handle (a larger batch than fit_init "
                                "allocated, other frame counts, load_state_dict or another device) while it holds "
                                "training state; call sync() and fit_end() first, then fit_init again")
-        if self._handle is not None:
-            native.lib().cm_model_destroy(self._handle)
-            self._handle = None
+        self._destroy()
         self._fit = False
 
     def __del__(self):
@@ -138,54 +98,13 @@ class DiT4D_V4:
             return self._handle
         self._release()
         self.max_batch = max(self.max_batch, batch)
-        L = native.lib()
-        c = self.native_config(self.max_batch, self.device)
-        h = C.c_void_p()
-        native.check(getattr(L, self._CREATE)(C.byref(c), C.byref(h)))
-        try:
-            for name, arr in self._params.items():
-                arr = np.ascontiguousarray(arr, dtype=np.float32)
-                native.check(L.cm_model_set_param(h, name.encode(), arr.ctypes.data, arr.size))
-            native.check(L.cm_model_finalize(h))
-        except Exception:
-            L.cm_model_destroy(h)
-            raise
-        self._handle, self._native_max_batch = h, self.max_batch
-        return h
+        return self._create_handle()
 
     # -- forward -------------------------------------------------------------------
-    def __call__(self, future, t, past=None):
-        return self.forward(future, t, past)
-
     def forward(self, future, t, past=None):
         """DiT4D_V4.forward (DiT4D_V4.py:347-375) / DiT2D.forward (DiT2D.py:255-296), eval mode.  numpy in -> numpy out (host staging); torch CUDA
         tensors in -> torch CUDA tensor out (device pointers)."""
-        if past is None:
-            raise ValueError("condition='Past' needs the past frames")
-        L = native.lib()
-        B, Cc, H, W, F = (int(v) for v in future.shape)
-        P = int(past.shape[4])
-        if Cc != self.cfg.input_channels or tuple(past.shape[:4]) != (B, Cc, H, W):
-            raise ValueError(f"shape mismatch: future {tuple(future.shape)}, past {tuple(past.shape)}")
-        h = self.ensure(H, W, P, F, B)
-        if _is_torch(future):
-            import torch
-            if not future.is_cuda:
-                raise ValueError("torch inputs must live on the GPU; pass numpy arrays for host staging")
-            fut = future.contiguous().float()
-            pst = past.contiguous().float()
-            tt = t.to(device=future.device, dtype=torch.long).contiguous()
-            out = torch.empty_like(fut)
-            torch.cuda.current_stream(future.device).synchronize()
-            native.check(L.cm_unet_forward(h, fut.data_ptr(), tt.data_ptr(), pst.data_ptr(), out.data_ptr(), B, None))
-            native.check(L.cm_device_synchronize(self.device))
-            return out
-        fut = np.ascontiguousarray(future, dtype=np.float32)
-        pst = np.ascontiguousarray(past, dtype=np.float32)
-        tt = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,)))
-        out = np.empty_like(fut)
-        native.check(L.cm_unet_forward_host(h, fut.ctypes.data, tt.ctypes.data, pst.ctypes.data, out.ctypes.data, B))
-        return out
+        return self._denoise(future, t, past)
 
     def debug_activation(self, name: str) -> np.ndarray:
         """Residual stream [B, T_p * N_s, D] of the last forward after `blocks.<i>` (what a forward hook on that module
@@ -207,10 +126,7 @@ class DiT4D_V4:
         return f.value, b.value
 
     # -- training (cm_dit4d_train_* here, cm_dit_train_* on DiT2D: `_FAMILY`) ---------
-    def _fn(self, entry: str):
-        return getattr(native.lib(), f"{self._FAMILY}_{entry}")
-
-    def _fit_handle(self):
+    def _train_handle(self):
         if self._handle is None or not getattr(self, "_fit", False):
             raise RuntimeError(f"{self._NAME}.fit_init has not been called (or the handle was re-created since)")
         return self._handle
@@ -232,37 +148,23 @@ class DiT4D_V4:
         self._fit = True
         return self
 
-    def set_lr(self, lr: float):
-        native.check(self._fn("set_lr")(self._fit_handle(), float(lr)))
+    def _fit_step(self, entry, first, items, seed, apply_update, sample_base) -> float:
+        """`entry(h, *first, *items, seed, &loss, B, apply_update, stream)` on the staged `items` (numpy arrays through
+        device buffers freed after the call, torch CUDA tensors as they are); B is that of the first item."""
+        h, loss = self._train_handle(), C.c_float()
+        B = int(items[0][0].shape[0])
+        if B > self._native_max_batch:
+            raise ValueError(f"batch {B} exceeds the {self._native_max_batch} samples fit_init allocated")
+        native.check(self._fn("set_sample_base")(h, int(sample_base)))
+        with self._staged(items, B, free=True) as ptrs:
+            native.check(self._fn(entry)(h, *first, *ptrs, int(seed), C.byref(loss), B, int(bool(apply_update)), None))
+        return float(loss.value)
 
     def fit_step_xt(self, xt, t, past, target, seed: int = 0, apply_update: bool = True, sample_base: int = 0) -> float:
         """One training step: u = denoiser(xt, t, past) in train mode, loss = mse(u, target), backward, Adam when
         `apply_update`.  numpy arrays (host staging) or torch CUDA tensors; returns the loss."""
-        L, h = native.lib(), self._fit_handle()
-        B = int(xt.shape[0])
-        if B > self._native_max_batch:
-            raise ValueError(f"batch {B} exceeds the {self._native_max_batch} samples fit_init allocated")
-        native.check(self._fn("set_sample_base")(h, int(sample_base)))
-        loss = C.c_float()
-        if _is_torch(xt):
-            import torch
-            a = [v.contiguous().float() for v in (xt, past, target)]
-            tt = t.to(device=xt.device, dtype=torch.long).contiguous()
-            torch.cuda.current_stream(xt.device).synchronize()
-            native.check(self._fn("step_xt")(h, a[0].data_ptr(), a[1].data_ptr(), tt.data_ptr(), a[2].data_ptr(),
-                                                int(seed), C.byref(loss), B, int(bool(apply_update)), None))
-            return float(loss.value)
-        bufs = [native.DeviceBuffer.from_array(np.ascontiguousarray(v, dtype=np.float32), self.device)
-                for v in (xt, past, target)]
-        tb = native.DeviceBuffer.from_array(
-            np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,))), self.device)
-        try:
-            native.check(self._fn("step_xt")(h, bufs[0].ptr, bufs[1].ptr, tb.ptr, bufs[2].ptr, int(seed),
-                                                C.byref(loss), B, int(bool(apply_update)), None))
-        finally:
-            for b in bufs + [tb]:
-                b.free()
-        return float(loss.value)
+        return self._fit_step("step_xt", (), [(xt, np.float32), (past, np.float32), (t, np.int64), (target, np.float32)],
+                              seed, apply_update, sample_base)
 
     def fit_step(self, schedule, future, past, t, eps=None, seed: int = 0, apply_update: bool = True,
                  sample_base: int = 0) -> float:
@@ -275,100 +177,39 @@ class DiT4D_V4:
         sched = getattr(schedule, "_handle", None)
         if sched is None:
             raise TypeError("fit_step takes the DDPM schedule object (diffusion.DDPM), not a handle")
-        h = self._fit_handle()
-        B = int(future.shape[0])
-        if B > self._native_max_batch:
-            raise ValueError(f"batch {B} exceeds the {self._native_max_batch} samples fit_init allocated")
-        native.check(self._fn("set_sample_base")(h, int(sample_base)))
-        loss = C.c_float()
-        if _is_torch(future):
-            import torch
-            a = [v.contiguous().float() for v in (future, past)]
-            e = eps.contiguous().float() if eps is not None else None
-            tt = t.to(device=future.device, dtype=torch.long).contiguous()
-            torch.cuda.current_stream(future.device).synchronize()
-            native.check(self._fn("step")(h, sched, a[0].data_ptr(), a[1].data_ptr(), tt.data_ptr(),
-                                          e.data_ptr() if e is not None else None, int(seed), C.byref(loss), B,
-                                          int(bool(apply_update)), None))
-            return float(loss.value)
-        bufs = [native.DeviceBuffer.from_array(np.ascontiguousarray(v, dtype=np.float32), self.device)
-                for v in ((future, past) if eps is None else (future, past, eps))]
-        tb = native.DeviceBuffer.from_array(
-            np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,))), self.device)
-        try:
-            native.check(self._fn("step")(h, sched, bufs[0].ptr, bufs[1].ptr, tb.ptr,
-                                          bufs[2].ptr if eps is not None else None, int(seed), C.byref(loss), B,
-                                          int(bool(apply_update)), None))
-        finally:
-            for b in bufs + [tb]:
-                b.free()
-        return float(loss.value)
-
-    def _tensor(self, fn, name, *extra):
-        out = np.empty(self._shapes[name], dtype=np.float32)
-        native.check(fn(self._fit_handle(), name.encode(), *extra, out.ctypes.data, out.size))
-        return out
-
-    def grad(self, name: str) -> np.ndarray:
-        """Gradient of one state_dict tensor after the last step."""
-        return self._tensor(self._fn("get_grad"), name)
+        return self._fit_step("step", (sched,), [(future, np.float32), (past, np.float32), (t, np.int64), (eps, np.float32)],
+                              seed, apply_update, sample_base)
 
     def opt_state(self, name: str, which: int) -> np.ndarray:
         """0 exp_avg, 1 exp_avg_sq, 2 the master weights (what the next step reads; `sync` publishes them)."""
-        return self._tensor(self._fn("get_opt_state"), name, int(which))
+        return self._opt_tensor(name, which)
 
     def set_opt_state(self, name: str, which: int, value):
-        v = np.ascontiguousarray(value, dtype=np.float32).reshape(self._shapes[name])
-        native.check(self._fn("set_opt_state")(self._fit_handle(), name.encode(), int(which),
-                                                             v.ctypes.data, v.size))
-
-    def opt_step(self, set_to: Optional[int] = None) -> int:
-        s = C.c_int32(0 if set_to is None else int(set_to))
-        native.check(self._fn("opt_step")(self._fit_handle(), C.byref(s), int(set_to is not None)))
-        return int(s.value)
-
-    def flat_grads(self):
-        """(device address, element count) of the flat fp32 gradient buffer in state_dict order (the all-reduce
-        operand of data-parallel training: step(apply_update=False), all-reduce, apply_update())."""
-        p, n = C.c_void_p(), C.c_int64()
-        native.check(self._fn("flat_grads")(self._fit_handle(), C.byref(p), C.byref(n)))
-        return p.value, int(n.value)
-
-    def apply_update(self):
-        native.check(self._fn("apply")(self._fit_handle(), None))
+        self._set_opt_tensor(name, which, np.asarray(value, dtype=np.float32).reshape(self._shapes[name]))
 
     def train_pred(self, B: int) -> np.ndarray:
         """Train-mode prediction [B, C, H, W, F] of the last step."""
         g = self.cfg
         out = np.empty((int(B), g.output_channels, g.grid_rows, g.grid_cols, g.future_len), dtype=np.float32)
-        native.check(self._fn("get_pred")(self._fit_handle(), out.ctypes.data, out.size))
+        native.check(self._fn("get_pred")(self._train_handle(), out.ctypes.data, out.size))
         return out
 
     def sync(self):
         """Publish the trained weights: state_dict(), the eval forward and the sampling loops see them from here on."""
-        L, h = native.lib(), self._fit_handle()
-        native.check(self._fn("sync")(h))
-        for name, shp in self._shapes.items():
-            buf = np.empty(shp, dtype=np.float32)
-            native.check(L.cm_model_get_param(h, name.encode(), buf.ctypes.data, buf.size))
-            self._params[name] = buf
+        self._pull_trained()
         return self
 
     sync_trained = sync   # the name the shared epoch loop (DDPM_model.train / save_checkpoint) calls
-
-    def trainable_names(self):
-        return list(self._shapes)
 
     def optimizer_state_dict(self, lr: float, betas, eps: float, weight_decay: float):
         """torch.optim.Adam.state_dict() of the reference optimizer (flow_matching.py:27-30, ddpm.py:52-57) over
         the denoiser's parameters(): what a checkpoint stores under "opt".  The frozen sinusoid table is a parameter
         without state."""
-        return optim_state.dump(self.trainable_names(), (self._TABLE,), optim_state.ADAM_KEYS, lr, betas, eps, weight_decay,
-                                self.opt_state, self.opt_step())
+        return self._dump_opt((self._TABLE,), optim_state.ADAM_KEYS, lr, betas, eps, weight_decay, self.opt_state)
 
     def load_optimizer_state_dict(self, opt: dict):
         """Inverse of optimizer_state_dict (resume from a checkpoint's "opt" entry)."""
-        self.opt_step(optim_state.load(opt, self.trainable_names(), optim_state.ADAM_KEYS, self.set_opt_state))
+        self._load_opt(opt, optim_state.ADAM_KEYS, self.set_opt_state)
 
 
 class DiT2D(DiT4D_V4):
@@ -385,21 +226,12 @@ class DiT2D(DiT4D_V4):
                  depth=6, num_heads=4, mlp_ratio=4.0, dropout_rate=0.1, time_multiple=4, total_time_steps=1000,
                  condition="Past", t_max=8, *, past_len: int = 5, future_len: int = 3, device: int = 0,
                  max_batch: int = 64, seed: Optional[int] = 42):
-        if condition != "Past":
-            raise NotImplementedError("only condition='Past' (the configuration every reference config uses)")
-        if int(total_time_steps) != 1000:
-            raise NotImplementedError("total_time_steps other than 1000 (the reference never sets it)")
+        self._check_ctor(condition, total_time_steps)
         self.cfg = dit2d_spec.DiT2DConfig(int(input_channels), int(output_channels), int(grid_rows), int(grid_cols),
                                           int(past_len), int(future_len), int(patch_size), int(hidden_size), int(depth),
                                           int(num_heads), float(mlp_ratio), float(dropout_rate), int(time_multiple),
                                           condition, int(t_max))
-        self.input_channels = self.cfg.input_channels
-        self.condition = condition
-        self.device = int(device)
-        self.max_batch = int(max_batch)
-        self._native_max_batch = 0
-        self.training = False
-        self._init_state(seed)
+        self._init_state(self._SPEC, device, max_batch, seed)
 
     def native_config(self, max_batch: int, device: int) -> native.cm_dit2d_config:
         c, g = native.cm_dit2d_config(), self.cfg

@@ -71,38 +71,28 @@ class FM_model(DDPM_model):
 
     def _train_one_epoch_fm(self, loader, epoch, *, rng: Optional[np.random.Generator] = None, grad_sync=None,
                             x0=None, t=None, drop_masks=None):
-        try:
-            w_fn = self.w_type_fns[self.w_type]
-        except KeyError:
+        if self.w_type not in self.w_type_fns:
             raise ValueError(f"Unsupported W_TYPE '{self.w_type}'. Available: {list(self.w_type_fns.keys())}")
-        rng = rng or np.random.default_rng([self.seed + epoch, self.dp_rank] if self.dp_world > 1 else self.seed + epoch)
-        total, count = 0.0, 0
-        for past, future in loader:
-            past = np.ascontiguousarray(past, dtype=np.float32)
-            x1 = np.ascontiguousarray(future, dtype=np.float32)
-            self._ensure_training(past, x1)
-            B = x1.shape[0]
-            self._fm_calls += 1
-            tag = f"fm/x0/{self._fm_calls}" + (f"/r{self.dp_rank}" if self.dp_world > 1 else "")   # own x0 per rank
-            x0b = prng.normal(self.seed, tag, x1.size).reshape(x1.shape) if x0 is None else x0
-            tb = rng.random(B, dtype=np.float32) if t is None else np.asarray(t, dtype=np.float32)
-            tv = tb.reshape(-1, 1, 1, 1, 1)
-            xt, u_target = w_fn(np.asarray(x0b, dtype=np.float32), x1, tv)
-            t_idx = (tb * np.float32(self.time_max_pos)).astype(np.int64)   # (t * time_max_pos).long(): truncation
-            if self.arch == "FM-DiT":   # the DiT2D draws its masks on the device only: (seed, step, global sample index)
-                loss = self.denoiser.fit_step_xt(xt.astype(np.float32), t_idx, past, u_target.astype(np.float32),
-                                                 seed=self.seed + self._fm_calls, apply_update=grad_sync is None,
-                                                 sample_base=self.dp_rank * B)
-            else:
-                loss = self.denoiser.train_step_xt(xt.astype(np.float32), past, t_idx, u_target.astype(np.float32),
-                                                   drop_masks=drop_masks, seed=self.seed + self._fm_calls,
-                                                   apply_update=grad_sync is None)
-            if grad_sync is not None:
-                grad_sync(self.denoiser)
-                self.denoiser.apply_update()
-            total += loss
-            count += 1
-        return total / max(count, 1)
+        return super()._train_one_epoch(None, loader, epoch, rng=rng, grad_sync=grad_sync, x0=x0, t=t, drop_masks=drop_masks)
+
+    def _train_batch(self, forward_sampler, past, x1, rng: np.random.Generator, apply_update: bool, x0=None, t=None,
+                     drop_masks=None) -> float:
+        """flow_matching.py:128-146: x0 ~ N(0,1), t ~ U(0,1), (x_t, u_target) on the probability path, and the step of the
+        velocity predictor on them."""
+        B = x1.shape[0]
+        self._fm_calls += 1
+        tag = f"fm/x0/{self._fm_calls}" + (f"/r{self.dp_rank}" if self.dp_world > 1 else "")   # own x0 per rank
+        x0b = prng.normal(self.seed, tag, x1.size).reshape(x1.shape) if x0 is None else x0
+        tb = rng.random(B, dtype=np.float32) if t is None else np.asarray(t, dtype=np.float32)
+        tv = tb.reshape(-1, 1, 1, 1, 1)
+        xt, u_target = self.w_type_fns[self.w_type](np.asarray(x0b, dtype=np.float32), x1, tv)
+        t_idx = (tb * np.float32(self.time_max_pos)).astype(np.int64)   # (t * time_max_pos).long(): truncation
+        if self.arch == "FM-DiT":   # the DiT2D draws its masks on the device only: (seed, step, global sample index)
+            return self.denoiser.fit_step_xt(xt.astype(np.float32), t_idx, past, u_target.astype(np.float32),
+                                             seed=self.seed + self._fm_calls, apply_update=apply_update,
+                                             sample_base=self.dp_rank * B)
+        return self.denoiser.train_step_xt(xt.astype(np.float32), past, t_idx, u_target.astype(np.float32),
+                                           drop_masks=drop_masks, seed=self.seed + self._fm_calls, apply_update=apply_update)
 
     def checkpoint_path(self, epoch_tag) -> str:
         """utils/utils.py:130-131: the FM checkpoints carry the W_TYPE where the DDPM ones say "NA"."""
@@ -123,29 +113,18 @@ class FM_model(DDPM_model):
             raise NotImplementedError(f"training {self.arch} through train() is not implemented on this path; use "
                                       "FM_model.fit / train_fm_dit.py (DiT2D backward, dropout from the device Philox "
                                       "stream, Adam)")
-        keep = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
-        self._keep_override = keep
+        self._keep_override = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
         return super().train(batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save,
                              loss_sync=loss_sync)
 
     def _refuse_training(self):
-        if self.arch == "FM-UNet":      # the UNet backbone trains through train() (cm_train_step_xt), like DDPM-UNet
-            return
-        if not getattr(self, "_fitting", False):
+        if self.arch != "FM-UNet":      # the UNet backbone trains through train() (cm_train_step_xt), like DDPM-UNet
             super()._refuse_training()
 
     def _ensure_training(self, past, future):
-        if self.arch != "FM-DiT":
-            return super()._ensure_training(past, future)
-        from .ddpm_model import ReduceLROnPlateau
-        net = self.denoiser
-        B, _, H, W, F = future.shape
-        if not getattr(net, "_fit", False):
-            s = self._solver()
-            net.ensure(H, W, int(past.shape[4]), F, max(B, net.max_batch))
-            net.fit_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], dropout_rate=self.res.dit.dropout_rate)
-            self._lr = s["lr"]
-            self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
+        if self.arch == "FM-DiT":
+            return self._ensure_dit_training(past, future)
+        return super()._ensure_training(past, future)
 
     def fit(self, batched_train_data, baseline_ckpt=None, *, log=None, grad_sync=None, save=True, loss_sync=None):
         """Train the DiT2D of arch "FM-DiT" (flow_matching.py:104-201): the epoch loop of `train` -- the same w_fn and
@@ -154,12 +133,7 @@ class FM_model(DDPM_model):
         if self.arch != "FM-DiT":
             raise NotImplementedError(f"FM_model.fit trains FM-DiT only; {self.arch} goes through train()")
         self._keep_override = int(self.cfg.MODEL.FM.get("CHECKPOINTS_TO_KEEP", 0) or 0)
-        self._fitting = True
-        try:
-            return DDPM_model.train(self, batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save,
-                                    loss_sync=loss_sync)
-        finally:
-            self._fitting = False
+        return self._run_epochs(batched_train_data, baseline_ckpt, log=log, grad_sync=grad_sync, save=save, loss_sync=loss_sync)
 
     # -- sampling entry (flow_matching.py:250-292) ------------------------------------------
     def sampling(self, batched_test_data, plotType=None, model_fullname=None, plotMprop=None, plotPast=None,

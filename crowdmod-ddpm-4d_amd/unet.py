@@ -6,23 +6,28 @@
 `nn.Module` methods the reference's drivers touch (`eval/train/to/state_dict/
 load_state_dict/parameters`, models/diffusion/ddpm.py:50,118,209,288).  All
 arithmetic happens in libcrowdmod_hip.so; this class only owns the weights on
-the host and the native handle.
+the host and the native handle.  The state surface, the handle's creation, the
+staging of inputs and the trainer accessors (cm_train_*) are `NativeModule`'s
+(native_module.py), shared with the DiT and ConvRNN wrappers; here are the UNet's
+geometry and precision, its training step and what its handle carries across a
+re-creation.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Iterable, Optional
+from typing import Iterable, Optional
 
 import numpy as np
 
 from . import native, optim_state, spec
+from .native_module import NativeModule
+
+_PRECISIONS = {"f32": None, "f16": native.PRECISION_F16, "f32r": native.PRECISION_F32R, "f32x": native.PRECISION_F32X}
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch"
+class UNet(NativeModule):
+    _NAME = "UNet"
 
-
-class UNet:
     def __init__(self, input_channels=4, output_channels=4, num_res_blocks=2, base_channels=128,
                  base_channels_multiples=(1, 2, 4, 8), apply_attention=(False, False, True, False, False),
                  dropout_rate=0.1, time_multiple=4, condition="Past", *, device: int = 0, max_batch: int = 64,
@@ -33,17 +38,8 @@ class UNet:
                                    tuple(int(v) for v in base_channels_multiples),
                                    tuple(bool(v) for v in apply_attention), float(dropout_rate), int(time_multiple),
                                    condition)
-        self.input_channels = self.cfg.input_channels
         self.condition = condition
-        self.device = int(device)
-        self.max_batch = int(max_batch)
-        self._native_max_batch = 0
-        self.training = False
-        self._shapes = spec.param_shapes(self.cfg)
-        # random init with torch-default ranges (the reference's nn.Module ctor does the same)
-        self._params: Dict[str, np.ndarray] = spec.init_params(self.cfg, seed if seed is not None else 0,
-                                                               perturb_norm=False)
-        self._handle = None
+        self._init_state(spec, device, max_batch, seed, perturb_norm=False)
         self._geom = None
         self.precision = "f32"
 
@@ -56,7 +52,7 @@ class UNet:
         # reference, not inside the default plan's 2e-6.  Inference only.
         # 'f32x' (strict fp32, round 3's arithmetic): the default plan without the f16 two-way-split form -- exact three-way bf16
         # splits, six cross terms, in every split layer (CM_PRECISION_F32X): same measured error, 16 % slower.
-        if precision not in ("f32", "f16", "f32r", "f32x"):
+        if precision not in _PRECISIONS:
             raise ValueError(f"precision {precision!r}: 'f32', 'f32x', 'f32r' or 'f16'")
         if precision != self.precision:
             self._release()
@@ -64,46 +60,16 @@ class UNet:
         return self
 
     # -- nn.Module surface ---------------------------------------------------------
-    def eval(self):
-        self.training = False
-        return self
-
     def train(self, mode: bool = True):
         self.training = bool(mode)
-        return self
-
-    def to(self, device=None):
-        if isinstance(device, int):
-            if device != self.device:
-                self._release()
-                self.device = device
         return self
 
     def parameters(self) -> Iterable[np.ndarray]:
         return [v for k, v in self._params.items() if k != "time_embeddings.time_blocks.0.weight"]
 
-    def state_dict(self) -> Dict[str, np.ndarray]:
-        return {k: v.copy() for k, v in self._params.items()}
-
-    def load_state_dict(self, state: Dict[str, object], strict: bool = True):
-        got = {}
-        for k, v in state.items():
-            if _is_torch(v):
-                v = v.detach().cpu().numpy()
-            got[k] = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
-        missing = [k for k in self._shapes if k not in got]
-        unexpected = [k for k in got if k not in self._shapes]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for UNet: missing keys {missing}, "
-                               f"unexpected keys {unexpected}")
-        for k, shp in self._shapes.items():
-            if k in got:
-                if tuple(got[k].shape) != tuple(shp):
-                    raise RuntimeError(f"size mismatch for {k}: got {tuple(got[k].shape)}, expected {tuple(shp)}")
-                self._params[k] = got[k]
+    def _release_for_load(self):
         self._carry_opt = None
         self._release(keep_training=False)
-        return self
 
     # -- native handle -------------------------------------------------------------
     def _release(self, keep_training: bool = True):
@@ -115,8 +81,7 @@ class UNet:
                 self.sync_trained()
                 hp = self._train_hparams
                 self._carry_opt = (self.optimizer_state_dict(hp["lr"], hp["betas"], hp["eps"], hp["weight_decay"]), hp)
-            native.lib().cm_model_destroy(self._handle)
-            self._handle = None
+            self._destroy()
             self._geom = None
             self._train_ready = False
 
@@ -125,6 +90,19 @@ class UNet:
             self._release(keep_training=False)
         except Exception:
             pass
+
+    def native_config(self, max_batch: int, device: int) -> native.cm_unet_config:
+        c, g = native.cm_unet_config(), self.cfg
+        c.in_channels, c.out_channels = g.input_channels, g.output_channels
+        c.num_res_blocks, c.base_channels = g.num_res_blocks, g.base_channels
+        c.n_levels = len(g.base_channels_multiples)
+        for i, v in enumerate(g.base_channels_multiples):
+            c.channel_mult[i] = v
+            c.apply_attention[i] = int(g.apply_attention[i])
+        c.time_multiple = g.time_multiple
+        c.rows, c.cols, c.past_len, c.future_len = self._geom
+        c.max_batch, c.device = int(max_batch), int(device)
+        return c
 
     def ensure(self, rows: int, cols: int, past_len: int, future_len: int, batch: int):
         """Create (or re-create) the native model for this tensor geometry."""
@@ -135,34 +113,14 @@ class UNet:
             return self._handle
         self._release()
         self.max_batch = max(self.max_batch, batch)
-        L = native.lib()
-        c = native.cm_unet_config()
-        c.in_channels, c.out_channels = self.cfg.input_channels, self.cfg.output_channels
-        c.num_res_blocks, c.base_channels = self.cfg.num_res_blocks, self.cfg.base_channels
-        c.n_levels = len(self.cfg.base_channels_multiples)
-        for i, v in enumerate(self.cfg.base_channels_multiples):
-            c.channel_mult[i] = v
-            c.apply_attention[i] = int(self.cfg.apply_attention[i])
-        c.time_multiple = self.cfg.time_multiple
-        c.rows, c.cols, c.past_len, c.future_len = rows, cols, past_len, future_len
-        c.max_batch, c.device = self.max_batch, self.device
-        h = C.c_void_p()
-        native.check(L.cm_model_create(C.byref(c), C.byref(h)))
-        try:
-            if self.precision == "f16":
-                native.check(L.cm_model_set_precision(h, native.PRECISION_F16))
-            elif self.precision == "f32r":
-                native.check(L.cm_model_set_precision(h, native.PRECISION_F32R))
-            elif self.precision == "f32x":
-                native.check(L.cm_model_set_precision(h, native.PRECISION_F32X))
-            for name, arr in self._params.items():
-                arr = np.ascontiguousarray(arr, dtype=np.float32)
-                native.check(L.cm_model_set_param(h, name.encode(), arr.ctypes.data, arr.size))
-            native.check(L.cm_model_finalize(h))
-        except Exception:
-            L.cm_model_destroy(h)
-            raise
-        self._handle, self._geom, self._native_max_batch = h, geom, self.max_batch
+        self._geom = geom
+        return self._create_handle()
+
+    def _before_upload(self, h):
+        if _PRECISIONS[self.precision] is not None:
+            native.check(native.lib().cm_model_set_precision(h, _PRECISIONS[self.precision]))
+
+    def _after_finalize(self, h):
         carry = getattr(self, "_carry_opt", None)
         if carry is not None:
             # the handle this one replaces was training: continue from its optimizer state
@@ -172,45 +130,14 @@ class UNet:
             self.train_init(lr=hp["lr"], betas=hp["betas"], eps=hp["eps"], weight_decay=hp["weight_decay"], autocast=on,
                             loss_scale_log2=k)
             self.load_optimizer_state_dict(opt)
-        return h
 
     # -- forward -------------------------------------------------------------------
-    def __call__(self, future, t, past=None):
-        return self.forward(future, t, past)
-
     def forward(self, future, t, past=None):
         """UNet.forward (unet.py:124-167), eval mode.  numpy in -> numpy out (host
         staging); torch CUDA tensors in -> torch CUDA tensor out (device pointers)."""
-        if past is None:
-            raise ValueError("condition='Past' needs the past frames")
-        if self.training:
+        if self.training and past is not None:
             return self.forward_train(future, t, past)
-        L = native.lib()
-        B, Cc, H, W, F = (int(v) for v in future.shape)
-        P = int(past.shape[4])
-        if Cc != self.cfg.input_channels or tuple(past.shape[:4]) != (B, Cc, H, W):
-            raise ValueError(f"shape mismatch: future {tuple(future.shape)}, past {tuple(past.shape)}")
-        h = self.ensure(H, W, P, F, B)
-        if _is_torch(future):
-            import torch
-            if not future.is_cuda:
-                raise ValueError("torch inputs must live on the GPU; pass numpy arrays for host staging")
-            fut = future.contiguous().float()
-            pst = past.contiguous().float()
-            tt = t.to(device=future.device, dtype=torch.long).contiguous()
-            out = torch.empty_like(fut)
-            # the library runs on its own stream: order it after the producers of the
-            # inputs and hand back a finished result
-            torch.cuda.current_stream(future.device).synchronize()
-            native.check(L.cm_unet_forward(h, fut.data_ptr(), tt.data_ptr(), pst.data_ptr(), out.data_ptr(), B, None))
-            native.check(L.cm_device_synchronize(self.device))
-            return out
-        fut = np.ascontiguousarray(future, dtype=np.float32)
-        pst = np.ascontiguousarray(past, dtype=np.float32)
-        tt = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,)))
-        out = np.empty_like(fut)
-        native.check(L.cm_unet_forward_host(h, fut.ctypes.data, tt.ctypes.data, pst.ctypes.data, out.ctypes.data, B))
-        return out
+        return self._denoise(future, t, past)
 
     def dropout_layout(self):
         """[(prefix, offset, Cout)] of the per-block slices of the training-mode mask row."""
@@ -226,27 +153,15 @@ class UNet:
         ResnetBlock prefix to its [B, Cout] keep-mask/(1-p); None draws the masks on the device.
         numpy in -> numpy out."""
         L = native.lib()
-        fut = np.ascontiguousarray(future, dtype=np.float32)
-        pst = np.ascontiguousarray(past, dtype=np.float32)
-        B, Cc, H, W, F = fut.shape
-        P = pst.shape[4]
-        h = self.ensure(H, W, P, F, B)
-        tt = np.ascontiguousarray(np.broadcast_to(np.asarray(t, dtype=np.int64).reshape(-1), (B,)))
-        dev = self.device
-        dfut, dpst, dt = (native.DeviceBuffer.from_array(a, dev) for a in (fut, pst, tt))
-        dout = native.DeviceBuffer(fut.nbytes, dev)
-        dmask = None
-        if drop_masks is not None:
-            layout, width = self.dropout_layout()
-            row = np.ones((B, width), dtype=np.float32)
-            for prefix, off, cout in layout:
-                row[:, off:off + cout] = np.asarray(drop_masks[prefix], dtype=np.float32)
-            dmask = native.DeviceBuffer.from_array(row, dev)
-        native.check(L.cm_unet_forward_train(h, dfut.ptr, dt.ptr, dpst.ptr, dmask.ptr if dmask else None,
-                                             float(self.cfg.dropout_rate), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                             int(sample_id_base), dout.ptr, B, None))
-        native.check(L.cm_device_synchronize(dev))
-        return dout.download(fut.shape)
+        B, Cc, H, W, F = np.shape(future)
+        h = self.ensure(H, W, np.shape(past)[4], F, B)
+        dout = native.DeviceBuffer(4 * B * Cc * H * W * F, self.device)
+        mask = self._mask_rows(B, drop_masks) if drop_masks is not None else None
+        with self._staged([(future, np.float32), (t, np.int64), (past, np.float32), (mask, np.float32)], B) as (dfut, dt, dpst, dmask):
+            native.check(L.cm_unet_forward_train(h, dfut, dt, dpst, dmask, float(self.cfg.dropout_rate),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_id_base), dout.ptr, B, None))
+            native.check(L.cm_device_synchronize(self.device))
+        return dout.download((B, Cc, H, W, F))
 
     # -- training step (ddpm.py:111-121,142-144) -------------------------------------
     def train_init(self, lr=5e-5, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.003, autocast=False, loss_scale_log2=-1):
@@ -271,10 +186,13 @@ class UNet:
         fp32.  The loss gradient is scaled by 2^loss_scale_log2 inside the step (< 0: automatic, the largest power of two
         <= B*C*H*W*F) and the gradients are unscaled before anything reads them.  Governs train_step, train_step_xt and
         forward_train; the eval forward and the sampling loop are untouched."""
+        native.check(native.lib().cm_train_set_autocast(self._train_handle(), 1 if on else 0, int(loss_scale_log2)))
+        self._autocast = (bool(on), int(loss_scale_log2) if on else -1)
+
+    def _train_handle(self):
         if not getattr(self, "_train_ready", False):
             raise RuntimeError("train_init() has not been called")
-        native.check(native.lib().cm_train_set_autocast(self._handle, 1 if on else 0, int(loss_scale_log2)))
-        self._autocast = (bool(on), int(loss_scale_log2) if on else -1)
+        return self._handle
 
     @property
     def autocast(self):
@@ -286,7 +204,7 @@ class UNet:
         return (bool(mode.value), int(k.value))
 
     def set_lr(self, lr: float):
-        native.check(native.lib().cm_train_set_lr(self._handle, float(lr)))
+        super().set_lr(lr)
         self._train_hparams["lr"] = float(lr)
 
     def set_sample_base(self, sample_id_base: int):
@@ -303,73 +221,33 @@ class UNet:
             row[:, off:off + cout] = np.asarray(drop_masks[prefix], dtype=np.float32)
         return row
 
+    def _step_batch(self, t, drop_masks):
+        """(B, the mask row) of a training step: `drop_masks` as forward_train takes it, or the [B, width] row itself."""
+        B = int(t.nbytes // 8) if isinstance(t, native.DeviceBuffer) else int(np.asarray(t).size)
+        return B, self._mask_rows(B, drop_masks) if isinstance(drop_masks, dict) else drop_masks
+
     def train_step(self, schedule_handle, future, past, t, eps, drop_masks=None, seed: int = 0,
                    apply_update: bool = True) -> float:
         """q-sample + train-mode forward + MSE + backward (+ Adam) on the device; returns the loss.
-        Inputs are numpy arrays (host staging) or native.DeviceBuffer objects already in HBM."""
-        L = native.lib()
-        dev = self.device
-
-        def dbuf(a, dtype):
-            if isinstance(a, native.DeviceBuffer):
-                return a
-            return native.DeviceBuffer.from_array(np.ascontiguousarray(a, dtype=dtype), dev)
-
-        B = int(t.nbytes // 8) if isinstance(t, native.DeviceBuffer) else int(np.asarray(t).size)
-        if not getattr(self, "_train_ready", False):
-            raise RuntimeError("train_init() has not been called")
-        dfut, dpst = dbuf(future, np.float32), dbuf(past, np.float32)
-        deps = dbuf(eps, np.float32) if eps is not None else None  # None: drawn on the device
-        dt = dbuf(t, np.int64)
-        dmask = None
-        if drop_masks is not None:
-            dmask = dbuf(self._mask_rows(B, drop_masks) if isinstance(drop_masks, dict) else drop_masks, np.float32)
-        loss = C.c_float()
-        native.check(L.cm_train_step(self._handle, schedule_handle, dfut.ptr, dpst.ptr, dt.ptr,
-                                     deps.ptr if deps else None,
-                                     dmask.ptr if dmask else None, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(loss), B,
-                                     1 if apply_update else 0, None))
+        Inputs are numpy arrays (host staging) or native.DeviceBuffer objects already in HBM; eps=None is drawn on the device."""
+        h, loss = self._train_handle(), C.c_float()
+        B, mask = self._step_batch(t, drop_masks)
+        with self._staged([(future, np.float32), (past, np.float32), (t, np.int64), (eps, np.float32), (mask, np.float32)],
+                          B) as (dfut, dpst, dt, deps, dmask):
+            native.check(self._fn("step")(h, schedule_handle, dfut, dpst, dt, deps, dmask, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          C.byref(loss), B, 1 if apply_update else 0, None))
         return float(loss.value)
 
     def train_step_xt(self, xt, past, t, target, drop_masks=None, seed: int = 0, apply_update: bool = True) -> float:
         """The training step with the caller's noised input and regression target (flow matching):
         loss = mse(UNet_train(xt, t, past), target); backward; Adam."""
-        L = native.lib()
-        dev = self.device
-
-        def dbuf(a, dtype):
-            if isinstance(a, native.DeviceBuffer):
-                return a
-            return native.DeviceBuffer.from_array(np.ascontiguousarray(a, dtype=dtype), dev)
-
-        B = int(t.nbytes // 8) if isinstance(t, native.DeviceBuffer) else int(np.asarray(t).size)
-        if not getattr(self, "_train_ready", False):
-            raise RuntimeError("train_init() has not been called")
-        dxt, dpst, dtg, dt = dbuf(xt, np.float32), dbuf(past, np.float32), dbuf(target, np.float32), dbuf(t, np.int64)
-        dmask = None
-        if drop_masks is not None:
-            dmask = dbuf(self._mask_rows(B, drop_masks) if isinstance(drop_masks, dict) else drop_masks, np.float32)
-        loss = C.c_float()
-        native.check(L.cm_train_step_xt(self._handle, dxt.ptr, dpst.ptr, dt.ptr, dtg.ptr, dmask.ptr if dmask else None,
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(loss), B, 1 if apply_update else 0, None))
+        h, loss = self._train_handle(), C.c_float()
+        B, mask = self._step_batch(t, drop_masks)
+        with self._staged([(xt, np.float32), (past, np.float32), (t, np.int64), (target, np.float32), (mask, np.float32)],
+                          B) as (dxt, dpst, dt, dtg, dmask):
+            native.check(self._fn("step_xt")(h, dxt, dpst, dt, dtg, dmask, int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(loss), B,
+                                             1 if apply_update else 0, None))
         return float(loss.value)
-
-    def grad(self, name: str) -> np.ndarray:
-        """Gradient of a state_dict tensor after the last train_step (reference layout)."""
-        shape = self._params[name].shape
-        out = np.empty(shape, dtype=np.float32)
-        native.check(native.lib().cm_train_get_grad(self._handle, name.encode(), out.ctypes.data, out.size))
-        return out
-
-    def flat_grads(self):
-        """(device pointer, numel) of the flat fp32 gradient buffer in state_dict order (data-parallel
-        all-reduce between train_step(apply_update=False) and apply_update())."""
-        ptr, n = C.c_void_p(), C.c_int64()
-        native.check(native.lib().cm_train_flat_grads(self._handle, C.byref(ptr), C.byref(n)))
-        return ptr.value, int(n.value)
-
-    def apply_update(self):
-        native.check(native.lib().cm_train_apply(self._handle, None))
 
     def trainable_names(self):
         """Names in model.parameters() order; index 0 (the frozen sinusoid table) carries no Adam state."""
@@ -378,37 +256,16 @@ class UNet:
     def optimizer_state_dict(self, lr: float, betas, eps: float, weight_decay: float):
         """torch.optim.Adam.state_dict() of the reference optimizer (ddpm.py:53-56): what
         save_checkpoint stores under "opt" (utils/utils.py:140-147)."""
-        L = native.lib()
-        step = C.c_int32()
-        native.check(L.cm_train_opt_step(self._handle, C.byref(step), 0))
-        names = self.trainable_names()
-
-        def get(name, which):
-            out = np.empty(self._params[name].shape, np.float32)
-            native.check(L.cm_train_get_opt_state(self._handle, name.encode(), which, out.ctypes.data, out.size))
-            return out
-
-        # names[0], the sinusoid table, has requires_grad=False: the optimizer never created state for it
-        return optim_state.dump(names, names[:1], optim_state.ADAM_KEYS, lr, betas, eps, weight_decay, get, step.value)
+        # the sinusoid table has requires_grad=False: the optimizer never created state for it
+        return self._dump_opt(self.trainable_names()[:1], optim_state.ADAM_KEYS, lr, betas, eps, weight_decay)
 
     def load_optimizer_state_dict(self, opt: dict):
         """Inverse of optimizer_state_dict (resume from a checkpoint's "opt" entry)."""
-        L = native.lib()
-
-        def put(name, which, arr):
-            native.check(L.cm_train_set_opt_state(self._handle, name.encode(), which, arr.ctypes.data, arr.size))
-
-        cs = C.c_int32(optim_state.load(opt, self.trainable_names(), optim_state.ADAM_KEYS, put))
-        native.check(L.cm_train_opt_step(self._handle, C.byref(cs), 1))
+        self._load_opt(opt, optim_state.ADAM_KEYS)
 
     def sync_trained(self):
         """Pull the trained master weights back into state_dict()."""
-        L = native.lib()
-        native.check(L.cm_train_sync(self._handle))
-        for name, arr in self._params.items():
-            out = np.empty(arr.shape, dtype=np.float32)
-            native.check(L.cm_model_get_param(self._handle, name.encode(), out.ctypes.data, out.size))
-            self._params[name] = out
+        self._pull_trained()
 
     def mse_loss(self, pred, target) -> float:
         """F.mse_loss(pred, target) on the device (ddpm.py:120)."""
