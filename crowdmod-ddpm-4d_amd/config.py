@@ -147,8 +147,9 @@ def resolve_convrnn(cfg) -> ConvRNNKeys:
 
 
 def train_autocast(train) -> bool:
-    """MODEL.<DDPM|FM>.UNET.TRAIN.AUTOCAST of a resolved TRAIN node (Resolved.train): the UNet's training step on f16
-    matrix-core operands in its Winograd layers (the reference's torch.amp.autocast, ddpm.py:116-120).  Absent = False."""
+    """TRAIN.AUTOCAST of a resolved TRAIN node (Resolved.train: MODEL.DDPM.UNET.TRAIN or MODEL.DDPM.DIT.TRAIN): the DDPM
+    training step on f16 matrix-core operands -- the UNet's Winograd layers, the DiT4D_V4 blocks' token Linears (the
+    reference's torch.amp.autocast, ddpm.py:116-120).  Absent = False.  The FM drivers train in fp32 and do not read it."""
     if train is None or not hasattr(train, "get"):
         return False
     v = train.get("AUTOCAST", False)

@@ -9,6 +9,9 @@
 //                     (conditioning tables), exact-erf GELU, gated residual, patch embedding + both position
 //                     embeddings, and the unpatchify scatter of the final linear into eps_cl.  A row subset (the
 //                     temporal queries, the future slots of the final layer) maps logical GEMM rows to token rows.
+//   dit_gemm_f16_kernel  its sibling on v_mfma_f32_32x32x16_f16 for the blocks' token Linears of an autocast TRAINING step
+//                     (cm_dit4d_train_set_autocast): operands rounded to f16 when staged, fp32 accumulation and output.  The eval
+//                     forward never takes it.
 //   dit_attn_*        softmax(q k^T / 8) v per head (head dim 64) on the vector ALUs: spatial self-attention over the
 //                     N_s tokens of one (sample, slot), temporal cross-attention of the future slots of one (sample,
 //                     patch) over all T_p slots.
@@ -18,6 +21,7 @@
 // chain; fixed butterfly reductions), no atomics, and a sample only reads its own rows -- a chain's result does not
 // depend on the batch it runs in, the batch lane, or graph replay.
 #include "cm_kernels.h"
+#include "cm_dit_f16.h"
 
 #include <math.h>
 
@@ -43,6 +47,47 @@ __device__ __forceinline__ long long phys_row(const DitGemmArgs &a, long long r)
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 
+// LayerNorm statistics of the 64 token rows of the tile at m0 (K = D, the whole row), and each row's conditioning row: wave w
+// owns rows 16w .. 16w + 15.  Shared by dit_gemm_kernel and dit_gemm_f16_kernel, so both normalise with the same bits.
+__device__ __forceinline__ void ln_tile_stats(const DitGemmArgs &a, long long m0, int lane, int wave, float *s_mu, float *s_rs,
+                                              const float **s_mod) {
+  // Eight rows at a time, so that eight independent loads are in flight per k step instead of one: each row's sums keep their
+  // order (k ascending per lane, then the butterfly), so the statistics are the bits of the one-row-at-a-time loop.  A row past M
+  // reads row M - 1 and is discarded.
+  constexpr int R = 8;
+  for (int r0 = wave * 16; r0 < wave * 16 + 16; r0 += R) {
+    const float *x[R];
+    long long pr[R];
+    float s[R], q[R], mu[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      pr[j] = phys_row(a, min(m0 + r0 + j, a.M - 1));
+      x[j] = a.A + pr[j] * a.lda;
+      s[j] = q[j] = 0.f;
+    }
+    for (int k = lane; k < a.K; k += 64) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) s[j] += x[j][k];
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) mu[j] = wave_sum(s[j]) / (float)a.K;
+    for (int k = lane; k < a.K; k += 64) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) { const float d = x[j][k] - mu[j]; q[j] += d * d; }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const bool ok = m0 + r0 + j < a.M;
+      const float rs = 1.0f / sqrtf(wave_sum(q[j]) / (float)a.K + 1e-6f);
+      if (lane == 0) {
+        s_mu[r0 + j] = ok ? mu[j] : 0.f;
+        s_rs[r0 + j] = ok ? rs : 0.f;
+        s_mod[r0 + j] = ok ? a.mod + a.tbuf[pr[j] / a.tok] * (long long)a.ldmod : nullptr;
+      }
+    }
+  }
+}
+
 template <int PRO, int EPI>
 __global__ __launch_bounds__(256) void dit_gemm_kernel(const DitGemmArgs a) {
   __shared__ float As[GB * GS], Ws[GB * GS];
@@ -53,24 +98,7 @@ __global__ __launch_bounds__(256) void dit_gemm_kernel(const DitGemmArgs a) {
   const int n0 = blockIdx.y * GB;
 
   if (PRO == DIT_PRO_LN) {
-    // row statistics of the tile's 64 token rows (K = D, the whole row): wave w owns rows 16w .. 16w + 15
-    for (int rr = wave * 16; rr < wave * 16 + 16; ++rr) {
-      const long long r = m0 + rr;
-      float mu = 0.f, rs = 0.f;
-      const float *mrow = nullptr;
-      if (r < a.M) {
-        const long long pr = phys_row(a, r);
-        const float *x = a.A + pr * a.lda;
-        float s = 0.f;
-        for (int k = lane; k < a.K; k += 64) s += x[k];
-        mu = wave_sum(s) / (float)a.K;
-        float q = 0.f;
-        for (int k = lane; k < a.K; k += 64) { const float d = x[k] - mu; q += d * d; }
-        rs = 1.0f / sqrtf(wave_sum(q) / (float)a.K + 1e-6f);
-        mrow = a.mod + a.tbuf[pr / a.tok] * (long long)a.ldmod;
-      }
-      if (lane == 0) { s_mu[rr] = mu; s_rs[rr] = rs; s_mod[rr] = mrow; }
-    }
+    ln_tile_stats(a, m0, lane, wave, s_mu, s_rs, s_mod);
     __syncthreads();
   }
 
@@ -150,6 +178,91 @@ __global__ __launch_bounds__(256) void dit_gemm_kernel(const DitGemmArgs a) {
       const int fr = tp * pt + it, y = hp * p + ih, x = wp * p + iw;
       a.Y[((((b * a.L) + fr) * a.Hh + y) * a.Ww + x) * 8 + c] = v;
     }
+  }
+}
+
+// The f16-operand sibling of dit_gemm_kernel for the token Linears of an autocast training step (DitGemmArgs::f16): the same
+// 64 x 64 tile, row-subset addressing and LayerNorm statistics; the A operand is the fp32 value dit_gemm_kernel would stage
+// (LayerNorm + modulate in fp32, where torch's autocast casts it) and W the fp32 master weight, both rounded to f16 when staged.
+// Layout, rounding and the bank arithmetic: cm_dit_f16.h.  Staging: thread -> row tid >> 3 (and + 32), k group 8 (tid & 7).
+// Edges as dit_gemm_kernel: rows >= M, columns >= N and k >= K are staged as zeros.
+template <int PRO, int EPI>
+__global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) {
+  static_assert((PRO == DIT_PRO_NONE || PRO == DIT_PRO_LN) && EPI == DIT_EPI_BIAS, "token Linears of the training step only");
+  __shared__ __attribute__((aligned(16))) _Float16 As[GB * DH_S], Ws[GB * DH_S];
+  __shared__ float s_mu[GB], s_rs[GB];
+  __shared__ const float *s_mod[GB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * GB;
+  const int n0 = blockIdx.y * GB;
+
+  if (PRO == DIT_PRO_LN) {
+    ln_tile_stats(a, m0, lane, wave, s_mu, s_rs, s_mod);
+    __syncthreads();
+  }
+
+  dit_f32x16 acc;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int sr = tid >> 3, sk = (tid & 7) * 8;
+  const float *arow[2], *wrow[2], *mrow[2];
+  float mu[2], rs[2];
+  for (int h = 0; h < 2; ++h) {
+    const long long r = m0 + sr + 32 * h;
+    const int n = n0 + sr + 32 * h;
+    arow[h] = r < a.M ? a.A + (a.a_compact ? r : phys_row(a, r)) * a.lda : nullptr;
+    wrow[h] = n < a.N ? a.W + (long long)n * a.K : nullptr;
+    mrow[h] = PRO == DIT_PRO_LN ? s_mod[sr + 32 * h] : nullptr;
+    mu[h] = PRO == DIT_PRO_LN ? s_mu[sr + 32 * h] : 0.f;
+    rs[h] = PRO == DIT_PRO_LN ? s_rs[sr + 32 * h] : 0.f;
+  }
+  // the chunk in flight: raw fp32 values in registers, fetched one chunk ahead so that the global loads run under the matrix
+  // instructions of the chunk before; the prologue arithmetic and the rounding happen when they are stored to LDS
+  float v[2][8], w[2][8], sc[2][8], sh[2][8];
+  auto fetch = [&](int k) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[h][e] = w[h][e] = sc[h][e] = sh[h][e] = 0.f;
+      if (arow[h]) {
+        dh_load8(arow[h], k, a.K, v[h]);
+        if (PRO == DIT_PRO_LN) {
+          dh_load8(mrow[h] + a.off_scale, k, a.K, sc[h]);
+          dh_load8(mrow[h] + a.off_shift, k, a.K, sh[h]);
+        }
+      }
+      if (wrow[h]) dh_load8(wrow[h], k, a.K, w[h]);
+    }
+  };
+  fetch(sk);
+  for (int k0 = 0; k0 < a.K; k0 += DH_K) {
+    const int k = k0 + sk;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      if (PRO == DIT_PRO_LN && arow[h]) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float xn = (v[h][e] - mu[h]) * rs[h];
+          v[h][e] = k + e < a.K ? xn * (1.0f + sc[h][e]) + sh[h][e] : 0.f;   // modulate, DiT4D_V4.py:101-103
+        }
+      }
+      *(dit_f16x8 *)(As + (sr + 32 * h) * DH_S + sk) = dh_round8(v[h]);
+      *(dit_f16x8 *)(Ws + (sr + 32 * h) * DH_S + sk) = dh_round8(w[h]);
+    }
+    __syncthreads();
+    if (k0 + DH_K < a.K) fetch(k + DH_K);
+    acc = dh_mfma_chunk(As + (wm * 32 + (lane & 31)) * DH_S + 8 * (lane >> 5), Ws + (wn * 32 + (lane & 31)) * DH_S + 8 * (lane >> 5), acc);
+    __syncthreads();
+  }
+
+  const int col = n0 + wn * 32 + (lane & 31);
+  if (col >= a.N) return;
+  const float bias = a.bias ? a.bias[col] : 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const long long rl = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
+    if (rl >= a.M) continue;
+    a.Y[phys_row(a, rl) * a.ldy + col] = acc[i] + bias;
   }
 }
 
@@ -338,6 +451,13 @@ __global__ __launch_bounds__(64) void dit_attn_full_kernel(const DitAttnArgs a) 
 hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st) {
   if (a.M <= 0) return hipSuccess;
   dim3 grid((unsigned)((a.M + GB - 1) / GB), (unsigned)((a.N + GB - 1) / GB));
+  if (a.f16) {   // a missing f16 form is an error, never the fp32 kernel
+    if (a.epi != DIT_EPI_BIAS) return hipErrorInvalidValue;
+    if (a.pro == DIT_PRO_NONE) hipLaunchKernelGGL((dit_gemm_f16_kernel<DIT_PRO_NONE, DIT_EPI_BIAS>), grid, dim3(256), 0, st, a);
+    else if (a.pro == DIT_PRO_LN) hipLaunchKernelGGL((dit_gemm_f16_kernel<DIT_PRO_LN, DIT_EPI_BIAS>), grid, dim3(256), 0, st, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+  }
 #define CM_DIT_G(P, E) \
   if (a.pro == P && a.epi == E) { hipLaunchKernelGGL((dit_gemm_kernel<P, E>), grid, dim3(256), 0, st, a); return hipGetLastError(); }
   CM_DIT_G(DIT_PRO_NONE, DIT_EPI_BIAS)

@@ -1,7 +1,8 @@
 // Training step of the DiT4D_V4 denoiser (arch "DDPM-DiT"), included by cm_dit_train_host.inc at the end of cm_model.cpp.  Mirrors
 // DDPM_model._train_step (models/diffusion/ddpm.py:111-154) below the host driver: eps_hat = DiT4D_V4(x_t, t, past) in train mode
 // (models/backbones/DiT4D_V4.py:106-204, 347-375), loss = mse(eps_hat, eps), backward, torch.optim.Adam with coupled L2; fp32
-// throughout.  Kernels: cm_dit4d_train.hip, cm_dit_train.hip, cm_dit.hip.
+// unless cm_dit4d_train_set_autocast puts the blocks' six token Linears on f16 operands (the reference's torch.amp.autocast,
+// ddpm.py:116-120).  Kernels: cm_dit4d_train.hip, cm_dit_train.hip, cm_dit.hip.
 //
 // The state (cm_dit_train), the OptStore with the sinusoid table frozen, the conditioning chain (9 depth + 2 chunks), the final
 // layer, the MLP half, the patch / position embeddings and the entry-point bodies are cm_dit_train_host.inc's.  What is here is
@@ -31,6 +32,12 @@ int ditt4_forward(cm_model *m, int B, uint64_t seed, hipStream_t st) {
     a.pro = pro; a.epi = epi; a.M = rows; a.N = N; a.K = K; a.grp = (int)rows;
     return a;
   };
+  // a token Linear of a block (bias epilogue): the one place the forward picks the f16-operand form of an autocast step
+  auto linear = [&](int pro, long long rows, int N, int K) {
+    cm::DitGemmArgs a = gemm(pro, cm::DIT_EPI_BIAS, rows, N, K);
+    a.f16 = T->autocast;
+    return a;
+  };
   cm::DitDrop dr{seed, T->sample_base, T->opt.step, 0, T->dropout, 1};
   cm::DitGemmArgs a = gemm(cm::DIT_PRO_PATCH, cm::DIT_EPI_PATCH, M, D, d.Kp);
   a.x8 = m->x8; a.W = W(9); a.bias = W(10); a.Y = T->Xs[0]; a.ldy = D; a.spos = W(0); a.tpos = W(1);
@@ -40,33 +47,33 @@ int ditt4_forward(cm_model *m, int B, uint64_t seed, hipStream_t st) {
     dr.block = i;
     float *Xin = T->Xs[3 * i], *Xsp = T->Xs[3 * i + 1], *Xtm = T->Xs[3 * i + 2], *Xout = T->Xs[3 * i + 3];
     // spatial self-attention per (sample, slot) (DiT4D_V4.py:160-169)
-    a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
+    a = linear(cm::DIT_PRO_LN, M, D3, D);
     a.A = Xin; a.lda = D; a.W = W(w0); a.bias = W(w0 + 1); a.Y = T->QKV[i]; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     cm::DitDrop ds = dr;
     ds.gps = d.Tp;
     cm::DitTrAttnArgs at{T->QKV[i], T->AO[i], T->LSE[i], nullptr, nullptr, nullptr, B * d.Tp, d.Ns, D, c.num_heads, ds};
     CM_HIP(cm::launch_ditt_attn_fwd(at, st));
-    a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, M, D, D);
+    a = linear(cm::DIT_PRO_NONE, M, D, D);
     a.A = T->AO[i]; a.lda = D; a.W = W(w0 + 2); a.bias = W(w0 + 3); a.Y = T->Yo[i]; a.ldy = D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     CM_HIP(cm::launch_ditt_gate(Xin, Xsp, T->Yo[i], nullptr, T->mod, d.ldmod, mo + 2 * D, M, D, d.tok, cm::DITT_SITE_NONE, dr, st));
     // temporal cross-attention per (sample, patch): keys / values every slot, queries and the residual the slots >= qs (:173-198)
-    a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
+    a = linear(cm::DIT_PRO_LN, M, D3, D);
     a.A = Xsp; a.lda = D; a.W = W(w0 + 4); a.bias = W(w0 + 5); a.Y = T->QKVt[i]; a.ldy = D3; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     cm::DitTrTAttnArgs tt{T->QKVt[i], T->AOt[i], T->LSEt[i], nullptr, nullptr, B, d.Tp, d.Ns, d.qs, D, c.num_heads, dr};
     CM_HIP(cm::launch_ditt4_tattn_fwd(tt, st));
-    a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, Mf, D, D);
+    a = linear(cm::DIT_PRO_NONE, Mf, D, D);
     a.A = T->AOt[i]; a.lda = D; a.W = W(w0 + 6); a.bias = W(w0 + 7); a.Y = T->Yot[i]; a.ldy = D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     CM_HIP(cm::launch_ditt4_gate_rows(Xsp, Xtm, T->Yot[i], nullptr, nullptr, T->mod, d.ldmod, mo + 5 * D, B, d.tok, d.qs * d.Ns, D, st));
     // MLP (:201-202)
-    a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, mlp, D);
+    a = linear(cm::DIT_PRO_LN, M, mlp, D);
     a.A = Xtm; a.lda = D; a.W = W(w0 + 8); a.bias = W(w0 + 9); a.Y = T->H1[i]; a.ldy = mlp; a.off_shift = mo + 6 * D; a.off_scale = mo + 7 * D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->Hm, M, mlp, d.tok, dr, 0, st));
-    a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_BIAS, M, D, mlp);
+    a = linear(cm::DIT_PRO_NONE, M, D, mlp);
     a.A = T->Hm; a.lda = mlp; a.W = W(w0 + 10); a.bias = W(w0 + 11); a.Y = T->Y2[i]; a.ldy = D;
     CM_HIP(cm::launch_dit_gemm(a, st));
     CM_HIP(cm::launch_ditt_gate(Xtm, Xout, T->Y2[i], nullptr, T->mod, d.ldmod, mo + 8 * D, M, D, d.tok, cm::DITT_SITE_MLP2, dr, st));
@@ -92,9 +99,9 @@ int ditt4_bwd_temporal(DittBwd &o, int i, const float *Xsp, int w, int mo) {
   CM_HIP(cm::launch_ditt_segsum_rows(T->dX + (size_t)row0 * D, D, d.tok, T->Yot[i], D, (long long)nq * d.Ns, T->dmod + mo + 2 * D, d.ldmod,
                                      B, (long long)nq * d.Ns, D, st));
   CM_HIP(cm::launch_ditt4_gate_rows(nullptr, nullptr, nullptr, T->G1, T->dX, T->mod, d.ldmod, mo + 2 * D, B, d.tok, row0, D, st));
-  CM_HIP(o.gemm_dw(T->G1, D, T->AOt[i], D, o.G(w + 2), Mf, D, D));
+  CM_HIP(o.gemm_dw(T->G1, D, T->AOt[i], D, o.G(w + 2), Mf, D, D, true));
   CM_HIP(o.colsum(T->G1, D, o.G(w + 3), Mf, D));
-  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->G2, Mf, D, D, 0));
+  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->G2, Mf, D, D, 0, true));
   cm::DitTrTAttnArgs tt{T->QKVt[i], nullptr, T->LSEt[i], T->G2, T->G3, B, d.Tp, d.Ns, d.qs, D, d.cfg.num_heads, o.dr};
   CM_HIP(cm::launch_ditt4_tattn_bwd(tt, st));
   return ditt_bwd_ln_linear(o, Xsp, T->G3, 3 * D, w, mo, T->G1);
@@ -113,7 +120,21 @@ int ditt4_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hip
     if (ditt4_bwd_temporal(o, i, T->Xs[3 * i + 1], w0 + 4, mo + 3 * D)) return 1;
     if (ditt_bwd_attn(o, i, T->Xs[3 * i], w0, mo, B * d.Tp, d.Ns)) return 1;
   }
-  return ditt_bwd_tail(o);
+  if (ditt_bwd_tail(o)) return 1;
+  // autocast: every gradient above carries the loss scale 2^k exactly (fp32 tensors); take it out once, so that the readers of the
+  // flat buffer (cm_dit4d_train_get_grad, flat_grads and the all-reduce, Adam, checkpoints) see unscaled gradients
+  if (T->ls_k > 0) CM_HIP(cm::launch_scale_inplace(T->opt.g, (long long)T->opt.nfloats, ldexpf(1.f, -T->ls_k), st));
+  return 0;
+}
+
+// the requested exponent, or the largest k with 2^k <= B*C*H*W*F (loss gradient O(1)): a function of B alone
+int ditt4_scale_log2(const cm_model *m, int B) {
+  const cm_dit_train *T = m->dit->train;
+  if (T->ls_req >= 0) return T->ls_req;
+  const long long N = (long long)B * m->per_sample();
+  int k = 0;
+  while (k < 24 && (2LL << k) <= N) ++k;
+  return k;
 }
 
 }  // namespace
@@ -127,6 +148,28 @@ int cm_dit4d_train_init(cm_model *m, float lr, float beta1, float beta2, float e
 int cm_dit4d_train_set_lr(cm_model *m, float lr) {
   if (ditt_check(m, "cm_dit4d_train_set_lr", true, true)) return 1;
   m->dit->train->opt.lr = lr;
+  return 0;
+}
+
+// The reference wraps DDPM_model._train_step in torch.amp.autocast without a GradScaler (ddpm.py:116-120), whatever the denoiser.
+// The fp32 master weights are read and rounded while staging, so no f16 copy exists that an update, cm_dit4d_train_set_opt_state,
+// a loaded checkpoint or cm_dit4d_train_sync could leave stale.
+int cm_dit4d_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2) {
+  if (ditt_check(m, "cm_dit4d_train_set_autocast", true, true)) return 1;
+  if (mode != 0 && mode != 1) return fail("cm_dit4d_train_set_autocast: mode %d: 0 = fp32 step, 1 = autocast", (int)mode);
+  if (loss_scale_log2 > 24) return fail("cm_dit4d_train_set_autocast: loss_scale_log2 %d above 24", (int)loss_scale_log2);
+  cm_dit_train *T = m->dit->train;
+  T->autocast = mode; T->ls_req = mode ? (int)loss_scale_log2 : -1;
+  if (T->ls_req < 0) T->ls_req = -1;
+  return 0;
+}
+
+int cm_dit4d_train_get_autocast(const cm_model *m, int32_t *mode, int32_t *loss_scale_log2) {
+  if (ditt_check(m, "cm_dit4d_train_get_autocast", true, true)) return 1;
+  if (!mode || !loss_scale_log2) return fail("cm_dit4d_train_get_autocast: null argument");
+  const cm_dit_train *T = m->dit->train;
+  *mode = T->autocast;
+  *loss_scale_log2 = T->autocast ? ditt4_scale_log2(m, T->ls_last_B > 0 ? T->ls_last_B : m->cfg.max_batch) : 0;
   return 0;
 }
 

@@ -4,6 +4,8 @@
 // What is here: the train-mode attention (log-sum-exp kept, probabilities dropped), its two-pass backward, the backward
 // GEMM (dX = dY W and dW = dY^T A, both on v_mfma_f32_32x32x2_f32: exact fp32 products, so the error budget is summation order),
 // and the element-wise / reduction kernels between them (LayerNorm + modulate, GELU, gates, SiLU, gathers, column sums).
+// ditt_gemm_f16_kernel is the backward GEMM's sibling on v_mfma_f32_32x32x16_f16 for the token Linears of a DiT4D_V4 step under
+// autocast (cm_dit4d_train_set_autocast): f16 operands, the same fp32 partials and reduce; DiT2D never takes it.
 // Determinism as in cm_dit.hip: one writer per element, fixed summation order, no atomics; sums over the B * S rows are either
 // one thread's fixed-order chain (segsum, float64) or fixed k ranges written as partials and added in ascending order (GEMM).
 //
@@ -15,6 +17,7 @@
 // attention runs the kernels below per (sample, slot) group and draws at the group's place in its sample (DitDrop::gps).  Bit 31 of the fourth counter word keeps these draws apart from the
 // Dropout3d masks (0xD120) and from philox_normal ((sample >> 32) ^ 0x5eed < 2^31).
 #include "cm_kernels.h"
+#include "cm_dit_f16.h"
 
 #include <math.h>
 
@@ -74,6 +77,92 @@ __global__ __launch_bounds__(256) void ditt_gemm_kernel(const DitTrGemmArgs a) {
     const float *bp = Bs + (wn * 32 + (lane & 31)) * GS + (lane >> 5);
 #pragma unroll
     for (int kk = 0; kk < GK; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ap[kk], bp[kk], acc, 0, 0, 0);
+    __syncthreads();
+  }
+  const int col = n0 + wn * 32 + (lane & 31);
+  if (col >= a.N) return;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const long long rl = m0 + wm * 32 + acc_row(i, lane >> 5);
+    if (rl >= a.M) continue;
+    if (a.nsplit > 1) {
+      a.part[((long long)z * a.M + rl) * a.N + col] = acc[i];
+    } else {
+      float *c = a.C + rl * a.ldc + col;
+      *c = a.accum ? *c + acc[i] : acc[i];
+    }
+  }
+}
+
+// Two adjacent columns c, c + 1 of eight consecutive k rows of the row-major matrix P [k][ld]: x = column c, y = column c + 1,
+// element j = row k + j; zeros at and past kend / cmax.
+__device__ __forceinline__ void dh_load_t8(const float *__restrict__ P, int ld, long long k, long long kend, long long c, long long cmax,
+                                           float x[8], float y[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    x[j] = y[j] = 0.f;
+    if (k + j < kend && c < cmax) {
+      const float *q = P + (k + j) * ld + c;
+      if (c + 1 < cmax && (((uintptr_t)q) & 7) == 0) {
+        const float2 t = *(const float2 *)q;
+        x[j] = t.x; y[j] = t.y;
+      } else {
+        x[j] = q[0];
+        if (c + 1 < cmax) y[j] = q[1];
+      }
+    }
+  }
+}
+
+// The f16-operand sibling of ditt_gemm_kernel for the token Linears of an autocast training step (DitTrGemmArgs::f16): the same
+// arguments, tile, k ranges and fp32 partials; dY, W and the saved A operand are rounded to f16 when staged (cm_dit_f16.h), and a
+// k past the range's end is staged as zero (wgrad's K is a row count, a multiple of nothing).
+// The instruction wants k contiguous per lane, but the contraction index is the slow index of W in dX = dY W and of both operands
+// in dW = dY^T A.  Transposing staging: thread -> column pair 2 np, 2 np + 1 (np = tid & 31) and k group 8 (tid >> 5); it reads the
+// pair as one 8-byte load from each of its eight k rows (a wave reads 256 contiguous bytes of two k rows per instruction), so it
+// holds eight consecutive k of two columns and stores each as one 16-byte ds_write_b128 into the [column][k] image.  A store is
+// served in groups of 8 consecutive lanes; lanes np & 4 store their odd column first and the others their even one, so the 8 rows
+// of a group are 16 g + {0, 2, 4, 6, 9, 11, 13, 15} (then {1, 3, 5, 7, 8, 10, 12, 14}): distinct mod 8, conflict-free at 144-byte rows.
+template <int TA>
+__global__ __launch_bounds__(256) void ditt_gemm_f16_kernel(const DitTrGemmArgs a) {
+  __shared__ __attribute__((aligned(16))) _Float16 As[GB * DH_S], Bs[GB * DH_S];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * GB;
+  const int n0 = blockIdx.y * GB, z = blockIdx.z;
+  const long long kbeg = (long long)z * a.kchunk, kend = min(a.K, kbeg + a.kchunk);
+  ditt_f32x16 acc;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  const int wm = wave & 1, wn = wave >> 1;
+  const int np = tid & 31, tk = (tid >> 5) * 8, odd = (np >> 2) & 1;   // transposing staging
+  const int sr = tid >> 3, sk = (tid & 7) * 8;                          // staging along k: rows sr and sr + 32, eight k
+  // the chunk in flight: raw fp32 values in registers, fetched one chunk ahead so that the global loads run under the matrix
+  // instructions of the chunk before; they are rounded when they are stored to LDS
+  float ax[8], ay[8], bx[8], by[8];
+  auto fetch = [&](long long k0) {
+    if (TA) {
+      dh_load_t8(a.A, a.lda, k0 + tk, kend, m0 + 2 * np, a.M, ax, ay);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) ax[e] = ay[e] = 0.f;
+      if (m0 + sr < a.M) dh_load8(a.A + (m0 + sr) * a.lda, k0 + sk, kend, ax);
+      if (m0 + sr + 32 < a.M) dh_load8(a.A + (m0 + sr + 32) * a.lda, k0 + sk, kend, ay);
+    }
+    dh_load_t8(a.B, a.ldb, k0 + tk, kend, n0 + 2 * np, a.N, bx, by);
+  };
+  fetch(kbeg);
+  for (long long k0 = kbeg; k0 < kend; k0 += DH_K) {
+    if (TA) {
+      *(dit_f16x8 *)(As + (2 * np + odd) * DH_S + tk) = dh_round8(odd ? ay : ax);
+      *(dit_f16x8 *)(As + (2 * np + 1 - odd) * DH_S + tk) = dh_round8(odd ? ax : ay);
+    } else {
+      *(dit_f16x8 *)(As + sr * DH_S + sk) = dh_round8(ax);
+      *(dit_f16x8 *)(As + (sr + 32) * DH_S + sk) = dh_round8(ay);
+    }
+    *(dit_f16x8 *)(Bs + (2 * np + odd) * DH_S + tk) = dh_round8(odd ? by : bx);
+    *(dit_f16x8 *)(Bs + (2 * np + 1 - odd) * DH_S + tk) = dh_round8(odd ? bx : by);
+    __syncthreads();
+    if (k0 + DH_K < kend) fetch(k0 + DH_K);
+    acc = dh_mfma_chunk(As + (wm * 32 + (lane & 31)) * DH_S + 8 * (lane >> 5), Bs + (wn * 32 + (lane & 31)) * DH_S + 8 * (lane >> 5), acc);
     __syncthreads();
   }
   const int col = n0 + wn * 32 + (lane & 31);
@@ -287,7 +376,7 @@ __global__ __launch_bounds__(256) void ditt_loss_grad_kernel(const DitTrPatchArg
   if (f < 0) { a.dYf[i] = 0.f; return; }
   const long long e = ((((b * a.C + c) * a.Hh + hp * p + ih) * a.Ww + wp * p + iw) * F + f);
   const double n = (double)a.B * a.C * a.Hh * a.Ww * F;
-  a.dYf[i] = (float)(((double)a.pred[e] - (double)a.target[e]) * (2.0 / n));
+  a.dYf[i] = (float)(((double)a.pred[e] - (double)a.target[e]) * ldexp(2.0 / n, a.ls_k));   // autocast: times the loss scale 2^ls_k
 }
 
 // spatial_pos_embed sums over batch and frames, temporal_pos_embed over batch and patches (rows >= T_p are left as they are: 0)
@@ -550,7 +639,9 @@ hipError_t launch_ditt_gemm(const DitTrGemmArgs &a, hipStream_t st) {
   DitTrGemmArgs k = a;
   if (k.nsplit <= 1) { k.nsplit = 1; k.kchunk = ((a.K + GK - 1) / GK) * GK; if (k.kchunk < GK) k.kchunk = GK; }
   dim3 grid((unsigned)((a.M + GB - 1) / GB), (unsigned)((a.N + GB - 1) / GB), (unsigned)k.nsplit);
-  if (a.ta) hipLaunchKernelGGL((ditt_gemm_kernel<1>), grid, dim3(256), 0, st, k);
+  if (a.f16 && a.ta) hipLaunchKernelGGL((ditt_gemm_f16_kernel<1>), grid, dim3(256), 0, st, k);
+  else if (a.f16) hipLaunchKernelGGL((ditt_gemm_f16_kernel<0>), grid, dim3(256), 0, st, k);
+  else if (a.ta) hipLaunchKernelGGL((ditt_gemm_kernel<1>), grid, dim3(256), 0, st, k);
   else hipLaunchKernelGGL((ditt_gemm_kernel<0>), grid, dim3(256), 0, st, k);
   if (k.nsplit > 1) hipLaunchKernelGGL(ditt_gemm_reduce_kernel, dim3(blocks_of((long long)a.M * a.N)), dim3(256), 0, st, k);
   return hipGetLastError();

@@ -33,6 +33,11 @@ struct cm_dit_train {
   float *mse_partial = nullptr, *mse_loss = nullptr;
   float *eps_dev = nullptr, *xt = nullptr;   // cm_dit4d_train_step: the drawn eps and q_sample's x_t [max_batch][C H W F]
   long long draws = 0;                       // eps draws so far (the Philox step word of the next one)
+  // autocast (cm_dit4d_train_set_autocast; DiT4D_V4 only): f16 operands in the blocks' six token Linears, all three passes; the loss
+  // gradient is multiplied by 2^ls_k and the flat gradient buffer by 2^-ls_k at the end of the backward
+  int autocast = 0, ls_req = -1;             // mode; requested scale exponent (< 0: automatic)
+  int ls_k = 0;                              // exponent of the step in flight (0 with the mode off)
+  int ls_last_B = 0;                         // batch of the last autocast step (cm_dit4d_train_get_autocast)
 };
 
 void cm_free_dit_train(cm_dit_train *t) { delete t; }
@@ -59,6 +64,7 @@ int ditt_check(const cm_model *m, const char *what, bool need_train, bool v4 = f
 
 int ditt4_forward(cm_model *m, int B, uint64_t seed, hipStream_t st);                           // cm_dit4d_train_host.inc
 int ditt4_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hipStream_t st);
+int ditt4_scale_log2(const cm_model *m, int B);   // the loss-scale exponent of an autocast step at batch B
 
 int ditt_setup(cm_model *m) {
   cm_dit_plan &d = *m->dit;
@@ -197,14 +203,18 @@ struct DittBwd {
   cm::DitDrop dr{};
   float *W(int i) const { return T->opt.p + T->opt.off[i]; }
   float *G(int i) const { return T->opt.g + T->opt.off[i]; }
+  // `tok`: the product belongs to one of a block's six token Linears, which take the f16-operand kernels in an autocast step
+  // (the one place the backward picks them); the head, the patch embedding and the conditioning chain never pass it
   // dX [rows][Kin] (+)= dY [rows][Nout] W [Nout][Kin]
-  hipError_t gemm_dx(const float *dY, int ldy, const float *Wm, float *dXo, long long rows, int Kin, int Nout, int accum) const {
-    cm::DitTrGemmArgs g{dY, Wm, dXo, (int)rows, Kin, Nout, ldy, Kin, Kin, 0, accum, 1, 0, nullptr};
+  hipError_t gemm_dx(const float *dY, int ldy, const float *Wm, float *dXo, long long rows, int Kin, int Nout, int accum,
+                     bool tok = false) const {
+    cm::DitTrGemmArgs g{dY, Wm, dXo, (int)rows, Kin, Nout, ldy, Kin, Kin, 0, accum, 1, 0, nullptr, tok && T->autocast};
     return cm::launch_ditt_gemm(g, st);
   }
   // dW [Nout][Kin] = dY^T A over `rows` rows, in fixed row ranges
-  hipError_t gemm_dw(const float *dY, int ldy, const float *A, int lda, float *dW, long long rows, int Nout, int Kin) const {
-    cm::DitTrGemmArgs g{dY, A, dW, Nout, Kin, rows, ldy, lda, Kin, 1, 0, 1, 0, nullptr};
+  hipError_t gemm_dw(const float *dY, int ldy, const float *A, int lda, float *dW, long long rows, int Nout, int Kin,
+                     bool tok = false) const {
+    cm::DitTrGemmArgs g{dY, A, dW, Nout, Kin, rows, ldy, lda, Kin, 1, 0, 1, 0, nullptr, tok && T->autocast};
     long long ns = (rows + DITT_KCHUNK - 1) / DITT_KCHUNK;
     if (ns > 1) {
       ns = std::min<long long>(ns, DITT_MAX_SPLIT);
@@ -237,7 +247,7 @@ int ditt_bwd_head(DittBwd &o, const float *d_target, uint64_t seed) {
   pa.dspos = o.G(0); pa.dtpos = o.G(1);
   pa.B = B; pa.C = c.out_channels; pa.L = m->L(); pa.Hh = c.rows; pa.Ww = c.cols; pa.p = c.patch_size; pa.Ns = d.Ns;
   pa.wpn = c.cols / c.patch_size; pa.tok = d.tok; pa.qs = d.qs; pa.Kp = d.Kp; pa.Nout = d.Nout; pa.D = D;
-  pa.pt = c.t_patch_size; pa.P = c.past_len;
+  pa.pt = c.t_patch_size; pa.P = c.past_len; pa.ls_k = T->ls_k;
   CM_HIP(cm::launch_ditt_loss_grad(pa, st));
   const int wf = DIT_HEAD + pb * c.depth, mof = c.depth * nch * D;
   ln.X = T->Xs.back(); ln.M = Mf; ln.grp = nq * d.Ns; ln.grp_stride = d.tok; ln.grp_off = d.qs * d.Ns;
@@ -263,9 +273,9 @@ int ditt_bwd_ln_linear(DittBwd &o, const float *X, const float *Gr, int N, int w
   cm::DitTrLnArgs &ln = o.ln;
   ln.X = X; ln.off_shift = mo; ln.off_scale = mo + D; ln.dA = scratch;
   CM_HIP(cm::launch_ditt_ln_fwd(ln, o.st));
-  CM_HIP(o.gemm_dw(Gr, N, T->Aln, D, o.G(wi), M, N, D));
+  CM_HIP(o.gemm_dw(Gr, N, T->Aln, D, o.G(wi), M, N, D, true));
   CM_HIP(o.colsum(Gr, N, o.G(wi + 1), M, N));
-  CM_HIP(o.gemm_dx(Gr, N, o.W(wi), scratch, M, D, N, 0));
+  CM_HIP(o.gemm_dx(Gr, N, o.W(wi), scratch, M, D, N, 0, true));
   CM_HIP(cm::launch_ditt_segsum(scratch, D, nullptr, 0, T->dmod + mo, d.ldmod, o.B, d.tok, D, o.st));
   CM_HIP(cm::launch_ditt_segsum(scratch, D, T->XN, D, T->dmod + mo + D, d.ldmod, o.B, d.tok, D, o.st));
   CM_HIP(cm::launch_ditt_ln_bwd(ln, o.st));
@@ -282,9 +292,9 @@ int ditt_bwd_mlp(DittBwd &o, int i, const float *Xmid, int w, int mo) {
   CM_HIP(cm::launch_ditt_segsum(T->dX, D, T->Y2[i], D, T->dmod + mo + 2 * D, d.ldmod, B, d.tok, D, st));
   CM_HIP(cm::launch_ditt_gate(nullptr, nullptr, T->G1, T->dX, T->mod, d.ldmod, mo + 2 * D, M, D, d.tok, cm::DITT_SITE_MLP2, o.dr, st));
   CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->Hm, M, mlp, d.tok, o.dr, 0, st));
-  CM_HIP(o.gemm_dw(T->G1, D, T->Hm, mlp, o.G(w + 2), M, D, mlp));
+  CM_HIP(o.gemm_dw(T->G1, D, T->Hm, mlp, o.G(w + 2), M, D, mlp, true));
   CM_HIP(o.colsum(T->G1, D, o.G(w + 3), M, D));
-  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->GH, M, mlp, D, 0));
+  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->GH, M, mlp, D, 0, true));
   CM_HIP(cm::launch_ditt_gelu_drop(T->H1[i], T->GH, M, mlp, d.tok, o.dr, 1, st));
   return ditt_bwd_ln_linear(o, Xmid, T->GH, mlp, w, mo, T->G2);
 }
@@ -299,9 +309,9 @@ int ditt_bwd_attn(DittBwd &o, int i, const float *Xin, int w, int mo, int groups
   const long long M = (long long)B * d.tok;
   CM_HIP(cm::launch_ditt_segsum(T->dX, D, T->Yo[i], D, T->dmod + mo + 2 * D, d.ldmod, B, d.tok, D, st));
   CM_HIP(cm::launch_ditt_gate(nullptr, nullptr, T->G1, T->dX, T->mod, d.ldmod, mo + 2 * D, M, D, d.tok, cm::DITT_SITE_NONE, o.dr, st));
-  CM_HIP(o.gemm_dw(T->G1, D, T->AO[i], D, o.G(w + 2), M, D, D));
+  CM_HIP(o.gemm_dw(T->G1, D, T->AO[i], D, o.G(w + 2), M, D, D, true));
   CM_HIP(o.colsum(T->G1, D, o.G(w + 3), M, D));
-  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->G2, M, D, D, 0));
+  CM_HIP(o.gemm_dx(T->G1, D, o.W(w + 2), T->G2, M, D, D, 0, true));
   cm::DitDrop dr = o.dr;
   dr.gps = groups / B;
   cm::DitTrAttnArgs at{T->QKV[i], T->AO[i], T->LSE[i], T->G2, T->delta, T->G3, groups, S, D, d.cfg.num_heads, dr};
@@ -400,6 +410,8 @@ int ditt_e_step_xt(cm_model *m, const char *what, bool v4, const float *d_xt, co
   hipStream_t st = stream ? (hipStream_t)stream : m->stream;
   cm_dit_train *T = m->dit->train;
   const cm_unet_config &c = m->cfg;
+  T->ls_k = T->autocast ? ditt4_scale_log2(m, B) : 0;
+  if (T->autocast) T->ls_last_B = B;
   CM_HIP(hipMemcpyAsync(m->tbuf, d_t, (size_t)B * sizeof(long long), hipMemcpyDeviceToDevice, st));
   CM_HIP(cm::launch_assemble_input(d_past, d_xt, m->x8, B, c.in_channels, c.rows, c.cols, c.past_len, c.future_len, 3, st));
   if (ditt_conditioning(m, B, st) || (v4 ? ditt4_forward(m, B, seed, st) : ditt_forward(m, B, seed, st))) return 1;

@@ -487,6 +487,8 @@ struct DitGemmArgs {
   const float *x8;                // PRO_PATCH: sampler tensor [B][L][H][W][8]
   const float *spos, *tpos;       // EPI_PATCH: spatial [N_s][D] and temporal [T_p][D] position embeddings
   int L, Hh, Ww, p, pt, Ns, wpn, Cout;
+  int f16;                        // autocast training: A (after the prologue) and W rounded to f16 when staged, v_mfma_f32_32x32x16_f16,
+                                  // fp32 accumulation and output (dit_gemm_f16_kernel; PRO_NONE / PRO_LN with EPI_BIAS only)
 };
 struct DitAttnArgs {
   const float *qkv;               // [B][T_p * N_s][3E] (q | k | v)
@@ -518,6 +520,7 @@ struct DitTrGemmArgs {
   int M, N; long long K;
   int lda, ldb, ldc, ta, accum;
   int nsplit; long long kchunk; float *part;
+  int f16;                        // autocast training: both operands rounded to f16 when staged (ditt_gemm_f16_kernel), fp32 partials and sums
 };
 hipError_t launch_ditt_gemm(const DitTrGemmArgs &a, hipStream_t st);
 // out[seg * ldo + col] = sum over the seg_rows rows of segment seg of U[r][col] * (V ? V[r][col] : 1), float64 accumulation
@@ -549,6 +552,7 @@ struct DitTrPatchArgs {
   const float *dX0; float *dspos, *dtpos;      // gradient of the embedded tokens -> position-embedding gradients
   int B, C, L, Hh, Ww, p, Ns, wpn, tok, qs, Kp, Nout, D;
   int pt, P;                                   // frames per temporal slot (DiT2D: 1); past frames (the loss reaches frames >= P)
+  int ls_k;                                    // loss scale of an autocast step: the loss gradient is multiplied by 2^ls_k (0: the same bits)
 };
 hipError_t launch_ditt_patch_gather(const DitTrPatchArgs &a, hipStream_t st);
 hipError_t launch_ditt_loss_grad(const DitTrPatchArgs &a, hipStream_t st);

@@ -5,7 +5,9 @@ DiT4D_V4 training step.
 grad_sync / loss_sync hooks, ReduceLROnPlateau, the NaN stop, CHECKPOINTS_TO_KEEP, the {"opt", "model"} checkpoint named
 with "NA", the solver from MODEL.DDPM.DIT.TRAIN -- with ONE native call per batch (cm_dit4d_train_step: eps from the
 device Philox stream, q_sample, the train-mode DiT4D_V4 forward with its dropout, MSE, backward, Adam).  The reference
-runs the forward under fp16 autocast; this path is fp32.
+runs the step under fp16 autocast; here MODEL.DDPM.DIT.TRAIN.AUTOCAST (absent: False, the fp32 step) or
+`autocast_override` (train_ddpm_dit.py --autocast) switches the blocks' token Linears to f16 operands
+(DiT4D_V4.set_autocast).
 """
 from __future__ import annotations
 

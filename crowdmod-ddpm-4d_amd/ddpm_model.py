@@ -279,7 +279,19 @@ class DDPM_model:
         if not getattr(net, "_fit", False):
             s = self._solver()
             net.ensure(H, W, int(past.shape[4]), F, max(B, net.max_batch))
-            net.fit_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], dropout_rate=self.res.dit.dropout_rate)
+            # DDPM-DiT: TRAIN.AUTOCAST (absent: False), or the caller's override (train_ddpm_dit.py --autocast); the FM driver
+            # trains in fp32, as the reference does
+            autocast = False
+            if self.arch == "DDPM-DiT":
+                over = getattr(self, "autocast_override", None)
+                autocast = cfgmod.train_autocast(self.res.train) if over is None else bool(over)
+            net.fit_init(lr=s["lr"], betas=s["betas"], weight_decay=s["weight_decay"], dropout_rate=self.res.dit.dropout_rate,
+                         autocast=autocast)
+            if autocast:
+                import logging
+                # (automatic scale: the largest 2^k <= B*C*H*W*F of THIS batch -- the handle reports it for max_batch until a step has run)
+                logging.info("DiT4D_V4 training step under autocast: f16 operands in the blocks' token Linears, loss scale 2^%d at batch %d",
+                             min(24, int(future.size).bit_length() - 1), B)
             self._lr = s["lr"]
             self._plateau = ReduceLROnPlateau(s["lr"], s["factor"], s["patience"], s["min_lr"])
 

@@ -136,17 +136,50 @@ class DiT4D_V4(NativeModule):
         self._fit = False
         return self
 
-    def fit_init(self, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None, batch=None):
+    def fit_init(self, lr=1e-4, betas=(0.5, 0.999), eps=1e-8, weight_decay=0.0, dropout_rate=None, batch=None,
+                 autocast=None, loss_scale_log2=-1):
         """Allocate the training state (master weights, gradients, Adam moments, the tape) on the native handle, for
         batches of at most `batch` (default max_batch) samples.  torch.optim.Adam(lr, betas, eps, weight_decay);
-        dropout_rate defaults to the constructor's."""
+        dropout_rate defaults to the constructor's.  autocast: True = the step of the reference's torch.amp.autocast
+        (ddpm.py:116-120), see set_autocast; False = the fp32 step; None (default) = False on a first call, and the mode
+        of the trainer this one replaces (after fit_end, or a re-created handle) on a later one."""
+        if autocast is None:
+            autocast, loss_scale_log2 = getattr(self, "_autocast", (False, -1))
+        if autocast and self._FAMILY != "cm_dit4d_train":
+            raise NotImplementedError(self._NO_AUTOCAST)
         g = self.cfg
         p = g.dropout_rate if dropout_rate is None else float(dropout_rate)
         h = self.ensure(g.grid_rows, g.grid_cols, g.past_len, g.future_len, int(batch or self.max_batch))
         native.check(self._fn("init")(h, float(lr), float(betas[0]), float(betas[1]), float(eps),
                                                     float(weight_decay), p))
         self._fit = True
+        if self._FAMILY == "cm_dit4d_train":
+            self.set_autocast(bool(autocast), loss_scale_log2)
         return self
+
+    _NO_AUTOCAST = ("DiT2D trains in fp32: the reference trains flow matching without autocast (flow_matching.py:104-157); "
+                    "autocast is DiT4D_V4's (DDPM-DiT)")
+
+    def set_autocast(self, on: bool, loss_scale_log2: int = -1):
+        """Training step under autocast: in every block the spatial and temporal q|k|v in-projections, both
+        out-projections, fc1 and fc2 take f16 matrix-core operands with fp32 accumulation, in the forward, the data
+        gradient and the weight gradient; everything else, the tape, the gradients and Adam stay fp32.  The loss gradient
+        is scaled by 2^loss_scale_log2 inside the step (< 0: automatic, the largest power of two <= B*C*H*W*F) and the
+        gradients are unscaled before anything reads them.  Governs fit_step and fit_step_xt; the eval forward and the
+        sampling loops are untouched."""
+        if self._FAMILY != "cm_dit4d_train":
+            raise NotImplementedError(self._NO_AUTOCAST)
+        native.check(self._fn("set_autocast")(self._train_handle(), 1 if on else 0, int(loss_scale_log2)))
+        self._autocast = (bool(on), int(loss_scale_log2) if on else -1)
+
+    @property
+    def autocast(self):
+        """(mode, loss_scale_log2 in force) of the training step; (False, 0) before fit_init and on DiT2D."""
+        if self._FAMILY != "cm_dit4d_train" or self._handle is None or not getattr(self, "_fit", False):
+            return (False, 0)
+        mode, k = C.c_int32(), C.c_int32()
+        native.check(self._fn("get_autocast")(self._handle, C.byref(mode), C.byref(k)))
+        return (bool(mode.value), int(k.value))
 
     def _fit_step(self, entry, first, items, seed, apply_update, sample_base) -> float:
         """`entry(h, *first, *items, seed, &loss, B, apply_update, stream)` on the staged `items` (numpy arrays through

@@ -164,6 +164,8 @@ SIGNATURES = {
     "cm_dit4d_train_init": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),
     "cm_dit4d_train_set_lr": (C.c_int, [_P, C.c_float]),
     "cm_dit4d_train_set_sample_base": (C.c_int, [_P, C.c_int64]),
+    "cm_dit4d_train_set_autocast": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "cm_dit4d_train_get_autocast": (C.c_int, [_P, _P, _P]),
     "cm_dit4d_train_step_xt": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),
     "cm_dit4d_train_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_float), C.c_int32, C.c_int32, _P]),
     "cm_dit4d_train_flat_grads": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),

@@ -445,8 +445,9 @@ int cm_dit_train_get_pred(cm_model *m, float *h_out, int64_t numel);
 
 /* ---- DDPM-DiT training: DDPM_model._train_step (models/diffusion/ddpm.py:111-154) on the DiT4D_V4 denoiser --------------
  * (t ~ U{0..T-1}; (x_t, eps) = q_sample(future, t); eps_hat = DiT4D_V4(x_t, t, past) in train mode; loss = mse(eps_hat,
- * eps); backward; torch.optim.Adam with coupled L2.  The reference runs the forward under fp16 autocast; this path is
- * fp32 throughout.)  The sibling of cm_dit_train_*, entry for entry; only a finalized DiT4D_V4 handle on a device
+ * eps); backward; torch.optim.Adam with coupled L2.  The reference runs this step under fp16 autocast; the path is
+ * fp32 unless cm_dit4d_train_set_autocast switches the blocks' token Linears to f16 operands, below.)
+ * The sibling of cm_dit_train_*, entry for entry; only a finalized DiT4D_V4 handle on a device
  * trains: a UNet handle, an FM-DiT (DiT2D) handle and a host-only handle are refused by name.  Head dim 64, at most 64
  * heads.  dropout_rate is DiT4D_V4's DROPOUT_RATE (both attentions' probabilities, after GELU, after fc2), in [0, 1);
  * the masks are a function of (seed, optimizer step, GLOBAL sample index, block, site, head, row, column). */
@@ -454,6 +455,23 @@ int cm_dit4d_train_init(cm_model *m, float lr, float beta1, float beta2, float e
                         float dropout_rate);
 int cm_dit4d_train_set_lr(cm_model *m, float lr);
 int cm_dit4d_train_set_sample_base(cm_model *m, int64_t sample_id_base);
+/* The reference trains this denoiser under torch.amp.autocast("cuda") without a GradScaler (ddpm.py:116-120).
+ * 0 = fp32 step (default: exactly the launches of a handle that never heard of the mode), 1 = autocast: in every block the
+ * spatial and temporal q|k|v in-projections, both out-projections, fc1 and fc2 take f16 operands with fp32 accumulation
+ * (v_mfma_f32_32x32x16_f16) in the training forward, the data gradient and the weight gradient.  An operand is rounded
+ * once, to nearest even, from its fp32 value when it is staged (the LayerNorm + modulate output, the saved activations, dY and
+ * the fp32 master weights: no f16 weight copy exists); a value outside f16's range becomes +-inf and shows as a non-finite
+ * loss.  The patch embedding, the final layer, the conditioning chain, both attention cores, LayerNorm, GELU, the gates, the
+ * tape, every gradient tensor and Adam stay fp32.  The loss gradient is multiplied by 2^k and the flat gradient buffer by
+ * 2^-k at the end of the backward, so every reader of the gradients sees unscaled numbers.
+ * loss_scale_log2 < 0 = automatic: the largest k with 2^k <= B*C*H*W*F of the step (a function of B alone); an explicit k
+ * in [0, 24] is taken as is.  Call after cm_dit4d_train_init, between steps.  Governs cm_dit4d_train_step and
+ * cm_dit4d_train_step_xt; cm_unet_forward and the sampling loops are untouched.  Refused by name: a null, UNet, FM-DiT
+ * (DiT2D: the reference trains flow matching in fp32) or untrained handle, and an unknown mode. */
+int cm_dit4d_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2);
+/* *loss_scale_log2: the exponent in force (automatic: for the batch of the last step, max_batch before the first; 0 with the
+ * mode off). */
+int cm_dit4d_train_get_autocast(const cm_model *m, int32_t *mode, int32_t *loss_scale_log2);
 /* One step on device buffers with the caller's noised input and regression target; *h_loss = mse(eps_hat, d_target);
  * backward; if apply_update != 0: Adam.  Synchronous. */
 int cm_dit4d_train_step_xt(cm_model *m, const float *d_xt, const float *d_past, const int64_t *d_t,

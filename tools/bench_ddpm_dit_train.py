@@ -11,6 +11,10 @@ the tape.
 
     python tools/bench_ddpm_dit_train.py [--batch 64] [--steps 10] [--warmup 3] [--repeats 7]
 
+--autocast: the native step under DiT4D_V4.set_autocast(True).  --alternate N: N rounds of (fp32, autocast) timed
+alternately on ONE handle in one process, without update (so both modes step from the same weights); prints the ms per
+step of every round, both medians and spreads (max - min, ms) and the loss scale.
+
 Kernel time per launch: run the native path alone under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_ddpm_dit_train.py --only native ...`."""
 import argparse
@@ -104,6 +108,38 @@ def tape_bytes(cfg, B):
     return 4 * (cfg.depth * per_block + rows * D)
 
 
+def alternate(a, net, data, flops, tape):
+    """N rounds of (fp32, autocast) on one handle; no update, so every round of a mode computes the same step."""
+    import torch
+    xt, t, past, target = data
+    ms, loss = {False: [], True: []}, {}
+    for on in (False, True):
+        net.set_autocast(on)
+        for i in range(a.warmup):
+            net.fit_step_xt(xt, t, past, target, seed=1234 + i, apply_update=False)
+    for r in range(a.alternate):
+        for on in (False, True):
+            net.set_autocast(on)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(a.steps):
+                loss[on] = net.fit_step_xt(xt, t, past, target, seed=1234 + i, apply_update=False)
+            torch.cuda.synchronize()
+            ms[on].append((time.perf_counter() - t0) * 1e3 / a.steps)
+    net.set_autocast(True)
+    med = {on: float(np.median(v)) for on, v in ms.items()}
+    print(json.dumps({"bench": "ddpm_dit_train", "metric": "training step without update, fp32 and autocast alternated on one handle",
+                      "unit": "ms", "batch": a.batch, "steps": a.steps, "warmup": a.warmup, "rounds": a.alternate, "dropout": DROP,
+                      "fp32_ms": [round(v, 3) for v in ms[False]], "autocast_ms": [round(v, 3) for v in ms[True]],
+                      "fp32_median": round(med[False], 3), "autocast_median": round(med[True], 3),
+                      "fp32_spread": round(max(ms[False]) - min(ms[False]), 3),
+                      "autocast_spread": round(max(ms[True]) - min(ms[True]), 3),
+                      "fp32_over_autocast": round(med[False] / med[True], 3),
+                      "loss_fp32": loss[False], "loss_autocast": loss[True], "loss_scale_log2": net.autocast[1],
+                      "flops_per_step": flops, "fp32_tflops": round(flops / (med[False] * 1e-3) / 1e12, 2),
+                      "autocast_tflops": round(flops / (med[True] * 1e-3) / 1e12, 2), "tape_mib": round(tape / 2 ** 20, 1)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -111,6 +147,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--only", choices=("native", "torch"), default=None, help="time one path only (profiling runs)")
+    ap.add_argument("--autocast", action="store_true", help="f16 operands in the blocks' token Linears (DiT4D_V4.set_autocast)")
+    ap.add_argument("--alternate", type=int, default=0, help="rounds of (fp32, autocast) timed alternately on one handle, without update")
     a = ap.parse_args()
     import torch
     from crowdmod_ddpm_4d_amd import dit_spec, prng
@@ -129,8 +167,10 @@ def main():
         net = DiT4D_V4(G["C"], G["C"], G["H"], G["W"], G["P"], G["F"], cfg.t_patch_size, cfg.patch_size, cfg.hidden_size,
                        cfg.depth, cfg.num_heads, cfg.mlp_ratio, DROP, cfg.time_multiple, max_batch=B)
         net.load_state_dict(params)
-        net.fit_init(lr=LR, betas=BETAS, weight_decay=WD, dropout_rate=DROP)
+        net.fit_init(lr=LR, betas=BETAS, weight_decay=WD, dropout_rate=DROP, autocast=a.autocast)
         flops = 3.0 * net.cost(B)[0]
+        if a.alternate > 0:
+            return alternate(a, net, (xt, t, past, target), flops, tape_bytes(cfg, B))
         paths["native"] = lambda i: net.fit_step_xt(xt, t, past, target, seed=1234 + i, apply_update=True)
     if a.only != "native":
         step = torch_step_fn(cfg, params, dev)
@@ -149,7 +189,7 @@ def main():
             torch.cuda.synchronize()
             ms[k].append((time.perf_counter() - t0) * 1e3 / a.steps)
             assert np.isfinite(last), (k, last)
-    out = {"bench": "ddpm_dit_train", "batch": B, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "dropout": DROP}
+    out = {"bench": "ddpm_dit_train", "autocast": bool(a.autocast), "batch": B, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "dropout": DROP}
     for k, v in ms.items():
         med = float(np.median(v))
         out[k] = {"ms_per_step": round(med, 3), "spread": round((max(v) - min(v)) / med, 4)}

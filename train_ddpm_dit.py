@@ -48,7 +48,7 @@ def make_loader(past, future, batch_size, seed, rank=0, world=1):
     return Loader()
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser(description="Train a crowd-macroprops DDPM-DiT (MI355X-native path).")
     ap.add_argument('--config-yml-file', type=str, default='config/ATC.yml')
     ap.add_argument('--configList-yml-file', type=str, default=None)
@@ -58,7 +58,13 @@ def main():
     ap.add_argument('--synthetic-samples', type=int, default=1024)
     ap.add_argument('--epochs', type=int, default=None, help='override TRAIN.EPOCHS')
     ap.add_argument('--device', type=int, default=None)
-    args = ap.parse_args()
+    ap.add_argument('--autocast', action='store_true',
+                    help='train DiT4D_V4 under autocast (f16 operands in the token Linears): overrides TRAIN.AUTOCAST')
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if args.arch != "DDPM-DiT":
         raise SystemExit(f"{args.arch}: train_ddpm_dit.py trains DDPM-DiT only; the UNet-backbone generators go through "
@@ -74,6 +80,8 @@ def main():
         res.train["EPOCHS"] = int(args.epochs)
     mprops = 3  # train.py:61 of the reference
     model = DDPM_DiT_model(cfg, args.arch, mprops, device=device)
+    if args.autocast:
+        model.autocast_override = True
     if args.epochs is not None:
         model.res = res
     nparams = sum(int(np.prod(v.shape)) for k, v in model.denoiser.state_dict().items()
