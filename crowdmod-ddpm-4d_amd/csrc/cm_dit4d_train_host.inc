@@ -128,14 +128,7 @@ int ditt4_backward(cm_model *m, const float *d_target, int B, uint64_t seed, hip
 }
 
 // the requested exponent, or the largest k with 2^k <= B*C*H*W*F (loss gradient O(1)): a function of B alone
-int ditt4_scale_log2(const cm_model *m, int B) {
-  const cm_dit_train *T = m->dit->train;
-  if (T->ls_req >= 0) return T->ls_req;
-  const long long N = (long long)B * m->per_sample();
-  int k = 0;
-  while (k < 24 && (2LL << k) <= N) ++k;
-  return k;
-}
+int ditt4_scale_log2(const cm_model *m, int B) { return loss_scale_log2(m->dit->train->ls_req, (long long)B * m->per_sample()); }
 
 }  // namespace
 

@@ -1194,9 +1194,199 @@ void test_opt_store() {
   printf("test_opt_store ok\n");
 }
 
+// wgrad_route / dgrad_route: the one place that decides which kernel a conv's weight gradient and data gradient run on.  The fifteen
+// layer classes of test_conv_route (with the backward's facts added: reference taps, an output tensor of the op's own width, the
+// UNet input as the first conv's source), crossed with precision x autocast x f16 fragments x every kernel-disabling switch, against
+// the table below -- written from cm_train_host.inc as it stood before the routes were functions -- and the invariants.
+void test_bwd_route() {
+  struct Want { WgradKernel wg; DgradKernel dg; ConvForm dform; };
+  // Default switches, fp32 plan, autocast off.  A data gradient is a stride-1 conv on the op's INPUT grid whatever the forward's stride
+  // or upsampling (zero-stuffed dY; the upsampled grid, sum-pooled afterwards), so the stride-2 and upsample convs of these widths take
+  // the Winograd kernel as well; the last conv's dY has 8 channels, which the Winograd kernel does not take.
+  const Want want[RC_COUNT] = {
+      /* WINO_FULL         */ {WG_WINO, DG_WINO, FORM_B6},
+      /* WINO_FULL_SKIP    */ {WG_WINO, DG_WINO, FORM_B6},
+      /* WINO_HALF         */ {WG_WINO, DG_WINO, FORM_B6},
+      /* WINO_HALF_SKIP    */ {WG_WINO, DG_WINO, FORM_B6},
+      /* QUARTER           */ {WG_ZS, DG_QR, FORM_B6},
+      /* QUARTER_NO_TRAIN  */ {WG_ZS, DG_GENERIC, FORM_FP32},     // (the class of the CM_NO_TRAIN_QR switch: walked with it set)
+      /* KSPLIT            */ {WG_GENERIC, DG_WINO, FORM_B6},
+      /* STRIDE2           */ {WG_GENERIC, DG_WINO, FORM_B6},
+      /* UPS_STATS         */ {WG_PAR, DG_WINO, FORM_B6},
+      /* UPS_NO_STATS      */ {WG_PAR, DG_WINO, FORM_B6},
+      /* FIRST             */ {WG_PACK, DG_NONE, FORM_FP32},
+      /* LAST              */ {WG_PACK, DG_GENERIC, FORM_FP32},
+      /* 1X1               */ {WG_1X1, DG_GENERIC, FORM_FP32},
+      /* 1X1_STATS         */ {WG_1X1, DG_GENERIC, FORM_FP32},
+      /* SKIP_ABSORBED     */ {WG_1X1, DG_GENERIC, FORM_FP32},
+  };
+  bool BwdKnobs::*const sw[] = {nullptr, &BwdKnobs::no_wino, &BwdKnobs::no_wino_b6, &BwdKnobs::no_train_b6, &BwdKnobs::no_train_qr,
+                                &BwdKnobs::no_wino_wgrad, &BwdKnobs::no_wgrad_zsplit, &BwdKnobs::no_wgrad_pack, &BwdKnobs::no_wgrad_par,
+                                &BwdKnobs::no_wgrad_1x1, &BwdKnobs::no_wgrad_zs_kernel};
+  int walked = 0;
+  for (int rc = 0; rc < RC_COUNT; ++rc)
+    for (const int prec : {CM_PRECISION_F32, CM_PRECISION_F32X, CM_PRECISION_F16})   // (training refuses an f16 handle; the routes still answer)
+      for (int ac = 0; ac < 2; ++ac)
+        for (int frags = 0; frags < 2; ++frags)
+          for (auto s : sw) {
+            Op op = route_class_op(rc, prec);
+            Act in, out;
+            in.C = op.ca.C0; out.C = op.ca.out_cs; op.in0 = &in; op.out_act = &out;
+            op.ref_taps = op.cls == K_CONV1 ? 1 : 27;
+            BwdCtx ctx;
+            ctx.precision = prec; ctx.autocast = ac; ctx.f16_frags = frags; ctx.max_batch = 2; ctx.in_channels = 3;
+            if (rc == RC_FIRST) ctx.x8 = &in;
+            BwdKnobs k;
+            if (s) k.*s = true;
+            if (rc == RC_QUARTER_NO_TRAIN_QR) k.no_train_qr = true;
+            const BwdGeom g = bwd_geom(op, ctx, k);
+            const WgradRoute w = wgrad_route(op, g, ctx, k);
+            const DgradRoute d = dgrad_route(op, g, ctx, k);
+            ++walked;
+            // the table, then what each switch moves: exactly the rows it names, to the fallback the old else-branch reached
+            Want e = want[rc];
+            const bool f16 = ac && frags;
+            ConvForm wform = (e.wg == WG_WINO && f16) ? FORM_F16 : FORM_FP32;
+            if (e.dg == DG_WINO) e.dform = f16 ? FORM_F16 : prec == CM_PRECISION_F16 ? FORM_FP32 : FORM_B6;
+            if (e.dg == DG_QR && prec == CM_PRECISION_F16) { e.dg = DG_GENERIC; e.dform = FORM_FP32; }   // (no six-term fragments on that plan)
+            if (k.no_wino && e.dg == DG_WINO) { e.dg = DG_GENERIC; e.dform = FORM_FP32; }
+            if ((k.no_wino_b6 || k.no_train_b6) && e.dform == FORM_B6 && e.dg == DG_WINO) e.dform = FORM_FP32;
+            if (k.no_train_qr && e.dg == DG_QR) { e.dg = DG_GENERIC; e.dform = FORM_FP32; }
+            if (k.no_wino_wgrad && e.wg == WG_WINO) { e.wg = WG_GENERIC; wform = FORM_FP32; }
+            if ((k.no_wgrad_zsplit || k.no_wgrad_zs_kernel) && e.wg == WG_ZS) e.wg = WG_GENERIC;
+            if (k.no_wgrad_pack && e.wg == WG_PACK) e.wg = WG_GENERIC;
+            if (k.no_wgrad_par && e.wg == WG_PAR) e.wg = WG_GENERIC;
+            if (k.no_wgrad_1x1 && e.wg == WG_1X1) e.wg = WG_GENERIC;
+            EXPECT(w.kernel == e.wg && w.form == wform && d.kernel == e.dg && d.form == e.dform);
+            // the invariants
+            if (w.form == FORM_F16 || d.form == FORM_F16) EXPECT(ac && frags);
+            EXPECT(w.form == FORM_FP32 || (w.form == FORM_F16 && w.kernel == WG_WINO));
+            if (d.form == FORM_B6) EXPECT(prec != CM_PRECISION_F16);
+            if (d.kernel == DG_QR) EXPECT(op.qr && op.d_wqr_b6 && d.form == FORM_B6);
+            if (d.kernel == DG_WINO) EXPECT(dgrad_wino_ok(g, k) && cm::conv_wino_ok(g.da));
+            EXPECT((d.kernel == DG_NONE) == (rc == RC_FIRST));
+            EXPECT(g.zsplit == ((rc == RC_QUARTER || rc == RC_QUARTER_NO_TRAIN_QR) && !k.no_wgrad_zsplit));   // the z-split row order without its kernel: the generic one takes it
+          }
+  printf("test_bwd_route: %d combinations walked\n", walked);
+}
+
+// plan_backward on the op lists of host-only handles (cm_model_create with device = -1, then the list building of cm_model_finalize:
+// "device" buffers are host memory nothing launches on).
+struct HostList {
+  cm_model *m = nullptr;
+  BwdCtx ctx;
+  explicit HostList(cm_unet_config c) {
+    EXPECT(cm_model_create(&c, &m) == 0);
+    EXPECT(dev_alloc(m, (void **)&m->tbuf, (size_t)c.max_batch * sizeof(long long)) == 0 && build_ops(m) == 0);
+    for (Op &op : m->ops)
+      if (op.kind == OP_CONV) EXPECT(resolve_conv(m, op) == 0);
+    ctx = bwd_ctx(m);
+  }
+  ~HostList() { cm_model_destroy(m); }
+};
+
+void check_bwd_plan(const HostList &h, int nparams) {
+  const cm_model *m = h.m;
+  const BwdKnobs k;
+  const BwdPlan P = plan_backward(m->ops, h.ctx, k);
+  EXPECT(P.err.empty() && P.ops.size() == m->ops.size());
+  // every gradient buffer: exactly one first writer, before every accumulator and before the entry that reads it as dY
+  std::map<const Act *, int> first, reads;   // -> position in the plan
+  std::map<const Act *, std::vector<int>> accs;
+  for (int i = 0; i < (int)P.ops.size(); ++i) {
+    const BwdOp &e = P.ops[i];
+    const Op &op = m->ops[e.op];
+    EXPECT(e.op == (int)m->ops.size() - 1 - i && &P.of(e.op) == &e);
+    auto wrote = [&](const Act *a, bool acc) { if (acc) accs[a].push_back(i); else { EXPECT(!first.count(a)); first[a] = i; } };
+    if (op.kind == OP_ATTN) { EXPECT(e.qa && e.oa && e.qa->d == op.qkv && e.oa->d == op.aout); reads[e.oa] = i; wrote(e.qa, false); }
+    if (op.kind != OP_CONV) continue;
+    reads[op.out_act] = i;
+    if (op.resid_act) wrote(op.resid_act, e.acc_resid);
+    if (e.dg.kernel == DG_NONE) continue;
+    wrote(op.in0, e.acc_in0);
+    if (op.in1 && e.tail != TAIL_POOL) wrote(op.in1, e.acc_in1);
+  }
+  for (auto &a : m->acts) {
+    const Act *t = a.get();
+    if (t == h.ctx.x8 || t == h.ctx.seed) { EXPECT(!first.count(t) && !accs.count(t)); continue; }   // data; the loss gradient's own buffer
+    EXPECT(first.count(t) == 1 && reads.count(t) == 1);
+    if (!first.count(t) || !reads.count(t)) continue;
+    EXPECT(first[t] < reads[t]);
+    for (int i : accs[t]) EXPECT(first[t] < i && i < reads[t]);
+  }
+  // the batch-sum pool: pairwise disjoint regions whose union is [0, reported size)
+  std::vector<std::pair<size_t, size_t>> regions;
+  for (const BwdOp &e : P.ops) {
+    const Op &op = m->ops[e.op];
+    if (op.kind != OP_CONV) continue;
+    regions.push_back({e.bias_off, (size_t)h.ctx.max_batch * op.ca.Co});
+    if (e.tail == TAIL_GN && e.dg.kernel != DG_NONE) regions.push_back({e.gn_off, (size_t)h.ctx.max_batch * 2 * (op.ca.C0 + op.ca.C1)});
+  }
+  std::sort(regions.begin(), regions.end());
+  size_t end = 0;
+  for (auto &r : regions) { EXPECT(r.first == end && r.second > 0); end = r.first + r.second; }
+  EXPECT(end == P.pool_floats);
+  for (const BwdSumJob &j : P.bsum) EXPECT(j.off + (size_t)(h.ctx.max_batch - 1) * j.stride + j.C <= P.pool_floats);
+  // every trainable parameter's gradient is the destination of exactly one job or launch, the frozen sinusoid table of none
+  std::map<std::string, int> dst;
+  for (const BwdOp &e : P.ops) if (m->ops[e.op].kind == OP_CONV) ++dst[m->ops[e.op].wname];
+  for (const BwdSumJob &j : P.bsum) ++dst[j.param];
+  for (const BwdCopyJob &j : P.copy) ++dst[j.param];
+  for (const char *n : {"time_embeddings.time_blocks.1.weight", "time_embeddings.time_blocks.1.bias", "time_embeddings.time_blocks.3.weight",
+                        "time_embeddings.time_blocks.3.bias"}) ++dst[n];   // launch_time_bwd
+  EXPECT((int)m->params.size() == nparams && (int)dst.size() == nparams - 1);
+  for (const Param &p : m->params) EXPECT(dst.count(p.name) ? dst[p.name] == 1 : p.name == "time_embeddings.time_blocks.0.weight");
+  // the copy jobs tile the stacked dense_1 gradients
+  int off = 0;
+  for (size_t i = 0; i < P.copy.size(); i += 2) {
+    EXPECT(!P.copy[i].bias && P.copy[i + 1].bias && P.copy[i].off == off && P.copy[i + 1].off == off && P.copy[i].n == P.copy[i + 1].n * h.ctx.tx);
+    off += (int)P.copy[i + 1].n;
+  }
+  EXPECT(off == m->nproj);
+  // partial copies: at least one with the 256 MiB buffer, a clean failure without one
+  for (const BwdOp &e : P.ops) {
+    if (m->ops[e.op].kind != OP_CONV) continue;
+    for (int B : {1, h.ctx.max_batch}) EXPECT(wgrad_groups(e, B, (size_t)64 << 20) >= 1);
+    EXPECT(wgrad_groups(e, 1, 0) == 0 && std::string(cm_last_error()).find("partial buffer") != std::string::npos);
+  }
+  // autocast with the f16 fragments in place moves the Winograd layers' forms and nothing else
+  BwdCtx ac = h.ctx; ac.autocast = ac.f16_frags = true;
+  const BwdPlan Q = plan_backward(m->ops, ac, k);
+  EXPECT(Q.err.empty() && Q.pool_floats == P.pool_floats && Q.ops.size() == P.ops.size());
+  for (size_t i = 0; i < P.ops.size() && i < Q.ops.size(); ++i) {
+    const BwdOp &a = P.ops[i], &b = Q.ops[i];
+    EXPECT(a.wg.kernel == b.wg.kernel && a.dg.kernel == b.dg.kernel && a.bias_off == b.bias_off && a.gn_off == b.gn_off && a.acc_in0 == b.acc_in0);
+    EXPECT(b.wg.form == (a.wg.kernel == WG_WINO ? FORM_F16 : FORM_FP32) && b.dg.form == (a.dg.kernel == DG_WINO ? FORM_F16 : a.dg.form));
+  }
+  // a list without its last conv: the op in front of it is an orphan, and the plan says so
+  std::vector<Op> cut(m->ops.begin(), m->ops.end() - 1);
+  int orphan = (int)cut.size() - 1;
+  while (orphan >= 0 && cut[orphan].kind != OP_CONV && cut[orphan].kind != OP_ATTN) --orphan;
+  const BwdPlan C = plan_backward(cut, h.ctx, k);
+  EXPECT(!C.err.empty() && orphan >= 0 && C.err.find(cut[orphan].label) != std::string::npos);
+}
+
+void test_bwd_plan() {
+  for (int C : {3, 4}) check_bwd_plan(HostList(atc_cfg(C, 12, 36, -1)), 169);   // ATC
+  check_bwd_plan(HostList(atc_cfg(3, 28, 24, -1)), 169);                          // HERMES-CR-120
+  check_bwd_plan(HostList(atc_cfg(3, 8, 20, -1)), 169);                           // the odd grid of tests/test_gpu_odd_grid.py
+  check_bwd_plan(HostList(atc_cfg(3, 24, 72, -1)), 169);                          // attention scratch in a global slab
+  {
+    cm_unet_config c = atc_cfg(3, 4, 8, -1);                                      // the narrow model of the parity tests (base 8)
+    c.base_channels = 8; c.max_batch = 3;
+    check_bwd_plan(HostList(c), 169);
+  }
+  {
+    HostList big(atc_cfg(3, 24, 72, -1)), atc(atc_cfg(3, 12, 36, -1));
+    EXPECT(plan_backward(big.m->ops, big.ctx, BwdKnobs()).attn_floats > 0 && plan_backward(atc.m->ops, atc.ctx, BwdKnobs()).attn_floats == 0);
+  }
+}
+
 }  // namespace
 
 int main() {
+  test_bwd_route();
+  test_bwd_plan();
   test_opt_store();
   test_schedule();
   test_plan_and_params();

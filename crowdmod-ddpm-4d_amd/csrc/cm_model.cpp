@@ -390,15 +390,21 @@ void build_plan(cm_model *m) {
   add_param(m, "final.2.bias", {c.out_channels});
 }
 
+// A host-only handle (device < 0) can still build its op list (build_ops, resolve_conv) for the planners' self-tests: its "device"
+// buffers are zeroed host memory that nothing launches on, and the few device calls of that path go through CM_DEV.
+#define CM_DEV(m, expr) do { if ((m)->device >= 0) CM_HIP(expr); } while (0)
+
 int dev_alloc(cm_model *m, void **p, size_t bytes) {
-  CM_HIP(hipMalloc(p, bytes ? bytes : 4));
+  if (m->device < 0) { if (!(*p = calloc(bytes ? bytes : 4, 1))) return fail("out of host memory"); }
+  else CM_HIP(hipMalloc(p, bytes ? bytes : 4));
   m->allocs.push_back(*p);
   return 0;
 }
 
 int upload(cm_model *m, const std::vector<float> &h, float **d) {
   if (dev_alloc(m, (void **)d, h.size() * sizeof(float))) return 1;
-  CM_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (m->device < 0) std::memcpy(*d, h.data(), h.size() * sizeof(float));
+  else CM_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -592,8 +598,8 @@ static int add_h2(cm_model *m, Op &op, H2Kind kind, const float *w_ref, float **
   if (!(ws > 0.f)) return 0;
   if (kind == H2_FIN) {
     if (dev_alloc(m, (void **)d_frag, cm::CM_FIN_W_FLOATS * sizeof(float))) return 1;
-    CM_HIP(cm::launch_fin_pack(op.d_wfin_src, *d_frag, op.ca.Co, 2, m->stream, ws));
-    CM_HIP(hipStreamSynchronize(m->stream));
+    CM_DEV(m, cm::launch_fin_pack(op.d_wfin_src, *d_frag, op.ca.Co, 2, m->stream, ws));
+    CM_DEV(m, hipStreamSynchronize(m->stream));
   } else if (upload(m, frag, d_frag)) return 1;
   op.h2_oscale = 1.f / ws;
   return 0;
@@ -708,12 +714,12 @@ int add_conv(cm_model *m, const ConvSpec &s) {
     if (s.Co <= 4 && Ci_ref == 32 && Ci_pad == 32 && !s.s1 && !cm::diag_env("CM_NO_FIN") && cm::conv_fin_pick(s.out->Y, s.out->X, &op.fin_by, &op.fin_bx)) {
       if (upload(m, w.host, &op.d_wfin_src)) return 1;
       if (dev_alloc(m, (void **)&op.d_wfin, cm::CM_FIN_W_FLOATS * sizeof(float))) return 1;
-      CM_HIP(cm::launch_fin_pack(op.d_wfin_src, op.d_wfin, s.Co, 0, m->stream));
+      CM_DEV(m, cm::launch_fin_pack(op.d_wfin_src, op.d_wfin, s.Co, 0, m->stream));
       if (m->precision == CM_PRECISION_F16) {
         if (dev_alloc(m, (void **)&op.d_wfin16, cm::CM_FIN_W_FLOATS * sizeof(float))) return 1;
-        CM_HIP(cm::launch_fin_pack(op.d_wfin_src, op.d_wfin16, s.Co, 1, m->stream));
+        CM_DEV(m, cm::launch_fin_pack(op.d_wfin_src, op.d_wfin16, s.Co, 1, m->stream));
       }
-      CM_HIP(hipStreamSynchronize(m->stream));
+      CM_DEV(m, hipStreamSynchronize(m->stream));
       op.fin = true;
     }
   }
@@ -890,7 +896,7 @@ int build_ops(cm_model *m) {
   auto xin = std::make_unique<Act>();
   xin->name = "input"; xin->C = 8; xin->Z = L; xin->Y = c.rows; xin->X = c.cols;
   if (dev_alloc(m, (void **)&xin->d, (size_t)c.max_batch * xin->V() * 8 * sizeof(float))) return 1;
-  CM_HIP(hipMemset(xin->d, 0, (size_t)c.max_batch * xin->V() * 8 * sizeof(float)));
+  CM_DEV(m, hipMemset(xin->d, 0, (size_t)c.max_batch * xin->V() * 8 * sizeof(float)));
   m->x8 = xin->d; m->x8_act = xin.get();
   m->acts.push_back(std::move(xin));
 
@@ -1032,7 +1038,7 @@ int build_ops(cm_model *m) {
     auto eo = std::make_unique<Act>();
     eo->name = "final"; eo->C = 8; eo->Z = L; eo->Y = c.rows; eo->X = c.cols;
     if (dev_alloc(m, (void **)&eo->d, (size_t)c.max_batch * eo->V() * 8 * sizeof(float))) return 1;
-    CM_HIP(hipMemset(eo->d, 0, (size_t)c.max_batch * eo->V() * 8 * sizeof(float)));
+    CM_DEV(m, hipMemset(eo->d, 0, (size_t)c.max_batch * eo->V() * 8 * sizeof(float)));
     m->eps_cl = eo->d;
     Act *eop = eo.get();
     m->act_by_name["final"] = eop;
@@ -1077,9 +1083,9 @@ int resolve_conv(cm_model *m, Op &op) {
   cm::conv_build_tables(op.ca, op.MB, hv.data(), mt.data());
   if (dev_alloc(m, (void **)&op.d_hvtab, 16384 * sizeof(int))) return 1;
   if (dev_alloc(m, (void **)&op.d_mtab, 256 * sizeof(int))) return 1;
-  CM_HIP(hipMemcpyAsync(op.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
-  CM_HIP(hipMemcpyAsync(op.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
-  CM_HIP(hipStreamSynchronize(m->stream));
+  CM_DEV(m, hipMemcpyAsync(op.d_hvtab, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+  CM_DEV(m, hipMemcpyAsync(op.d_mtab, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+  CM_DEV(m, hipStreamSynchronize(m->stream));
   op.ca.hvtab = op.d_hvtab;
   op.ca.mtab = op.d_mtab;
   return 0;
@@ -1149,6 +1155,135 @@ ConvRoute conv_route(const Op &op, int precision, bool train_fwd, bool h2_stale,
   }
   if (op.d_w1x1_16 && infer && cm::conv1x1_f16_ok(a, op.NB)) return {CONV_1X1_F16, FORM_F16};
   return {CONV_GENERIC, form(cm::conv_par_f16_variant(op.MB, op.NB, g.bz, g.by, g.bx) ? op.d_wfrag16 : nullptr, nullptr, nullptr)};
+}
+
+// The training backward of a conv (cm_train_host.inc) asks the same way: wgrad_route names the kernel of the weight gradient,
+// dgrad_route that of the data gradient.  Same contract as conv_route -- the resolved op, the geometry bwd_geom derives from it, a
+// context (fragment sets as present / absent) and the diagnostic switches as a value (BwdKnobs: the one reader of the backward's
+// CM_DIAG variables, so that the self-test flips a switch without an environment).
+struct BwdKnobs {
+  bool no_wino = false, no_wino_b6 = false, no_train_b6 = false, no_train_qr = false, no_wino_wgrad = false, no_wgrad_zsplit = false,
+       no_wgrad_pack = false, no_wgrad_par = false, no_wgrad_1x1 = false, no_wgrad_zs_kernel = false, wgrad_one_stream = false;
+  // workgroups per weight-gradient launch.  Winograd: one workgroup per CU (80 KB image, 192 accumulators; with the weight gradients on
+  // their own stream 128 / 192 / 256 / 512 -> 14.63 / 13.59 / 13.69 / 13.88 ms per step); generic: two per CU fit (62 KB LDS each; 768:
+  // 26.0 ms, 512: 23.2 ms per step); two-plane: one per CU, fewest partial copies (128 / 256 / 512 / 1024: 16.84 / 16.30 / 16.46 / 16.75 ms)
+  int wino_wgs = 192, wgs = 256, zs_wgs = 128, x1_wgs = 768, par_wgs = 1024;
+};
+BwdKnobs read_bwd_knobs() {
+  BwdKnobs k;
+  auto on = [](const char *name) { return cm::diag_env(name) != nullptr; };
+  auto num = [](const char *name, int dflt) { const char *v = cm::diag_env(name); return v ? atoi(v) : dflt; };
+  k.no_wino = on("CM_NO_WINO"); k.no_wino_b6 = on("CM_NO_WINO_B6"); k.no_train_b6 = on("CM_NO_TRAIN_B6"); k.no_train_qr = on("CM_NO_TRAIN_QR");
+  k.no_wino_wgrad = on("CM_NO_WINO_WGRAD"); k.no_wgrad_zsplit = on("CM_NO_WGRAD_ZSPLIT"); k.no_wgrad_pack = on("CM_NO_WGRAD_PACK");
+  k.no_wgrad_par = on("CM_NO_WGRAD_PAR"); k.no_wgrad_1x1 = on("CM_NO_WGRAD_1X1"); k.no_wgrad_zs_kernel = on("CM_NO_WGRAD_ZS_KERNEL");
+  k.wgrad_one_stream = on("CM_WGRAD_ONE_STREAM");
+  k.wino_wgs = num("CM_WGRAD_WINO_WGS", k.wino_wgs); k.wgs = num("CM_WGRAD_WGS", k.wgs); k.zs_wgs = num("CM_WGRAD_ZS_WGS", k.zs_wgs);
+  k.x1_wgs = num("CM_WGRAD_1X1_WGS", k.x1_wgs); k.par_wgs = num("CM_WGRAD_PAR_WGS", k.par_wgs);
+  return k;
+}
+
+// f16_frags: the f16 siblings of the Winograd fragments exist (cm_train_set_autocast has run with mode 1)
+struct BwdCtx { int precision = CM_PRECISION_F32; bool autocast = false, f16_frags = false; int max_batch = 1, in_channels = 8, tx = 0;
+                const Act *x8 = nullptr, *seed = nullptr; };   // the UNet's input (no data gradient) and the tensor the loss gradient lands in
+
+// Geometry of a conv's backward, from the resolved op alone (tiles through pick_tile / conv_wino_pick: no device).
+struct BwdGeom {
+  bool first = false;          // the first conv: its input is data
+  int Co = 0, Ci = 0;          // of the reference weight (Ci < C0 + C1 on the first conv only)
+  // data gradient dA[.., Ci_pad] = conv(dY, W'), W'[ci][co][t'] = W[co][ci][flip t']: a stride-1 conv on the op's INPUT grid
+  // (stride-2: of the zero-stuffed dY; upsample: on the upsampled grid, pooled afterwards); C0 = Cy, the channel stride of dY
+  cm::ConvArgs da{};
+  int dMB = 1, dNB = 1;
+  bool dwino = false;          // ... a Winograd tile fits it (da then carries the tile)
+  // weight gradient of the generic kernel: the op's own geometry, one sample per tile, 32-channel rows (the parity-mode upsample
+  // conv keeps its 2x2x2 parity form: 8 taps on the low-resolution input); zsplit: two-plane grids in z-split row order -- plane z
+  // in row block z -- so that the kernel can skip the z tap on the padding plane, as the forward's z-split form does (cm_conv.hip)
+  cm::ConvArgs wa{};
+  int wMB = 1;
+  bool zsplit = false;
+};
+
+void tune_tile(cm::ConvArgs &ca, int &MB, int NB, bool wgrad) {
+  Op tmp;
+  tmp.kind = OP_CONV; tmp.ca = ca; tmp.NB = NB;
+  static Act dummy;
+  tmp.stat_act = wgrad ? &dummy : nullptr;  // the weight-gradient kernel wants one sample per tile
+  if (wgrad) tmp.ca.CK = 32;                 // ... and stages 32-channel rows whatever the forward chunking
+  pick_tile(tmp, TUNE_BATCH);
+  const int ck = ca.CK;
+  ca = tmp.ca; ca.CK = ck; MB = tmp.MB;
+}
+
+// train_setup keeps the Winograd fragments of a data gradient by these two, the route below launches by them
+bool dgrad_wino_ok(const BwdGeom &g, const BwdKnobs &k) { return g.dwino && !k.no_wino; }
+bool dgrad_wino_b6(const BwdGeom &g, const BwdCtx &ctx, const BwdKnobs &k) {
+  return dgrad_wino_ok(g, k) && ctx.precision != CM_PRECISION_F16 && !k.no_wino_b6 && !k.no_train_b6 &&
+         cm::conv_wino_b6_ok(g.da.bz, g.da.by, g.da.bx, g.Ci, g.da.Zo);
+}
+
+BwdGeom bwd_geom(const Op &op, const BwdCtx &ctx, const BwdKnobs &k) {
+  BwdGeom g;
+  const int nt = op.ref_taps, Cy = op.out_act->C, Ci_pad = op.ca.C0 + op.ca.C1;
+  g.first = op.in0 == ctx.x8; g.Co = op.ca.Co; g.Ci = g.first ? ctx.in_channels : Ci_pad;
+  cm::ConvArgs &a = g.da;
+  a.C0 = Cy; a.C1 = 0; a.Co = g.Ci;
+  a.ntaps = nt; a.td = nt == 27 ? 3 : 1; a.stride = 1; a.ups = 0; a.par = 0; a.ks = 1;
+  const int up = op.ca.par ? 2 : 1;
+  a.Zs = a.Zo = op.ca.Zs * up; a.Ys = a.Yo = op.ca.Ys * up; a.Xs = a.Xo = op.ca.Xs * up;
+  a.out_cs = Ci_pad; a.CK = pick_ck(Cy, 0);
+  a.nch0 = a.CK ? Cy / a.CK : 0; a.nch1 = 0;
+  g.dNB = g.Ci > 32 ? 2 : 1;
+  int wz = 0, wy = 0, wx = 0;
+  g.dwino = !g.first && nt == 27 && Cy % 16 == 0 && g.Ci % 32 == 0 && g.Ci == Ci_pad && (long)a.Zo * a.Yo * a.Xo > 64 &&
+            cm::conv_wino_pick(a.Zo, a.Yo, a.Xo, &wz, &wy, &wx);
+  if (dgrad_wino_ok(g, k)) {
+    a.bs = 1; a.bz = wz; a.by = wy; a.bx = wx;
+    a.ntz = a.Zo / wz; a.nty = (a.Yo + wy - 1) / wy; a.ntx = (a.Xo + wx - 1) / wx;
+  } else if (!g.first) tune_tile(a, g.dMB, g.dNB, false);
+  cm::ConvArgs &wa = g.wa;
+  wa = op.ca; wa.ks = 1;
+  tune_tile(wa, g.wMB, 1, true);
+  g.zsplit = wa.ntaps == 27 && wa.stride == 1 && !wa.par && !wa.ups && wa.Zo == 2 && wa.Zs == 2 && wa.bz == 2 && wa.by * wa.bx <= 32 && !k.no_wgrad_zsplit;
+  return g;
+}
+
+enum WgradKernel { WG_WINO, WG_PACK, WG_PAR, WG_1X1, WG_ZS, WG_GENERIC };
+enum DgradKernel { DG_NONE, DG_QR, DG_WINO, DG_GENERIC };
+struct WgradRoute { WgradKernel kernel; ConvForm form; };   // FORM_F16 on the Winograd kernel under autocast, FORM_FP32 otherwise
+struct DgradRoute { DgradKernel kernel; ConvForm form; };   // Winograd: FP32 / B6 / F16; conv_qr2: B6 (its six-term form, raw source)
+
+WgradRoute wgrad_route(const Op &op, const BwdGeom &g, const BwdCtx &ctx, const BwdKnobs &k) {
+  const cm::ConvArgs &a = op.ca;
+  const bool plain27 = op.ref_taps == 27 && a.stride == 1 && !a.par && !a.ups;
+  // the forward op is a Winograd layer: weight gradient in the Winograd domain, on f16 operands under autocast
+  if (op.wino && g.Ci % 32 == 0 && g.Co % 32 == 0 && !k.no_wino_wgrad) return {WG_WINO, (ctx.autocast && ctx.f16_frags) ? FORM_F16 : FORM_FP32};
+  // few channels on one side (first / last conv of the UNet): taps packed with the narrow side into the MFMA columns
+  if (plain27 && op.pm_off < 0 && !k.no_wgrad_pack &&
+      ((a.Co == 32 && !op.in1 && op.in0->C == 8 && !a.gn) || (a.Co <= 4 && a.C0 + a.C1 == 32 && !op.in1))) return {WG_PACK, FORM_FP32};
+  // upsample convs: parity-form kernel with all 8 tap blocks per wave
+  if (a.par && !a.gn && op.pm_off < 0 && !k.no_wgrad_par) return {WG_PAR, FORM_FP32};
+  // 1x1x1 convs (skip convs, attention projections): flat-row kernel, NKB input blocks per workgroup
+  if (op.ref_taps == 1 && a.stride == 1 && !a.par && !a.ups && !k.no_wgrad_1x1) return {WG_1X1, FORM_FP32};
+  // two-plane grids: the dedicated kernel (two input blocks per workgroup, arithmetic coordinates, one load batch per tile)
+  if (g.zsplit && !k.no_wgrad_zs_kernel && cm::wgrad_zs_ok(g.wa)) return {WG_ZS, FORM_FP32};
+  return {WG_GENERIC, FORM_FP32};
+}
+
+DgradRoute dgrad_route(const Op &op, const BwdGeom &g, const BwdCtx &ctx, const BwdKnobs &k) {
+  if (g.first) return {DG_NONE, FORM_FP32};
+  const cm::ConvArgs &a = g.da;
+  const int Cy = a.C0, Ci_pad = a.out_cs;
+  // quarter resolution (two planes): forward and data gradient of the training step on conv_qr2's six-term form
+  if (op.qr && op.d_wqr_b6 && op.ref_taps == 27 && Cy == g.Co && g.Co % 64 == 0 && g.Ci % 32 == 0 && g.Ci == Ci_pad && a.Zo == 2 &&
+      a.Yo * a.Xo <= 64 && 8 * (a.Yo + 2) * (a.Xo + 2) <= 64 * 9 && ctx.precision != CM_PRECISION_F16 && !k.no_train_qr) return {DG_QR, FORM_B6};
+  // the data gradient of a 3x3x3 conv is a stride-1 3x3x3 conv of dY with the flipped / transposed weights: same Winograd kernel.
+  // fp32 plan: the six-term bf16 form wherever the forward's tile takes it (exact three-way splits, fp32 accumulate: fp32-level
+  // products at 2.7x the matrix rate); autocast: f16 operands
+  if (dgrad_wino_ok(g, k)) {
+    if (ctx.autocast && ctx.f16_frags) return {DG_WINO, FORM_F16};
+    return {DG_WINO, dgrad_wino_b6(g, ctx, k) ? FORM_B6 : FORM_FP32};
+  }
+  return {DG_GENERIC, FORM_FP32};
 }
 
 // Which routes read / write tensors stored as _Float16, by the launch's tensor mask (h16_mask): the direct f16 conv (source, residual,
@@ -1862,7 +1997,11 @@ int cm_model_create(const cm_unet_config *cfg, cm_model **out) {
 int cm_model_destroy(cm_model *m) {
   if (!m) return 0;
   delete m->dit;
-  if (m->device < 0) { delete m; return 0; }
+  if (m->device < 0) {
+    for (void *p : m->allocs) free(p);
+    delete m;
+    return 0;
+  }
   DevGuard g(m->device);
   hipDeviceSynchronize();
   for (void *p : m->allocs) hipFree(p);

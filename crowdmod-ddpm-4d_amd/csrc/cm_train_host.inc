@@ -3,7 +3,8 @@
 // (/root/reference/models/diffusion/ddpm.py:111-121,142-144): q-sample, UNet forward with
 // Dropout3d, MSE, full backward, Adam with coupled L2.
 //
-// The backward walks the forward op list in reverse.  For a conv op
+// The backward walks the forward op list in reverse, from a plan built once (plan_backward: routes, pool regions, first writers, job
+// tables; train_setup allocates what it names, backward_ops executes it).  For a conv op
 //   out = conv(T(in0|in1)) + temb + resid,   T = pm * silu(groupnorm(.)) or identity
 // it accumulates  d resid += dY,  d temb_proj = sum_v dY,  d bias = sum dY,
 // dW = wgrad(dY, T(in)) on the matrix cores, and the data gradient
@@ -17,8 +18,164 @@
 // forward kernel, wgrad_wino_f16_kernel), the loss gradient is multiplied by 2^k and the flat gradient buffer by 2^-k at the
 // end of the pass; everything else, and every launch of a handle that never switches it on, is unchanged.
 
+namespace {
+
+// One op of the backward: what runs, on which geometry, where its sums go.  No buffer of the training state appears here:
+// train_setup allocates what an entry names (cm_train_state::Dgrad), the executor (backward_ops) joins the two.
+enum BwdTail { TAIL_ADD, TAIL_POOL, TAIL_GN };   // the data gradient reaches the inputs by a plain accumulate / the 2x2x2 sum-pool / the GroupNorm + SiLU backward
+struct BwdOp {
+  int op = -1;                                   // index in the forward list; OP_CONV and OP_ATTN entries launch
+  const Act *qa = nullptr, *oa = nullptr;        // OP_ATTN: the activations behind qkv (gradient written) and aout (gradient read)
+  BwdGeom g;
+  WgradRoute wg{WG_GENERIC, FORM_FP32};
+  DgradRoute dg{DG_NONE, FORM_FP32};
+  cm::ConvArgs wa{}; int wMB = 1;                // weight gradient: the geometry of its kernel's own tile
+  cm::WgradPackArgs pa{}; int CN = 0;            // ... of the packed-column kernel (narrow side: 4 = mirrored, the last conv; 8 = the first)
+  // partial copies of a weight-gradient launch (wgrad_groups): min(g_unit tiles per sample x B, max(g_floor, g_target / g_div) -- one
+  // full round of resident workgroups, as few partial copies as that allows --, what the partial buffer holds at per_g floats each)
+  int ncb = 1, nkb = 1, NKB = 1, g_target = 0, g_floor = 1, g_div = 1;
+  long long g_unit = 1; size_t per_g = 1;
+  BwdTail tail = TAIL_ADD;
+  size_t bias_off = 0, gn_off = 0;               // batch-sum pool: [max_batch][Co] voxel sums of dY; [max_batch][2][Ctot] gamma / beta sums (TAIL_GN)
+  bool acc_resid = false, acc_in0 = false, acc_in1 = false;   // the gradient buffer already holds a contribution: accumulate (else: first write)
+};
+struct BwdSumJob { size_t off; std::string param; int C, stride; };   // pool region, summed over the batch -> the parameter's gradient
+struct BwdCopyJob { std::string param; bool bias; int off; long long n; };   // slice of the dense_1 weight / bias gradients of all blocks -> the parameter's
+struct BwdPlan {
+  std::vector<BwdOp> ops;                        // one per forward op, in execution (reverse) order
+  size_t pool_floats = 0, attn_floats = 0;       // batch-sum pool; attention scratch at max_batch
+  std::vector<BwdSumJob> bsum; std::vector<BwdCopyJob> copy;
+  int bs_maxC = 0, vs_maxC = 0, nconv = 0; long long cp_max = 0;
+  std::string err;                               // the list cannot run
+  const BwdOp &of(size_t oi) const { return ops[ops.size() - 1 - oi]; }
+};
+
+// partial copies of entry e's weight-gradient launch at batch B; 0 (and the error text set) when the partial buffer holds none
+int wgrad_groups(const BwdOp &e, int B, size_t wpart_floats) {
+  const long long units = e.wg.kernel == WG_1X1 ? ((long long)B * e.g_unit + 127) / 128 : (long long)B * e.g_unit;
+  const long long G = std::min<long long>(std::min<long long>(units, std::max(e.g_floor, e.g_target / e.g_div)), (long long)(wpart_floats / e.per_g));
+  if (G < 1) fail("wgrad partial buffer too small");
+  return (int)std::max<long long>(G, 0);
+}
+
+// the weight-gradient part of a conv entry: tile and partial-copy constants of the routed kernel
+std::string plan_wgrad(const Op &op, const BwdKnobs &k, BwdOp &e) {
+  const int Co = op.ca.Co;
+  cm::ConvArgs &wa = e.wa;
+  wa = e.g.wa; e.wMB = e.g.wMB;
+  e.ncb = (Co + 31) / 32; e.nkb = (wa.C0 + wa.C1 + 31) / 32;
+  const int nn = e.ncb * e.nkb;
+  auto tiles = [&] { return (long long)wa.ntz * wa.nty * wa.ntx; };
+  switch (e.wg.kernel) {
+    case WG_WINO:
+      wa = op.ca; wa.bs = 1; wa.ks = 1;
+      if (!cm::conv_wino_pick(wa.Zo, wa.Yo, wa.Xo, &wa.bz, &wa.by, &wa.bx)) return "no Winograd tile for the weight gradient of " + op.label;
+      wa.ntz = wa.Zo / wa.bz; wa.nty = (wa.Yo + wa.by - 1) / wa.by; wa.ntx = (wa.Xo + wa.bx - 1) / wa.bx;
+      e.g_unit = tiles(); e.per_g = (size_t)nn * 48 * 1024; e.g_target = k.wino_wgs; e.g_floor = 1; e.g_div = nn;
+      break;
+    case WG_PACK: {
+      cm::WgradPackArgs &pa = e.pa;
+      pa.mirror = Co <= 4; e.CN = pa.mirror ? 4 : 8; pa.cn_valid = pa.mirror ? Co : e.g.Ci;
+      pa.Z = op.ca.Zo; pa.Y = op.ca.Yo; pa.X = op.ca.Xo;
+      pa.bz = std::min(pa.Z, 8); pa.by = std::min(pa.Y, 4); pa.bx = std::min(pa.X, 6);
+      if ((pa.bz * pa.by * pa.bx) & 1) pa.bx += 1;   // (an even number of rows: voxel pairs; rows outside the grid are zero)
+      pa.ntz = (pa.Z + pa.bz - 1) / pa.bz; pa.nty = (pa.Y + pa.by - 1) / pa.by; pa.ntx = (pa.X + pa.bx - 1) / pa.bx;
+      e.g_unit = (long long)pa.ntz * pa.nty * pa.ntx; e.per_g = (size_t)((27 * e.CN + 31) / 32) * 1024; e.g_target = 256;
+      break;
+    }
+    case WG_PAR:
+      wa.bz = std::min(wa.Zs, 4); wa.by = std::min(wa.Ys, 6); wa.bx = std::min(wa.Xs, wa.Zs <= 2 ? 9 : 6);
+      wa.ntz = (wa.Zs + wa.bz - 1) / wa.bz; wa.nty = (wa.Ys + wa.by - 1) / wa.by; wa.ntx = (wa.Xs + wa.bx - 1) / wa.bx;
+      e.g_unit = tiles(); e.per_g = (size_t)nn * 64 * 1024; e.g_target = k.par_wgs; e.g_floor = 2; e.g_div = 8 * nn;
+      break;
+    case WG_1X1:
+      e.NKB = e.nkb % 4 == 0 ? 4 : (e.nkb % 3 == 0 ? 3 : (e.nkb % 2 == 0 ? 2 : 1));
+      e.g_unit = op.out_act->V(); e.per_g = (size_t)nn * 1024; e.g_target = k.x1_wgs; e.g_floor = 4; e.g_div = e.ncb * (e.nkb / e.NKB);
+      break;
+    case WG_ZS: case WG_GENERIC:
+      if (e.g.zsplit) { wa.zsplit = 1; e.wMB = 2; }
+      e.g_unit = tiles(); e.g_floor = 4;
+      e.per_g = (size_t)nn * (wa.par ? 64 : (op.ref_taps == 1 ? 4 : op.ref_taps)) * 1024;   // parity form: 8 classes x 8 taps per group; 1x1x1: 4 per-wave partials
+      if (e.wg.kernel == WG_ZS) { e.g_target = k.zs_wgs; e.g_div = e.ncb * ((e.nkb + 1) / 2); }   // two input blocks per workgroup
+      else { e.g_target = k.wgs; e.g_div = nn; }
+      break;
+  }
+  return "";
+}
+
+// The backward sibling of plan_forward: everything the backward's launches depend on, decided in one walk over the op list in
+// reverse -- each conv's two routes (wgrad_route, dgrad_route), the partial-copy constants, every region of the batch-sum pool, who
+// writes each gradient buffer first, the job tables of the deferred sums.  Pure: allocates nothing, launches nothing.
+BwdPlan plan_backward(const std::vector<Op> &ops, const BwdCtx &ctx, const BwdKnobs &k) {
+  BwdPlan P;
+  std::map<const Act *, int> have{{ctx.seed, -1}};   // gradient buffers that hold a contribution so far -> the forward op that wrote first (-1: the loss gradient)
+  auto first_write = [&](const Act *a, int oi) { return have.emplace(a, oi).second; };
+  for (int oi = (int)ops.size() - 1; oi >= 0 && P.err.empty(); --oi) {
+    const Op &op = ops[oi];
+    P.ops.emplace_back();
+    BwdOp &e = P.ops.back();
+    e.op = oi;
+    if (op.kind == OP_ATTN) {
+      // qkv is the op's input tensor, aout its output: their activations are the neighbouring convs' output / source
+      for (const Op &o : ops) {
+        if (o.kind == OP_CONV && o.out_act->d == op.qkv) e.qa = o.out_act;
+        if (o.kind == OP_CONV && o.in0->d == op.aout) e.oa = o.in0;
+      }
+      if (!e.qa || !e.oa || !have.count(e.oa)) { P.err = "attention backward: missing gradient (" + op.label + ")"; break; }
+      P.attn_floats = std::max(P.attn_floats, cm::attn_bwd_scratch_floats(ctx.max_batch, op.S, op.E, ATTN_HEADS));
+      have.emplace(e.qa, oi);
+      continue;
+    }
+    if (op.kind != OP_CONV) continue;
+    if (!have.count(op.out_act)) { P.err = "backward: no gradient reached " + op.label; break; }
+    ++P.nconv;
+    const int Co = op.ca.Co, Ctot = op.ca.C0 + op.ca.C1;
+    e.g = bwd_geom(op, ctx, k);
+    e.wg = wgrad_route(op, e.g, ctx, k);
+    e.dg = dgrad_route(op, e.g, ctx, k);
+    if (op.resid_act) e.acc_resid = !first_write(op.resid_act, oi);
+    // bias gradient and the broadcast time-embedding term: voxel sums of dY, which stays intact until the end of the pass (every
+    // act owns its buffer and all of its consumers have already contributed)
+    e.bias_off = P.pool_floats; P.pool_floats += (size_t)ctx.max_batch * Co;
+    P.bsum.push_back({e.bias_off, op.bname, Co, Co});
+    P.vs_maxC = std::max(P.vs_maxC, Co); P.bs_maxC = std::max(P.bs_maxC, Co);
+    P.err = plan_wgrad(op, k, e);
+    if (e.dg.kernel == DG_NONE || !P.err.empty()) continue;
+    if (dgrad_wino_ok(e.g, k) && !cm::conv_wino_ok(e.g.da)) P.err = "Winograd data-gradient tile does not fit " + op.label;
+    if (e.dg.kernel == DG_QR) {
+      static float set;
+      cm::QrArgs q{};
+      q.C0 = e.g.da.C0; q.raw = 1; q.groups = 8; q.wq6 = &set; q.out_cs = e.g.da.out_cs; q.Co = e.g.da.Co; q.Y = e.g.da.Yo; q.X = e.g.da.Xo;
+      if (!cm::conv_qr2_b6_ok(q)) P.err = "quarter-resolution data gradient of " + op.label + ": no six-term form";
+    }
+    e.tail = op.ca.par ? TAIL_POOL : op.gn_op >= 0 ? TAIL_GN : TAIL_ADD;
+    if (e.tail == TAIL_GN) {
+      const Op &gop = ops[op.gn_op];
+      e.gn_off = P.pool_floats; P.pool_floats += (size_t)ctx.max_batch * 2 * Ctot;
+      P.bsum.push_back({e.gn_off, gop.gname, Ctot, 2 * Ctot});
+      P.bsum.push_back({e.gn_off + Ctot, gop.bename, Ctot, 2 * Ctot});
+      P.bs_maxC = std::max(P.bs_maxC, Ctot);
+      e.acc_in1 = op.in1 && have.count(op.in1);
+    }
+    e.acc_in0 = !first_write(op.in0, oi);
+    if (op.in1 && e.tail != TAIL_POOL) { const bool fw = first_write(op.in1, oi); if (e.tail == TAIL_ADD) e.acc_in1 = !fw; }
+  }
+  // the per-block slices of the time-projection gradients -> their parameters' slots (conv_1 of every ResnetBlock, forward order)
+  for (const Op &op : ops)
+    if (op.kind == OP_CONV && op.temb_off >= 0) {
+      const std::string prefix = op.wname.substr(0, op.wname.size() - std::string(".conv_1.weight").size());
+      P.copy.push_back({prefix + ".dense_1.weight", false, op.temb_off, (long long)op.ca.Co * ctx.tx});
+      P.copy.push_back({prefix + ".dense_1.bias", true, op.temb_off, (long long)op.ca.Co});
+      P.cp_max = std::max(P.cp_max, (long long)op.ca.Co * ctx.tx);
+    }
+  return P;
+}
+
+}  // namespace
+
 struct cm_train_state {
-  std::set<const Act *> gset;  // backward pass: tensors whose gradient buffer has received a contribution
+  BwdKnobs knobs;             // the backward's diagnostic switches, read once (cm_train_init)
+  BwdPlan bwd;                 // what the backward launches, decided once from the op list (plan_backward)
   // master weights, gradients, Adam moments; frozen: the sinusoid table, first tensor of the state_dict (requires_grad False, embeddings.py:24)
   OptStore opt;
   float dropout = 0.1f;  // nn.Dropout3d(p) of the ResnetBlocks (layers.py:42), cfg DROPOUT_RATE
@@ -35,43 +192,32 @@ struct cm_train_state {
   cm::WinoPackJob *d_wjobs16 = nullptr;   // autocast: the same jobs writing the f16 fragments (wino_pack_jobs_f16_kernel; same workgroup map)
   int njobs = 0;
   long long pack_total = 0;
-  // per conv op: data-gradient launch
+  // per conv op: the device buffers its plan entry (BwdOp) names
   struct Dgrad {
-    bool have = false;
-    cm::ConvArgs ca{};
-    int MB = 1, NB = 1;
-    int *d_hv = nullptr, *d_mt = nullptr;
+    int *d_hv = nullptr, *d_mt = nullptr;   // data gradient on the generic kernel: coordinate tables, fragments, a zero bias
     float *wfrag = nullptr, *zero_bias = nullptr;
-    bool wino = false;          // stride-1 3x3x3 data gradient on an even in-plane grid: Winograd kernel (cm_conv_wino.hip)
-    float *wwino = nullptr;
+    float *wwino = nullptr;     // ... on the Winograd kernel (cm_conv_wino.hip): transformed weights
     float *wwino_b6 = nullptr;  // six-term bf16 split of wwino (pack_wino_b6 order), re-derived after every optimizer step
     long long wwino_floats = 0;
     float *wwino16 = nullptr;   // autocast: f16 sibling of wwino_b6 (pack_wino_f16 order), allocated when mode 1 is first set
     // two-plane grids: the data gradient on the whole-sample kernel conv_qr2 in its six-term form (no normalisation: `raw`)
-    bool qr = false;
     float *wqr = nullptr, *wqr_b6 = nullptr;
-    long long wqr_floats = 0;
-    bool wwg = false;           // weight gradient in the Winograd domain (the forward op is a Winograd layer)
-    cm::ConvArgs wwa{};
-    // weight-gradient geometry when it differs from the forward op (parity / upsample convs)
-    bool own_wgeom = false;
-    cm::ConvArgs wa{};
-    int wMB = 1;
-    int *w_hv = nullptr, *w_mt = nullptr;
+    long long wqr_floats = 0; int wqr_C0 = 0;   // (C0: the input channels of the data gradient = Cy)
+    int *w_hv = nullptr, *w_mt = nullptr;   // weight gradient: coordinate tables of its own tile
   };
   std::vector<Dgrad> dg;  // indexed like m->ops
   // scratch
   float *scrA = nullptr, *scrB = nullptr, *scrC = nullptr;  // [B][Vfull][Cmax]
   float *wpart = nullptr; size_t wpart_floats = 0;
   float *tmp_bc = nullptr;       // [B][Cmax]
-  cm::CopyJob *d_cp_jobs = nullptr; int n_cp_jobs = 0; long long cp_max = 0;
-  float *attn_big = nullptr; size_t attn_big_floats = 0;   // S x S scratch of the attention backward at large token counts
+  cm::CopyJob *d_cp_jobs = nullptr;
+  float *attn_big = nullptr;     // S x S scratch of the attention backward at large token counts (BwdPlan::attn_floats)
   // deferred batch reductions: every conv / GroupNorm of the backward pass leaves its per-sample sums in its own region
-  // of bs_pool; one job-table launch at the end turns them into the parameter gradients (the table is recorded during
-  // the first pass: the op sequence, region offsets and strides never change, only B, which is a launch argument)
-  float *bs_pool = nullptr; size_t bs_pool_floats = 0, bs_cursor = 0;
-  std::vector<cm::BsumJob> bs_jobs; cm::BsumJob *d_bs_jobs = nullptr; bool bs_ready = false; int bs_maxC = 0;
-  std::vector<cm::VsumJob> vs_jobs; cm::VsumJob *d_vs_jobs = nullptr; int vs_maxC = 0;   // the per-sample voxel sums feeding them, deferred the same way
+  // of bs_pool; one job-table launch at the end turns them into the parameter gradients (the plan fixes the regions and the
+  // jobs, train_setup uploads the tables: only B, a launch argument, changes between steps)
+  float *bs_pool = nullptr;
+  cm::BsumJob *d_bs_jobs = nullptr;
+  cm::VsumJob *d_vs_jobs = nullptr;   // the per-sample voxel sums feeding them, deferred the same way
   float *vs_part = nullptr;      // [16][B][Cmax] voxel-slice partials of the bias / time-row gradient sums
   float *dproj = nullptr;        // [B][nproj]
   float *train_temb = nullptr;   // [B][nproj] forward projection of the batch's timesteps
@@ -139,23 +285,16 @@ int add_derived_wino(cm_model *m, float *dst, const std::vector<int> &idx27, int
   return 0;
 }
 
-int tune_launch(cm_model *m, cm::ConvArgs &ca, int &MB, int NB, int *&d_hv, int *&d_mt, bool wgrad) {
-  Op tmp;
-  tmp.kind = OP_CONV; tmp.ca = ca; tmp.NB = NB;
-  static Act dummy;
-  tmp.stat_act = wgrad ? &dummy : nullptr;  // the weight-gradient kernel wants one sample per tile
-  if (wgrad) tmp.ca.CK = 32;                 // ... and stages 32-channel rows whatever the forward chunking
-  pick_tile(tmp, TUNE_BATCH);
-  const int ck = ca.CK;
-  ca = tmp.ca; ca.CK = ck; MB = tmp.MB;
+int upload_ints(cm_model *m, const std::vector<int> &h, int **d) {
+  if (dev_alloc(m, (void **)d, h.size() * sizeof(int))) return 1;
+  CM_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+  return 0;
+}
+// the box coordinate tables of a tile the plan picked (tune_tile)
+int upload_tables(cm_model *m, const cm::ConvArgs &ca, int MB, int **d_hv, int **d_mt) {
   std::vector<int> hv((size_t)cm::conv_halo_voxels(ca)), mt((size_t)32 * MB);
   cm::conv_build_tables(ca, MB, hv.data(), mt.data());
-  if (dev_alloc(m, (void **)&d_hv, hv.size() * sizeof(int))) return 1;
-  if (dev_alloc(m, (void **)&d_mt, mt.size() * sizeof(int))) return 1;
-  CM_HIP(hipMemcpy(d_hv, hv.data(), hv.size() * sizeof(int), hipMemcpyHostToDevice));
-  CM_HIP(hipMemcpy(d_mt, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice));
-  ca.hvtab = d_hv; ca.mtab = d_mt;
-  return 0;
+  return upload_ints(m, hv, d_hv) || upload_ints(m, mt, d_mt);
 }
 
 // The h2 fragments (f16 two-way splits of w * 2^k, cm_model.cpp: add_conv) re-derived from the MASTER weights of a handle that has
@@ -215,15 +354,16 @@ int repack_f16(cm_model *m, hipStream_t st) {
   return 0;
 }
 
-// the loss-scale exponent of a step at batch B: the requested one, or the largest k with 2^k <= B*C*H*W*F (loss gradient O(1))
-int autocast_scale_log2(const cm_model *m, int B) {
-  const cm_train_state *T = m->train;
-  if (T->ls_req >= 0) return T->ls_req;
-  const cm_unet_config &c = m->cfg;
-  const long long N = (long long)B * c.out_channels * c.rows * c.cols * c.future_len;
+// the loss-scale exponent of an autocast step over N loss elements (UNet and DiT4D trainers): the requested one, or the largest k
+// with 2^k <= N (loss gradient O(1))
+int loss_scale_log2(int ls_req, long long N) {
   int k = 0;
   while (k < 24 && (2LL << k) <= N) ++k;
-  return k;
+  return ls_req >= 0 ? ls_req : k;
+}
+int autocast_scale_log2(const cm_model *m, int B) {
+  const cm_unet_config &c = m->cfg;
+  return loss_scale_log2(m->train->ls_req, (long long)B * c.out_channels * c.rows * c.cols * c.future_len);
 }
 
 int repack_all(cm_model *m, hipStream_t st) {
@@ -277,15 +417,28 @@ int repack_all(cm_model *m, hipStream_t st) {
   }
   for (auto &D : T->dg) {
     if (D.wwino_b6) CM_HIP(cm::launch_wino_b6_repack(D.wwino, D.wwino_b6, D.wwino_floats, st));
-    if (D.qr) CM_HIP(cm::launch_qr_b6_repack(D.wqr, D.wqr_b6, D.wqr_floats, D.ca.C0, st));
+    if (D.wqr_b6) CM_HIP(cm::launch_qr_b6_repack(D.wqr, D.wqr_b6, D.wqr_floats, D.wqr_C0, st));
   }
   return T->autocast ? repack_f16(m, st) : 0;
 }
 
+BwdCtx bwd_ctx(const cm_model *m) {
+  BwdCtx x;
+  x.precision = m->precision; x.max_batch = m->cfg.max_batch; x.in_channels = m->cfg.in_channels;
+  x.tx = m->cfg.base_channels * m->cfg.time_multiple; x.x8 = m->x8_act; x.seed = m->act_by_name.at("final");   // (written by mse_grad)
+  if (m->train) { x.autocast = m->train->autocast != 0; x.f16_frags = m->train->ac_ready; }
+  return x;
+}
+
+// The plan first; then the buffers it names, in forward op order (the order of `derived` / `derived_wino` is that of the re-pack
+// job tables, which cm_train_set_autocast checks).
 int train_setup(cm_model *m) {
   cm_train_state *T = m->train;
   const cm_unet_config &c = m->cfg;
   const size_t B = (size_t)c.max_batch;
+  T->knobs = read_bwd_knobs();
+  T->bwd = plan_backward(m->ops, bwd_ctx(m), T->knobs);
+  if (!T->bwd.err.empty()) return fail("%s", T->bwd.err.c_str());
   if (T->opt.init(m->params, {0}, false, [&](float **p, size_t n) { return dev_alloc(m, (void **)p, n * sizeof(float)); })) return 1;
 
   // ---- activation gradients, GroupNorm mean/rstd, maximal channel count ----
@@ -313,13 +466,8 @@ int train_setup(cm_model *m) {
   for (float **b : {&T->scrA, &T->scrB, &T->scrC})
     if (dev_alloc(m, (void **)b, B * smax * sizeof(float))) return 1;
   if (dev_alloc(m, (void **)&T->tmp_bc, B * Cmax * sizeof(float))) return 1;
-  {
-    size_t need = 0;
-    for (auto &op : m->ops)
-      if (op.kind == OP_CONV) need += B * ((size_t)op.ca.Co + 2 * (size_t)(op.ca.C0 + op.ca.C1));
-    T->bs_pool_floats = need;
-    if (dev_alloc(m, (void **)&T->bs_pool, need * sizeof(float))) return 1;
-  }
+  if (dev_alloc(m, (void **)&T->bs_pool, T->bwd.pool_floats * sizeof(float))) return 1;
+  if (T->bwd.attn_floats && dev_alloc(m, (void **)&T->attn_big, T->bwd.attn_floats * sizeof(float))) return 1;
   if (dev_alloc(m, (void **)&T->vs_part, 16 * B * Cmax * sizeof(float))) return 1;
   if (dev_alloc(m, (void **)&T->dproj, B * m->nproj * sizeof(float))) return 1;
   if (dev_alloc(m, (void **)&T->train_temb, B * m->nproj * sizeof(float))) return 1;
@@ -403,98 +551,49 @@ int train_setup(cm_model *m) {
       for (int i = 0; i < Co; ++i) ib[i] = (int)(off_of(m, op.bname) + i);
       if (add_derived(m, const_cast<float *>(op.ca.bias), ib, 1)) return 1;
     }
-    // ---- data gradient: dA[.., Ctot_in] = conv(dY, W'),  W'[ci][co][t'] = W[co][ci][flip t'] ----
+    // ---- what the op's plan entry names: fragments and tables of its data gradient (BwdGeom::da), tables of its weight gradient ----
     cm_train_state::Dgrad &D = T->dg[oi];
-    const bool first = (op.in0 == m->x8_act);
-    const int Cy = op.out_act->C;  // channel stride of dY (>= Co)
-    if (!first) {
-      D.have = true;
-      std::vector<int> src((size_t)Ci * Co * nt);
+    const BwdOp &e = T->bwd.of(oi);
+    const BwdGeom &g = e.g;
+    op.train_qr = e.dg.kernel == DG_QR;              // the training forward takes conv_qr2 where the data gradient does (conv_route)
+    if (!g.first) {
+      const int Cy = g.da.C0;
+      std::vector<int> src((size_t)Ci * Co * nt);    // W'[ci][co][t'] = W[co][ci][flip t']
       for (int ci = 0; ci < Ci; ++ci)
         for (int co = 0; co < Co; ++co)
           for (int t = 0; t < nt; ++t) src[((size_t)ci * Co + co) * nt + t] = ii[((size_t)co * Ci + ci) * nt + (nt - 1 - t)];
-      cm::ConvArgs &a = D.ca;
-      a = cm::ConvArgs{};
-      a.C0 = Cy; a.C1 = 0; a.Co = Ci;
-      a.ntaps = nt; a.td = nt == 27 ? 3 : 1; a.stride = 1; a.ups = 0; a.par = 0; a.ks = 1;
-      // spatial dims: the data gradient lives on the conv's INPUT grid (stride-2: zero-stuffed dY;
-      // upsample: the upsampled grid, pooled afterwards)
-      const int up = op.ca.par ? 2 : 1;
-      a.Zs = a.Zo = op.ca.Zs * up; a.Ys = a.Yo = op.ca.Ys * up; a.Xs = a.Xo = op.ca.Xs * up;
-      a.out_cs = Ci_pad; a.CK = pick_ck(Cy, 0);
-      a.nch0 = Cy / a.CK; a.nch1 = 0;
-      D.NB = Ci > 32 ? 2 : 1;
-      const std::vector<int> pidx = pack_conv(src.data(), Ci, Co, nt, Cy, a.CK, D.NB, -1);
+      const std::vector<int> pidx = pack_conv(src.data(), Ci, Co, nt, Cy, g.da.CK, g.dNB, -1);
       if (dev_alloc(m, (void **)&D.wfrag, pidx.size() * sizeof(float))) return 1;
       if (add_derived(m, D.wfrag, pidx, 1, true)) return 1;
-      const int TN = 32 * D.NB, cop = (Ci + TN - 1) / TN * TN;
+      const int TN = 32 * g.dNB, cop = (Ci + TN - 1) / TN * TN;
       std::vector<float> zb((size_t)cop, 0.f);
       if (upload(m, zb, &D.zero_bias)) return 1;
-      a.wfrag = D.wfrag; a.bias = D.zero_bias;
-      int wz = 0, wy = 0, wx = 0;
-      if (nt == 27 && Cy % 16 == 0 && Ci % 32 == 0 && Ci == Ci_pad && (long)a.Zo * a.Yo * a.Xo > 64 &&
-          cm::conv_wino_pick(a.Zo, a.Yo, a.Xo, &wz, &wy, &wx) && !cm::diag_env("CM_NO_WINO")) {
-        // the data gradient of a 3x3x3 conv is a stride-1 3x3x3 conv of dY with the flipped / transposed weights:
-        // same Winograd kernel, its transformed weights re-derived from the master copy after every update
-        D.wino = true;
+      if (dgrad_wino_ok(g, T->knobs)) {
+        // the Winograd kernel's transformed weights, re-derived from the master copy after every update, and their six-term split
         const size_t nel = (size_t)((Ci + 31) / 32) * (Cy / 16) * 4 * 24 * 64 * 4;
         if (dev_alloc(m, (void **)&D.wwino, nel * sizeof(float))) return 1;
         if (add_derived_wino(m, D.wwino, src, Ci, Co, Cy)) return 1;
         D.wwino_floats = (long long)nel;
-        // fp32 plan: the data gradient takes the six-term bf16 form wherever the forward's tile does (exact three-way
-        // splits, fp32 accumulate: fp32-level products at 2.7x the matrix rate)
-        if (m->precision != CM_PRECISION_F16 && !cm::diag_env("CM_NO_WINO_B6") && !cm::diag_env("CM_NO_TRAIN_B6") &&
-            cm::conv_wino_b6_ok(wz, wy, wx, Ci, a.Zo) && dev_alloc(m, (void **)&D.wwino_b6, nel * 3 / 2 * sizeof(float)))
-          return 1;
-        a.bs = 1; a.bz = wz; a.by = wy; a.bx = wx;
-        a.ntz = a.Zo / wz; a.nty = (a.Yo + wy - 1) / wy; a.ntx = (a.Xo + wx - 1) / wx;
-        if (!cm::conv_wino_ok(a)) return fail("Winograd data-gradient tile does not fit %s", op.label.c_str());
-      } else if (tune_launch(m, a, D.MB, D.NB, D.d_hv, D.d_mt, false)) return 1;
-      // quarter resolution (two planes): forward and data gradient of the training step on conv_qr2's six-term form
-      if (op.qr && op.d_wqr_b6 && nt == 27 && Cy == Co && Co % 64 == 0 && Ci % 32 == 0 && Ci == Ci_pad && a.Zo == 2 &&
-          a.Yo * a.Xo <= 64 && 8 * (a.Yo + 2) * (a.Xo + 2) <= 64 * 9 && m->precision != CM_PRECISION_F16 && !cm::diag_env("CM_NO_TRAIN_QR")) {
-        op.train_qr = true;
+        if (dgrad_wino_b6(g, bwd_ctx(m), T->knobs) && dev_alloc(m, (void **)&D.wwino_b6, nel * 3 / 2 * sizeof(float))) return 1;
+      } else if (upload_tables(m, g.da, g.dMB, &D.d_hv, &D.d_mt)) return 1;
+      if (e.dg.kernel == DG_QR) {
         const int ntn = Ci / 32, cw = Co / 8, nsw = (cw + 15) >> 4;
         const std::vector<int> wq = pack_qr(src, Ci, Co);                 // dgrad output channels Ci, input channels Co (= Cy)
-        D.wqr_floats = (long long)wq.size();
+        D.wqr_floats = (long long)wq.size(); D.wqr_C0 = Cy;
         if (dev_alloc(m, (void **)&D.wqr, wq.size() * sizeof(float))) return 1;
         if (add_derived(m, D.wqr, wq, 1, true)) return 1;
         const size_t n6 = (size_t)ntn * 8 * nsw * 9 * 3 * 3 * 64 * 4;      // pack_qr_b6 order, padded steps stay zero
         if (dev_alloc(m, (void **)&D.wqr_b6, n6 * sizeof(float))) return 1;
         CM_HIP(hipMemset(D.wqr_b6, 0, n6 * sizeof(float)));
-        D.qr = true;
       }
     }
-    // weight-gradient geometry (one sample per tile; the parity-mode upsample conv is taken in
-    // its plain 27-tap form over the materialised upsampled input)
-    if (op.wino && Ci % 32 == 0 && Co % 32 == 0 && !cm::diag_env("CM_NO_WINO_WGRAD")) {
-      D.wwg = true;
-      D.wwa = op.ca;
-      cm::ConvArgs &w2 = D.wwa;
-      w2.bs = 1; w2.ks = 1;
-      if (!cm::conv_wino_pick(w2.Zo, w2.Yo, w2.Xo, &w2.bz, &w2.by, &w2.bx)) return fail("no Winograd tile for the weight gradient of %s", op.label.c_str());
-      w2.ntz = w2.Zo / w2.bz; w2.nty = (w2.Yo + w2.by - 1) / w2.by; w2.ntx = (w2.Xo + w2.bx - 1) / w2.bx;
-    }
-    {
-      D.own_wgeom = true;
-      cm::ConvArgs &wa = D.wa;
-      wa = op.ca;
-      wa.ks = 1;   // (parity-mode upsample convs keep their 2x2x2 parity form: 8 taps on the low-resolution input)
-      if (tune_launch(m, wa, D.wMB, 1, D.w_hv, D.w_mt, true)) return 1;
-      // two-plane grids (quarter resolution): z-split row order -- plane z in row block z -- so that the kernel can
-      // skip the z tap on the padding plane, as the forward's z-split form does (cm_conv.hip)
-      if (wa.ntaps == 27 && wa.stride == 1 && !wa.par && !wa.ups && wa.Zo == 2 && wa.Zs == 2 && wa.bz == 2 && wa.by * wa.bx <= 32 &&
-          !cm::diag_env("CM_NO_WGRAD_ZSPLIT")) {
-        std::vector<int> mt(64, -1);
-        for (int z = 0; z < 2; ++z)
-          for (int y = 0; y < wa.by; ++y)
-            for (int x = 0; x < wa.bx; ++x) mt[(size_t)z * 32 + y * wa.bx + x] = (z << 18) | (y << 9) | x;
-        if (dev_alloc(m, (void **)&D.w_mt, mt.size() * sizeof(int))) return 1;
-        CM_HIP(hipMemcpy(D.w_mt, mt.data(), mt.size() * sizeof(int), hipMemcpyHostToDevice));
-        wa.mtab = D.w_mt;
-        wa.zsplit = 1;
-        D.wMB = 2;
-      }
+    if (upload_tables(m, g.wa, g.wMB, &D.w_hv, &D.w_mt)) return 1;
+    if (g.zsplit) {
+      std::vector<int> mt(64, -1);
+      for (int z = 0; z < 2; ++z)
+        for (int y = 0; y < g.wa.by; ++y)
+          for (int x = 0; x < g.wa.bx; ++x) mt[(size_t)z * 32 + y * g.wa.bx + x] = (z << 18) | (y << 9) | x;
+      if (upload_ints(m, mt, &D.w_mt)) return 1;
     }
   }
   // time-embedding MLP copies
@@ -515,6 +614,24 @@ int train_setup(cm_model *m) {
     if (add_derived(m, m->d_time[5], wd, 1)) return 1;
     if (add_derived(m, m->d_time[6], bd, 1)) return 1;
   }
+  // the plan's job tables of the deferred sums, as device tables
+  {
+    std::vector<cm::VsumJob> vs; std::vector<cm::BsumJob> bs; std::vector<cm::CopyJob> cp;
+    for (const BwdOp &e : T->bwd.ops) {
+      const Op &op = m->ops[e.op];
+      if (op.kind != OP_CONV) continue;
+      const int Co = op.ca.Co;
+      vs.push_back({op.out_act->g, op.out_act->V(), Co, op.out_act->C, T->bs_pool + e.bias_off, Co, op.temb_off >= 0 ? T->dproj + op.temb_off : nullptr, m->nproj});
+    }
+    for (const BwdSumJob &j : T->bwd.bsum) bs.push_back({T->bs_pool + j.off, grad_of(m, j.param), j.C, j.stride});
+    for (const BwdCopyJob &j : T->bwd.copy)
+      cp.push_back({grad_of(m, j.param), j.bias ? T->dbd_all + j.off : T->dWd_all + (size_t)j.off * tx, j.n});
+    if (dev_alloc(m, (void **)&T->d_vs_jobs, vs.size() * sizeof(cm::VsumJob)) || dev_alloc(m, (void **)&T->d_bs_jobs, bs.size() * sizeof(cm::BsumJob)) ||
+        dev_alloc(m, (void **)&T->d_cp_jobs, cp.size() * sizeof(cm::CopyJob))) return 1;
+    CM_HIP(hipMemcpy(T->d_vs_jobs, vs.data(), vs.size() * sizeof(cm::VsumJob), hipMemcpyHostToDevice));
+    CM_HIP(hipMemcpy(T->d_bs_jobs, bs.data(), bs.size() * sizeof(cm::BsumJob), hipMemcpyHostToDevice));
+    CM_HIP(hipMemcpy(T->d_cp_jobs, cp.data(), cp.size() * sizeof(cm::CopyJob), hipMemcpyHostToDevice));
+  }
   // every derived tensor (forward fragments included) is rebuilt from the master copy by the same
   // kernel that re-packs after an optimizer step, so a handle resumed from a checkpoint continues
   // bit-identically to the handle that wrote it
@@ -523,9 +640,9 @@ int train_setup(cm_model *m) {
   return 0;
 }
 
-// accumulate a channels-last gradient slice into an activation's gradient buffer
-int accum_act(cm_model *m, const Act *a, const float *src, int src_cs, int B, hipStream_t st) {
-  CM_HIP(cm::launch_add_into(a->g, a->C, src, src_cs, a->C, (long long)B * a->V(), m->train->gset.insert(a).second ? 0 : 1, st));
+// accumulate a channels-last gradient slice into an activation's gradient buffer (acc = 0: first write)
+int accum_act(const Act *a, const float *src, int src_cs, int B, bool acc, hipStream_t st) {
+  CM_HIP(cm::launch_add_into(a->g, a->C, src, src_cs, a->C, (long long)B * a->V(), acc ? 1 : 0, st));
   return 0;
 }
 
@@ -539,216 +656,101 @@ int backward_ops(cm_model *m, int B, hipStream_t st) {
   return rc;
 }
 
-int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
+// The weight gradient of one conv entry on the kernel its route names, into the parameter's gradient.  Inputs: dY and forward activations.
+int run_wgrad(cm_model *m, const BwdOp &e, int B, hipStream_t wst) {
   cm_train_state *T = m->train;
-  std::set<const Act *> &gset = T->gset;
-  gset = {m->act_by_name.at("final")};      // written by mse_grad
-  T->bs_cursor = 0;
-  if (!T->bs_ready) {
-    // the deferred job tables are appended during the first COMPLETE pass: a first pass that returned early (an
-    // allocation failure, a partial buffer too small) must not leave half a table behind for the next call to extend
-    T->bs_jobs.clear();
-    T->vs_jobs.clear();
-    T->bs_maxC = T->vs_maxC = 0;
-  }
-  CM_HIP(hipMemsetAsync(T->dproj, 0, (size_t)B * m->nproj * sizeof(float), st));
-  static const bool one_stream = cm::diag_env("CM_WGRAD_ONE_STREAM") != nullptr;
-  hipStream_t wst = (one_stream || !m->lane_stream[1]) ? st : m->lane_stream[1];
-  if (wst != st && !T->ev_dy) {
-    CM_HIP(hipEventCreateWithFlags(&T->ev_dy, hipEventDisableTiming));
-    CM_HIP(hipEventCreateWithFlags(&T->ev_wdone, hipEventDisableTiming));
-  }
-  static const bool sync_ops = cm::diag_env("CM_SYNC_OPS") != nullptr;   // debugging: name every op and drain the device after it
-  for (int oi = (int)m->ops.size() - 1; oi >= 0; --oi) {
-    Op &op = m->ops[oi];
-    if (sync_ops) {
-      const hipError_t e = hipDeviceSynchronize();
-      fprintf(stderr, "[cm] backward reaches op %d %s (%s)\n", oi, op.label.c_str(), hipGetErrorString(e));
-      fflush(stderr);
-    }
-    if (op.kind == OP_ATTN) {
-      // qkv is the op's input tensor, aout its output: locate their activations by pointer
-      Act *qa = nullptr, *oa = nullptr;
-      for (auto &a : m->acts) { if (a->d == op.qkv) qa = a.get(); if (a->d == op.aout) oa = a.get(); }
-      if (!qa || !oa || !gset.count(oa)) return fail("attention backward: missing gradient");
-      const size_t need = cm::attn_bwd_scratch_floats(m->cfg.max_batch, op.S, op.E, ATTN_HEADS);
-      if (need > T->attn_big_floats) {              // (large token counts only: the S x S matrices go to a global slab)
-        if (dev_alloc(m, (void **)&T->attn_big, need * sizeof(float))) return 1;
-        T->attn_big_floats = need;
-      }
-      CM_HIP(cm::launch_attn_bwd(op.qkv, oa->g, qa->g, B, op.S, op.E, ATTN_HEADS, need ? T->attn_big : nullptr, st));
-      gset.insert(qa);
-      continue;
-    }
-    if (op.kind != OP_CONV) continue;
-    const Act *out = op.out_act;
-    if (!gset.count(out)) return fail("backward: no gradient reached %s", op.label.c_str());
-    const float *dY = out->g;
-    const int Cy = out->C, Co = op.ca.Co;
-    const int Vo = out->V();
-    cm_train_state::Dgrad &D = T->dg[oi];
-    // residual branch
-    if (op.resid_act && accum_act(m, op.resid_act, dY, Cy, B, st)) return 1;
-    // bias gradient and the broadcast time-embedding term
-    float *bc = T->bs_pool + T->bs_cursor;
-    T->bs_cursor += (size_t)m->cfg.max_batch * Co;
-    if (T->bs_cursor > T->bs_pool_floats) return fail("batch-sum pool overflow");
-    // (dY = the output activation's gradient buffer stays intact until the end of the pass: every act owns its buffer
-    // and all of its consumers have already contributed -- so its voxel sum can wait for the one job-table launch)
-    if (!T->bs_ready) {
-      T->vs_jobs.push_back({dY, Vo, Co, Cy, bc, Co, op.temb_off >= 0 ? T->dproj + op.temb_off : nullptr, m->nproj});
-      T->vs_maxC = std::max(T->vs_maxC, Co);
-      T->bs_jobs.push_back({bc, grad_of(m, op.bname), Co, Co});
-      T->bs_maxC = std::max(T->bs_maxC, Co);
-    }
-    // weight gradient: off the critical path (only the optimizer reads it), so its launches go to a second stream and fill
-    // the tails / launch gaps of the data-gradient chain.  Inputs: dY (final: every consumer of this op's output has already
-    // contributed, and nothing writes it again in this pass) and forward activations; outputs: the parameter's gradient and
-    // the partial buffer, which only this stream touches.
-    if (wst != st) {
-      CM_HIP(hipEventRecord(T->ev_dy, st));
-      CM_HIP(hipStreamWaitEvent(wst, T->ev_dy, 0));
-    }
-    if (D.wwg) {
-      cm::ConvArgs wa = D.wwa;
-      wa.B = B;
-      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
-      const int ncb = (Co + 31) / 32, nkb = (wa.C0 + wa.C1 + 31) / 32;
-      const long ntile = (long)wa.ntz * wa.nty * wa.ntx * B;
-      const size_t per_g = (size_t)ncb * nkb * 48 * 1024;
-      static const int wino_wgs = cm::diag_env("CM_WGRAD_WINO_WGS") ? atoi(cm::diag_env("CM_WGRAD_WINO_WGS")) : 192;   // (with the weight gradients on their own stream: 128 / 192 / 256 / 512 -> 14.63 / 13.59 / 13.69 / 13.88 ms per step)
-      int G = (int)std::min<long>(ntile, std::max(1, wino_wgs / (ncb * nkb)));      // one workgroup per CU (80 KB image, 192 accumulators)
-      G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
-      if (G < 1) return fail("wgrad partial buffer too small");
-      const Param &w = P(m, op.wname);
-      if (T->autocast) CM_HIP(cm::launch_wgrad_wino_f16(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
+  const Op &op = m->ops[e.op];
+  const cm_train_state::Dgrad &D = T->dg[e.op];
+  const float *dY = op.out_act->g;
+  const int Cy = op.out_act->C, ncb = e.ncb, nkb = e.nkb;
+  float *dW = grad_of(m, op.wname);
+  const int G = wgrad_groups(e, B, T->wpart_floats);
+  if (G < 1) return 1;
+  cm::ConvArgs wa = e.wa;
+  wa.B = B;
+  if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
+  if (e.wg.kernel != WG_WINO) { wa.hvtab = D.w_hv; wa.mtab = D.w_mt; }
+  switch (e.wg.kernel) {
+    case WG_WINO:
+      if (e.wg.form == FORM_F16) CM_HIP(cm::launch_wgrad_wino_f16(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
       else CM_HIP(cm::launch_wgrad_wino(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
-      CM_HIP(cm::launch_wgrad_wino_reduce(T->wpart, G, ncb, nkb, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
-    } else if (op.ref_taps == 27 && op.ca.stride == 1 && !op.ca.par && !op.ca.ups && op.pm_off < 0 && !cm::diag_env("CM_NO_WGRAD_PACK") &&
-               ((Co == 32 && !op.in1 && op.in0->C == 8 && !op.ca.gn) || (Co <= 4 && op.ca.C0 + op.ca.C1 == 32 && !op.in1))) {
-      // few channels on one side (first / last conv of the UNet): taps packed with the narrow side into the MFMA columns
-      const Param &w = P(m, op.wname);
-      const bool last = Co <= 4;
-      cm::WgradPackArgs pa{};
-      if (last) {
+      CM_HIP(cm::launch_wgrad_wino_reduce(T->wpart, G, ncb, nkb, e.g.Co, e.g.Ci, dW, wst));
+      break;
+    case WG_PACK: {
+      cm::WgradPackArgs pa = e.pa;
+      if (pa.mirror) {
         pa.wide = op.in0->d; pa.wide_cs = op.in0->C; pa.gn = op.ca.gn; pa.silu = op.ca.silu;
-        pa.narrow = dY; pa.narrow_cs = Cy; pa.cn_valid = Co; pa.mirror = 1;
+        pa.narrow = dY; pa.narrow_cs = Cy;
       } else {
         pa.wide = dY; pa.wide_cs = Cy; pa.gn = nullptr; pa.silu = 0;
-        pa.narrow = op.in0->d; pa.narrow_cs = op.in0->C; pa.cn_valid = (int)w.shape[1]; pa.mirror = 0;
+        pa.narrow = op.in0->d; pa.narrow_cs = op.in0->C;
       }
-      const int CN = last ? 4 : 8;
-      pa.B = B; pa.Z = op.ca.Zo; pa.Y = op.ca.Yo; pa.X = op.ca.Xo;
-      pa.bz = std::min(pa.Z, 8); pa.by = std::min(pa.Y, 4); pa.bx = std::min(pa.X, 6);
-      if ((pa.bz * pa.by * pa.bx) & 1) pa.bx += 1;   // (an even number of rows: voxel pairs; rows outside the grid are zero)
-      pa.ntz = (pa.Z + pa.bz - 1) / pa.bz; pa.nty = (pa.Y + pa.by - 1) / pa.by; pa.ntx = (pa.X + pa.bx - 1) / pa.bx;
-      const long ntile = (long)B * pa.ntz * pa.nty * pa.ntx;
-      const size_t per_g = (size_t)((27 * CN + 31) / 32) * 1024;
-      int G = (int)std::min<long>(ntile, 256);
-      G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
-      if (G < 1) return fail("wgrad partial buffer too small");
-      pa.part = T->wpart;
-      CM_HIP(cm::launch_wgrad_pack(pa, CN, G, wst));
-      CM_HIP(cm::launch_wgrad_pack_reduce(T->wpart, G, CN, pa.cn_valid, pa.mirror, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
-    } else if (D.wa.par && !D.wa.gn && op.pm_off < 0 && !cm::diag_env("CM_NO_WGRAD_PAR")) {
-      // upsample convs: parity-form kernel with all 8 tap blocks per wave
-      cm::ConvArgs wa = D.wa;
-      wa.B = B;
-      wa.bz = std::min(wa.Zs, 4); wa.by = std::min(wa.Ys, 6); wa.bx = std::min(wa.Xs, wa.Zs <= 2 ? 9 : 6);
-      wa.ntz = (wa.Zs + wa.bz - 1) / wa.bz; wa.nty = (wa.Ys + wa.by - 1) / wa.by; wa.ntx = (wa.Xs + wa.bx - 1) / wa.bx;
-      const int Ctot = wa.C0 + wa.C1;
-      const int ncb = (Co + 31) / 32, nkb = (Ctot + 31) / 32;
-      const long ntile = (long)wa.ntz * wa.nty * wa.ntx * B;
-      const size_t per_g = (size_t)ncb * nkb * 64 * 1024;
-      static const int wgs_par = cm::diag_env("CM_WGRAD_PAR_WGS") ? atoi(cm::diag_env("CM_WGRAD_PAR_WGS")) : 1024;
-      int G = (int)std::min<long>(ntile, std::max(2, wgs_par / (8 * ncb * nkb)));
-      G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
-      if (G < 1) return fail("wgrad partial buffer too small");
-      const Param &w = P(m, op.wname);
+      pa.B = B; pa.part = T->wpart;
+      CM_HIP(cm::launch_wgrad_pack(pa, e.CN, G, wst));
+      CM_HIP(cm::launch_wgrad_pack_reduce(T->wpart, G, e.CN, pa.cn_valid, pa.mirror, e.g.Co, e.g.Ci, dW, wst));
+      break;
+    }
+    case WG_PAR:
       CM_HIP(cm::launch_wgrad_par(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
-      CM_HIP(cm::launch_wgrad_reduce_par(T->wpart, G, ncb, nkb, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
-    } else if (op.ref_taps == 1 && op.ca.stride == 1 && !op.ca.par && !op.ca.ups && !cm::diag_env("CM_NO_WGRAD_1X1")) {
-      // 1x1x1 convs (skip convs, attention projections): flat-row kernel, NKB input blocks per workgroup
-      cm::ConvArgs wa = D.wa;
-      wa.B = B;
-      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
-      const int Ctot = wa.C0 + wa.C1;
-      const int ncb = (Co + 31) / 32, nkb = (Ctot + 31) / 32;
-      const int NKB = nkb % 4 == 0 ? 4 : (nkb % 3 == 0 ? 3 : (nkb % 2 == 0 ? 2 : 1));
-      const long long N = (long long)B * Vo;
-      const size_t per_g = (size_t)ncb * nkb * 1024;
-      static const int wgs_1x1 = cm::diag_env("CM_WGRAD_1X1_WGS") ? atoi(cm::diag_env("CM_WGRAD_1X1_WGS")) : 768;
-      int G = (int)std::min<long long>((N + 127) / 128, std::max(4, wgs_1x1 / (ncb * (nkb / NKB))));
-      G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
-      if (G < 1) return fail("wgrad partial buffer too small");
-      const Param &w = P(m, op.wname);
-      CM_HIP(cm::launch_wgrad_1x1(wa, dY, Cy, Vo, T->wpart, G, ncb, nkb, NKB, wst));
-      CM_HIP(cm::launch_wgrad_reduce(T->wpart, G, ncb, nkb, 1, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst, 1));
-    } else {
-      cm::ConvArgs wa = D.wa;
-      const int wMB = D.wMB;
-      wa.B = B; wa.nts = B; wa.ks = 1;
-      if (op.pm_off >= 0) { wa.pm = m->dropmask + op.pm_off; wa.pm_stride = m->nproj; }
-      const int Ctot = wa.C0 + wa.C1;
-      const int ncb = (Co + 31) / 32, nkb = (Ctot + 31) / 32;
-      const long ntile = (long)wa.ntz * wa.nty * wa.ntx * B;
-      const size_t per_g = (size_t)ncb * nkb * (wa.par ? 64 : (op.ref_taps == 1 ? 4 : op.ref_taps)) * 1024;   // parity form: 8 classes x 8 taps per group; 1x1x1: 4 per-wave partials
-      // one full round of resident workgroups, as few partial copies as that allows
-      static const int wg_target = cm::diag_env("CM_WGRAD_WGS") ? atoi(cm::diag_env("CM_WGRAD_WGS")) : 256;   // two workgroups per CU fit (62 KB LDS each): 512 = one even round (768: 26.0 ms, 512: 23.2 ms per step)
-      int G = (int)std::min<long>(ntile, std::max(4, wg_target / (ncb * nkb)));
-      G = (int)std::min<size_t>((size_t)G, T->wpart_floats / per_g);
-      if (G < 1) return fail("wgrad partial buffer too small");
-      const Param &w = P(m, op.wname);
-      static const bool no_zs_kernel = cm::diag_env("CM_NO_WGRAD_ZS_KERNEL") != nullptr;
-      if (wa.zsplit && !no_zs_kernel && cm::wgrad_zs_ok(wa)) {
-        // two-plane grids: the dedicated kernel (two input blocks per workgroup, arithmetic coordinates, one load batch per tile)
-        const int nkg = (nkb + 1) / 2;
-        static const int zs_wgs = cm::diag_env("CM_WGRAD_ZS_WGS") ? atoi(cm::diag_env("CM_WGRAD_ZS_WGS")) : 128;   // one workgroup per CU, fewest partial copies (128 / 256 / 512 / 1024: 16.84 / 16.30 / 16.46 / 16.75 ms per step)
-        int Gz = (int)std::min<long>(ntile, std::max(4, zs_wgs / (ncb * nkg)));
-        Gz = (int)std::min<size_t>((size_t)Gz, T->wpart_floats / per_g);
-        CM_HIP(cm::launch_wgrad_zs(wa, dY, Cy, T->wpart, Gz, ncb, nkb, wst));
-        CM_HIP(cm::launch_wgrad_reduce(T->wpart, Gz, ncb, nkb, op.ref_taps, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
-      } else {
-        CM_HIP(cm::launch_wgrad(wa, wMB, dY, Cy, T->wpart, G, ncb, nkb, wst));
-        if (wa.par)
-          CM_HIP(cm::launch_wgrad_reduce_par(T->wpart, G, ncb, nkb, (int)w.shape[0], (int)w.shape[1], grad_of(m, op.wname), wst));
-        else
-          CM_HIP(cm::launch_wgrad_reduce(T->wpart, G, ncb, nkb, op.ref_taps, (int)w.shape[0], (int)w.shape[1],
-                                         grad_of(m, op.wname), wst));
-      }
-    }
-    if (!D.have) continue;  // first conv: its input is data
-    // data gradient into scrA [B][Vin][Ctot]
-    cm::ConvArgs da = D.ca;
-    da.B = B; da.nts = (B + da.bs - 1) / da.bs;
-    const float *dysrc = dY;
-    if (op.ca.stride == 2) {
-      CM_HIP(cm::launch_zero_stuff2(dY, T->scrB, B, op.ca.Zo, op.ca.Yo, op.ca.Xo, Cy, st));
-      dysrc = T->scrB;
-    }
-    da.src0 = dysrc; da.out = T->scrA; da.tidx = m->tbuf;
-    if (D.qr) {
+      CM_HIP(cm::launch_wgrad_reduce_par(T->wpart, G, ncb, nkb, e.g.Co, e.g.Ci, dW, wst));
+      break;
+    case WG_1X1:
+      CM_HIP(cm::launch_wgrad_1x1(wa, dY, Cy, op.out_act->V(), T->wpart, G, ncb, nkb, e.NKB, wst));
+      CM_HIP(cm::launch_wgrad_reduce(T->wpart, G, ncb, nkb, 1, e.g.Co, e.g.Ci, dW, wst, 1));
+      break;
+    case WG_ZS:
+      wa.nts = B;
+      CM_HIP(cm::launch_wgrad_zs(wa, dY, Cy, T->wpart, G, ncb, nkb, wst));
+      CM_HIP(cm::launch_wgrad_reduce(T->wpart, G, ncb, nkb, op.ref_taps, e.g.Co, e.g.Ci, dW, wst));
+      break;
+    case WG_GENERIC:
+      wa.nts = B;
+      CM_HIP(cm::launch_wgrad(wa, e.wMB, dY, Cy, T->wpart, G, ncb, nkb, wst));
+      if (wa.par) CM_HIP(cm::launch_wgrad_reduce_par(T->wpart, G, ncb, nkb, e.g.Co, e.g.Ci, dW, wst));
+      else CM_HIP(cm::launch_wgrad_reduce(T->wpart, G, ncb, nkb, op.ref_taps, e.g.Co, e.g.Ci, dW, wst));
+      break;
+  }
+  return 0;
+}
+
+// The data gradient of one conv entry into scrA [B][Vin][Ctot], then on to the inputs' gradient buffers (BwdTail).
+int run_dgrad(cm_model *m, const BwdOp &e, int B, hipStream_t st) {
+  cm_train_state *T = m->train;
+  const Op &op = m->ops[e.op];
+  const cm_train_state::Dgrad &D = T->dg[e.op];
+  const float *dysrc = op.out_act->g;
+  const int Cy = op.out_act->C, Ctot = op.ca.C0 + op.ca.C1;
+  cm::ConvArgs da = e.g.da;
+  da.B = B; da.nts = (B + da.bs - 1) / da.bs;
+  da.wfrag = D.wfrag; da.bias = D.zero_bias; da.hvtab = D.d_hv; da.mtab = D.d_mt;
+  if (op.ca.stride == 2) {
+    CM_HIP(cm::launch_zero_stuff2(dysrc, T->scrB, B, op.ca.Zo, op.ca.Yo, op.ca.Xo, Cy, st));
+    dysrc = T->scrB;
+  }
+  da.src0 = dysrc; da.out = T->scrA; da.tidx = m->tbuf;
+  switch (e.dg.kernel) {
+    case DG_QR: {
       cm::QrArgs q{};
       q.src0 = dysrc; q.C0 = da.C0; q.raw = 1; q.groups = 8;
       q.wq = D.wqr; q.wq6 = D.wqr_b6; q.bias = D.zero_bias; q.tidx = m->tbuf;
       q.out = T->scrA; q.out_cs = da.out_cs; q.Co = da.Co; q.B = B; q.Y = da.Yo; q.X = da.Xo;
-      if (!cm::conv_qr2_b6_ok(q)) return fail("quarter-resolution data gradient of %s: no six-term form", op.label.c_str());
       CM_HIP(cm::launch_conv_qr(q, st));
-    } else if (D.wino) {
-      da.wfrag = D.wwino;
-      const bool f16 = T->autocast && D.wwino16;
-      if (f16) da.wfrag = D.wwino16;
-      else if (D.wwino_b6) { da.wfrag = D.wwino_b6; da.f16 = 2; }
-      CM_HIP(cm::launch_conv_wino(da, f16, st));
-    } else {
-      CM_HIP(cm::launch_conv(da, D.MB, D.NB, st));
+      break;
     }
-    const int Ctot = op.ca.C0 + op.ca.C1;
-    if (op.ca.par) {
-      const Act *in = op.in0;
-      CM_HIP(cm::launch_sumpool2(T->scrA, in->g, B, op.ca.Zs, op.ca.Ys, op.ca.Xs, in->C, gset.insert(in).second ? 0 : 1, st));
-    } else if (op.gn_op >= 0) {
-      Op &gop = m->ops[op.gn_op];
+    case DG_WINO:
+      da.wfrag = e.dg.form == FORM_F16 ? D.wwino16 : e.dg.form == FORM_B6 ? D.wwino_b6 : D.wwino;
+      if (e.dg.form == FORM_B6) da.f16 = 2;
+      CM_HIP(cm::launch_conv_wino(da, e.dg.form == FORM_F16, st));
+      break;
+    default:
+      CM_HIP(cm::launch_conv(da, e.g.dMB, e.g.dNB, st));
+  }
+  switch (e.tail) {
+    case TAIL_POOL:
+      CM_HIP(cm::launch_sumpool2(T->scrA, op.in0->g, B, op.ca.Zs, op.ca.Ys, op.ca.Xs, op.in0->C, e.acc_in0 ? 1 : 0, st));
+      break;
+    case TAIL_GN: {
+      const Op &gop = m->ops[op.gn_op];
       cm::GnbArgs ga{};
       ga.x0 = op.in0->d; ga.x1 = op.in1 ? op.in1->d : nullptr; ga.C0 = op.ca.C0; ga.C1 = op.ca.C1;
       ga.dA = T->scrA; ga.dA_cs = Ctot;
@@ -757,39 +759,59 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
       ga.silu = op.ca.silu;
       ga.V = op.in0->V(); ga.B = B; ga.groups = GN_GROUPS;
       ga.nsl = std::max(1, std::min(MAX_SLICES, ga.V / 128));
-      float *dgb = T->bs_pool + T->bs_cursor;
-      T->bs_cursor += (size_t)m->cfg.max_batch * 2 * Ctot;
-      if (T->bs_cursor > T->bs_pool_floats) return fail("batch-sum pool overflow");
-      ga.part = T->gnb_part; ga.coef = T->gnb_coef; ga.dgb = dgb;
-      ga.g1 = op.in1 ? op.in1->g : nullptr; ga.acc1 = (op.in1 && gset.count(op.in1)) ? 1 : 0;
-      ga.g0 = op.in0->g; ga.acc0 = gset.insert(op.in0).second ? 0 : 1;
-      if (op.in1) gset.insert(op.in1);
+      ga.part = T->gnb_part; ga.coef = T->gnb_coef; ga.dgb = T->bs_pool + e.gn_off;
+      ga.g1 = op.in1 ? op.in1->g : nullptr; ga.acc1 = e.acc_in1 ? 1 : 0;
+      ga.g0 = op.in0->g; ga.acc0 = e.acc_in0 ? 1 : 0;
       CM_HIP(cm::launch_gn_backward(ga, st));
-      if (!T->bs_ready) {
-        T->bs_jobs.push_back({dgb, grad_of(m, gop.gname), Ctot, 2 * Ctot});
-        T->bs_jobs.push_back({dgb + Ctot, grad_of(m, gop.bename), Ctot, 2 * Ctot});
-        T->bs_maxC = std::max(T->bs_maxC, Ctot);
-      }
-    } else {
-      if (accum_act(m, op.in0, T->scrA, Ctot, B, st)) return 1;
-      if (op.in1 && accum_act(m, op.in1, T->scrA + op.ca.C0, Ctot, B, st)) return 1;
+      break;
     }
+    case TAIL_ADD:
+      if (accum_act(op.in0, T->scrA, Ctot, B, e.acc_in0, st)) return 1;
+      if (op.in1 && accum_act(op.in1, T->scrA + op.ca.C0, Ctot, B, e.acc_in1, st)) return 1;
+  }
+  return 0;
+}
+
+// The executor of T->bwd: one pass over its entries.  Weight gradients are off the critical path (only the optimizer reads them), so
+// their launches go to a second stream and fill the tails / launch gaps of the data-gradient chain; their inputs are dY (final: every
+// consumer of the op's output has already contributed, and nothing writes it again in this pass) and forward activations, their
+// outputs the parameter's gradient and the partial buffer, which only that stream touches.
+int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
+  cm_train_state *T = m->train;
+  const BwdPlan &P = T->bwd;
+  CM_HIP(hipMemsetAsync(T->dproj, 0, (size_t)B * m->nproj * sizeof(float), st));
+  hipStream_t wst = (T->knobs.wgrad_one_stream || !m->lane_stream[1]) ? st : m->lane_stream[1];
+  if (wst != st && !T->ev_dy) {
+    CM_HIP(hipEventCreateWithFlags(&T->ev_dy, hipEventDisableTiming));
+    CM_HIP(hipEventCreateWithFlags(&T->ev_wdone, hipEventDisableTiming));
+  }
+  static const bool sync_ops = cm::diag_env("CM_SYNC_OPS") != nullptr;   // debugging: name every op and drain the device after it
+  for (const BwdOp &e : P.ops) {
+    const Op &op = m->ops[e.op];
+    if (sync_ops) {
+      const hipError_t err = hipDeviceSynchronize();
+      fprintf(stderr, "[cm] backward reaches op %d %s (%s)\n", e.op, op.label.c_str(), hipGetErrorString(err));
+      fflush(stderr);
+    }
+    if (op.kind == OP_ATTN)   // (large token counts only: the S x S matrices go to a global slab)
+      CM_HIP(cm::launch_attn_bwd(op.qkv, e.oa->g, e.qa->g, B, op.S, op.E, ATTN_HEADS,
+                                 cm::attn_bwd_scratch_floats(m->cfg.max_batch, op.S, op.E, ATTN_HEADS) ? T->attn_big : nullptr, st));
+    if (op.kind != OP_CONV) continue;
+    if (op.resid_act && accum_act(op.resid_act, op.out_act->g, op.out_act->C, B, e.acc_resid, st)) return 1;
+    if (wst != st) {
+      CM_HIP(hipEventRecord(T->ev_dy, st));
+      CM_HIP(hipStreamWaitEvent(wst, T->ev_dy, 0));
+    }
+    if (run_wgrad(m, e, B, wst)) return 1;
+    if (e.dg.kernel != DG_NONE && run_dgrad(m, e, B, st)) return 1;   // (the first conv: its input is data)
   }
   if (wst != st) {                                 // every weight gradient is complete before the optimizer reads it
     CM_HIP(hipEventRecord(T->ev_wdone, wst));
     CM_HIP(hipStreamWaitEvent(st, T->ev_wdone, 0));
   }
-  // the deferred batch reductions (bias, gamma, beta gradients) in one launch
-  if (!T->bs_ready) {
-    if (dev_alloc(m, (void **)&T->d_bs_jobs, T->bs_jobs.size() * sizeof(cm::BsumJob))) return 1;
-    if (dev_alloc(m, (void **)&T->d_vs_jobs, T->vs_jobs.size() * sizeof(cm::VsumJob))) return 1;
-    CM_HIP(hipMemcpyAsync(T->d_bs_jobs, T->bs_jobs.data(), T->bs_jobs.size() * sizeof(cm::BsumJob), hipMemcpyHostToDevice, st));
-    CM_HIP(hipMemcpyAsync(T->d_vs_jobs, T->vs_jobs.data(), T->vs_jobs.size() * sizeof(cm::VsumJob), hipMemcpyHostToDevice, st));
-    CM_HIP(hipStreamSynchronize(st));
-    T->bs_ready = true;
-  }
-  CM_HIP(cm::launch_voxel_sum_jobs(T->d_vs_jobs, (int)T->vs_jobs.size(), B, T->vs_maxC, st));
-  CM_HIP(cm::launch_batch_sum_jobs(T->d_bs_jobs, (int)T->bs_jobs.size(), B, T->bs_maxC, st));
+  // the deferred voxel and batch reductions (bias, time-row, gamma, beta gradients): one job-table launch each
+  CM_HIP(cm::launch_voxel_sum_jobs(T->d_vs_jobs, P.nconv, B, P.vs_maxC, st));
+  CM_HIP(cm::launch_batch_sum_jobs(T->d_bs_jobs, (int)P.bsum.size(), B, P.bs_maxC, st));
   // time-embedding path
   const cm_unet_config &c = m->cfg;
   cm::TimeBwdArgs ta{};
@@ -801,25 +823,7 @@ int backward_ops_impl(cm_model *m, int B, hipStream_t st) {
   ta.dW2 = grad_of(m, "time_embeddings.time_blocks.3.weight"); ta.db2 = grad_of(m, "time_embeddings.time_blocks.3.bias");
   ta.dWd = T->dWd_all; ta.dbd = T->dbd_all;
   CM_HIP(cm::launch_time_bwd(ta, st));
-  if (!T->d_cp_jobs) {            // the per-block slices -> their parameters' gradient slots: one job-table launch
-    std::vector<cm::CopyJob> jobs;
-    int off = 0;
-    auto visit = [&](const BlockDesc &b) {
-      if (b.kind != 0) return;
-      jobs.push_back({grad_of(m, b.prefix + ".dense_1.weight"), T->dWd_all + (size_t)off * ta.tx, (long long)b.cout * ta.tx});
-      jobs.push_back({grad_of(m, b.prefix + ".dense_1.bias"), T->dbd_all + off, (long long)b.cout});
-      T->cp_max = std::max<long long>(T->cp_max, (long long)b.cout * ta.tx);
-      off += b.cout;
-    };
-    for (auto &b : m->enc) visit(b);
-    for (auto &b : m->bott) visit(b);
-    for (auto &b : m->dec) visit(b);
-    T->n_cp_jobs = (int)jobs.size();
-    if (dev_alloc(m, (void **)&T->d_cp_jobs, jobs.size() * sizeof(cm::CopyJob))) return 1;
-    CM_HIP(hipMemcpyAsync(T->d_cp_jobs, jobs.data(), jobs.size() * sizeof(cm::CopyJob), hipMemcpyHostToDevice, st));
-    CM_HIP(hipStreamSynchronize(st));
-  }
-  CM_HIP(cm::launch_copy_jobs(T->d_cp_jobs, T->n_cp_jobs, T->cp_max, st));
+  CM_HIP(cm::launch_copy_jobs(T->d_cp_jobs, (int)P.copy.size(), P.cp_max, st));   // the per-block slices -> their parameters' gradient slots
   // autocast: every gradient above carries the loss scale 2^k exactly (fp32 tensors); take it out once, so that the readers of the
   // flat buffer (cm_train_get_grad, the all-reduce, Adam, checkpoints) see unscaled gradients
   if (T->ls_k > 0) CM_HIP(cm::launch_scale_inplace(T->opt.g, (long long)T->opt.nfloats, ldexpf(1.f, -T->ls_k), st));
@@ -869,7 +873,7 @@ int cm_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2) {
         if (op.kind == OP_CONV && op.wino && op.d_wwino && op.wwino_floats > 0 &&
             dev_alloc(m, (void **)&op.d_wwino16t, (size_t)op.wwino_floats / 2 * sizeof(float))) return 1;
       for (auto &D : T->dg)
-        if (D.wino && D.wwino && dev_alloc(m, (void **)&D.wwino16, (size_t)D.wwino_floats / 2 * sizeof(float))) return 1;
+        if (D.wwino && dev_alloc(m, (void **)&D.wwino16, (size_t)D.wwino_floats / 2 * sizeof(float))) return 1;
       // the job table of wino_pack_jobs_kernel with the f16 buffers as destinations: same order, same workgroup -> job map
       // (a model without Winograd layers -- narrow widths, odd grids -- has no such table and nothing to re-pack)
       if (!T->derived_wino.empty() && (!T->d_wjobs || !T->d_wblk2job)) return fail("cm_train_set_autocast: the Winograd re-pack table has not been built");
@@ -898,6 +902,7 @@ int cm_train_set_autocast(cm_model *m, int32_t mode, int32_t loss_scale_log2) {
   }
   T->autocast = mode; T->ls_req = mode ? (int)loss_scale_log2 : -1;
   if (!mode) T->ls_k = 0;
+  T->bwd = plan_backward(m->ops, bwd_ctx(m), T->knobs);   // the f16 forms of the Winograd layers' two gradients come and go with the mode
   m->train_autocast = mode == 1;
   return 0;
 }
