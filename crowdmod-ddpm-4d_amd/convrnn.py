@@ -486,9 +486,11 @@ class ConvRNN_model:
         raise ValueError("empty test data")
 
     def generate_metrics(self, batched_test_data, chunkRepdPastSeq, metric, batches_to_use, samples_per_batch,
-                         model_fullname=None, output_dir=None, *, rng: Optional[np.random.Generator] = None, eps=None):
+                         model_fullname=None, output_dir=None, *, rng: Optional[np.random.Generator] = None, eps=None,
+                         tables=None):
         """convRNN.py:269-316: per test batch the forecasts of `samples_per_batch` (repeated) past windows, sliced to
-        METRICS.MPROPS_COUNT channels, through the MetricsGenerator the generative models use.  Returns it."""
+        METRICS.MPROPS_COUNT channels, through the MetricsGenerator the generative models use.  Returns it.
+        tables: "host" | "device" route of its SSIM / energy / motion-feature tables; None reads METRICS.TABLES ("host")."""
         from .metrics import MetricsGenerator, compute_metrics
         if model_fullname is not None:
             self.load_checkpoint(model_fullname)
@@ -511,12 +513,15 @@ class ConvRNN_model:
                 break
         if not preds:
             raise ValueError("empty test data")
-        mg = MetricsGenerator(np.concatenate(preds), np.concatenate(gts), mcount, device=self.device)
+        if tables is None:
+            tables = (mt.get("TABLES", None) if hasattr(mt, "get") else None) or "host"
         if eps is None:
             mp = self.cfg.get("MACROPROPS", {}) if hasattr(self.cfg, "get") else {}
             eps = float(mp.get("EPS", 1e-6)) if hasattr(mp, "get") else 1e-6
         mf = mt.get("MOTION_FEATURE", None) if hasattr(mt, "get") else None
-        compute_metrics(mg, metric, chunk, eps, motion_feature=mf)
+        with MetricsGenerator(np.concatenate(preds), np.concatenate(gts), mcount, device=self.device,
+                              tables=str(tables)) as mg:
+            compute_metrics(mg, metric, chunk, eps, motion_feature=mf)
         if output_dir:
             title = (f"{self.res.batch_size * chunk * count} samples in total (BS:{self.res.batch_size}, Rep:{chunk}, "
                      f"TB:{count})-({self.arch}-{self.base_cell_name})")

@@ -1150,6 +1150,21 @@ void test_misc_errors() {
   EXPECT(cm_profile_enable(nullptr, 1) != 0);
   EXPECT(cm_frame_metrics(0, nullptr, nullptr, 1, 1, 1, 1, 1, nullptr, nullptr) != 0);
   EXPECT(std::string(cm_last_error()).size() > 0);
+  // the SSIM / energy / motion-feature entry points refuse before any device call (the pointers are never dereferenced)
+  {
+    const float *d = reinterpret_cast<const float *>(0x1000);
+    double r[3] = {1, 1, 1}, o[8];
+    EXPECT(cm_ssim_frames(0, nullptr, d, 1, 3, 8, 8, 1, r, o) != 0);
+    EXPECT(cm_ssim_frames(0, d, d, 1, 3, 6, 8, 1, r, o) != 0 && std::string(cm_last_error()).find("6 x 8") != std::string::npos);
+    EXPECT(cm_ssim_frames(0, d, d, 1, 3, 8, 129, 8, r, o) != 0 && std::string(cm_last_error()).find("W * F = 1032") != std::string::npos);
+    EXPECT(cm_energy(0, d, 1, 2, 8, 8, 2, 1.f, 1.f, nullptr, o) != 0 && std::string(cm_last_error()).find("C = 2") != std::string::npos);
+    EXPECT(cm_energy(0, d, 1, 3, 8, 8, 0, 1.f, 1.f, nullptr, o) != 0 && std::string(cm_last_error()).find("L = 0") != std::string::npos);
+    EXPECT(cm_motion_feature_vectors(0, d, 1, 3, 8, 8, 2, 0, 4, 0.5, o, o) != 0 && std::string(cm_last_error()).find("f = 0") != std::string::npos);
+    EXPECT(cm_motion_feature_tables(0, d, d, 1, 3, 8, 8, 2, 1, -1, 0.5, o) != 0 && std::string(cm_last_error()).find("k = -1") != std::string::npos);
+    EXPECT(cm_motion_feature_tables(0, d, d, 1, 3, 8, 8, 2, 1, 4, 0.5, nullptr) != 0);
+    EXPECT(cm::motion_feature_volumes(12, 36, 3, 1, 4) == 81 && cm::motion_feature_volumes(12, 36, 3, 2, 5) == 48);
+    EXPECT(cm::ssim_frames_ok(128, 8) && !cm::ssim_frames_ok(147, 7));
+  }
   // linspace restatement: endpoints and symmetry
   EXPECT(linspace_f32(0.f, 1.f, 10, 0) == 0.f && linspace_f32(0.f, 1.f, 10, 9) == 1.f && linspace_f32(3.f, 5.f, 1, 0) == 3.f);
 }

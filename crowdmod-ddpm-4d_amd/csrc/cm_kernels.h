@@ -885,6 +885,23 @@ hipError_t launch_randn(float *x, int B, long long per, unsigned long long seed,
 // per-(sample, channel, frame) reductions of the sampling metrics (see cm_misc.hip)
 hipError_t launch_frame_metrics(const float *pred, const float *gt, int N, int C, int H, int W, int F, double *out,
                                 float *minmax, hipStream_t st);
+// ---- the other sampling-metric tables (cm_metrics.hip): SSIM, energy, motion-feature histograms; all results float64 ----
+// SSIM stages bands of rows in LDS: a row of W F floats may hold at most kSsimMaxRow elements (128 columns x 8 frames)
+constexpr int kSsimMaxRow = 1024;
+constexpr int kSsimBandFloats = 15360;   // both tensors' band, 60 KiB; >= 14 rows of kSsimMaxRow
+bool ssim_frames_ok(int W, int F);
+// out [N][C][F] = mean SSIM of the 7 x 7 windows of each (sample, channel, frame) image; range [C] on the device
+hipError_t launch_ssim_frames(const float *pred, const float *gt, int N, int C, int H, int W, int F, const double *range,
+                              double *out, hipStream_t st);
+// out [N] = compute_energy of x [N][C][H][W][L] (channels 0-2, each scaled by fac[c] in float32 first)
+hipError_t launch_energy(const float *x, int N, int C, int H, int W, int L, float inv_dt, float inv_dl, const float fac[3],
+                         double *out, hipStream_t st);
+// volumes of f frames x k x k cells (ragged at the far edges) in one sequence
+long long motion_feature_volumes(int H, int W, int F, int f, int k);
+// b == nullptr: the normalised vectors of a -> mf2 [N][nvol * 256], mf1 [N][nvol * 16];
+// otherwise the six table columns of (a = pred, b = gt) -> out [N][6], nothing dense is written
+hipError_t launch_motion_features(const float *a, const float *b, int N, int C, int H, int W, int F, int f, int k, double gamma,
+                                  double *mf2, double *mf1, double *out, hipStream_t st);
 // generic strided copy channels-last -> reference layout (debug hook)
 hipError_t launch_cl_to_ref(const float *x_cl, int cs, float *out, int B, int C, int Z, int Y, int X, hipStream_t st);
 

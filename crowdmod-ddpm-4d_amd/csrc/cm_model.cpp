@@ -3024,3 +3024,4 @@ int cm_model_class_flops(const cm_model *m, int32_t B, double flops[8]) {
 #include "cm_train_host.inc"
 #include "cm_dit_train_host.inc"
 #include "cm_convrnn_host.inc"
+#include "cm_metrics_host.inc"

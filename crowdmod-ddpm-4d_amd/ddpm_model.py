@@ -423,15 +423,16 @@ class DDPM_model:
         return x
 
     def generate_metrics(self, batched_test_data, chunkRepdPastSeq, metric, batches_to_use, samples_per_batch,
-                         model_fullname=None, output_dir=None, *, rng: Optional[np.random.Generator] = None, eps=None):
+                         model_fullname=None, output_dir=None, *, rng: Optional[np.random.Generator] = None, eps=None,
+                         tables=None):
         """ddpm.py:336-392: per test batch draw `samples_per_batch / chunkRepdPastSeq` past windows, repeat each
         `chunkRepdPastSeq` times (torch.repeat_interleave), sample all `samples_per_batch` chains (NSAMPLES = 1280 =
         64 pasts x 20 repeats in config/ATC.yml) in ONE device loop, and hand predictions / ground truth to the
         MetricsGenerator -- whose per-frame reductions run on the device as well (cm_frame_metrics), so neither the
         1280 samples' Python double loop nor a `.cpu()` round trip per sample remains.  Returns the MetricsGenerator;
         with `output_dir` its tables are written there as CSV + metrics_files.json (utils/metrics/metricsGenerator.py:
-        342-358).  metric: PSNR | MASK_PSNR | RE_DENSITY | TV | ALL (SSIM, motion-feature and energy metrics are CPU
-        library code on the reference side and out of scope here)."""
+        342-358).  metric: as compute_metrics takes it.  tables: "host" | "device", the route of the SSIM, energy and
+        motion-feature tables (MetricsGenerator); None reads METRICS.TABLES of the config, "host" where the key is absent."""
         import logging
         from .metrics import MetricsGenerator, compute_metrics
         r = self.res
@@ -458,13 +459,16 @@ class DDPM_model:
                 break
         if not preds:
             raise ValueError("empty test data")
-        mg = MetricsGenerator(np.concatenate(preds), np.concatenate(gts), self.mprops_count, device=self.device)
+        mt = self.cfg.get("METRICS", {}) if hasattr(self.cfg, "get") else {}
+        if tables is None:
+            tables = (mt.get("TABLES", None) if hasattr(mt, "get") else None) or "host"
         if eps is None:
             mp = self.cfg.get("MACROPROPS", {}) if hasattr(self.cfg, "get") else {}
             eps = float(mp.get("EPS", 1e-6)) if hasattr(mp, "get") else 1e-6
-        mt = self.cfg.get("METRICS", {}) if hasattr(self.cfg, "get") else {}
         mf = mt.get("MOTION_FEATURE", None) if hasattr(mt, "get") else None    # f, k, GAMMA (metricsGenerator.py:244-245)
-        compute_metrics(mg, metric, chunk, eps, motion_feature=mf)
+        with MetricsGenerator(np.concatenate(preds), np.concatenate(gts), self.mprops_count, device=self.device,
+                              tables=str(tables)) as mg:
+            compute_metrics(mg, metric, chunk, eps, motion_feature=mf)
         if output_dir:
             title = f"{r.batch_size * chunk * count} samples in total (BS:{r.batch_size}, Rep:{chunk}, TB:{count})-({self.arch})"
             mg.save_data_metrics(output_dir, title, samples_per_batch)

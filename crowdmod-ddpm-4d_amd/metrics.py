@@ -4,9 +4,15 @@ Mirror of the reduction-type metrics of the reference's `MetricsGenerator`
 (/root/reference/utils/metrics/metricsGenerator.py): PSNR / masked PSNR (+ MAX over the repeats of a past
 sequence, + per-frame tables), relative density error (+ MIN), total variation over time.  The reference loops
 over every sample and frame in Python on `.cpu()` copies; here one kernel (cm_frame_metrics) reduces
-`[N,C,H,W,F]` to `[N,C,F]` partial sums and only those come back.  SSIM and the energy metric run on the host
-(scipy / numpy), as the reference's own do (skimage / torch CPU), and so do the motion-feature histogram metrics
-(MF_MSE, MF_BHATT: numpy, vectorised over all volumes)."""
+`[N,C,H,W,F]` to `[N,C,F]` partial sums and only those come back.
+
+SSIM, the energy metric and the motion-feature histogram metrics (MF_MSE, MF_BHATT) have two routes, chosen by
+`MetricsGenerator(tables=...)`:
+  "host"    (default, and the yardstick) scipy / numpy on the host, as the reference's own do (skimage / torch CPU / numpy,
+            vectorised over all volumes);
+  "device"  the same quantities from cm_ssim_frames, cm_energy and cm_motion_feature_tables on the device copies the
+            generator already holds; only the [N, C, F] / [N] / [N, 6] results come back, and the chunk MAX / MIN tables are
+            formed from them on the host as before.  The arithmetic rules the device keeps are in include/crowdmod_hip.h."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,6 +55,12 @@ def ssim_tables(pred, gt, ranges, chunk, mprops_count=3):
         for j in range(F):
             for c in range(m):
                 over_time[i, j * m + c] = _ssim2d(gt[i, c, :, :, j], pred[i, c, :, :, j], ranges[c])
+    return _ssim_tables_from_frames(over_time, chunk, m, F)
+
+
+def _ssim_tables_from_frames(over_time, chunk, m, F):
+    """The four SSIM tables from the per-frame values [N, F * m] (frame-major: rho_f0, vx_f0, vy_f0, rho_f1, ...)."""
+    N = over_time.shape[0]
     avg = over_time.reshape(N, F, m).sum(axis=1) / F
     nchunk = N // chunk
     mx = np.stack([avg[i * chunk:(i + 1) * chunk].max(axis=0) for i in range(nchunk)]) if nchunk else np.zeros((0, m))
@@ -83,7 +95,12 @@ def energy_tables(pred, gt, chunk, mprops_factor=None):
         fac = np.asarray(mprops_factor, dtype=np.float32)[:pred.shape[1], None, None, None]
         pred, gt = pred * fac[None], gt * fac[None]
     e = np.stack([compute_energy(gt, 1, 1), compute_energy(pred, 1, 1)], axis=1).astype(np.float64)
-    nchunk = pred.shape[0] // chunk
+    return _energy_tables_from_samples(e, chunk)
+
+
+def _energy_tables_from_samples(e, chunk):
+    """ENERGY [N, 2] (GT, PRED) and its minima over each chunk of repeats."""
+    nchunk = e.shape[0] // chunk
     mn = np.stack([e[i * chunk:(i + 1) * chunk].min(axis=0) for i in range(nchunk)]) if nchunk else np.zeros((0, 2))
     return {"ENERGY": e, "MIN-ENERGY": mn}
 
@@ -177,8 +194,15 @@ def motion_feature_tables(pred, gt, f, k, gamma, mse_metric=True, bhatt_metrics=
 
 
 class MetricsGenerator:
-    def __init__(self, pred, gt, mprops_count: int = 3, device: int = 0):
-        """pred / gt: arrays [N, C, H, W, F] (or lists of [C,H,W,F] sequences like the reference takes)."""
+    def __init__(self, pred, gt, mprops_count: int = 3, device: int = 0, tables: str = "host"):
+        """pred / gt: arrays [N, C, H, W, F] (or lists of [C,H,W,F] sequences like the reference takes).
+        tables: "host" (default) computes the SSIM, energy and motion-feature tables with scipy / numpy; "device" computes
+        them with cm_ssim_frames / cm_energy / cm_motion_feature_tables on the device copies of pred / gt, which then live
+        until close() (or the end of a `with` block)."""
+        if tables not in ("host", "device"):
+            raise ValueError(f"tables={tables!r}: 'host' or 'device'")
+        self.tables = tables
+        self._dev = None
         pred = np.ascontiguousarray(np.stack([np.asarray(p) for p in pred]) if isinstance(pred, (list, tuple)) else pred,
                                     dtype=np.float32)
         gt = np.ascontiguousarray(np.stack([np.asarray(p) for p in gt]) if isinstance(gt, (list, tuple)) else gt,
@@ -193,7 +217,18 @@ class MetricsGenerator:
         dg = native.DeviceBuffer.from_array(gt, device)
         out = np.empty((N, C_, F, 8), dtype=np.float64)
         mm = np.empty((N, C_, F, 2), dtype=np.float32)
-        native.check(native.lib().cm_frame_metrics(device, dp.ptr, dg.ptr, N, C_, H, W, F, out.ctypes.data, mm.ctypes.data))
+        try:
+            native.check(native.lib().cm_frame_metrics(device, dp.ptr, dg.ptr, N, C_, H, W, F, out.ctypes.data, mm.ctypes.data))
+        except Exception:
+            dp.free()
+            dg.free()
+            raise
+        if tables == "device":
+            self._dev = (dp, dg)
+        else:
+            dp.free()
+            dg.free()
+        self.device, self.shape = int(device), (N, C_, H, W, F)
         self.N, self.F, self.npix = N, F, H * W
         self._pred_gt = (pred, gt)
         self._red = out
@@ -202,6 +237,29 @@ class MetricsGenerator:
         self.ranges = [float(mm[:, c, :, 1].max() - mm[:, c, :, 0].min()) for c in range(m)]
         self.rho_range, self.vx_range, self.vy_range = (self.ranges + [0.0, 0.0])[:3]
         self.data_dict = {}
+
+    def close(self):
+        """Release the device copies of pred / gt (tables="device"); the tables already computed stay."""
+        dev, self._dev = self._dev, None
+        for b in dev or ():
+            b.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _device_buffers(self):
+        if self._dev is None:
+            raise RuntimeError("MetricsGenerator(tables='device'): the device copies have been released (close())")
+        return self._dev
 
     # metricsGenerator.py:70-86
     @staticmethod
@@ -243,17 +301,56 @@ class MetricsGenerator:
         self.data_dict["MIN_RE_DENSITY"] = mn
 
     def compute_ssim_metric(self, chunkRepdPastSeq):
-        """metricsGenerator.py:188-238, on the host (scipy), like the reference's skimage call."""
+        """metricsGenerator.py:188-238: on the host (scipy), like the reference's skimage call, or per (sample, property,
+        frame) on the device (cm_ssim_frames)."""
+        if self.tables == "device":
+            dp, dg = self._device_buffers()
+            N, C_, H, W, F = self.shape
+            m = self.mprops_count
+            if min(H, W) < 7:
+                raise ValueError(f"SSIM needs images of at least 7x7 (got {(H, W)}); the reference raises as well")
+            rng = np.asarray(list(self.ranges) + [1.0] * (C_ - m), dtype=np.float64)
+            out = np.empty((N, C_, F), dtype=np.float64)
+            native.check(native.lib().cm_ssim_frames(self.device, dg.ptr, dp.ptr, N, C_, H, W, F, rng.ctypes.data, out.ctypes.data))
+            over_time = np.ascontiguousarray(np.transpose(out[:, :m], (0, 2, 1))).reshape(N, F * m)
+            self.data_dict.update(_ssim_tables_from_frames(over_time, chunkRepdPastSeq, m, F))
+            return
         pred, gt = self._pred_gt
         self.data_dict.update(ssim_tables(pred, gt, self.ranges, chunkRepdPastSeq, self.mprops_count))
 
     def compute_energy_metric(self, chunkRepdPastSeq, mprops_factor=None):
-        """metricsGenerator.py:260-291, on the host."""
+        """metricsGenerator.py:260-291, on the host or on the device (cm_energy)."""
+        if self.tables == "device":
+            dp, dg = self._device_buffers()
+            N, C_, H, W, F = self.shape
+            fac = None
+            if mprops_factor is not None:
+                fac = np.asarray(mprops_factor, dtype=np.float32).reshape(-1)[:C_]
+                if fac.size not in (1, C_):
+                    raise ValueError(f"mprops_factor has {fac.size} entries for {C_} channels")
+                fac = np.ascontiguousarray(np.broadcast_to(fac, (C_,)))
+            e = np.empty((2, N), dtype=np.float64)
+            for row, buf in zip(e, (dg, dp)):                  # columns GT, PRED
+                native.check(native.lib().cm_energy(self.device, buf.ptr, N, C_, H, W, F, 1.0, 1.0,
+                                                    None if fac is None else fac.ctypes.data, row.ctypes.data))
+            self.data_dict.update(_energy_tables_from_samples(np.ascontiguousarray(e.T), chunkRepdPastSeq))
+            return
         pred, gt = self._pred_gt
         self.data_dict.update(energy_tables(pred, gt, chunkRepdPastSeq, mprops_factor))
 
     def compute_motion_feature_metrics(self, mse_metric=False, bhatt_metrics=False, f=1, k=4, gamma=0.5):
-        """metricsGenerator.py:240-258, on the host (numpy), like the reference's; f / k / gamma = METRICS.MOTION_FEATURE."""
+        """metricsGenerator.py:240-258: on the host (numpy), like the reference's, or on the device
+        (cm_motion_feature_tables, which never materialises the histogram vectors); f / k / gamma = METRICS.MOTION_FEATURE."""
+        if self.tables == "device":
+            dp, dg = self._device_buffers()
+            N, C_, H, W, F = self.shape
+            out = np.empty((N, 6), dtype=np.float64)
+            native.check(native.lib().cm_motion_feature_tables(self.device, dp.ptr, dg.ptr, N, C_, H, W, F, int(f), int(k),
+                                                               float(gamma), out.ctypes.data))
+            self.data_dict.update({"MF_MSE": out[:, 0:2].copy() if mse_metric else None,
+                                   "MF_BHATT_DIST": out[:, 2:4].copy() if bhatt_metrics else None,
+                                   "MF_BHATT_COEF": out[:, 4:6].copy() if bhatt_metrics else None})
+            return
         pred, gt = self._pred_gt
         self.data_dict.update(motion_feature_tables(pred, gt, int(f), int(k), float(gamma), mse_metric, bhatt_metrics))
 

@@ -4,8 +4,10 @@
 For every test batch: `samples_per_batch / chunk` past windows, each repeated `chunk` times, are sampled in ONE
 device loop (cfg MODEL.NSAMPLES = 1280 = 64 pasts x 20 repeats by default), and the per-frame reductions behind
 PSNR / masked PSNR / relative density error / total variation run on the device too (cm_frame_metrics); the
-tables land in <OUTPUT_DIR>/metrics as CSV + metrics_files.json.  SSIM and ENERGY run on the host (scipy / numpy), as
-the reference's do (skimage / torch CPU), and so do the motion-feature histogram metrics MF_MSE / MF_BHATT.
+tables land in <OUTPUT_DIR>/metrics as CSV + metrics_files.json.  SSIM, ENERGY and the motion-feature histogram metrics
+MF_MSE / MF_BHATT run on the host by default (scipy / numpy, as the reference's do: skimage / torch CPU / numpy);
+`--tables device` (or METRICS.TABLES: device in the config) computes them on the device as well (cm_ssim_frames, cm_energy,
+cm_motion_feature_tables), the host route being the yardstick they are held to.
 
 Data: `--data-npy` takes sequences [N, C>=3, ROWS, COLS, T] cut into past/future windows (utils/dataset.py:22-53);
 without it synthetic windows ~ N(0,1) with a non-negative density channel are used (no dataset ships here).
@@ -34,6 +36,8 @@ def main(argv=None):
     ap.add_argument('--test-windows', type=int, default=None, help='synthetic test windows per batch (default: BATCH_SIZE)')
     ap.add_argument('--timesteps', type=int, default=None, help='override MODEL.DDPM.TIMESTEPS, or MODEL.FM.INTEGRATOR_STEPS.EULER for FM-DiT (smoke runs)')
     ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--tables', choices=('host', 'device'), default=None,
+                    help='route of the SSIM / ENERGY / MF_* tables (default: METRICS.TABLES of the config, else host)')
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     if args.arch not in ("DDPM-UNet", "DDPM-DiT", "FM-DiT", "ConvRNN"):
@@ -88,7 +92,8 @@ def main(argv=None):
             batches.append((p, f))
     logging.info("=======>>>> Init metrics compute for %s dataset with %s architecture: %d chains per batch (%d repeats)",
                  cfg.DATASET.get("NAME", "?"), args.arch, samples_per_batch, chunk)
-    mg = model.generate_metrics(batches, chunk, args.metric, args.batches_to_use, samples_per_batch, None, out_dir)
+    mg = model.generate_metrics(batches, chunk, args.metric, args.batches_to_use, samples_per_batch, None, out_dir,
+                                tables=args.tables)
     for k, v in mg.data_dict.items():
         if v is not None and len(v):
             logging.info("%-24s %s mean %s", k, np.asarray(v).shape, np.round(np.nanmean(np.asarray(v, dtype=np.float64), axis=0), 3)[:6])

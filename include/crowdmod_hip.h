@@ -305,6 +305,52 @@ int cm_model_issue_flops(const cm_model *m, int32_t B, double f32[8], double b16
 int cm_frame_metrics(int32_t device, const float *d_pred, const float *d_gt, int32_t N, int32_t C, int32_t H,
                      int32_t W, int32_t F, double *h_out, float *h_minmax);
 
+/* ---- sampling metrics: the SSIM, energy and motion-feature tables on the device (cm_metrics.hip) ----
+ * The host route (crowdmod-ddpm-4d_amd/metrics.py: _ssim2d, compute_energy, _mf_polar, motion_feature_vectors,
+ * bhattacharyya) is the yardstick these restate.  Inputs are float32 device tensors [N,C,H,W,F], F innermost; results are
+ * float64 host arrays.  Every argument is checked before the first device call.  Each output element has one writer, every
+ * floating-point sum a fixed order, and the only atomics are integer LDS counters: two runs give identical bits.
+ *
+ * cm_ssim_frames: h_out[n][c][f] = mean SSIM of the (sample, channel, frame) image pair -- 7 x 7 uniform window, only the
+ *   (H - 6)(W - 6) windows wholly inside the image, cov_norm = 49 / 48, C1 = (0.01 R)^2, C2 = (0.03 R)^2 with R = h_range[c],
+ *   v = cov_norm (mean(x^2) - mean(x)^2) and so on; everything in float64.  min(H, W) < 7 is refused (the host raises
+ *   ValueError), and so is W * F > 1024 (a band of rows is staged in LDS; H is not limited).
+ *
+ * cm_energy: h_out[n] = compute_energy (models/guidance.py:10-42) of x[n]: the residual f = term1 + term2 + term3 + term4
+ *   over interior cells in float32, in the host's operation order without fused multiply-add; f f and the sum in float64;
+ *   0.5 sum / (H W L).  h_factor [C] (or NULL) multiplies each channel in float32 first.  C < 3 is refused; a grid with no
+ *   interior cell (H < 3, W < 3 or L < 2) gives 0.
+ *
+ * cm_motion_feature_vectors / cm_motion_feature_tables (utils/metrics/motionFeatureExtractor.py:34-59,166-303,
+ *   metricsGenerator.py:240-258; 16 x 16 bins, volumes of f frames x k x k cells, ragged at the far edges, in
+ *   (frame block, row block, column block) order).  `vectors` returns the two normalised vectors of d_seq (h_mf2
+ *   [N][nvol 256], h_mf1 [N][nvol 16]); `tables` returns per sample MSE 2-D, MSE 1-D, Bhattacharyya distance 2-D, 1-D,
+ *   coefficient 2-D, 1-D (h_out [N][6]) without materialising the vectors: its device workspace is those six numbers.
+ *   C < 3, f < 1, k < 1 are refused.  The arithmetic that decides a bin:
+ *     magnitude   sqrt(vx vx + vy vy) in float32 (each product rounded, then the sum, then a correctly rounded root),
+ *                 widened; per grid cell lo / hi over its F frames, rng = hi - lo (1 when below 10 DBL_EPSILON),
+ *                 scale = 255.0 / rng, y = mag scale + (0.0 - lo scale) + 1.0 in that order in IEEE float64 without
+ *                 contraction, lm = log2(y).  A NaN in any frame of a cell makes its lo / hi NaN: all its frames leave
+ *                 the 2-D histogram (and carry a NaN weight in the 1-D one, as on the host); no other cell changes.
+ *     top edge    decided on y, not on the device's log2: 256 <= y <= 256 + 2 * 2^-44 is the last magnitude bin (a
+ *                 correctly rounded log2 gives 8.0 exactly there, which histogram2d keeps), anything above and NaN are
+ *                 outside, every y below 256 stays at or below bin 15.  Interior edges i / 2 are decided on lm.
+ *     angle       atan2f(vy, vx) in float32, widened; edges -pi + i pi / 8 in float64; the 2-D histogram closes its last
+ *                 bin on == pi (float64), the 1-D one does not; float32 +-pi fall outside both.
+ *     bins        searchsorted(side = 'right') - 1; the whole first magnitude bin moves to angle bin 8.
+ *     1-D weight  lm ** gamma in float64.  Normalisers: sum + 1.
+ *     tables      MSE = mean over all nvol 256 (nvol 16) bins of the squared difference of the two normalised values (the
+ *                 difference is formed per bin: identical sequences give exactly 0); coefficient = clip(sum sqrt(P Q),
+ *                 0.01, 1), distance = -log(coefficient). */
+int cm_ssim_frames(int32_t device, const float *d_pred, const float *d_gt, int32_t N, int32_t C, int32_t H, int32_t W,
+                   int32_t F, const double *h_range, double *h_out);
+int cm_energy(int32_t device, const float *d_x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t L, float delta_t,
+              float delta_l, const float *h_factor, double *h_out);
+int cm_motion_feature_vectors(int32_t device, const float *d_seq, int32_t N, int32_t C, int32_t H, int32_t W, int32_t F,
+                              int32_t f, int32_t k, double gamma, double *h_mf2, double *h_mf1);
+int cm_motion_feature_tables(int32_t device, const float *d_pred, const float *d_gt, int32_t N, int32_t C, int32_t H,
+                             int32_t W, int32_t F, int32_t f, int32_t k, double gamma, double *h_out);
+
 /* ---- mass_preservation guidance: preservationMassNumericalGradientOptimal (models/guidance.py:44-69) ----
  * d_grad[i] = (E(x + eps e_i) - E(x)) / eps for every element i of d_x [B,C,H,W,L], E = compute_energy(x, delta_t,
  * delta_l) (guidance.py:10-42) -- the reference's forward-difference quotient, evaluated in closed form (f is linear in
