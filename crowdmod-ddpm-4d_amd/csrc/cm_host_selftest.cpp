@@ -1300,11 +1300,29 @@ struct HostList {
   ~HostList() { cm_model_destroy(m); }
 };
 
-void check_bwd_plan(const HostList &h, int nparams) {
+// nparams < 0: whatever the handle holds.  refusal: the plan must say so in these words instead (a status for cm_train_init, no abort).
+void check_bwd_plan(const HostList &h, int nparams, const char *refusal = nullptr) {
   const cm_model *m = h.m;
   const BwdKnobs k;
   const BwdPlan P = plan_backward(m->ops, h.ctx, k);
+  if (refusal) { EXPECT(P.err.find(refusal) != std::string::npos); return; }
+  if (nparams < 0) nparams = (int)m->params.size();
   EXPECT(P.err.empty() && P.ops.size() == m->ops.size());
+  // every launching entry has both routes, and the text names each of them on a line of its own
+  {
+    int launching = 0;
+    for (const BwdOp &e : P.ops) {
+      const Op &op = m->ops[e.op];
+      if (op.kind == OP_ATTN) { ++launching; EXPECT(cm::attn_bwd_limit(op.S, op.E, ATTN_HEADS) == nullptr); }
+      if (op.kind != OP_CONV) continue;
+      ++launching;
+      EXPECT(e.wg.kernel >= WG_WINO && e.wg.kernel <= WG_GENERIC && e.dg.kernel >= DG_NONE && e.dg.kernel <= DG_GENERIC);
+      EXPECT((e.dg.kernel == DG_NONE) == (op.in0 == h.ctx.x8));
+      if (e.dg.kernel == DG_QR) EXPECT(train_qr_forms_ok(op, e.g));   // (the training forward takes conv_qr2 exactly there: no late refusal in run_conv_qr)
+    }
+    const std::string text = bwd_plan_text(m->ops, P, h.ctx.max_batch);
+    EXPECT((int)std::count(text.begin(), text.end(), '\n') == launching && launching > 0);
+  }
   // every gradient buffer: exactly one first writer, before every accumulator and before the entry that reads it as dY
   std::map<const Act *, int> first, reads;   // -> position in the plan
   std::map<const Act *, std::vector<int>> accs;
@@ -1397,11 +1415,70 @@ void test_bwd_plan() {
   }
 }
 
+// The geometries of tests/train_limit_cases.py (the rows that differ in dropout alone share a plan with "ethucy"): what a handle
+// admits beyond the tuned grids.  Each is planned on a host-only handle and held to the same invariants; print: the plan's text.
+// refusal: the words of the status instead -- "build: ..." from the list building of cm_model_finalize, anything else from plan_backward
+struct LimitCase { const char *id; int rows, cols, past, future, C, base, levels, mult[4], att[4], res, B; const char *refusal; };
+const LimitCase kLimitCases[] = {
+    {"ethucy", 8, 12, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 3, nullptr},
+    {"hermes_bn", 28, 16, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 3, nullptr},
+    {"hermes_bo", 12, 24, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"hermes_cr90", 12, 20, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 3, nullptr},
+    {"ethucy_b9", 8, 12, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 9, nullptr},
+    {"grid4x4", 4, 4, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 1, nullptr},
+    {"plane64", 32, 32, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 1, nullptr},
+    {"plane72", 48, 24, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 1, nullptr},
+    {"attn_half", 16, 32, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 1, 1}, 1, 1, nullptr},
+    {"attn_half640", 16, 40, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 1, 1}, 1, 1, "too many tokens"},
+    {"frames4", 8, 12, 3, 1, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"frames12", 8, 12, 8, 4, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"base8", 8, 12, 5, 3, 3, 8, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"base16", 8, 12, 5, 3, 3, 16, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"base24", 8, 12, 5, 3, 3, 24, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, "build: head width"},
+    {"ch1", 8, 12, 5, 3, 1, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"ch4", 8, 12, 5, 3, 4, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"ch5", 8, 12, 5, 3, 5, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"ch8", 8, 12, 5, 3, 8, 32, 3, {1, 2, 4}, {0, 0, 1}, 1, 2, nullptr},
+    {"res2", 8, 12, 5, 3, 3, 32, 3, {1, 2, 4}, {0, 0, 1}, 2, 2, nullptr},
+    {"levels2", 8, 12, 5, 3, 3, 32, 2, {1, 2}, {0, 1}, 1, 2, nullptr},
+    {"levels4", 8, 16, 5, 3, 3, 32, 4, {1, 2, 2, 4}, {0, 0, 0, 1}, 1, 2, nullptr},
+    {"mult112", 8, 12, 5, 3, 3, 32, 3, {1, 1, 2}, {0, 0, 1}, 1, 2, nullptr},
+};
+cm_unet_config limit_cfg(const LimitCase &t) {
+  cm_unet_config c{};
+  c.in_channels = c.out_channels = t.C;
+  c.num_res_blocks = t.res; c.base_channels = t.base; c.n_levels = t.levels;
+  for (int i = 0; i < t.levels; ++i) { c.channel_mult[i] = t.mult[i]; c.apply_attention[i] = t.att[i]; }
+  c.time_multiple = 4; c.rows = t.rows; c.cols = t.cols; c.past_len = t.past; c.future_len = t.future; c.max_batch = t.B; c.device = -1;
+  return c;
+}
+void test_bwd_plan_limits(bool print) {
+  for (const LimitCase &t : kLimitCases) {
+    if (t.refusal && !strncmp(t.refusal, "build: ", 7)) {   // no op list: the handle itself is refused, by name
+      cm_unet_config c = limit_cfg(t);
+      cm_model *m = nullptr;
+      EXPECT(cm_model_create(&c, &m) == 0 && dev_alloc(m, (void **)&m->tbuf, sizeof(long long)) == 0);
+      EXPECT(build_ops(m) != 0 && strstr(cm_last_error(), t.refusal + 7));
+      if (print) printf("== %s: %s\n", t.id, cm_last_error());
+      cm_model_destroy(m);
+      continue;
+    }
+    HostList h(limit_cfg(t));
+    check_bwd_plan(h, -1, t.refusal);
+    if (!print) continue;
+    const BwdPlan P = plan_backward(h.m->ops, h.ctx, BwdKnobs());
+    printf("== %s%s%s\n%s", t.id, P.err.empty() ? "" : ": ", P.err.c_str(), P.err.empty() ? bwd_plan_text(h.m->ops, P, h.ctx.max_batch).c_str() : "");
+  }
+  printf("test_bwd_plan_limits: %zu geometries planned\n", sizeof kLimitCases / sizeof kLimitCases[0]);
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char **argv) {
+  if (argc > 1 && std::string(argv[1]) == "plans") { test_bwd_plan_limits(true); return 0; }   // the limit geometries' backward plans, as text
   test_bwd_route();
   test_bwd_plan();
+  test_bwd_plan_limits(false);
   test_opt_store();
   test_schedule();
   test_plan_and_params();

@@ -431,6 +431,7 @@ hipError_t launch_time_mlp(const float *table, const float *W1, const float *b1,
                            float *out, const long long *rowidx, hipStream_t st);
 // softmax(q k^T / sqrt(d)) v per (sample, head); qkv channels-last [B][S][3E]
 hipError_t launch_attn_core(const float *qkv, float *out, int B, int S, int E, int heads, hipStream_t st);
+bool attn_core_width_ok(int E, int heads);   // channels per head in {8, 16, 32, 64}: what the core and its backward are instantiated for
 // the same on f16 matrix-core operands (fp32 accumulate, fp32 softmax): reduced-precision plan, head dimension 32
 hipError_t launch_attn_core_f16(const float *qkv, float *out, int B, int S, int E, int heads, hipStream_t st);
 
@@ -941,6 +942,8 @@ hipError_t launch_mse_grad(const float *pred, const float *target, float *g, int
 hipError_t launch_scale_inplace(float *g, long long n, float s, hipStream_t st);
 // `big`: global scratch of attn_bwd_scratch_floats() floats when the S x S matrices exceed LDS (0 floats = not needed)
 size_t attn_bwd_scratch_floats(int B, int S, int E, int heads);
+// null, or why launch_attn_bwd cannot run this core (head width without a kernel, tokens past the LDS tiles), in words
+const char *attn_bwd_limit(int S, int E, int heads);
 hipError_t launch_attn_bwd(const float *qkv, const float *dO, float *dqkv, int B, int S, int E, int heads, float *big, hipStream_t st);
 struct TimeBwdArgs {
   const float *table; const long long *t;

@@ -722,7 +722,15 @@ __global__ __launch_bounds__(256) void attn_core_kernel(const float *__restrict_
   }
 }
 
+// the head widths attn_core_kernel (and attn_bwd_kernel, cm_train.hip) is instantiated for: a head is split over a power-of-two
+// group of lanes, 8 channels each
+bool attn_core_width_ok(int E, int heads) {
+  const int D = heads > 0 ? E / heads : 0;
+  return heads > 0 && E % heads == 0 && (D == 8 || D == 16 || D == 32 || D == 64);
+}
+
 hipError_t launch_attn_core(const float *qkv, float *out, int B, int S, int E, int heads, hipStream_t st) {
+  if (!attn_core_width_ok(E, heads)) return hipErrorInvalidValue;
   const int D = E / heads;
   const size_t smem = (size_t)2 * S * D * sizeof(float);
   if (smem > 160 * 1024) return hipErrorInvalidValue;

@@ -948,6 +948,8 @@ int build_ops(cm_model *m) {
       Op at; at.kind = OP_ATTN; at.cls = K_ATTN; at.label = ap + ".core"; at.qkv = qkv->d; at.aout = ao->d; at.S = qkv->V(); at.E = b.cout;
       if ((size_t)2 * at.S * (at.E / ATTN_HEADS) * 4 > 160 * 1024)
         return fail("attention with %d tokens exceeds the LDS-resident K/V design", at.S);
+      if (!cm::attn_core_width_ok(at.E, ATTN_HEADS))   // (no kernel, fused or not, takes it: said here, not by the first forward's launch)
+        return fail("%s: %d channels over %d heads: head width outside the attention kernels' 8, 16, 32 and 64 channels per head", ap.c_str(), at.E, ATTN_HEADS);
       m->ops.push_back(at);
       Act *h3 = new_act(m, p, b.cout, Zl[l], Yl[l], Xl[l], true, &rc);
       if (rc) return 1;
@@ -1269,13 +1271,24 @@ WgradRoute wgrad_route(const Op &op, const BwdGeom &g, const BwdCtx &ctx, const 
   return {WG_GENERIC, FORM_FP32};
 }
 
+// conv_qr2's six-term form holds both launches of a quarter-resolution conv's training step: the forward on the op's own sources
+// (conv_route takes the kernel there exactly where the data gradient does: Op::train_qr) and the data gradient on dY.  Asked here, so
+// that a width or a plane the form cannot hold trains on the generic kernels instead of failing inside its first step.
+bool train_qr_forms_ok(const Op &op, const BwdGeom &g) {
+  cm::QrArgs f{}, d{};
+  f.C0 = op.ca.C0; f.C1 = op.ca.C1; f.Co = op.ca.Co; f.Y = op.ca.Yo; f.X = op.ca.Xo; f.groups = GN_GROUPS; f.raw = 1; f.wq6 = op.d_wqr_b6;
+  d.C0 = g.da.C0; d.Co = g.da.Co; d.Y = g.da.Yo; d.X = g.da.Xo; d.groups = 8; d.raw = 1; d.wq6 = op.d_wqr_b6; d.out_cs = g.da.out_cs;
+  return cm::conv_qr2_b6_ok(f) && cm::conv_qr2_b6_ok(d);
+}
+
 DgradRoute dgrad_route(const Op &op, const BwdGeom &g, const BwdCtx &ctx, const BwdKnobs &k) {
   if (g.first) return {DG_NONE, FORM_FP32};
   const cm::ConvArgs &a = g.da;
   const int Cy = a.C0, Ci_pad = a.out_cs;
   // quarter resolution (two planes): forward and data gradient of the training step on conv_qr2's six-term form
   if (op.qr && op.d_wqr_b6 && op.ref_taps == 27 && Cy == g.Co && g.Co % 64 == 0 && g.Ci % 32 == 0 && g.Ci == Ci_pad && a.Zo == 2 &&
-      a.Yo * a.Xo <= 64 && 8 * (a.Yo + 2) * (a.Xo + 2) <= 64 * 9 && ctx.precision != CM_PRECISION_F16 && !k.no_train_qr) return {DG_QR, FORM_B6};
+      a.Yo * a.Xo <= 64 && 8 * (a.Yo + 2) * (a.Xo + 2) <= 64 * 9 && ctx.precision != CM_PRECISION_F16 && !k.no_train_qr && train_qr_forms_ok(op, g))
+    return {DG_QR, FORM_B6};
   // the data gradient of a 3x3x3 conv is a stride-1 3x3x3 conv of dY with the flipped / transposed weights: same Winograd kernel.
   // fp32 plan: the six-term bf16 form wherever the forward's tile takes it (exact three-way splits, fp32 accumulate: fp32-level
   // products at 2.7x the matrix rate); autocast: f16 operands

@@ -1354,7 +1354,8 @@ hipError_t launch_mse_grad(const float *pred, const float *target, float *g, int
 // --------------------------------------------------------------------------------
 // Attention core backward per (sample, head): P = softmax(q k^T * s);  O = P v
 //   dV = P^T dO ; dP = dO V^T ; dS = P o (dP - rowsum(dP o P)) ; dQ = s * dS K ; dK = s * dS^T Q
-// qkv / dqkv channels-last [B][S][3E]; dO [B][S][E].  S <= 256 (rows handled by threads).
+// qkv / dqkv channels-last [B][S][3E]; dO [B][S][E].  Every loop strides over S: the token count is limited by storage alone
+// (attn_bwd_limit: the four S x (D + 1) operand tiles in LDS; P and dS in LDS or in the global slab).
 // --------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float *__restrict__ qkv, const float *__restrict__ dO,
@@ -1427,19 +1428,31 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float *__restrict__
   }
 }
 
+// P and dS [S][S] beside the four operand tiles, or the operand tiles alone (P and dS in the global slab)
+static size_t attn_bwd_lds(int S, int D, bool slab) {
+  return ((size_t)4 * S * (D + 1) + (slab ? 0 : (size_t)2 * S * S)) * sizeof(float);
+}
+
 size_t attn_bwd_scratch_floats(int B, int S, int E, int heads) {
-  const int D = E / heads;
-  const size_t smem = ((size_t)4 * S * (D + 1) + (size_t)2 * S * S) * sizeof(float);
-  return smem > 160 * 1024 ? (size_t)B * heads * 2 * S * S : 0;
+  return attn_bwd_lds(S, E / heads, false) > 160 * 1024 ? (size_t)B * heads * 2 * S * S : 0;
+}
+
+// What the launcher below cannot run, in words (null: it can): a head width it is not instantiated for (the forward core's:
+// cm_model_finalize already refuses those), tokens whose four operand tiles do not fit LDS -- fewer than the forward core holds
+// (two tiles).  The backward plan asks at cm_train_init, so that no step meets the launcher's bare error.
+const char *attn_bwd_limit(int S, int E, int heads) {
+  if (!attn_core_width_ok(E, heads)) return "head width: the attention kernels take 8, 16, 32 or 64 channels per head";
+  if (S < 1 || attn_bwd_lds(S, E / heads, true) > 160 * 1024) return "too many tokens for the attention backward, which keeps four tiles of tokens x (head width + 1) floats in 160 KB of LDS";
+  return nullptr;
 }
 
 hipError_t launch_attn_bwd(const float *qkv, const float *dO, float *dqkv, int B, int S, int E, int heads, float *big, hipStream_t st) {
+  if (attn_bwd_limit(S, E, heads)) return hipErrorInvalidValue;
   const int D = E / heads;
-  size_t smem = ((size_t)4 * S * (D + 1) + (size_t)2 * S * S) * sizeof(float);
+  size_t smem = attn_bwd_lds(S, D, false);
   if (smem > 160 * 1024) {
     if (!big) return hipErrorInvalidValue;
-    smem = (size_t)4 * S * (D + 1) * sizeof(float);
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
+    smem = attn_bwd_lds(S, D, true);
   } else {
     big = nullptr;
   }

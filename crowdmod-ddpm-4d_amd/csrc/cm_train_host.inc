@@ -122,6 +122,10 @@ BwdPlan plan_backward(const std::vector<Op> &ops, const BwdCtx &ctx, const BwdKn
         if (o.kind == OP_CONV && o.in0->d == op.aout) e.oa = o.in0;
       }
       if (!e.qa || !e.oa || !have.count(e.oa)) { P.err = "attention backward: missing gradient (" + op.label + ")"; break; }
+      if (const char *why = cm::attn_bwd_limit(op.S, op.E, ATTN_HEADS)) {
+        P.err = "training refused: " + op.label + " (" + std::to_string(op.S) + " tokens, " + std::to_string(op.E / ATTN_HEADS) + " channels per head): " + why;
+        break;
+      }
       P.attn_floats = std::max(P.attn_floats, cm::attn_bwd_scratch_floats(ctx.max_batch, op.S, op.E, ATTN_HEADS));
       have.emplace(e.qa, oi);
       continue;
@@ -169,6 +173,30 @@ BwdPlan plan_backward(const std::vector<Op> &ops, const BwdCtx &ctx, const BwdKn
       P.cp_max = std::max(P.cp_max, (long long)op.ca.Co * ctx.tx);
     }
   return P;
+}
+
+// The plan as text, one line per launching entry in execution (reverse) order:
+//   conv <label> wgrad <kernel> <form> dgrad <kernel> <form>
+//   attn <label> S <tokens> D <channels per head> <lds | slab>     (where P and dS of a (sample, head) live)
+// Reads the plan and the op list only.
+const char *const kWgradName[] = {"WG_WINO", "WG_PACK", "WG_PAR", "WG_1X1", "WG_ZS", "WG_GENERIC"};
+const char *const kDgradName[] = {"DG_NONE", "DG_QR", "DG_WINO", "DG_GENERIC"};
+const char *form_name(ConvForm f) {
+  switch (f) { case FORM_FP32: return "fp32"; case FORM_B6: return "b6"; case FORM_B3: return "b3"; case FORM_H2: return "h2"; case FORM_F16: return "f16"; }
+  return "?";
+}
+std::string bwd_plan_text(const std::vector<Op> &ops, const BwdPlan &P, int max_batch) {
+  std::string out;
+  for (const BwdOp &e : P.ops) {
+    const Op &op = ops[e.op];
+    if (op.kind == OP_ATTN)
+      out += "attn " + op.label + " S " + std::to_string(op.S) + " D " + std::to_string(op.E / ATTN_HEADS) +
+             (cm::attn_bwd_scratch_floats(max_batch, op.S, op.E, ATTN_HEADS) ? " slab\n" : " lds\n");
+    if (op.kind == OP_CONV)
+      out += "conv " + op.label + " wgrad " + kWgradName[e.wg.kernel] + " " + form_name(e.wg.form) + " dgrad " + kDgradName[e.dg.kernel] + " " +
+             form_name(e.dg.form) + "\n";
+  }
+  return out;
 }
 
 }  // namespace
@@ -844,7 +872,11 @@ int cm_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, fl
   DevGuard g(m->device);
   if (!m->train) {
     m->train = new cm_train_state();
-    if (train_setup(m)) return 1;
+    if (train_setup(m)) {     // refused (the plan's limits, memory): the handle goes on as the inference handle it was
+      cm_free_train_state(m->train);
+      m->train = nullptr;
+      return 1;
+    }
   }
   m->train->opt.hyper(lr, beta1, beta2, eps, weight_decay);
   m->train->dropout = dropout_rate;
@@ -914,6 +946,16 @@ int cm_train_get_autocast(const cm_model *m, int32_t *mode, int32_t *loss_scale_
   const cm_train_state *T = m->train;
   *mode = T->autocast;
   *loss_scale_log2 = T->autocast ? autocast_scale_log2(m, T->ls_last_B > 0 ? T->ls_last_B : m->cfg.max_batch) : 0;
+  return 0;
+}
+
+int cm_debug_bwd_plan(const cm_model *m, char *buf, int64_t capacity, int64_t *needed) {
+  CM_NOT_DIT(m, "cm_debug_bwd_plan");
+  if (!m || !needed || capacity < 0 || (capacity > 0 && !buf)) return fail("cm_debug_bwd_plan: bad argument");
+  if (!m->train) return fail("cm_debug_bwd_plan: cm_train_init has not been called");
+  const std::string text = bwd_plan_text(m->ops, m->train->bwd, m->cfg.max_batch);
+  *needed = (int64_t)text.size() + 1;
+  if (capacity > 0) snprintf(buf, (size_t)capacity, "%s", text.c_str());
   return 0;
 }
 

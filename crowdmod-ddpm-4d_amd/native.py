@@ -135,6 +135,7 @@ SIGNATURES = {
     "cm_debug_conv_flags": (C.c_int, [C.c_int32]),
     "cm_debug_conv_count": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "cm_debug_conv_info": (C.c_int, [_P, C.c_int32, C.c_char_p, C.c_int64]),
+    "cm_debug_bwd_plan": (C.c_int, [_P, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "cm_debug_conv_io": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32]),
     "cm_debug_conv_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cm_debug_wino_form_counts": (C.c_int, [_P, C.c_int32]),

@@ -330,6 +330,25 @@ class UNet(NativeModule):
                     out.append(f[1])
         return out
 
+    def backward_plan(self):
+        """The backward plan of the training handle (cm_debug_bwd_plan), in execution order: one tuple per launching entry,
+        ("conv", weight name, wgrad kernel, wgrad form, dgrad kernel, dgrad form) or ("attn", label, S, D, "lds" | "slab")."""
+        L, h = native.lib(), self._train_handle()
+        need = C.c_int64()
+        native.check(L.cm_debug_bwd_plan(h, None, 0, C.byref(need)))
+        buf = C.create_string_buffer(int(need.value))
+        native.check(L.cm_debug_bwd_plan(h, buf, len(buf), C.byref(need)))
+        out = []
+        for line in buf.value.decode().splitlines():
+            f = line.split()
+            if f[0] == "conv" and len(f) == 8 and f[2] == "wgrad" and f[5] == "dgrad":
+                out.append(("conv", f[1], f[3], f[4], f[6], f[7]))
+            elif f[0] == "attn" and len(f) == 7 and f[2] == "S" and f[4] == "D":
+                out.append(("attn", f[1], int(f[3]), int(f[5]), f[6]))
+            else:
+                raise RuntimeError(f"cm_debug_bwd_plan: unexpected line {line!r}")
+        return out
+
     def conv3_issue_flops(self, B: int):
         """(fp32-instruction FLOPs, 16-bit-operand-instruction FLOPs) the 3x3x3 convolutions ISSUE on the matrix cores: a
         six-term layer (fp32 products from exact three-way bf16 splits) issues six bf16 products per fp32-equivalent one."""

@@ -373,6 +373,13 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count);
  * last forward (the whole-sample quarter-resolution conv, the second pass of a K-split conv / attention block, the Winograd
  * consumer's prologue, gn_finalize_kernel) and the slots per sample of its one or two sources.  Anything else: "other <label>". */
 int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity);
+/* The backward plan cm_train_init built (and cm_train_set_autocast re-plans), as text: one line per launching entry in execution
+ * (reverse) order.  "conv <label> wgrad <WG_...> <form> dgrad <DG_...> <form>": the kernels of the conv's weight gradient and
+ * data gradient (the enumerators of cm_model.cpp) and their operand forms (fp32 | b6 | f16).  "attn <label> S <tokens> D
+ * <channels per head> <lds | slab>": an attention core, and whether the S x S matrices of a (sample, head) live in LDS or in the
+ * global scratch slab.  Read-only: no device call.  *needed = bytes of the whole text with its terminator; at most `capacity`
+ * are written (capacity 0, buf NULL: size query).  An error before cm_train_init. */
+int cm_debug_bwd_plan(const cm_model *m, char *buf, int64_t capacity, int64_t *needed);
 /* Test hook: conv op `index` alone on caller data (no GroupNorm / SiLU / time row / residual / fused skip; bias stays).
  * h_in0 / h_in1: host channels-last [B][Zs][Ys][Xs][C0 / C1]; h_out: host [B][Zo][Yo][Xo][C of the output tensor -- the last
  * field of cm_debug_conv_info];
@@ -402,6 +409,9 @@ int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32
  * torch.optim.Adam(lr, betas, weight_decay) -- L2 coupled into the gradient.)
  * cm_train_init allocates master weights / gradients / Adam moments on the device
  * (state_dict order) and the backward workspace; call once after cm_model_finalize.
+ * A shape the forward admits and the backward cannot hold is refused HERE, in words ("training refused: ..."; today: an
+ * attention level with more tokens than the backward's LDS tiles hold) -- never inside a step; the handle then keeps no
+ * training state and goes on as the inference handle it was.
  * The step runs in fp32 unless cm_train_set_autocast switches its Winograd layers to f16 operands (below). */
 int cm_train_init(cm_model *m, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float dropout_rate /* cfg DROPOUT_RATE: nn.Dropout3d(p), layers.py:42 */);

@@ -34,33 +34,41 @@ def _t64(a):
     return torch.as_tensor(np.asarray(a)).to(torch.float64)
 
 
-def train_step64(params, plan, sab, s1m, future, past, t, eps, masks, chunk=8):
+def train_step64(params, plan, sab, s1m, future, past, t, eps, masks, chunk=8, dtype=None):
     """(loss, {name: grad}) in float64.  sab / s1m: the device's fp32 schedule tables (sqrt_alpha_bar,
-    sqrt_one_minus_alpha_bar); masks: {ResnetBlock prefix: [B, Cout]}."""
+    sqrt_one_minus_alpha_bar); masks: {ResnetBlock prefix: [B, Cout]}.  dtype: another torch dtype for the whole step
+    (train_step32)."""
     import torch
     from oracle import unet_torch as ot
     assert chunk <= 8
+    cast = _t64 if dtype is None else (lambda a: torch.as_tensor(np.asarray(a)).to(dtype))
     B = future.shape[0]
     n_total = float(future.size)
     with _threads():
-        P = {k: _t64(v) for k, v in params.items()}
+        P = {k: cast(v) for k, v in params.items()}
         for k, v in P.items():
             if k != FROZEN:
                 v.requires_grad_(True)
-        sab64, s1m64 = _t64(sab), _t64(s1m)
+        sab64, s1m64 = cast(sab), cast(s1m)
         loss = 0.0
         for b0 in range(0, B, chunk):
             sl = slice(b0, min(B, b0 + chunk))
             tt = torch.as_tensor(np.asarray(t)[sl], dtype=torch.long)
-            x0, e = _t64(future[sl]), _t64(eps[sl])
+            x0, e = cast(future[sl]), cast(eps[sl])
             xt = sab64[tt].view(-1, 1, 1, 1, 1) * x0 + s1m64[tt].view(-1, 1, 1, 1, 1) * e
-            dm = {k: _t64(v[sl]) for k, v in masks.items()}
-            pred = ot.unet_forward(P, plan, xt, tt, _t64(past[sl]), dm)
+            dm = {k: cast(v[sl]) for k, v in masks.items()}
+            pred = ot.unet_forward(P, plan, xt, tt, cast(past[sl]), dm)
             part = ((pred - e) ** 2).sum() / n_total
             part.backward()
             loss += float(part.detach())
         grads = {k: v.grad.numpy() for k, v in P.items() if v.grad is not None}
     return loss, grads
+
+
+def train_step32(*args, **kw):
+    """The same step with every tensor and every operation in float32: the reference's own CPU arithmetic."""
+    import torch
+    return train_step64(*args, dtype=torch.float32, **kw)
 
 
 def forward64(params, plan, future, t, past, masks=None):
