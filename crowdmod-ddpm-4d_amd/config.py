@@ -114,6 +114,7 @@ class DiTKeys:
     condition: str
     dropout_rate: float
     train: Optional[AttrDict]
+    precision: str = "f32"   # MODEL.DDPM.DIT.PRECISION: "f32" | "f16", the sampling plan of DiT4D_V4.set_precision (absent: "f32")
 
 
 @dataclass
@@ -201,7 +202,10 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
         else:
             dit = DiTKeys(int(req("PATCH_SIZE")), int(req("T_PATCH_SIZE")), int(req("HIDDEN_SIZE")), int(req("DEPTH")),
                           int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")),
-                          str(req("CONDITION")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
+                          str(req("CONDITION")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"),
+                          str(back.get("PRECISION", "f32")))
+            if dit.precision not in ("f32", "f16"):
+                raise ValueError(f"MODEL.DDPM.DIT.PRECISION {dit.precision!r}: 'f32' or 'f16'")
         if arch == "DDPM-DiT" and dit.condition != "Past":
             raise NotImplementedError(f"DIT.CONDITION {dit.condition!r}: only 'Past' (the configuration every reference config uses)")
     mult = tuple(int(v) for v in bk("BASE_CH_MULT", (1, 2, 4)))

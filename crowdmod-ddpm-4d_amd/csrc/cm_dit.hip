@@ -9,9 +9,10 @@
 //                     (conditioning tables), exact-erf GELU, gated residual, patch embedding + both position
 //                     embeddings, and the unpatchify scatter of the final linear into eps_cl.  A row subset (the
 //                     temporal queries, the future slots of the final layer) maps logical GEMM rows to token rows.
-//   dit_gemm_f16_kernel  its sibling on v_mfma_f32_32x32x16_f16 for the blocks' token Linears of an autocast TRAINING step
-//                     (cm_dit4d_train_set_autocast): operands rounded to f16 when staged, fp32 accumulation and output.  The eval
-//                     forward never takes it.
+//   dit_gemm_f16_kernel  its sibling on v_mfma_f32_32x32x16_f16 for the blocks' token Linears: operands rounded to f16, fp32
+//                     accumulation and output.  Taken by the autocast TRAINING step (cm_dit4d_train_set_autocast; fp32 master
+//                     weights rounded when staged) and by the eval forward of a handle on the f16 sampling plan
+//                     (cm_model_set_precision(CM_PRECISION_F16); weights rounded once by dit_finalize); the default plan never takes it.
 //   dit_attn_*        softmax(q k^T / 8) v per head (head dim 64) on the vector ALUs: spatial self-attention over the
 //                     N_s tokens of one (sample, slot), temporal cross-attention of the future slots of one (sample,
 //                     patch) over all T_p slots.
@@ -181,14 +182,19 @@ __global__ __launch_bounds__(256) void dit_gemm_kernel(const DitGemmArgs a) {
   }
 }
 
-// The f16-operand sibling of dit_gemm_kernel for the token Linears of an autocast training step (DitGemmArgs::f16): the same
-// 64 x 64 tile, row-subset addressing and LayerNorm statistics; the A operand is the fp32 value dit_gemm_kernel would stage
-// (LayerNorm + modulate in fp32, where torch's autocast casts it) and W the fp32 master weight, both rounded to f16 when staged.
+// The f16-operand sibling of dit_gemm_kernel for the blocks' token Linears (DitGemmArgs::f16): the same 64 x 64 tile, row-subset
+// addressing and LayerNorm statistics; the A operand is the fp32 value dit_gemm_kernel would stage (LayerNorm + modulate in fp32,
+// where torch's autocast casts it), rounded to f16 when staged.  Two weight sources:
+//   WH = false  the autocast training step: the fp32 master weight a.W, rounded when staged like A; bias epilogue only
+//   WH = true   the f16 sampling plan (cm_model_set_precision): a.Wh, the copy dit_finalize rounded once, [N][K] halves; one
+//               16-byte load gives eight k of a row with no conversion (launch_dit_gemm admits K % 8 == 0 only, so a group is whole
+//               and aligned).  Epilogues bias, GELU and gated residual, with dit_gemm_kernel's expressions.
 // Layout, rounding and the bank arithmetic: cm_dit_f16.h.  Staging: thread -> row tid >> 3 (and + 32), k group 8 (tid & 7).
 // Edges as dit_gemm_kernel: rows >= M, columns >= N and k >= K are staged as zeros.
-template <int PRO, int EPI>
+template <int PRO, int EPI, bool WH>
 __global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) {
-  static_assert((PRO == DIT_PRO_NONE || PRO == DIT_PRO_LN) && EPI == DIT_EPI_BIAS, "token Linears of the training step only");
+  static_assert(PRO == DIT_PRO_NONE || PRO == DIT_PRO_LN, "token Linears only");
+  static_assert(EPI == DIT_EPI_BIAS || (WH && (EPI == DIT_EPI_GELU || EPI == DIT_EPI_GATE)), "the training step has the bias epilogue only");
   __shared__ __attribute__((aligned(16))) _Float16 As[GB * DH_S], Ws[GB * DH_S];
   __shared__ float s_mu[GB], s_rs[GB];
   __shared__ const float *s_mod[GB];
@@ -206,19 +212,22 @@ __global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) 
   const int wm = wave & 1, wn = wave >> 1;
   const int sr = tid >> 3, sk = (tid & 7) * 8;
   const float *arow[2], *wrow[2], *mrow[2];
+  const _Float16 *whrow[2];
   float mu[2], rs[2];
   for (int h = 0; h < 2; ++h) {
     const long long r = m0 + sr + 32 * h;
     const int n = n0 + sr + 32 * h;
     arow[h] = r < a.M ? a.A + (a.a_compact ? r : phys_row(a, r)) * a.lda : nullptr;
-    wrow[h] = n < a.N ? a.W + (long long)n * a.K : nullptr;
+    wrow[h] = !WH && n < a.N ? a.W + (long long)n * a.K : nullptr;
+    whrow[h] = WH && n < a.N ? a.Wh + (long long)n * a.K : nullptr;
     mrow[h] = PRO == DIT_PRO_LN ? s_mod[sr + 32 * h] : nullptr;
     mu[h] = PRO == DIT_PRO_LN ? s_mu[sr + 32 * h] : 0.f;
     rs[h] = PRO == DIT_PRO_LN ? s_rs[sr + 32 * h] : 0.f;
   }
-  // the chunk in flight: raw fp32 values in registers, fetched one chunk ahead so that the global loads run under the matrix
+  // the chunk in flight: raw values in registers, fetched one chunk ahead so that the global loads run under the matrix
   // instructions of the chunk before; the prologue arithmetic and the rounding happen when they are stored to LDS
   float v[2][8], w[2][8], sc[2][8], sh[2][8];
+  dit_f16x8 wh[2];
   auto fetch = [&](int k) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -231,7 +240,13 @@ __global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) 
           dh_load8(mrow[h] + a.off_shift, k, a.K, sh[h]);
         }
       }
-      if (wrow[h]) dh_load8(wrow[h], k, a.K, w[h]);
+      if (WH) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) wh[h][e] = (_Float16)0.f;
+        if (whrow[h] && k < a.K) wh[h] = *(const dit_f16x8 *)(whrow[h] + k);   // K % 8 == 0: the group ends at or before K
+      } else if (wrow[h]) {
+        dh_load8(wrow[h], k, a.K, w[h]);
+      }
     }
   };
   fetch(sk);
@@ -247,7 +262,7 @@ __global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) 
         }
       }
       *(dit_f16x8 *)(As + (sr + 32 * h) * DH_S + sk) = dh_round8(v[h]);
-      *(dit_f16x8 *)(Ws + (sr + 32 * h) * DH_S + sk) = dh_round8(w[h]);
+      *(dit_f16x8 *)(Ws + (sr + 32 * h) * DH_S + sk) = WH ? wh[h] : dh_round8(w[h]);
     }
     __syncthreads();
     if (k0 + DH_K < a.K) fetch(k + DH_K);
@@ -262,7 +277,17 @@ __global__ __launch_bounds__(256) void dit_gemm_f16_kernel(const DitGemmArgs a) 
   for (int i = 0; i < 16; ++i) {
     const long long rl = m0 + wm * 32 + (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5);
     if (rl >= a.M) continue;
-    a.Y[phys_row(a, rl) * a.ldy + col] = acc[i] + bias;
+    const long long prow = phys_row(a, rl);
+    const float v = acc[i] + bias;
+    if (EPI == DIT_EPI_BIAS) {
+      a.Y[prow * a.ldy + col] = v;
+    } else if (EPI == DIT_EPI_GELU) {
+      a.Y[prow * a.ldy + col] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    } else {   // DIT_EPI_GATE
+      const float *mrow = a.mod + a.tbuf[prow / a.tok] * (long long)a.ldmod;
+      float *y = a.Y + prow * a.ldy + col;
+      *y = *y + mrow[a.off_gate + col] * v;
+    }
   }
 }
 
@@ -452,11 +477,16 @@ hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st) {
   if (a.M <= 0) return hipSuccess;
   dim3 grid((unsigned)((a.M + GB - 1) / GB), (unsigned)((a.N + GB - 1) / GB));
   if (a.f16) {   // a missing f16 form is an error, never the fp32 kernel
-    if (a.epi != DIT_EPI_BIAS) return hipErrorInvalidValue;
-    if (a.pro == DIT_PRO_NONE) hipLaunchKernelGGL((dit_gemm_f16_kernel<DIT_PRO_NONE, DIT_EPI_BIAS>), grid, dim3(256), 0, st, a);
-    else if (a.pro == DIT_PRO_LN) hipLaunchKernelGGL((dit_gemm_f16_kernel<DIT_PRO_LN, DIT_EPI_BIAS>), grid, dim3(256), 0, st, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+#define CM_DIT_H(P, E, WH) \
+  if (a.pro == P && a.epi == E && (a.Wh != nullptr) == WH) { hipLaunchKernelGGL((dit_gemm_f16_kernel<P, E, WH>), grid, dim3(256), 0, st, a); return hipGetLastError(); }
+    CM_DIT_H(DIT_PRO_NONE, DIT_EPI_BIAS, false)   // the autocast training step: fp32 master weights
+    CM_DIT_H(DIT_PRO_LN, DIT_EPI_BIAS, false)
+    if (a.K % 8) return hipErrorInvalidValue;     // the f16 sampling plan: 16-byte groups of pre-rounded halves
+    CM_DIT_H(DIT_PRO_LN, DIT_EPI_BIAS, true)
+    CM_DIT_H(DIT_PRO_LN, DIT_EPI_GELU, true)
+    CM_DIT_H(DIT_PRO_NONE, DIT_EPI_GATE, true)
+#undef CM_DIT_H
+    return hipErrorInvalidValue;
   }
 #define CM_DIT_G(P, E) \
   if (a.pro == P && a.epi == E) { hipLaunchKernelGGL((dit_gemm_kernel<P, E>), grid, dim3(256), 0, st, a); return hipGetLastError(); }

@@ -1,12 +1,14 @@
 // f16-operand staging shared by dit_gemm_f16_kernel (cm_dit.hip) and ditt_gemm_f16_kernel (cm_dit_train.hip): the token GEMMs of a
-// DDPM-DiT training step under autocast (cm_dit4d_train_set_autocast).  Device code only.
+// DDPM-DiT training step under autocast (cm_dit4d_train_set_autocast) and, dit_gemm_f16_kernel alone, of the eval forward of a handle
+// on the f16 sampling plan (cm_model_set_precision(CM_PRECISION_F16)).  Device code only.
 //
 // Instruction: v_mfma_f32_32x32x16_f16.  Lane l supplies A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31],
 // j = 0..7, as one f16x8; the C/D map is the fp32 instruction's (column = l & 31, row = (i & 3) + 8 (i >> 2) + 4 (l >> 5)).
 //
 // Rounding: an operand is rounded once, fp32 -> f16 round-to-nearest-even (v_cvt_f16_f32; no clamp, so a value outside f16's
-// range becomes +-inf and surfaces as a non-finite loss or gradient), when it is staged into LDS.  Products are exact in the
-// matrix unit and the accumulator, the partials and every output are fp32.
+// range becomes +-inf and surfaces as a non-finite loss or gradient), when it is staged into LDS -- or, the weights of the f16
+// sampling plan, by the same rule on the host when the handle is finalized (dit_finalize), and staged as they are.  Products are
+// exact in the matrix unit and the accumulator, the partials and every output are fp32.
 //
 // LDS image of either operand: [64 tile rows or columns][DH_K = 64 k] halves, k contiguous, row stride DH_S = 72 halves = 144 B =
 // 36 dwords.  Operand read: one 16-byte ds_read_b128 per lane and k step at row * 144 + 32 step + 16 (l >> 5).  That instruction

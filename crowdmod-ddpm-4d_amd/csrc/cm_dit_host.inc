@@ -24,6 +24,9 @@ struct cm_dit_plan {
                                // (DiT2D: depth * 6D + 2D, shift1 scale1 gate1 shift2 scale2 gate2)
   float *tab_h1 = nullptr, *tab_e = nullptr, *tab_cs = nullptr;   // scratch of dit_build_tables
   std::vector<const float *> w;  // device copies of the state_dict tensors, in state_dict order
+  std::vector<const _Float16 *> w16;   // f16 plan (cm_model::precision == CM_PRECISION_F16, DiT4D_V4 only): per tensor of `w`, its copy
+                               // rounded once to f16 (cm_dit_f16.h), same [out][in] order -- the six token-Linear weights of every block;
+                               // null elsewhere.  Empty on the fp32 plan.  Written by dit_finalize, read-only afterwards.
 };
 
 namespace {
@@ -31,6 +34,9 @@ namespace {
 // state_dict order of DiT4D_V4: own parameters first (spatial_pos_embed, temporal_pos_embed: DiT4D_V4.py:289-295), then the
 // child modules in registration order (dif_time_embeddings, time_proj, patch_embed, blocks, final_layer).
 constexpr int DIT_HEAD = 11;     // tensors before blocks.0 (both variants)
+// f16 plan: the weights of a DiT4D_V4 block (dit_build_params order) that get an f16 copy -- spatial in_proj, spatial out_proj,
+// temporal in_proj, temporal out_proj, mlp.0, mlp.3
+constexpr int DIT_F16_W[6] = {0, 2, 4, 6, 8, 10};
 
 // state_dict order of DiT2D: spatial_pos_embed, temporal_pos_embed (DiT2D.py:196-201 -- registered after time_embeddings
 // and patch_embed, but a module's own parameters come first), then time_embeddings, time_proj, patch_embed, blocks,
@@ -170,6 +176,21 @@ int dit_finalize(cm_model *m) {
     d.w.push_back(dp);
   }
   if (dit_build_tables(m)) return 1;
+  if (m->precision == CM_PRECISION_F16) {   // the fp32 copies stay: the tables above and cm_model_get_param read them
+    d.w16.assign(d.w.size(), nullptr);
+    std::vector<_Float16> h16;
+    for (int i = 0; i < c.depth; ++i)
+      for (const int j : DIT_F16_W) {
+        const size_t wi = (size_t)(DIT_HEAD + d.per_block() * i + j);
+        const std::vector<float> &h = m->params[wi].host;
+        h16.resize(h.size());
+        for (size_t e = 0; e < h.size(); ++e) h16[e] = (_Float16)h[e];   // round-to-nearest-even, no clamp
+        _Float16 *dp = nullptr;
+        if (dev_alloc(m, (void **)&dp, h16.size() * sizeof(_Float16))) return 1;
+        CM_HIP(hipMemcpy(dp, h16.data(), h16.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        d.w16[wi] = dp;
+      }
+  }
   const size_t per = (size_t)m->per_sample();
   const size_t per_past = (size_t)c.in_channels * c.rows * c.cols * c.past_len;
   if (dev_alloc(m, (void **)&m->xstate, B * per * sizeof(float))) return 1;
@@ -185,6 +206,8 @@ int dit_finalize(cm_model *m) {
 // of the future slots.  Capturable: no allocation, synchronisation or host read; t comes from tbuf on the device.
 // `nblocks`: stop after that many blocks (depth: the whole forward with the final layer; fewer: the residual stream X is
 // left as that stage wrote it and eps_cl is untouched -- dit_debug_activation).
+// f16 plan (d.w16 filled): the six token Linears of every block take dit_gemm_f16_kernel on the pre-rounded weights; the patch
+// embedding, the final layer, LayerNorm + modulate, both attention kernels, the gates and every tensor stay fp32.
 int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
   const cm_dit_plan &d = *m->dit;
   const cm_dit_config &c = d.cfg;
@@ -211,9 +234,15 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
   CM_HIP(cm::launch_dit_gemm(a, st));
   cm::DitAttnArgs at{QKV, AO, B, d.Tp, d.Ns, d.qs, D, c.num_heads};
   const int nch = d.nchunk(), pb = d.per_block();
+  const bool f16 = !d.w16.empty();
   for (int i = 0; i < nblocks; ++i) {
     const float *const *w = d.w.data() + DIT_HEAD + pb * i;
     const int mo = i * nch * D;
+    auto launch = [&](cm::DitGemmArgs &g, int j) {   // the token Linear on the block's weight j, in the plan's form
+      g.W = w[j]; g.bias = w[j + 1];
+      if (f16) { g.f16 = 1; g.Wh = d.w16[DIT_HEAD + pb * i + j]; }
+      return cm::launch_dit_gemm(g, st);
+    };
     if (d.full) {
       // self-attention over all tokens of the sample, gated residual on every row (DiT2D.py:104-106)
       a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
@@ -234,28 +263,28 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
     }
     // spatial self-attention (DiT4D_V4.py:160-169)
     a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
-    a.A = X; a.lda = D; a.W = w[0]; a.bias = w[1]; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.A = X; a.lda = D; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
+    CM_HIP(launch(a, 0));
     CM_HIP(cm::launch_dit_attn_spatial(at, st));
     a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, D);
-    a.A = AO; a.lda = D; a.W = w[2]; a.bias = w[3]; a.Y = X; a.ldy = D; a.off_gate = mo + 2 * D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.A = AO; a.lda = D; a.Y = X; a.ldy = D; a.off_gate = mo + 2 * D;
+    CM_HIP(launch(a, 2));
     // temporal cross-attention: keys / values over all slots, queries and the residual update on slots >= qs (:173-198)
     a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
-    a.A = X; a.lda = D; a.W = w[4]; a.bias = w[5]; a.Y = QKV; a.ldy = D3; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.A = X; a.lda = D; a.Y = QKV; a.ldy = D3; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
+    CM_HIP(launch(a, 4));
     CM_HIP(cm::launch_dit_attn_temporal(at, st));
     a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, D);
     future_rows(a, nq);
-    a.a_compact = 1; a.A = AO; a.lda = D; a.W = w[6]; a.bias = w[7]; a.Y = X; a.ldy = D; a.off_gate = mo + 5 * D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.a_compact = 1; a.A = AO; a.lda = D; a.Y = X; a.ldy = D; a.off_gate = mo + 5 * D;
+    CM_HIP(launch(a, 6));
     // MLP (:201-202)
     a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_GELU, M, mlp, D);
-    a.A = X; a.lda = D; a.W = w[8]; a.bias = w[9]; a.Y = Hm; a.ldy = mlp; a.off_shift = mo + 6 * D; a.off_scale = mo + 7 * D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.A = X; a.lda = D; a.Y = Hm; a.ldy = mlp; a.off_shift = mo + 6 * D; a.off_scale = mo + 7 * D;
+    CM_HIP(launch(a, 8));
     a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, mlp);
-    a.A = Hm; a.lda = mlp; a.W = w[10]; a.bias = w[11]; a.Y = X; a.ldy = D; a.off_gate = mo + 8 * D;
-    CM_HIP(cm::launch_dit_gemm(a, st));
+    a.A = Hm; a.lda = mlp; a.Y = X; a.ldy = D; a.off_gate = mo + 8 * D;
+    CM_HIP(launch(a, 10));
   }
   if (nblocks < c.depth) return 0;
   // final layer + unpatchify, future slots only: slots < qs hold past frames only (:223-225, :93-99; DiT2D computes

@@ -58,6 +58,8 @@ int ditt_check(const cm_model *m, const char *what, bool need_train, bool v4 = f
   }
   if (m->device < 0) return fail("%s: a host-only handle (device -1) cannot train", what);
   if (!m->finalized) return fail("%s: cm_model_finalize has not been called", what);
+  if (m->precision != CM_PRECISION_F32)
+    return fail("%s: training runs on fp32-plan handles: the f16 weight copies of an f16 sampling plan do not follow the optimizer", what);
   if (need_train && !m->dit->train) return fail("%s: %s has not been called", what, v4 ? "cm_dit4d_train_init" : "cm_dit_train_init");
   return 0;
 }

@@ -488,8 +488,11 @@ struct DitGemmArgs {
   const float *x8;                // PRO_PATCH: sampler tensor [B][L][H][W][8]
   const float *spos, *tpos;       // EPI_PATCH: spatial [N_s][D] and temporal [T_p][D] position embeddings
   int L, Hh, Ww, p, pt, Ns, wpn, Cout;
-  int f16;                        // autocast training: A (after the prologue) and W rounded to f16 when staged, v_mfma_f32_32x32x16_f16,
-                                  // fp32 accumulation and output (dit_gemm_f16_kernel; PRO_NONE / PRO_LN with EPI_BIAS only)
+  int f16;                        // A (after the prologue) rounded to f16 when staged, v_mfma_f32_32x32x16_f16, fp32 accumulation and
+                                  // output (dit_gemm_f16_kernel).  Wh null -- autocast training: W rounded when staged too; PRO_NONE /
+                                  // PRO_LN with EPI_BIAS only
+  const _Float16 *Wh;             // f16 sampling plan (f16 set): W rounded once, [N][K] halves, K % 8 == 0; PRO_LN with EPI_BIAS /
+                                  // EPI_GELU, PRO_NONE with EPI_GATE
 };
 struct DitAttnArgs {
   const float *qkv;               // [B][T_p * N_s][3E] (q | k | v)

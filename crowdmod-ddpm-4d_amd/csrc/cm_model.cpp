@@ -2071,9 +2071,12 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
 int cm_model_set_precision(cm_model *m, int32_t precision) {
   if (!m) return fail("null model handle");
   if (m->finalized) return fail("precision must be chosen before cm_model_finalize");
-  if (m->dit && precision != CM_PRECISION_F32) return refuse_dit(m, "a precision other than CM_PRECISION_F32");
   if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16 && precision != CM_PRECISION_F32R && precision != CM_PRECISION_F32X)
     return fail("unknown precision %d", precision);
+  if (m->dit && m->dit->full && precision != CM_PRECISION_F32) return refuse_dit(m, "a precision other than CM_PRECISION_F32");
+  if (m->dit && (precision == CM_PRECISION_F32R || precision == CM_PRECISION_F32X))
+    return fail("CM_PRECISION_F32R and CM_PRECISION_F32X are split forms of the UNet's convs: a DDPM-DiT (DiT4D_V4) handle takes "
+                "CM_PRECISION_F32 or CM_PRECISION_F16");
   m->precision = precision;
   return 0;
 }

@@ -99,7 +99,8 @@ class DDPM_model:
                             grid_cols=r.cols, past_len=r.past_len, future_len=r.future_len, t_patch_size=d.t_patch_size,
                             patch_size=d.patch_size, hidden_size=d.hidden_size, depth=d.depth, num_heads=d.num_heads,
                             mlp_ratio=d.mlp_ratio, dropout_rate=d.dropout_rate, time_multiple=d.time_emb_mult,
-                            condition=d.condition, device=self.device, max_batch=max(1, r.batch_size), seed=self.seed)
+                            condition=d.condition, device=self.device, max_batch=max(1, r.batch_size),
+                            seed=self.seed).set_precision(d.precision)
         if self.arch == "FM-DiT":
             # flow_matching.py:72-84: CONDITION and t_max are not passed on (DiT2D's defaults "Past" and 8)
             from .dit import DiT2D

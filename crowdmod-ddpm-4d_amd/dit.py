@@ -39,6 +39,25 @@ class DiT4D_V4(NativeModule):
                                       float(dropout_rate), int(time_multiple), condition, int(T_max))
         self._init_state(self._SPEC, device, max_batch, seed)
 
+    precision = "f32"
+
+    def set_precision(self, precision: str):
+        """'f32' (default: every GEMM on the exact-fp32 matrix instruction) or 'f16': the sampling plan whose six token
+        Linears per block (both q|k|v in-projections, both out-projections, fc1, fc2) take f16 matrix-core operands with
+        fp32 accumulation -- weights rounded once when the handle is built, activations when staged; everything else,
+        every tensor included, stays fp32 (cm_model_set_precision, CM_PRECISION_F16).  Inference only: fit_init on an
+        'f16' model is refused by the library.  Releases the native handle; returns self."""
+        if precision not in ("f32", "f16"):
+            raise ValueError(f"precision {precision!r}: 'f32' or 'f16'")
+        if precision != self.precision:
+            self._release()
+            self.precision = precision
+        return self
+
+    def _before_upload(self, h):
+        if self.precision == "f16":
+            native.check(native.lib().cm_model_set_precision(h, native.PRECISION_F16))
+
     def _check_ctor(self, condition, total_time_steps):
         if condition != "Past":
             raise NotImplementedError("only condition='Past' (the configuration every reference config uses)")
@@ -265,6 +284,13 @@ class DiT2D(DiT4D_V4):
                                           int(num_heads), float(mlp_ratio), float(dropout_rate), int(time_multiple),
                                           condition, int(t_max))
         self._init_state(self._SPEC, device, max_batch, seed)
+
+    def set_precision(self, precision: str):
+        """'f32' only: the reference trains and samples FM-DiT in fp32, and the f16 plan is DiT4D_V4's."""
+        if precision != "f32":
+            raise NotImplementedError(f"precision {precision!r}: FM-DiT (DiT2D) runs in 'f32' only; the f16 sampling plan "
+                                      "is DDPM-DiT's (DiT4D_V4)")
+        return self
 
     def native_config(self, max_batch: int, device: int) -> native.cm_dit2d_config:
         c, g = native.cm_dit2d_config(), self.cfg

@@ -59,6 +59,8 @@ def main():
     ap.add_argument('--from-fixed-past', type=bool, default=False)
     ap.add_argument('--data-npy', type=str, default=None, help='test sequences [N,C,ROWS,COLS,T] (.npy)')
     ap.add_argument('--device', type=int, default=0)
+    ap.add_argument('--precision', choices=('f32', 'f16'), default=None,
+                    help='DDPM-DiT sampling plan (default: MODEL.DDPM.DIT.PRECISION of the config, else f32)')
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
@@ -73,6 +75,10 @@ def main():
         from crowdmod_ddpm_4d_amd.flow_matching import FM_model as Model
     else:
         Model = DDPM_model
+    if args.precision is not None:
+        if args.arch != "DDPM-DiT":
+            raise SystemExit(f"--precision selects the DDPM-DiT sampling plan; {args.arch} does not take it")
+        cfg.MODEL.DDPM.DIT.PRECISION = args.precision
     model = Model(cfg, args.arch, mprops, output_dir=cfg.DATA_FS.get("OUTPUT_DIR", "output"),
                   from_fixed_past=args.from_fixed_past, device=args.device)
     ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch.startswith("FM-") or args.arch == "ConvRNN" else \

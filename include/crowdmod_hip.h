@@ -56,8 +56,8 @@ typedef struct cm_unet_config {
 
 /* Hyper-parameters of reference DiT4D_V4.__init__ (models/backbones/DiT4D_V4.py:235-254) plus the tensor geometry, as
  * DDPM_model builds it for arch "DDPM-DiT" (models/diffusion/ddpm.py:88-104).  A DiT handle is the same opaque cm_model,
- * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 only)
- * / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it, and
+ * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 or F16,
+ * see there) / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it, and
  * cm_debug_activation serves "patch_embed" and "blocks.<i>" (see there); every other handle entry point (training,
  * dropout width, the conv and loop debug hooks, profiling, FLOP splits) returns non-zero. */
 typedef struct cm_dit_config {
@@ -149,7 +149,14 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
  * CM_PRECISION_F32X ("strict fp32", round 3's arithmetic): the default plan with the f16 two-way-split form switched off -- every
  * split layer forms its products from exact three-way bf16 splits, six cross terms (all 24 mantissa bits of both operands, dropped
  * terms <= 2^-24 of a product, fp32's whole exponent range).  Same measured error as the default plan, 16 % slower; for callers
- * that want the stronger per-product statement, and the reference point of the A/B in DESIGN.md section 4. */
+ * that want the stronger per-product statement, and the reference point of the A/B in DESIGN.md section 4.
+ * DiT handles: a DDPM-DiT handle (cm_model_create_dit) takes CM_PRECISION_F32 (default) or CM_PRECISION_F16 -- the sampling plan
+ * whose six token Linears per block (both q|k|v in-projections, both out-projections, fc1, fc2) contract f16 operands with fp32
+ * accumulation: each weight rounded once at cm_model_finalize (round-to-nearest-even, no clamp; the fp32 copies stay), the
+ * activation operand rounded when staged; patch embedding, final layer, conditioning tables, LayerNorm + modulate, attention,
+ * gates, every tensor and the sampler stay fp32.  Inference only: cm_dit4d_train_init refuses such a handle.  Never worse than the
+ * reference's own autocast forward against float64 (tests/test_gpu_dit_f16.py; DESIGN.md section 10 "f16 plan").  F32R and F32X
+ * are conv split forms and are refused on it; an FM-DiT handle (cm_model_create_dit2d) takes CM_PRECISION_F32 only. */
 enum { CM_PRECISION_F32 = 0, CM_PRECISION_F16 = 1, CM_PRECISION_F32R = 2, CM_PRECISION_F32X = 3 };
 int cm_model_set_precision(cm_model *m, int32_t precision);
 /* Packs weights into MFMA fragment order and precomputes the time-embedding
