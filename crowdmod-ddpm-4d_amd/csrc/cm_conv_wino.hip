@@ -557,14 +557,20 @@ __global__ __launch_bounds__(256 * NBW, OCC) void conv_wino_kernel(const ConvArg
 //          the loads of chunk ch + 2 go out AFTER the last refill of chunk ch's phase: every refill waited on before step RD6 of the
 //          next phase is older than they are, and they have step A + step B + two barriers + RD6 steps to land.  In a SKIP instantiation
 //          the fused skip conv's operand chunks are double-buffered the same way (a ONE form holds no next tile's halo in its epilogue).
+//   UNDER  (AHEAD forms) step A of chunk ch + 1 runs inside the matrix phase of chunk ch, one round after the matrix instructions of
+//          each of the later ring steps.  The phase is bound by the weight stream: every wave of the workgroup sits in the same ring
+//          wait with its vector pipe idle.  The halo of chunk ch + 1 is in the other slot and older than every refill of this phase
+//          (the wait of step RD6 has retired it), R is dead once step B has passed its barrier, and the GroupNorm rows are in the
+//          slot's registers or in LDS.  Chunk 0 is staged in front of the loop; every chunk body is barrier, step B, barrier, phase.
 // Same arithmetic in the same order in every form: results are bit-identical to FM = 0 (tests/test_gpu_wino_forms.py,
 // tests/test_gpu_wino_prefetch.py).
 template <int BZ, int PY, int PX, bool F16, int NBW, bool SKIP, int B6 = 0, int FM = 0>   // B6: 0 off, 1 six bf16 cross terms, 2 three (relaxed plan), 3 three f16 cross terms (h2)
 __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArgs a, const int *__restrict__ tabA,
                                                                   const int *__restrict__ tabO, int G) {
   constexpr bool ONE = (FM & WINO_FORM_ONE) != 0, PLAIN = (FM & WINO_FORM_PLAIN) != 0, OWNGN = (FM & WINO_FORM_OWNGN) != 0;
-  constexpr bool WHOLE = (FM & WINO_FORM_WHOLE) != 0, AHEAD = (FM & WINO_FORM_AHEAD) != 0;
+  constexpr bool WHOLE = (FM & WINO_FORM_WHOLE) != 0, AHEAD = (FM & WINO_FORM_AHEAD) != 0, UNDER = (FM & WINO_FORM_UNDER) != 0;
   static_assert(!AHEAD || (ONE && PLAIN && B6 == 3), "the halo-ahead order is a variant of the h2 one-sample forms");
+  static_assert(!UNDER || AHEAD, "staging under the matrix phase reads the other slot of the halo-ahead buffer");
   static_assert(!WHOLE || (BZ == 8 && PY == 2 && PX == 2 && NBW == 1), "the whole-tile form is the full-resolution tile's");
   static_assert(!OWNGN || PLAIN, "own GroupNorm is a variant of the plain activation form");
   constexpr int NT = 256 * NBW;
@@ -750,6 +756,29 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       if (nchunks > 1) issue(NSL - 1, b, 1);
       asm volatile("" ::: "memory");
     }
+    // UNDER: one round of step A out of slot SLc (the plain branch of step A below, operation for operation), and the GroupNorm rows
+    // of chunk chn; chunk 0 is staged here, chunk ch + 1 under the matrix phase of chunk ch
+    auto gn_rows = [&](const int SLc, int chn, f32x4 &sc1, f32x4 &sh1) {
+      sc1 = scn[SLc]; sh1 = shn[SLc];
+      if (own_gn) {
+        const int cb0 = (chn < n0 ? chn * CS : a.C0 + (chn - n0) * CS) + 4 * aq;
+        sc1 = *reinterpret_cast<const f32x4 *>(GNL + cb0);
+        sh1 = *reinterpret_cast<const f32x4 *>(GNL + Ctot + cb0);
+      }
+    };
+    auto stage_round = [&](const int SLc, const int k, const f32x4 sc1, const f32x4 sh1) {
+      const int v = (tid >> 2) + (NT / 4) * k + RV0;
+      f32x4 w = ald[SLc][k] * sc1 + sh1;
+      w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]);
+      if (!((aok >> k) & 1u)) w = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (v >= RV0 && v < RV0 + RVC) *reinterpret_cast<f32x4 *>(R + (v - RV0) * RS_ + 4 * aq) = w;
+    };
+    if constexpr (UNDER) {
+      f32x4 sc1, sh1;
+      gn_rows(0, 0, sc1, sh1);
+#pragma unroll
+      for (int k = 0; k < RK; ++k) stage_round(0, k, sc1, sh1);
+    }
     // AHEAD: the loop runs over PAIRS of chunks (slot = ch & 1 is then a constant at every use), an odd last chunk follows as pass 1.
     // The pair loop has one exit and nothing between the loads and the next step A but straight code: a chunk skipped inside the
     // loop would leave a path from freshly issued loads back to the loop head, and the wait derived for the head would name them.
@@ -760,13 +789,11 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #pragma unroll
     for (int SL = 0; SL < NSL - pass; ++SL) {
       const int ch = ch0 + SL;
-      // ---- step A: this chunk's halo voxels -> activated image R ------------------------------------------
-      f32x4 sc1 = scn[SL], sh1 = shn[SL];
-      if (own_gn) {
-        const int cb0 = (ch < n0 ? ch * CS : a.C0 + (ch - n0) * CS) + 4 * aq;
-        sc1 = *reinterpret_cast<const f32x4 *>(GNL + cb0);
-        sh1 = *reinterpret_cast<const f32x4 *>(GNL + Ctot + cb0);
-      }
+      // ---- step A: this chunk's halo voxels -> activated image R (UNDER: staged already, in front of the loop or under the
+      // previous chunk's matrix phase) ------------------------------------------------------------------------------------
+      if constexpr (!UNDER) {
+      f32x4 sc1, sh1;
+      gn_rows(SL, ch, sc1, sh1);
       f32x4 pm1 = {1.f, 1.f, 1.f, 1.f};
       if (!((CM_WINO_ABL & 32) && ch > 0)) {
       if constexpr (!PLAIN) {
@@ -774,13 +801,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       }
       if (PLAIN || (norm && a.silu && !a.pm)) {
 #pragma unroll
-        for (int k = 0; k < RK; ++k) {
-          const int v = (tid >> 2) + (NT / 4) * k + RV0;
-          f32x4 w = ald[SL][k] * sc1 + sh1;
-          w[0] = silu_w(w[0]); w[1] = silu_w(w[1]); w[2] = silu_w(w[2]); w[3] = silu_w(w[3]);
-          if (!((aok >> k) & 1u)) w = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (v >= RV0 && v < RV0 + RVC) *reinterpret_cast<f32x4 *>(R + (v - RV0) * RS_ + 4 * aq) = w;
-        }
+        for (int k = 0; k < RK; ++k) stage_round(SL, k, sc1, sh1);
       } else {
 #pragma unroll
         for (int k = 0; k < RK; ++k) {
@@ -794,6 +815,7 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
           if (!((aok >> k) & 1u)) w = f32x4{0.f, 0.f, 0.f, 0.f};
           if (v >= RV0 && v < RV0 + RVC) *reinterpret_cast<f32x4 *>(R + (v - RV0) * RS_ + 4 * aq) = w;
         }
+      }
       }
       }
       __syncthreads();                          // R complete; every wave is past the previous matrix phase / exchange reads
@@ -876,6 +898,17 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
       if constexpr (B6) {
         const float *ab = arow;                    // (F16-style fragment: 8 halves per lane at 4 hh dwords, planes 8 dwords apart)
         f32x4 af6[2][3];
+        // UNDER: step A of chunk ch + 1 (slot SL ^ 1) goes under this phase, round k behind the matrix instructions of ring step
+        // UF + k: none before step RD6, whose ring wait retires the halo.  Measured (12 launches of a flagship step, parent 603.6 us):
+        // steps 6, 7, 8 ... 580.9, steps 4, 6, 8 586.8, steps 3, 4, 5 586.2, steps 3, 5, 7 593.9 -- late and on consecutive steps.
+        // The pair's first chunk always has a successor; the odd-tail pass stages nothing.
+        constexpr int UF = 6;
+        static_assert(!UNDER || (UF >= RD6 && UF + RK <= 12), "the rounds follow the ring wait that retires the halo, inside the phase");
+        const bool stage = UNDER && !(CM_WINO_ABL & 32) && pass == 0 && (SL == 0 || ch + 1 < nchunks);
+        f32x4 scu = {1.f, 1.f, 1.f, 1.f}, shu = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (UNDER && OWNGN) {
+          if (pass == 0) gn_rows((SL + 1) & 1, min(ch + 1, nchunks - 1), scu, shu);       // (LDS rows: read once, in front of the phase)
+        }
 #pragma unroll
         for (int tm = 0; tm < 3; ++tm) af6[0][tm] = *reinterpret_cast<const f32x4 *>(ab + rowoff[0] + TST * tm);
 #pragma unroll
@@ -915,6 +948,19 @@ __global__ __launch_bounds__(256 * NBW, 2) void conv_wino_p_kernel(const ConvArg
 #else
             (void)wn; (void)more;
 #endif
+          }
+          if constexpr (UNDER) {
+            if (sx >= UF && sx - UF < RK && stage) {
+              // (the explicit uses pin the round behind this step's fence: its arithmetic is pure, and hoisted to the head of the
+              // phase it would put a wait for the halo in front of step 0)
+              asm volatile("" : "+v"(ald[(SL + 1) & 1][sx - UF]));
+              if constexpr (OWNGN) {
+                stage_round((SL + 1) & 1, sx - UF, scu, shu);
+              } else {
+                asm volatile("" : "+v"(scn[(SL + 1) & 1]), "+v"(shn[(SL + 1) & 1]));
+                stage_round((SL + 1) & 1, sx - UF, scn[(SL + 1) & 1], shn[(SL + 1) & 1]);
+              }
+            }
           }
           asm volatile("" ::: "memory");
         }
@@ -1360,7 +1406,9 @@ bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn) {
 // diagnostic run (a.dbg != 0: the CM_CONV_DBG / cm_debug_conv_flags switches; bit 1 << 20 selects nothing else and is the
 // documented way to force the generic kernel for an A/B or a bit-identity check).
 // The launcher adds AHEAD (halo loads a chunk period ahead, skip operands double-buffered) to every specialised form unless
-// CM_NO_WINO_AHEAD is set under CM_DIAG: the same forms in the one-ahead order, for A/B runs.
+// CM_NO_WINO_AHEAD is set under CM_DIAG: the same forms in the one-ahead order, for A/B runs.  Every halo-ahead form but the
+// full-resolution launch with a fused skip conv also gets UNDER (the next chunk's step A under the matrix phase) unless
+// CM_NO_WINO_UNDER is set under CM_DIAG.
 int conv_wino_form(const ConvArgs &a, int G) {
   if (a.dbg != 0 || a.f16 != 4) return 0;
   if (G < a.B || a.pm || !a.silu) return 0;
@@ -1375,11 +1423,12 @@ int conv_wino_form(const ConvArgs &a, int G) {
   return WINO_FORM_ONE | WINO_FORM_PLAIN | (own ? WINO_FORM_OWNGN : 0);
 }
 
-static std::atomic<long long> wino_form_launches[16], wino_ahead_launches;
+static std::atomic<long long> wino_form_launches[16], wino_ahead_launches, wino_under_launches;
 void conv_wino_form_counts(long long counts[16], bool reset) {
   for (int i = 0; i < 16; ++i) counts[i] = reset ? wino_form_launches[i].exchange(0) : wino_form_launches[i].load();
 }
 long long conv_wino_ahead_count(bool reset) { return reset ? wino_ahead_launches.exchange(0) : wino_ahead_launches.load(); }
+long long conv_wino_under_count(bool reset) { return reset ? wino_under_launches.exchange(0) : wino_under_launches.load(); }
 
 hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
   ConvArgs a = a_in;
@@ -1414,13 +1463,17 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
     const dim3 gridp((unsigned)G, (unsigned)ntp, (unsigned)nz);
     static const bool no_ahead = cm::diag_env("CM_NO_WINO_AHEAD") != nullptr;
     const int fm0 = nbw == conv_wino_nbw(a.bz, a.Co) ? conv_wino_form(a, G) : 0;
-    const int fm = fm0 && !no_ahead ? fm0 | WINO_FORM_AHEAD : fm0;
+    static const bool no_under = cm::diag_env("CM_NO_WINO_UNDER") != nullptr;
+    const int fm1 = fm0 && !no_ahead ? fm0 | WINO_FORM_AHEAD : fm0;
+    // (the full-resolution fused-skip launches keep the halo-ahead order: staged under, they measured 0.7 - 1.8 us slower per launch)
+    const int fm = (fm1 & WINO_FORM_AHEAD) && !no_under && !(a.bz == 8 && a.s2w) ? fm1 | WINO_FORM_UNDER : fm1;
     int fm_run = 0;   // the form of the instantiation the dispatch below really takes (a form without one runs the generic kernel: counted as 0)
 #define CM_WINO_PGO1(KERNEL, THREADS)                                                               \
   {                                                                                                 \
     CM_WINO_ATTR(KERNEL)                                                                            \
     wino_form_launches[fm_run & 15].fetch_add(1, std::memory_order_relaxed);                        \
     if (fm_run & WINO_FORM_AHEAD) wino_ahead_launches.fetch_add(1, std::memory_order_relaxed);      \
+    if (fm_run & WINO_FORM_UNDER) wino_under_launches.fetch_add(1, std::memory_order_relaxed);      \
     hipLaunchKernelGGL(KERNEL, gridp, dim3(THREADS), ldsp, st, a, tb.tA, tb.tO, G);                 \
     return hipGetLastError();                                                                       \
   }
@@ -1433,6 +1486,11 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
     if (h2 && fm == (FM_)) {                                                                        \
       fm_run = (FM_);                                                                               \
       if (a.s2w) CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, true, 3, (FM_)>), THREADS) \
+      CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, false, 3, (FM_)>), THREADS)          \
+    }
+#define CM_WINO_PGOFM0(Z, PY_, PX_, NB, THREADS, FM_)    /* a form that launches without a fused skip conv only */ \
+    if (h2 && fm == (FM_) && !a.s2w) {                                                              \
+      fm_run = (FM_);                                                                               \
       CM_WINO_PGO1((conv_wino_p_kernel<Z, PY_, PX_, false, NB, false, 3, (FM_)>), THREADS)          \
     }
 #define CM_WINO_PGO6N(Z, PY_, PX_, NB, THREADS)                                                     \
@@ -1458,6 +1516,8 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
           CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN)       \
           CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_AHEAD)       \
           CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN | WINO_FORM_AHEAD) \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_AHEAD | WINO_FORM_UNDER) \
+          CM_WINO_PGOFM(z, py, px, 2, 512, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_OWNGN | WINO_FORM_AHEAD | WINO_FORM_UNDER) \
           CM_WINO_PGO6(z, py, px, 512)                                                              \
         }                                                                                           \
         if (nbw == 2 && f16) CM_WINO_PGO(z, py, px, true, 2, 512)                                   \
@@ -1468,6 +1528,7 @@ hipError_t launch_conv_wino(const ConvArgs &a_in, bool f16, hipStream_t st) {
         if (b6) {                                                                                   \
           CM_WINO_PGOFM(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE)       \
           CM_WINO_PGOFM(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE | WINO_FORM_AHEAD) \
+          CM_WINO_PGOFM0(z, py, px, 1, 256, WINO_FORM_ONE | WINO_FORM_PLAIN | WINO_FORM_WHOLE | WINO_FORM_AHEAD | WINO_FORM_UNDER) \
           CM_WINO_PGO61(z, py, px, 256)                                                             \
         }                                                                                           \
         CM_WINO_PGO(z, py, px, false, 1, 256)                                                       \

@@ -297,12 +297,14 @@ bool conv_wino_p_taken(const ConvArgs &a, bool f16, bool own_gn);
 // as compile-time facts.  conv_wino_form decides it from the launch's ConvArgs (a.dbg = the diagnostic flags of this launch, a.f16 and
 // the geometry set) and the number of sample lanes G of the grid; 0 = the generic kernel, which takes every launch.
 // WINO_FORM_AHEAD (only together with a specialised form): the halo loads run a whole chunk period ahead of the weight ring.
-enum { WINO_FORM_ONE = 1, WINO_FORM_PLAIN = 2, WINO_FORM_OWNGN = 4, WINO_FORM_WHOLE = 8, WINO_FORM_AHEAD = 16 };
+// WINO_FORM_UNDER (only together with AHEAD): the next chunk's GroupNorm + SiLU staging runs under the current chunk's matrix phase.
+enum { WINO_FORM_ONE = 1, WINO_FORM_PLAIN = 2, WINO_FORM_OWNGN = 4, WINO_FORM_WHOLE = 8, WINO_FORM_AHEAD = 16, WINO_FORM_UNDER = 32 };
 int conv_wino_form(const ConvArgs &a, int G);
 // launches of conv_wino_p_kernel per form (without the AHEAD bit) since the last reset (process-wide; tests assert which kernel a
-// launch took), and how many of them took the AHEAD order
+// launch took), how many of them took the AHEAD order, and how many the UNDER order
 void conv_wino_form_counts(long long counts[16], bool reset);
 long long conv_wino_ahead_count(bool reset);
+long long conv_wino_under_count(bool reset);
 // f16: a.wfrag holds the f16 packing (3 groups per chunk and wave, 8 halves per lane): fp32 accumulate, f16 operands
 hipError_t launch_conv_wino(const ConvArgs &a, bool f16, hipStream_t st);
 // six-term bf16 form (a.f16 = 2, wfrag = pack_wino_b6 fragments): two-tile table-driven kernel only

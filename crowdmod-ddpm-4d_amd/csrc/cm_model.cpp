@@ -2863,6 +2863,13 @@ int cm_debug_wino_ahead_count(int64_t *launches, int32_t reset) {
   return 0;
 }
 
+// ... and how many staged the next chunk under the matrix phase (cm::WINO_FORM_UNDER; none under CM_DIAG=1 CM_NO_WINO_UNDER=1).
+int cm_debug_wino_under_count(int64_t *launches, int32_t reset) {
+  if (!launches) return fail("bad argument");
+  *launches = (int64_t)cm::conv_wino_under_count(reset != 0);
+  return 0;
+}
+
 // The statistics slots conv op `index` writes for its output tensor in the last forward's plan: h_part [B][nslots][C][2] (mean, M2), h_cnt
 // [B][nslots] rows behind each slot.  h_part / h_cnt may be null: only *nslots / *C are returned (size the buffers, call again).
 int cm_debug_conv_stats(cm_model *m, int32_t index, int32_t B, float *h_part, float *h_cnt, int32_t *nslots, int32_t *C) {

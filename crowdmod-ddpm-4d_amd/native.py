@@ -140,6 +140,7 @@ SIGNATURES = {
     "cm_debug_conv_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "cm_debug_wino_form_counts": (C.c_int, [_P, C.c_int32]),
     "cm_debug_wino_ahead_count": (C.c_int, [_P, C.c_int32]),
+    "cm_debug_wino_under_count": (C.c_int, [_P, C.c_int32]),
     "cm_debug_time_conv": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_float)]),
     "cm_train_init": (C.c_int, [_P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]),

@@ -408,6 +408,8 @@ int cm_debug_wino_form_counts(int64_t counts[16], int32_t reset);
 /* ... and how many of those launches ran the halo-ahead order of the specialised forms (halo loads a chunk period ahead of the
  * weight ring, skip-conv operands double-buffered); the form index above does not carry that bit. */
 int cm_debug_wino_ahead_count(int64_t *launches, int32_t reset);
+/* ... and how many of the halo-ahead launches also staged the next chunk's activated image under the current chunk's matrix phase. */
+int cm_debug_wino_under_count(int64_t *launches, int32_t reset);
 int cm_debug_time_conv(cm_model *m, int32_t index, int32_t MB, int32_t bz, int32_t by, int32_t bx,
                        int32_t B, int32_t iters, float *us);
 
