@@ -17,13 +17,13 @@ Stated bounds (error per output relative to S = sum |x| |w| + |bias|, the backwa
     six-term form returns non-finite values at exactly the outputs whose receptive field holds such an element, where fp32
     instructions still return finite numbers -- the one documented deviation from fp32 arithmetic, the top 0.2 % of the fp32
     range; up to 3.396e38 the split is exact like everywhere else."""
-import ctypes as C
 import zlib
 
 import numpy as np
 import pytest
 
-from crowdmod_ddpm_4d_amd import native, spec
+from crowdmod_ddpm_4d_amd import spec
+from conv_oracle import _find, _ref64, _run          # noqa: F401  (tests/test_gpu_h2.py imports them from here)
 from helpers import SEED_W, full_cfg, synth_inputs
 
 pytestmark = pytest.mark.gpu
@@ -49,49 +49,6 @@ def net():
     n(fut, np.array([5, 900]), past)          # tiles are tuned at the first launch
     n._params_for_test = params
     return n
-
-
-def _find(net, label):
-    L, h = native.lib(), net._handle
-    cnt = C.c_int32()
-    native.check(L.cm_debug_conv_count(h, C.byref(cnt)))
-    buf = C.create_string_buffer(512)
-    for i in range(cnt.value):
-        native.check(L.cm_debug_conv_info(h, i, buf, len(buf)))
-        f = buf.value.decode().split()
-        if f[0] == "conv" and f[1] == label:
-            return i, dict(Ci=int(f[5]), Co=int(f[6]), Zo=int(f[7]), Yo=int(f[8]), Xo=int(f[9]))
-    raise KeyError(label)
-
-
-def _run(net, idx, mode, x, out_shape):
-    out = np.empty(out_shape, dtype=np.float32)
-    native.check(native.lib().cm_debug_conv_io(net._handle, idx, mode, x.ctypes.data, None, out.ctypes.data, x.shape[0]))
-    return out
-
-
-def _ref64(x, w, bias, ups):
-    """fp64 evaluation in the internal layout: x [B][Z][Y][X][Ci]; w the state_dict tensor [Co][Ci][kH][kW][kL]
-    (tap (dz, dy, dx) = element [dy][dx][dz]); returns (y, S) with S = sum |x| |w| + |bias|."""
-    x = x.astype(np.float64)
-    if ups:
-        x = x.repeat(2, axis=1).repeat(2, axis=2).repeat(2, axis=3)
-    Bn, Z, Y, X, Ci = x.shape
-    w64 = w.astype(np.float64)
-    y = np.zeros((Bn, Z, Y, X, w.shape[0])) + bias.astype(np.float64)
-    S = np.zeros_like(y) + np.abs(bias.astype(np.float64))
-    xp = np.zeros((Bn, Z + 2, Y + 2, X + 2, Ci))
-    xp[:, 1:-1, 1:-1, 1:-1] = x
-    ap = np.abs(xp)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for dz in range(3):
-            for dy in range(3):
-                for dx in range(3):
-                    wt = w64[:, :, dy, dx, dz].T                      # [Ci][Co]
-                    sl = (slice(None), slice(dz, dz + Z), slice(dy, dy + Y), slice(dx, dx + X))
-                    y += xp[sl] @ wt
-                    S += ap[sl] @ np.abs(wt)
-    return y, S
 
 
 def _inputs(kind, shape, seed):
