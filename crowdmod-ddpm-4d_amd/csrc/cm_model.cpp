@@ -2710,8 +2710,8 @@ int cm_debug_conv_count(const cm_model *m, int32_t *count) {
 // One line per op: "conv <label> ntaps stride par Ci Co Zo Yo Xo NB MB bz by bx ks flags out_C C0 C1 wino kernel form" or "other <label>";
 // kernel (a name of kConvKernelName) and form (a ConvForm number) are the op's inference route (conv_route).  A fused attention block:
 // "other <label> attn_sample_kernel" or "... attn_head_kernel", what the handle's inference plan launches for it.
-int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
-  CM_NOT_DIT(m, "cm_debug_conv_info");
+namespace {
+int conv_info_line(const cm_model *m, int32_t index, char *buf, int64_t capacity, bool ext) {
   if (!m || !m->finalized || !buf || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
   if (op.kind == OP_ATTNBLK) {   // ... "other <label> <kernel>": what the handle's inference plan launches for the block
@@ -2733,9 +2733,27 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
   // 0 = every step launches all tiles; "loop_planes <first>:<end> fuse <variant>")
   const LoopEnds le = loop_ends_plan(m->ops, m->x8, m->eps_cl, m->loop_ends, m->precision, m->h2_stale, m->cfg.past_len, m->cfg.future_len,
                                      m->cfg.in_channels, m->cfg.out_channels);
-  char tail[64] = "";
+  char tail[192] = "";
   if (r.kernel == CONV_FIRST && a.src0 == m->x8) snprintf(tail, sizeof tail, " loop_ztiles %d/%d", le.tz_first, a.ntz);
   if (r.kernel == CONV_FIN && a.out == m->eps_cl && le.zo_end) snprintf(tail, sizeof tail, " loop_planes %d:%d fuse %d", le.zo_first, le.zo_end, le.fuse);
+  // ... then, through cm_debug_conv_info_ext only (cm_debug_conv_info's line stays what its readers compare whole tails of), for
+  // every conv: "h16 <h16_mask of the product launch> res <channel stride of the residual tensor, 0 = none> skip <C of the
+  // fused skip conv's two sources, 0 0 = none>", and for the direct f16 kernel / the stage-once upsample conv the tile of its own that the
+  // statistics slots follow: "f16d <bz> <by> <bx> <mbw>" / "upst <tz> <ty> <tx> <mbw>"; for an absorbed skip conv "alone ..." (below)
+  if (ext) {
+    const size_t n = strlen(tail);
+    const bool fused = op.d_s2w != nullptr;
+    snprintf(tail + n, sizeof tail - n, " h16 %d res %d skip %d %d", h16_mask(op, false), (!fused && op.resid_act) ? op.resid_act->C : 0,
+             fused ? op.skip0->C : 0, (fused && op.skip1) ? op.skip1->C : 0);
+    const size_t n2 = strlen(tail);
+    if (r.kernel == CONV_F16D) snprintf(tail + n2, sizeof tail - n2, " f16d %d %d %d %d", op.f16d_bz, op.f16d_by, op.f16d_bx, op.f16d_mbw);
+    if (r.kernel == CONV_UPS) snprintf(tail + n2, sizeof tail - n2, " upst %d %d %d %d", op.ups_tz, op.ups_ty, op.ups_tx, op.ups_mbw);
+    if (op.skip_if_fused) {   // kernel "none": "alone <kernel> <form>", the route cm_debug_conv_io launches it on (as its own op, raw)
+      Op alone = op; alone.skip_if_fused = false; alone.dbg_raw = true;
+      const ConvRoute ra = conv_route(alone, m->precision, false, m->h2_stale);
+      snprintf(tail + n2, sizeof tail - n2, " alone %s %d", kConvKernelName[ra.kernel], (int)ra.form);
+    }
+  }
   snprintf(buf, (size_t)capacity, "conv %s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s %d%s", op.label.c_str(), a.ntaps, a.stride, a.par,
            a.C0 + a.C1, a.Co, a.Zo, a.Yo, a.Xo, op.NB, op.MB, a.bz, a.by, a.bx, op.ks,
            (op.small_n ? 1 : 0) | (op.first_k ? 2 : 0) | (op.stat_act ? 4 : 0) | (op.skip_if_fused ? 8 : 0) | (a.CK == 32 ? 16 : 0),
@@ -2743,6 +2761,20 @@ int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capa
            a.C0, a.C1, op.wino ? 1 : 0,              // (channels of the two sources; does the Winograd launcher take the op)
            kConvKernelName[r.kernel], (int)r.form, tail);
   return 0;
+}
+}  // namespace
+
+int cm_debug_conv_info(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
+  CM_NOT_DIT(m, "cm_debug_conv_info");
+  return conv_info_line(m, index, buf, capacity, false);
+}
+
+// Test hook, exported like cm_debug_loop_ends (tests/test_gpu_f16_layers.py): cm_debug_conv_info's line with, on a "conv" line, the
+// trailing tokens described in conv_info_line appended (f16-tensor mask, residual / fused skip channels, the direct f16 / stage-once
+// upsample kernel's own tile, the stand-alone route of an absorbed skip conv).
+extern "C" int cm_debug_conv_info_ext(const cm_model *m, int32_t index, char *buf, int64_t capacity) {
+  CM_NOT_DIT(m, "cm_debug_conv_info_ext");
+  return conv_info_line(m, index, buf, capacity, true);
 }
 
 // Test hook, exported but outside the public header (the binding table is fixed): which of the loop's end-conv savings the handle
@@ -2800,32 +2832,59 @@ extern "C" int cm_debug_attn_pack(const float *w, int32_t N, int32_t K, uint16_t
 // ... and its shape predicate (1: the whole-sample kernel admits S tokens of E channels in `heads` heads and `groups` groups)
 extern "C" int cm_debug_attn_sample_ok(int32_t S, int32_t E, int32_t heads, int32_t groups) { return cm::attn_sample_ok(S, E, heads, groups) ? 1 : 0; }
 
-// Test hook (tests/test_gpu_six_term_hostile.py): conv op `index` ALONE on the caller's data -- no GroupNorm / SiLU on load, no
-// time-embedding row, no residual, no fused skip conv; the bias stays.  h_in0 / h_in1: host, channels-last
-// [B][Zs][Ys][Xs][C0 / C1] (h_in1 null when the op has one source); h_out: host [B][Zo][Yo][Xo][channel stride of the output
-// tensor].  mode 0: the six-term bf16 form where the plan has one (raw operands are unbounded: never the h2 form); mode 1: the
-// same layer on fp32 matrix instructions (the split fragments withheld); mode 2: the h2 form where the plan has one (the caller
-// keeps its operands inside the bound the plan guarantees, tests/test_gpu_h2.py); mode 3: the op exactly as the sampling forward
-// launches it -- GroupNorm + SiLU on load, time-embedding row, residual, fused skip conv, h2 where the plan has it -- on the caller's
-// sources; the GroupNorm rows / slot partials, the time rows, the residual and the skip conv's source are what the last forward
-// left (tests/test_gpu_wino_forms.py compares two kernels for the SAME launch with it; cm_debug_conv_stats reads the slots it wrote).
-int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B) {
-  CM_NOT_DIT(m, "cm_debug_conv_io");
+namespace {
+// Host data <-> an activation of the handle, honouring Act::h16 (plan_h16).  An h16 tensor keeps the allocation new_act gave it --
+// max_batch * V * C FLOATS, made before plan_h16 runs and never resized -- and uses its first half: the same [B][Z][Y][X][C] order
+// in _Float16 elements (run_conv's `adv` halves the float offset).  Upload rounds to nearest even, overflow to infinity
+// (f32_to_f16_bits = the kernels' (_Float16) casts); download fetches the halves as stored and widens them, as cm_debug_activation does.
+int dbg_upload(const Act *t, const float *h, size_t n) {
+  if (!t->h16) { CM_HIP(hipMemcpy(t->d, h, n * sizeof(float), hipMemcpyHostToDevice)); return 0; }
+  std::vector<uint16_t> raw(n);
+  for (size_t i = 0; i < n; ++i) raw[i] = f32_to_f16_bits(h[i]);
+  CM_HIP(hipMemcpy(t->d, raw.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+  return 0;
+}
+int dbg_download(const Act *t, float *h, size_t n) {
+  if (!t->h16) { CM_HIP(hipMemcpy(h, t->d, n * sizeof(float), hipMemcpyDeviceToHost)); return 0; }
+  std::vector<uint16_t> raw(n);
+  CM_HIP(hipMemcpy(raw.data(), t->d, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) h[i] = f16_bits_to_f32(raw[i]);
+  return 0;
+}
+
+// cm_debug_conv_io / cm_debug_conv_tail.  `tail`: the raw launch keeps the op's residual or fused skip conv, on the caller's data h_t0 / h_t1.
+int debug_conv_launch(cm_model *m, int32_t index, int32_t mode, bool tail, const float *h_in0, const float *h_in1, const float *h_t0,
+                      const float *h_t1, float *h_out, int32_t B) {
   if (check_ready(m, B)) return 1;
   if (!h_in0 || !h_out || index < 0 || index >= (int)m->ops.size()) return fail("bad argument");
   const Op &op = m->ops[index];
   if (op.kind != OP_CONV || !op.in0 || !op.out_act) return fail("op %d is not a convolution", index);
   if ((op.in1 != nullptr) != (h_in1 != nullptr)) return fail("op %d has %d source tensors", index, op.in1 ? 2 : 1);
+  const bool fused = op.d_s2w != nullptr;
+  const Act *t0 = !tail ? nullptr : fused ? op.skip0 : op.resid_act, *t1 = (tail && fused) ? op.skip1 : nullptr;
+  if (tail) {
+    if (!t0) return fail("op %d has neither a residual nor a fused skip conv", index);
+    if ((t0 != nullptr) != (h_t0 != nullptr) || (t1 != nullptr) != (h_t1 != nullptr))
+      return fail("op %d takes %d tensor(s) behind its %s", index, t1 ? 2 : 1, fused ? "fused skip conv" : "residual");
+    for (const Act *t : {t0, t1})
+      if (t && (t == op.in0 || t == op.in1 || t == op.out_act)) return fail("op %d: a residual / skip tensor is also a source or the output", index);
+  }
   DevGuard g(m->device);
   hipStream_t st = m->stream;
   const size_t Vs = (size_t)op.in0->V(), Vo = (size_t)op.out_act->V();
-  CM_HIP(hipMemcpy(op.in0->d, h_in0, (size_t)B * Vs * op.in0->C * sizeof(float), hipMemcpyHostToDevice));
-  if (op.in1) CM_HIP(hipMemcpy(op.in1->d, h_in1, (size_t)B * Vs * op.in1->C * sizeof(float), hipMemcpyHostToDevice));
+  if (dbg_upload(op.in0, h_in0, (size_t)B * Vs * op.in0->C)) return 1;
+  if (op.in1 && dbg_upload(op.in1, h_in1, (size_t)B * Vs * op.in1->C)) return 1;
+  if (t0 && dbg_upload(t0, h_t0, (size_t)B * Vo * t0->C)) return 1;
+  if (t1 && dbg_upload(t1, h_t1, (size_t)B * Vo * t1->C)) return 1;
   if (mode < 0 || mode > 3) return fail("mode %d", mode);
+  // Modes 1 and 2 name operand forms of the fp32 plans.  The reduced-precision plan has one form per conv -- conv_route takes the f16
+  // fragments whatever the op's debug flags say -- so on such a handle they ARE mode 0, for every op (its quarter-resolution convs
+  // included: nothing is withheld, no source statistics are recomputed).
+  if (m->precision == CM_PRECISION_F16 && (mode == 1 || mode == 2)) mode = 0;
   Op tmp = op;
   if (mode != 3) {
-    tmp.ca.gn = nullptr; tmp.ca.silu = 0; tmp.ca.temb = nullptr; tmp.temb_off = -1; tmp.ca.resid = nullptr; tmp.resid_act = nullptr;
-    tmp.d_s2w = nullptr; tmp.d_wqr_skip = nullptr; tmp.dbg_raw = true; tmp.pm_off = -1;
+    tmp.ca.gn = nullptr; tmp.ca.silu = 0; tmp.ca.temb = nullptr; tmp.temb_off = -1; tmp.dbg_raw = true; tmp.pm_off = -1;
+    if (!tail) { tmp.ca.resid = nullptr; tmp.resid_act = nullptr; tmp.d_s2w = nullptr; tmp.d_wqr_skip = nullptr; }
     if (!tmp.qr) tmp.gn_op = -1;
   }
   tmp.skip_if_fused = false;
@@ -2843,7 +2902,53 @@ int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in
   const hipError_t e = hipStreamSynchronize(st);
   if (rc) return 1;
   if (e != hipSuccess) return fail("debug conv launch failed: %s", hipGetErrorString(e));
-  CM_HIP(hipMemcpy(h_out, op.out_act->d, (size_t)B * Vo * op.out_act->C * sizeof(float), hipMemcpyDeviceToHost));
+  return dbg_download(op.out_act, h_out, (size_t)B * Vo * op.out_act->C);
+}
+}  // namespace
+
+// Test hook (tests/test_gpu_six_term_hostile.py): conv op `index` ALONE on the caller's data -- no GroupNorm / SiLU on load, no
+// time-embedding row, no residual, no fused skip conv; the bias stays.  h_in0 / h_in1: host, channels-last
+// [B][Zs][Ys][Xs][C0 / C1] (h_in1 null when the op has one source); h_out: host [B][Zo][Yo][Xo][channel stride of the output
+// tensor].  mode 0: the six-term bf16 form where the plan has one (raw operands are unbounded: never the h2 form); mode 1: the
+// same layer on fp32 matrix instructions (the split fragments withheld); mode 2: the h2 form where the plan has one (the caller
+// keeps its operands inside the bound the plan guarantees, tests/test_gpu_h2.py); mode 3: the op exactly as the sampling forward
+// launches it -- GroupNorm + SiLU on load, time-embedding row, residual, fused skip conv, h2 where the plan has it -- on the caller's
+// sources; the GroupNorm rows / slot partials, the time rows, the residual and the skip conv's source are what the last forward
+// left (tests/test_gpu_wino_forms.py compares two kernels for the SAME launch with it; cm_debug_conv_stats reads the slots it wrote).
+// A handle on the reduced-precision plan: tensors plan_h16 stores as _Float16 are converted on the way in (round to nearest even) and
+// out, and modes 1 and 2 EQUAL mode 0 there (one operand form per conv; debug_conv_launch).  An fp32 handle's launches are unchanged.
+int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B) {
+  CM_NOT_DIT(m, "cm_debug_conv_io");
+  return debug_conv_launch(m, index, mode, false, h_in0, h_in1, nullptr, nullptr, h_out, B);
+}
+
+// Test hook, exported like cm_debug_attn_block (tests/test_gpu_f16_layers.py): the raw single launch of cm_debug_conv_io's mode 0 --
+// no GroupNorm / SiLU on load, no time-embedding row -- that KEEPS the tail of the op's inference launch, on the caller's data: the
+// residual (h_t0: [B][Zo][Yo][Xo][C of the residual tensor], h_t1 null), or, where the block's 1x1x1 skip conv is fused in, that conv
+// over its one or two raw sources (h_t0 / h_t1: [B][Zo][Yo][Xo][C of skip0 / skip1]; the bias is then conv bias + skip bias).  Which of
+// the two, and the channel counts: the "res" / "skip" tokens of cm_debug_conv_info.  An op with neither is an error.
+extern "C" int cm_debug_conv_tail(cm_model *m, int32_t index, const float *h_in0, const float *h_in1, const float *h_t0, const float *h_t1,
+                                  float *h_out, int32_t B) {
+  CM_NOT_DIT(m, "cm_debug_conv_tail");
+  return debug_conv_launch(m, index, 0, true, h_in0, h_in1, h_t0, h_t1, h_out, B);
+}
+
+// Test hook (tests/test_gpu_f16_layers.py): one attention core launch ALONE on host data, no handle -- f16 != 0: launch_attn_core_f16
+// (the reduced-precision plan's kernel, 32 channels per head), else launch_attn_core -- on the current device's default stream.
+// h_qkv: [B][S][3 E] (q | k | v per token, heads contiguous inside each); h_out: [B][S][E].
+extern "C" int cm_debug_attn_core(const float *h_qkv, float *h_out, int32_t B, int32_t S, int32_t E, int32_t heads, int32_t f16) {
+  if (!h_qkv || !h_out || B < 1 || S < 1 || E < 1 || heads < 1) return fail("bad argument");
+  const size_t nq = (size_t)B * S * 3 * E, no = (size_t)B * S * E;
+  float *d_qkv = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc((void **)&d_qkv, nq * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, no * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_qkv, h_qkv, nq * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_out, 0xff, no * sizeof(float));      // (NaN wherever the kernel writes nothing)
+  if (e == hipSuccess) e = (f16 ? cm::launch_attn_core_f16 : cm::launch_attn_core)(d_qkv, d_out, B, S, E, heads, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(h_out, d_out, no * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(d_qkv); hipFree(d_out);
+  if (e != hipSuccess) return fail("debug attention core launch failed: %s", hipGetErrorString(e));
   return 0;
 }
 

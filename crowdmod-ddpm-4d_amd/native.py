@@ -266,6 +266,9 @@ _HOOKS = {
     "cm_debug_attn_block": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32]),
     "cm_debug_attn_pack": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_float)]),
     "cm_debug_attn_sample_ok": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "cm_debug_conv_info_ext": (C.c_int, [_P, C.c_int32, _P, C.c_int64]),
+    "cm_debug_conv_tail": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32]),
+    "cm_debug_attn_core": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 
@@ -288,6 +291,26 @@ def debug_attn_block(handle, index: int, mode: int, x: np.ndarray):
     check(hook("cm_debug_attn_block")(handle, index, mode, x.ctypes.data, out.ctypes.data, part.ctypes.data,
                                       cnt.ctypes.data, B))
     return out, part, cnt
+
+
+def debug_conv_tail(handle, index: int, x0: np.ndarray, x1, t0: np.ndarray, t1, out_shape):
+    """Conv op `index` of a UNet handle as ONE raw launch (no GroupNorm / SiLU on load, no time row) that keeps its residual or its
+    fused 1x1x1 skip conv, on host data: x0 / x1 the sources [B, Zs, Ys, Xs, C0 / C1] (x1 None for one source), t0 the residual, or
+    t0 / t1 the skip conv's one or two sources, [B, Zo, Yo, Xo, C].  Returns the output tensor, out_shape = [B, Zo, Yo, Xo, stride]."""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (x0, x1, t0, t1)]
+    out = np.empty(out_shape, np.float32)
+    check(hook("cm_debug_conv_tail")(handle, index, *[None if a is None else a.ctypes.data for a in arrs], out.ctypes.data, arrs[0].shape[0]))
+    return out
+
+
+def debug_attn_core(qkv: np.ndarray, heads: int, f16: bool):
+    """One attention core launch alone on qkv [B, S, 3 E] (q | k | v per token): attn_core_f16_kernel (f16) or attn_core_kernel.
+    Returns out [B, S, E].  Needs no handle."""
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    B, S, E3 = qkv.shape
+    out = np.empty((B, S, E3 // 3), np.float32)
+    check(hook("cm_debug_attn_core")(qkv.ctypes.data, out.ctypes.data, B, S, E3 // 3, heads, 1 if f16 else 0))
+    return out
 
 
 def debug_attn_pack(w: np.ndarray):

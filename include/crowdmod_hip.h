@@ -396,7 +396,9 @@ int cm_debug_bwd_plan(const cm_model *m, char *buf, int64_t capacity, int64_t *n
  * forward launches it (GroupNorm + SiLU on load, time row, residual, fused skip conv) on the caller's sources; everything else it
  * reads is what the last forward left.  With cm_debug_conv_flags(1 << 20) -- a bit no kernel reads; any non-zero value marks a
  * diagnostic run -- the Winograd launcher takes its generic kernel instead of a specialised launch form: the two must agree
- * bit for bit (tests/test_gpu_wino_forms.py). */
+ * bit for bit (tests/test_gpu_wino_forms.py).  A CM_PRECISION_F16 handle: host data is converted to and from the tensors that
+ * plan stores as _Float16 (round to nearest even), and modes 1 and 2 equal mode 0 -- that plan has one operand form per conv
+ * (tests/test_gpu_f16_layers.py). */
 int cm_debug_conv_io(cm_model *m, int32_t index, int32_t mode, const float *h_in0, const float *h_in1, float *h_out, int32_t B);
 /* Statistics slots of conv op `index`, in the slot count of the last forward's plan: h_part [B][*nslots][*C][2], h_cnt [B][*nslots]; with null buffers
  * only the two sizes are returned. */

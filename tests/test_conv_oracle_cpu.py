@@ -6,7 +6,11 @@
   2. integer path == float64 path, exactly, and == a pure int64 einsum that shares no code with it;
   3. the condition that makes a zero tolerance possible on the device (conv_oracle: 16 max S < 2^24) for every conv of every row
      of tests/train_limit_cases.py that builds, from the worst S the integer operands can reach at spec.make_plan's channel counts;
-  4. parse_info on a line as cm_debug_conv_info prints it."""
+  4. parse_info on a line as cm_debug_conv_info prints it;
+  5. the additions of the reduced-precision plan's tests (tests/test_gpu_f16_layers.py): the fused skip conv and the residual against
+     torch in float64 and an int64 einsum, f16_round and its ties, the parity form (fold) against the plain upsample conv, and -- for
+     every conv of every row of tests/f16_layer_cases.py, raw and with its tail, on the very operands the device test uploads --
+     max |y| < 65504 (no f16-stored output overflows) and 16 max S < 2^24: conditions on the inputs, from the oracle alone."""
 import zlib
 
 import numpy as np
@@ -15,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_oracle as co
+import f16_layer_cases as FC
 import train_limit_cases as TL
 
 # (Z, Y, X) of the SOURCE: even, odd, one voxel, one plane, one row
@@ -184,3 +189,131 @@ def test_parse_info():
     assert co.parse_info("other gn_finalize(final.0.weight) fin alone 8 0") is None
     with pytest.raises(ValueError):
         co.parse_info("conv too short")
+
+
+# ---- 5. the reduced-precision plan's additions ----------------------------------------------------------------------------------
+def _tail_case(x0, Co, rng, integer, two, par=0):
+    """(x_s0, x_s1, w_skip, b_skip, resid) on the output grid of a stride-1 launch on x0."""
+    shape = tuple(2 * n if par and 0 < i < 4 else n for i, n in enumerate(x0.shape[:-1]))
+    if integer:
+        xs0, xs1 = co.int_source(shape + (5,), 3, "s0"), co.int_source(shape + (3,), 3, "s1") if two else None
+        return xs0, xs1, co.int_weight((Co, 8 if two else 5), 3, "ws"), co.int_bias((Co,), 3, "bs"), co.int_source(shape + (Co,), 3, "r")
+    xs0, xs1 = rng.standard_normal(shape + (5,)), rng.standard_normal(shape + (3,)) if two else None
+    return xs0, xs1, rng.standard_normal((Co, 8 if two else 5, 1, 1, 1)), rng.standard_normal(Co), rng.standard_normal(shape + (Co,))
+
+
+@pytest.mark.parametrize("ext", EXTENTS[:4], ids=lambda e: "x".join(map(str, e)))
+@pytest.mark.parametrize("kind", ["s1", "two", "ups", "1x1"])
+def test_skip_and_residual_equal_torch_and_int64(kind, ext):
+    rng = np.random.default_rng(zlib.crc32(f"tail/{kind}/{ext}".encode()))
+    for integer in (False, True):
+        x0, x1, w, b, kw = _case(kind, ext, rng, integer)
+        for two in (False, True):
+            xs0, xs1, ws, bs, r = _tail_case(x0, w.shape[0], rng, integer, two, kw["par"])
+            xs = xs0 if xs1 is None else np.concatenate([xs0, xs1], axis=-1)
+            base_y, base_S = (_einsum_int64(x0, x1, w, b, **kw), None) if integer else _torch_ref(x0, x1, w, b, **kw)
+            for what, extra in (("skip", dict(x_s0=xs0, x_s1=xs1, w_skip=ws, b_skip=bs)), ("res", dict(resid=r)),
+                                ("both", dict(x_s0=xs0, x_s1=xs1, w_skip=ws, b_skip=bs, resid=r))):
+                y, S = co.conv_ref(x0, w, b, x1=x1, **kw, **extra)
+                if integer:
+                    want = base_y.copy()
+                    if what != "res":
+                        want += np.einsum("bzyxc,oc->bzyxo", xs, ws) + bs
+                    if what != "skip":
+                        want += r
+                    assert y.dtype == np.int64 and np.array_equal(y, want), (kind, what)
+                    assert (np.abs(y) <= S).all()
+                else:
+                    ty, tS = base_y.copy(), base_S.copy()
+                    if what != "res":
+                        sy, sS = _torch_ref(xs0, xs1, ws, bs, 1, 1, 0)
+                        ty, tS = ty + sy, tS + sS
+                    if what != "skip":
+                        ty, tS = ty + r, tS + np.abs(r)
+                    assert float((np.abs(y - ty) / tS).max()) <= 1e-12 and float((np.abs(S - tS) / tS).max()) <= 1e-12
+                    y32 = co.conv_ref32(x0, w, b, x1=x1, **kw, **extra)
+                    assert y32.dtype == np.float32 and float((np.abs(y32 - ty) / tS).max()) <= 3e-6
+    with pytest.raises(ValueError):
+        co.conv_ref(x0, w, b, x1=x1, **kw, w_skip=ws)
+
+
+def test_f16_round_and_its_ties():
+    v = np.array([2048, 2049, 2050, 2051, 4102, 4098, 65504, 65519, 65520, -65520, 1e-8, 2.0 ** -25, 3 * 2.0 ** -25])
+    want = np.array([2048, 2048, 2050, 2052, 4104, 4096, 65504, 65504, np.inf, -np.inf, 0.0, 0.0, 2.0 ** -23])
+    assert np.array_equal(co.f16_round(v), want)
+    assert np.array_equal(co.f16_round(v.astype(np.int64)[:10]), want[:10])
+    ints = np.arange(-2048, 2049)
+    assert np.array_equal(co.f16_round(ints), ints)                # every integer up to 2048 is an f16
+    # a conv whose exact outputs are the tie cases: zero source, the values in the bias
+    y, _ = co.conv_ref(np.zeros((1, 1, 1, 1, 2), np.int64), np.zeros((3, 2), np.int64), np.array([2049, 2051, 4102]), ntaps=1, store_f16=True)
+    assert y.dtype == np.float64 and y.ravel().tolist() == [2048.0, 2052.0, 4104.0]
+    y32 = co.conv_ref32(np.zeros((1, 1, 1, 1, 2)), np.zeros((3, 2)), np.array([2049.0, 2051.0, 4102.0]), ntaps=1, store_f16=True)
+    assert y32.dtype == np.float32 and y32.ravel().tolist() == [2048.0, 2052.0, 4104.0]
+
+
+def test_integer_outputs_of_a_wide_conv_do_round_in_f16():
+    """27 taps x 256 channels of the integer operands: a real share of the outputs lies above 2048, where f16's grid is coarser
+    than the integers -- the exact f16 sweep holds the device's store rounding, ties included, not just its sums."""
+    x = co.int_source((1, 6, 6, 6, 256), 7, "wide")
+    w, b = co.int_weight((32, 256, 3, 3, 3), 7, "wide"), co.int_bias((32,), 7, "wide")
+    y, S = co.conv_ref(x, w, b)
+    yr, _ = co.conv_ref(x, w, b, store_f16=True)
+    inner = y[:, 1:-1, 1:-1, 1:-1]
+    share = float((np.abs(inner) > 2048).mean())
+    ties = int(((np.abs(y) > 2048) & (np.abs(y) < 4096) & (y % 2 != 0)).sum() + ((np.abs(y) >= 4096) & (y % 4 == 2)).sum())
+    print(f"sigma {inner.std():.0f}, {100 * share:.1f} % of the interior outputs above 2048, {int((yr != y).sum())} rounded, {ties} ties")
+    assert 800 < inner.std() < 1100 and 0.01 < share < 0.06 and ties > 0
+    assert (yr != y).any() and np.isfinite(yr).all() and 16 * int(S.max()) < co.EXACT_LIMIT
+    big = np.abs(y) > 2048
+    assert not (yr[big] % 2).any() and not (yr[np.abs(yr) > 4096] % 4).any() and np.array_equal(yr[~big], y[~big])
+    assert float(np.abs(yr - y).max()) <= 2.0
+
+
+@pytest.mark.parametrize("ext", [(4, 6, 8), (3, 5, 7), (1, 1, 1)], ids=lambda e: "x".join(map(str, e)))
+def test_parity_form_is_the_upsample_conv(ext):
+    x0, _, w, b, kw = _case("ups", ext, None, integer=True)
+    y, S = co.conv_ref(x0, w, b, **kw)
+    yf, Sf = co.conv_ref(x0, w, b, **kw, fold=lambda a: a)          # integer taps fold exactly
+    assert np.array_equal(y, yf) and (np.abs(yf) <= Sf).all() and (Sf <= S).all()
+    rng = np.random.default_rng(9)
+    x0, _, w, b, kw = _case("ups", ext, rng)
+    y, S = co.conv_ref(x0, w, b, **kw)
+    yf, _ = co.conv_ref(x0, w, b, **kw, fold=lambda a: a)           # folded taps rounded to float32: 2^-24 of each
+    assert float((np.abs(y - yf) / S).max()) <= 2.0 ** -23
+    y16, _ = co.conv_ref(x0, w, b, **kw, fold=co.f16_round)
+    assert 1e-5 < float((np.abs(y - y16) / S).max()) <= 2.0 ** -11
+    y32 = co.conv_ref32(x0, w, b, **kw, fold=co.f16_round)
+    assert float((np.abs(y32 - y16) / S).max()) <= 3e-6
+
+
+@pytest.mark.parametrize("key", list(FC.CASES))
+def test_every_f16_row_stays_exact_and_inside_f16(key):
+    c = FC.CASES[key]
+    cfg = FC.cfg_of(key)
+    params = co.int_state_dict(cfg, 42)
+    worst_y = worst_S = 0
+    descs = co.plan_convs(cfg, c.rows, c.cols, c.past + c.future)
+    assert sorted(d["label"] for d in descs) == sorted(n for n, _, _, _ in co.conv_shapes(cfg))
+    for d in descs:
+        w = np.rint(params[d["label"]]).astype(np.int64)
+        bias = np.rint(params[d["label"][:-len("weight")] + "bias"]).astype(np.int64)
+        assert w.shape[1] == d["Cw"] and w.shape[0] == d["Co"], d
+        for tail in (False, True) if d["tail"] else (False,):
+            x0, x1, t0, t1 = co.int_operands(key, d, c.B, d["Cw"], 11, tail)
+            extra = co.tail_args(d, t0, t1, {k: np.rint(v).astype(np.int64) for k, v in params.items() if "match_input" in k})
+            y, S = co.conv_ref(x0, w, bias, x1=x1, ntaps=d["ntaps"], stride=d["stride"], par=d["par"], **extra)
+            assert y.shape == (c.B,) + d["out"] + (d["Co"],)
+            worst_y, worst_S = max(worst_y, int(np.abs(y).max())), max(worst_S, int(S.max()))
+            assert int(np.abs(y).max()) < 65504 and 16 * int(S.max()) < co.EXACT_LIMIT, (key, d["label"], tail)
+    print(f"{key}: {len(descs)} convs, max |y| {worst_y} < 65504, 16 max S = {16 * worst_S:.3e} of {co.EXACT_LIMIT:.3e}")
+
+
+def test_parse_info_reads_the_trailing_tokens():
+    g = co.parse_info("conv decoder_blocks.7.conv_2.weight 27 1 0 32 32 8 12 36 1 4 8 4 4 1 4 32 32 0 1 f16d 1 h16 53 res 0 skip 32 32 f16d 4 6 9 2")
+    assert g["kernel"] == "f16d" and g["h16"] == 53 and g["res"] == 0 and g["skip"] == (32, 32) and g["f16d"] == (4, 6, 9, 2)
+    assert co.launch_of(g)["tail"] == ("skip", 32, 32) and co.launch_of(g)["out"] == (8, 12, 36)
+    g = co.parse_info("conv first.weight 27 1 0 8 32 8 12 36 1 1 1 1 36 1 6 32 8 0 0 first 0 loop_ztiles 3/8 h16 4 res 0 skip 0 0")
+    assert g["h16"] == 4 and co.launch_of(g)["tail"] is None
+    g = co.parse_info("conv a.conv_2.weight 27 1 0 32 32 8 8 12 1 4 8 4 4 1 4 32 32 0 1 f16d 1 h16 13 res 32 skip 0 0 f16d 8 8 4 2")
+    assert co.launch_of(g)["tail"] == ("res", 32)
+    assert co.skip_names("decoder_blocks.7.conv_2.weight") == ("decoder_blocks.7.match_input.weight", "decoder_blocks.7.match_input.bias")

@@ -29,9 +29,10 @@ smalln and generic kernels, one and two sources, stride 1 and 2, 27 taps, the pa
    on the same data: the margin test_gpu_six_term_hostile.py grants a differently ordered fp32 sum, here against the CPU
    reference's own rounding instead of the code's mode 1.
 
-Out of scope: the f16 plan (f16d / 1x1_f16: plan_h16 stores tensors as _Float16 and the hook copies fp32 host data into them
-unconverted -- a hook change of its own) and mode 3 (GroupNorm + SiLU on load, time row, residual, fused skip: not exact in
-integers; test_gpu_wino_forms.py and test_gpu_gn_stats.py hold it).
+Elsewhere: the f16 plan's kernels (f16d, 1x1_f16, the F16 forms of ups / wino / fin, f16-stored tensors) are swept the same way,
+with the residual and the fused skip conv kept, in test_gpu_f16_layers.py (the hook converts to and from the tensors plan_h16 stores
+as _Float16).  Out of scope: mode 3 (GroupNorm + SiLU on load, time row, residual, fused skip: not exact in integers;
+test_gpu_wino_forms.py and test_gpu_gn_stats.py hold it).
 
 MEASURED on the MI355X.  Exact sweep, default plan, 25 rows: 8217 launches compared, 0 mismatches -- generic 2823, qr 1980, wino 1368,
 ksplit 1191, ups 423, first 207, fin 189, smalln 36 (per row 0.3 - 1.0 s after the handle is built); the f32r and f32x sweeps of four

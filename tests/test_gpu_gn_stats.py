@@ -291,7 +291,7 @@ def test_every_producers_slots_are_the_float64_statistics_of_its_own_output(grid
     print(f"GNSTAT {grid} {model} (kernel, form) pairs: {sorted(seen)}")
     # every producer of the default plan: the first conv, the Winograd epilogue, conv_qr2, the K-split combine, the stage-once upsample conv, the
     # generic kernel and the attention block's two forms (HERMES-CR-120's 84 tokens keep the two-launch form).  Not producers here: conv_smalln
-    # and conv_fin (their launch predicates admit no statistics), the direct f16 conv (reduced-precision plan only), chan_stats_kernel (diagnostic
+    # and conv_fin (their launch predicates admit no statistics), the direct f16 conv and the f16 upsample conv (reduced-precision plan only: their slots are counted in test_gpu_f16_layers.py), chan_stats_kernel (diagnostic
     # builds only: asserted above)
     want = {"first", "wino", "qr", "ksplit", "ups", "generic", "attn_head_kernel + ksplit_combine_kernel"} | ({"attn_sample_kernel"} if grid != "cr120" else set())
     assert want <= kernels, (grid, sorted(kernels))
