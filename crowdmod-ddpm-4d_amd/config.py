@@ -127,6 +127,7 @@ class ConvRNNKeys:
     enc_kernels: Tuple[int, ...]
     forc_kernels: Tuple[int, ...]
     epochs: int
+    precision: str = "f32"   # MODEL.CONVRNN.PRECISION: "f32" | "f16", the forecast plan of Forecaster.set_precision (absent: "f32")
 
 
 def resolve_convrnn(cfg) -> ConvRNNKeys:
@@ -142,9 +143,12 @@ def resolve_convrnn(cfg) -> ConvRNNKeys:
     if cell not in ("ConvGRUCell", "ConvLSTMCell"):
         raise ValueError(f"Unsupported cell class: {cell}")   # convRNN.py:31-34
     train = node.get("TRAIN", None) or {}
+    precision = str(node.get("PRECISION", "f32"))
+    if precision not in ("f32", "f16"):
+        raise ValueError(f"MODEL.CONVRNN.PRECISION {precision!r}: 'f32' or 'f16'")
     return ConvRNNKeys(cell, bool(node.get("TEACHER_FORCING", False)), tuple(int(v) for v in req("ENC_HIDDEN_CH")),
                        tuple(int(v) for v in req("FORC_HIDDEN_CH")), tuple(int(v) for v in req("ENC_KERNELS")),
-                       tuple(int(v) for v in req("FORC_KERNELS")), int(train.get("EPOCHS", 0)))
+                       tuple(int(v) for v in req("FORC_KERNELS")), int(train.get("EPOCHS", 0)), precision)
 
 
 def train_autocast(train) -> bool:

@@ -28,6 +28,7 @@ import numpy as np
 from . import config as cfgmod, convrnn_spec, native, optim_state
 from .native_module import NativeModule
 
+_F16_REFUSAL = ("the f16 forecast plan (Forecaster.set_precision('f16')) is inference only: {} needs set_precision('f32')")
 _REFUSAL = ("ConvRNN training (Poisson-KL + masked MSE loss, AMSGrad) is not reached through train(): use "
             "ConvRNN_model.fit / Forecaster.train_step (train_convrnn.py); the forecaster has no train mode")
 
@@ -44,6 +45,28 @@ class Forecaster(NativeModule):
     _CREATE = "cm_convrnn_create"
     _MODEL = "cm_convrnn"
     _FAMILY = "cm_convrnn_train"
+    precision = "f32"
+
+    def set_precision(self, precision: str):
+        """The forecast plan.  "f32" (default): every product on the exact-fp32 matrix instruction.  "f16": every conv but
+        the first encoder conv and the forecaster's last one forms its products on v_mfma_f32_32x32x16_f16, operands rounded
+        once to f16, fp32 accumulation; every tensor, epilogue and state stays fp32 (cm_convrnn_set_precision,
+        CM_PRECISION_F16).  Inference only: the training and loss entry points refuse on it.  A change releases the
+        native handle; the next call re-creates it."""
+        if precision not in ("f32", "f16"):
+            raise ValueError(f"precision {precision!r}: 'f32' or 'f16'")
+        if precision != self.precision:
+            self._release()
+            self.precision = precision
+        return self
+
+    def _before_upload(self, h):
+        if self.precision == "f16":
+            native.check(native.lib().cm_convrnn_set_precision(h, native.PRECISION_F16))
+
+    def _inference_only(self, what: str):
+        if self.precision != "f32":
+            raise NotImplementedError(_F16_REFUSAL.format(what))
 
     def __init__(self, input_size, input_channels, enc_hidden_channels, forc_hidden_channels, enc_kernels, forc_kernels,
                  device=0, cell_class="ConvGRUCell", bias=False, *, past_len: int = 5, future_len: int = 3,
@@ -118,7 +141,8 @@ class Forecaster(NativeModule):
         return self._create_handle()
 
     def _after_finalize(self, h):
-        if self._hyper is not None:     # the optimizer of train_init lives in the handle: fresh state on the new one
+        if self._hyper is not None and self.precision == "f32":   # the optimizer of train_init lives in the handle: fresh
+            # state on the new one (an f16-plan handle is inference only and gets none)
             native.check(self._fn("init")(h, *self._hyper))
 
     # -- forward -------------------------------------------------------------------
@@ -141,6 +165,7 @@ class Forecaster(NativeModule):
     def train_init(self, lr, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
         """torch.optim.Adam(parameters(), lr, betas, eps, weight_decay, amsgrad=True) of convRNN.py:49-53: fresh optimizer
         state on the current weights.  The native state is (re)built with the next batch."""
+        self._inference_only("train_init")
         self._release()
         self._hyper = (float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
         return self
@@ -165,6 +190,7 @@ class Forecaster(NativeModule):
 
     def evaluate_loss(self, past, target, teacher_forcing=False, eps: float = 1e-6):
         """utils/loss.py:15-52 on the device: (rloss, vloss, loss_considering_density, loss_not_considering_density)."""
+        self._inference_only("evaluate_loss")
         h, B = self._step_handle(past, target)
         terms = (C.c_double * 4)()
         with self._pair(past, target) as (p, t):
@@ -180,6 +206,7 @@ class Forecaster(NativeModule):
         train_forward, `sums_sync(six sums) -> six global sums`, train_backward with them, `grad_sync(self)` on the flat
         gradient (a SUM over ranks: each rank's gradient is its share of the global objective's), apply_update.  The terms
         returned are those of the global batch, identical on every rank."""
+        self._inference_only("train_step")
         if self._hyper is None:
             raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
         if sums_sync is not None or grad_sync is not None:
@@ -211,12 +238,14 @@ class Forecaster(NativeModule):
     def train_forward(self, past, target, teacher_forcing=False) -> np.ndarray:
         """First half of a split step: the forward with its activations kept.  Returns np.float64[6]: the Poisson-KL sum,
         occupied MSE sum, occupied count, empty penalty sum, empty count of THIS batch, and its element count B*H*W*F."""
+        self._inference_only("train_forward")
         if self._hyper is None:
             raise RuntimeError("call train_init(lr, betas, eps, weight_decay) first")
         return self._forward_sums(self._fn("forward"), past, target, teacher_forcing)
 
     def loss_sums(self, past, target, teacher_forcing=False) -> np.ndarray:
         """The validation half: forward and the six sums; `terms_from_sums` of their total over ranks is the loss."""
+        self._inference_only("loss_sums")
         return self._forward_sums(native.lib().cm_convrnn_loss_sums, past, target, teacher_forcing)
 
     def train_backward(self, global_sums, eps: float = 1e-6, alpha: float = 1.0):
@@ -298,6 +327,23 @@ class Forecaster(NativeModule):
         shp = tuple(int(v) for v in shape)
         return buf[: int(np.prod(shp))].reshape(shp).copy()
 
+    def debug_launch(self, layer: int, part: int, x0, x1=None, hprev=None, u=None, c=None):
+        """ONE launch of layer `layer` (0-11, the layer table of cm_convrnn_host.inc) on host-supplied sources, with the
+        handle's weights under the handle's plan (cm_convrnn_debug_launch).  Arrays are [B, C, h, w].  A conv layer
+        (part 0): x0 -> y.  A GRU cell: part 0, (x0, x1 = h, hprev) -> (r * hprev, u); part 1, (x0, x1 = r * h, hprev, u)
+        -> h'.  An LSTM cell (part 0): (x0, x1 = h, c) -> (h', c').  Test hook."""
+        g = self.cfg
+        B = int(x0.shape[0])
+        h = self.ensure(g.rows, g.cols, g.past_len, g.future_len, B)
+        _, kind, _, cout, level = g.layers()[layer]
+        shp = (B, cout, g.rows >> (2 - level), g.cols >> (2 - level))
+        two = kind == "cell" and (part == 0 or not g.gru)
+        y0, y1 = np.empty(shp, np.float32), (np.empty(shp, np.float32) if two else None)
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (x0, x1, hprev, u, c)]
+        native.check(native.lib().cm_convrnn_debug_launch(h, int(layer), int(part), *[None if a is None else a.ctypes.data for a in arrs],
+                                                          y0.ctypes.data, None if y1 is None else y1.ctypes.data, B))
+        return (y0, y1) if two else y0
+
     def cost(self, B: int):
         f, b = C.c_double(), C.c_double()
         native.check(native.lib().cm_convrnn_cost(self._handle, B, C.byref(f), C.byref(b)))
@@ -318,7 +364,7 @@ class ConvRNN_model:
         self.teacher_forcing = k.teacher_forcing
         self.convRNN = Forecaster((self.res.rows, self.res.cols), self.mprops_count, k.enc_hidden, k.forc_hidden,
                                   k.enc_kernels, k.forc_kernels, self.device, k.cell_class, bias=False,
-                                  past_len=self.res.past_len, future_len=self.res.future_len, seed=seed)
+                                  past_len=self.res.past_len, future_len=self.res.future_len, seed=seed).set_precision(k.precision)
 
     def train(self, *a, **kw):
         raise NotImplementedError(_REFUSAL)

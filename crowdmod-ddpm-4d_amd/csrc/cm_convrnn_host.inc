@@ -15,11 +15,13 @@ struct CrnnLayer {
   CrnnKind kind; int cin, cout, level;   // CRNN_CELL: cin = the declared input_dim, cout = hidden_dim, level = its hidden state
   int p0 = 0;                            // index of its first state_dict tensor
   float *w0 = nullptr, *w1 = nullptr;    // packed device weights (GRU: gates, candidate)
+  _Float16 *h0 = nullptr, *h1 = nullptr; // f16 plan, layers 1-11: the same matrices rounded once to f16, instead of w0 / w1
 };
 
 struct cm_convrnn {
   cm_convrnn_config cfg{};
   int device = -1;
+  int precision = CM_PRECISION_F32;      // cm_convrnn_set_precision: CM_PRECISION_F32 or CM_PRECISION_F16
   bool finalized = false;
   int lastB = 0;
   hipStream_t stream = nullptr;
@@ -141,9 +143,10 @@ const Param *crnn_find(const cm_convrnn *m, const char *name) {
   return nullptr;
 }
 
-cm::CrnnConvArgs crnn_args(const cm_convrnn *m, int geo, int epi, const float *W, int B, int lin, int lout) {
+cm::CrnnConvArgs crnn_args(const cm_convrnn *m, int geo, int epi, const float *W, int B, int lin, int lout,
+                           const _Float16 *Wh = nullptr) {
   cm::CrnnConvArgs a{};
-  a.geo = geo; a.epi = epi; a.W = W; a.B = B;
+  a.geo = geo; a.epi = epi; a.W = W; a.Wh = Wh; a.B = B;
   a.Hi = m->lh[lin]; a.Wi = m->lw[lin]; a.Ho = m->lh[lout]; a.Wo = m->lw[lout];
   return a;
 }
@@ -153,13 +156,13 @@ int crnn_cell(cm_convrnn *m, const CrnnLayer &l, const float *x, int B, hipStrea
   const int lv = l.level, hid = l.cout;
   const long long pix = (long long)m->lh[lv] * m->lw[lv];
   float *hp = m->h[lv][m->cur[lv]], *hn = m->h[lv][m->cur[lv] ^ 1];
-  cm::CrnnConvArgs a = crnn_args(m, cm::CRNN_GEO_S1, 0, l.w0, B, lv, lv);
+  cm::CrnnConvArgs a = crnn_args(m, cm::CRNN_GEO_S1, 0, l.w0, B, lv, lv, l.h0);
   a.x0 = x; a.bs0 = pix * l.cin; a.C0 = l.cin;
   a.x1 = hp; a.bs1 = pix * hid; a.C1 = hid;
   if (m->cfg.cell == CM_CELL_GRU) {
     a.epi = cm::CRNN_EPI_GRU_GATES; a.N = 2 * hid; a.y = m->scr; a.u = m->u; a.hprev = hp;
     CM_HIP(cm::launch_crnn_conv(a, st));
-    a.epi = cm::CRNN_EPI_GRU_CAND; a.N = hid; a.W = l.w1; a.x1 = m->scr; a.y = hn;
+    a.epi = cm::CRNN_EPI_GRU_CAND; a.N = hid; a.W = l.w1; a.Wh = l.h1; a.x1 = m->scr; a.y = hn;
     CM_HIP(cm::launch_crnn_conv(a, st));
   } else {
     a.epi = cm::CRNN_EPI_LSTM; a.N = 4 * hid; a.y = hn; a.c = m->c[lv];
@@ -172,7 +175,7 @@ int crnn_cell(cm_convrnn *m, const CrnnLayer &l, const float *x, int B, hipStrea
 // A plain conv layer with LeakyReLU: x at level `lin` -> y at level l.level
 int crnn_conv(cm_convrnn *m, const CrnnLayer &l, const float *x, long long bs, int cx, int lin, float *y, int B, hipStream_t st) {
   const int geo = l.kind == CRNN_UP ? cm::CRNN_GEO_T4 : l.kind == CRNN_DOWN ? cm::CRNN_GEO_S2 : cm::CRNN_GEO_S1;
-  cm::CrnnConvArgs a = crnn_args(m, geo, cm::CRNN_EPI_LEAKY, l.w0, B, lin, l.level);
+  cm::CrnnConvArgs a = crnn_args(m, geo, cm::CRNN_EPI_LEAKY, l.w0, B, lin, l.level, l.h0);
   a.x0 = x; a.bs0 = bs; a.C0 = cx; a.N = l.cout; a.y = y;
   CM_HIP(cm::launch_crnn_conv(a, st));
   return 0;
@@ -322,6 +325,17 @@ int cm_convrnn_get_param(const cm_convrnn *m, const char *name, float *h_data, i
   return 0;
 }
 
+int cm_convrnn_set_precision(cm_convrnn *m, int32_t precision) {
+  if (!m) return fail("null ConvRNN handle");
+  if (precision == CM_PRECISION_F32R || precision == CM_PRECISION_F32X)
+    return fail("ConvRNN: CM_PRECISION_F32R / CM_PRECISION_F32X are conv split forms of the UNet; a ConvRNN handle takes "
+                "CM_PRECISION_F32 or CM_PRECISION_F16");
+  if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16) return fail("unknown precision %d", precision);
+  if (m->finalized) return fail("cm_convrnn_set_precision after cm_convrnn_finalize: create a new handle");
+  m->precision = precision;
+  return 0;
+}
+
 int cm_convrnn_finalize(cm_convrnn *m) {
   if (!m) return fail("null ConvRNN handle");
   if (m->device < 0) return fail("host-only ConvRNN handle (device < 0) cannot be finalized");
@@ -331,8 +345,23 @@ int cm_convrnn_finalize(cm_convrnn *m) {
   DevGuard g(m->device);
   const cm_convrnn_config &c = m->cfg;
   std::vector<float> w0, w1;
+  std::vector<_Float16> h16;
   for (int i = 0; i < 13; ++i) {
     crnn_pack_layer(m, i, &w0, &w1);
+    if (m->precision == CM_PRECISION_F16 && i >= 1 && i <= 11) {   // the f16 plan's operands; layers 0 and 12 stay fp32
+      for (int j = 0; j < 2; ++j) {
+        const std::vector<float> &w = j ? w1 : w0;
+        if (w.empty()) continue;
+        h16.resize(w.size());
+        for (size_t e = 0; e < w.size(); ++e) h16[e] = (_Float16)w[e];   // round-to-nearest-even, no clamp (as dit_finalize)
+        _Float16 *dp = nullptr;
+        CM_HIP(hipMalloc((void **)&dp, std::max<size_t>(h16.size(), 8) * sizeof(_Float16)));
+        m->allocs.push_back(dp);
+        CM_HIP(hipMemcpy(dp, h16.data(), h16.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        (j ? m->L[i].h1 : m->L[i].h0) = dp;
+      }
+      continue;
+    }
     if (crnn_alloc(m, &m->L[i].w0, w0.size())) return 1;
     CM_HIP(hipMemcpy(m->L[i].w0, w0.data(), w0.size() * sizeof(float), hipMemcpyHostToDevice));
     if (w1.empty()) continue;
@@ -405,25 +434,122 @@ int cm_convrnn_debug_state(cm_convrnn *m, int32_t level, int32_t which, float *h
   return 0;
 }
 
+namespace {
+
+// host [B][C][h][w] -> a fresh device buffer [B][h][w][Cpad] (channels C .. Cpad - 1 zero); null stays null
+int crnn_dbg_up(const float *src, int B, int C, int Cpad, int h, int w, std::vector<void *> *owned, float **dst) {
+  *dst = nullptr;
+  if (!src) return 0;
+  std::vector<float> t((size_t)B * h * w * Cpad, 0.f);
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < h * w; ++p) t[((size_t)b * h * w + p) * Cpad + c] = src[((size_t)b * C + c) * h * w + p];
+  CM_HIP(hipMalloc((void **)dst, t.size() * sizeof(float)));
+  owned->push_back(*dst);
+  CM_HIP(hipMemcpy(*dst, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// a device buffer [B][h][w][C] -> host [B][C][h][w]
+int crnn_dbg_down(const float *src, int B, int C, int h, int w, float *dst) {
+  std::vector<float> t((size_t)B * h * w * C);
+  CM_HIP(hipMemcpy(t.data(), src, t.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < C; ++c)
+      for (int p = 0; p < h * w; ++p) dst[((size_t)b * C + c) * h * w + p] = t[((size_t)b * h * w + p) * C + c];
+  return 0;
+}
+
+int crnn_debug_launch(cm_convrnn *m, int i, int part, const float *h_x0, const float *h_x1, const float *h_hprev, const float *h_u,
+                      const float *h_c, float *h_y0, float *h_y1, int B, std::vector<void *> *owned) {
+  const CrnnLayer &l = m->L[i];
+  const bool gru = m->cfg.cell == CM_CELL_GRU;
+  const int lout = l.level, lin = l.kind == CRNN_DOWN ? lout + 1 : l.kind == CRNN_UP ? lout - 1 : lout;
+  const int hi = m->lh[lin], wi = m->lw[lin], ho = m->lh[lout], wo = m->lw[lout];
+  const int cpad = (l.cin + 7) / 8 * 8;
+  float *x0 = nullptr, *x1 = nullptr, *hp = nullptr, *u = nullptr, *c = nullptr, *y0 = nullptr, *y1 = nullptr;
+  auto fresh = [&](float **p, size_t n) {
+    CM_HIP(hipMalloc((void **)p, n * sizeof(float)));
+    owned->push_back(*p);
+    CM_HIP(hipMemset(*p, 0, n * sizeof(float)));
+    return 0;
+  };
+  if (crnn_dbg_up(h_x0, B, l.cin, cpad, hi, wi, owned, &x0)) return 1;
+  if (l.kind != CRNN_CELL) {
+    if (part != 0) return fail("layer %d is a conv: it has part 0 only", i);
+    const int geo = l.kind == CRNN_UP ? cm::CRNN_GEO_T4 : l.kind == CRNN_DOWN ? cm::CRNN_GEO_S2 : cm::CRNN_GEO_S1;
+    if (fresh(&y0, (size_t)B * ho * wo * l.cout)) return 1;
+    cm::CrnnConvArgs a = crnn_args(m, geo, cm::CRNN_EPI_LEAKY, l.w0, B, lin, lout, l.h0);
+    a.x0 = x0; a.bs0 = (long long)hi * wi * cpad; a.C0 = cpad; a.N = l.cout; a.y = y0;
+    CM_HIP(cm::launch_crnn_conv(a, m->stream));
+    CM_HIP(hipStreamSynchronize(m->stream));
+    return crnn_dbg_down(y0, B, l.cout, ho, wo, h_y0);
+  }
+  const int hid = l.cout;
+  const size_t ns = (size_t)B * ho * wo * hid;
+  if (part != 0 && !(part == 1 && gru)) return fail("layer %d: part %d (0: the GRU gates or the LSTM; 1: the GRU candidate)", i, part);
+  if (!h_x1) return fail("a cell launch needs x1");
+  if (gru ? !h_hprev || (part == 1 && !h_u) : !h_c) return fail("a cell launch needs hprev (GRU; its candidate u as well) or c (LSTM)");
+  if (!gru || part == 0) { if (!h_y1) return fail("this launch has two outputs: y1 is null"); }
+  if (crnn_dbg_up(h_x1, B, hid, hid, ho, wo, owned, &x1) || crnn_dbg_up(h_hprev, B, hid, hid, ho, wo, owned, &hp) ||
+      crnn_dbg_up(h_u, B, hid, hid, ho, wo, owned, &u) || crnn_dbg_up(h_c, B, hid, hid, ho, wo, owned, &c))
+    return 1;
+  if (fresh(&y0, ns) || fresh(&y1, ns)) return 1;
+  const long long pix = (long long)ho * wo;
+  cm::CrnnConvArgs a = crnn_args(m, cm::CRNN_GEO_S1, 0, l.w0, B, lout, lout, l.h0);
+  a.x0 = x0; a.bs0 = pix * l.cin; a.C0 = l.cin;
+  a.x1 = x1; a.bs1 = pix * hid; a.C1 = hid;
+  if (gru && part == 0) {
+    a.epi = cm::CRNN_EPI_GRU_GATES; a.N = 2 * hid; a.y = y0; a.u = y1; a.hprev = hp;
+  } else if (gru) {
+    a.epi = cm::CRNN_EPI_GRU_CAND; a.N = hid; a.W = l.w1; a.Wh = l.h1; a.y = y0; a.u = u; a.hprev = hp;
+  } else {
+    a.epi = cm::CRNN_EPI_LSTM; a.N = 4 * hid; a.y = y0; a.c = c; a.cn = y1;
+  }
+  CM_HIP(cm::launch_crnn_conv(a, m->stream));
+  CM_HIP(hipStreamSynchronize(m->stream));
+  if (crnn_dbg_down(y0, B, hid, ho, wo, h_y0)) return 1;
+  if (!gru || part == 0) return crnn_dbg_down(y1, B, hid, ho, wo, h_y1);
+  return 0;
+}
+
+}  // namespace
+
+int cm_convrnn_debug_launch(cm_convrnn *m, int32_t layer, int32_t part, const float *h_x0, const float *h_x1, const float *h_hprev,
+                            const float *h_u, const float *h_c, float *h_y0, float *h_y1, int32_t B) {
+  if (crnn_ready(m, B)) return 1;
+  if (layer < 0 || layer > 11) return fail("layer %d outside [0, 11] (the last conv writes the forecast itself: cm_convrnn_forecast)", layer);
+  if (!h_x0 || !h_y0) return fail("null argument");
+  DevGuard g(m->device);
+  std::vector<void *> owned;
+  const int rc = crnn_debug_launch(m, layer, part, h_x0, h_x1, h_hprev, h_u, h_c, h_y0, h_y1, B, &owned);
+  hipDeviceSynchronize();
+  for (void *p : owned) hipFree(p);
+  return rc;
+}
+
 // Algorithmic FLOPs (2 per multiply-add of the reference's convolutions; a transposed 4x4 stride-2 conv has 4 taps per
-// output) and the bytes of every launch's sources, output and weights, of one forecast at batch B.
+// output) and the bytes of every launch's sources, output and weights, of one forecast at batch B.  On the f16 plan the
+// weights of layers 1-11 are two bytes each; every tensor a launch reads or writes is fp32 on either plan.
 int cm_convrnn_cost(const cm_convrnn *m, int32_t B, double *flops, double *bytes) {
   if (!m || !flops || !bytes) return fail("null argument");
   if (B < 1) return fail("batch must be >= 1");
   double f[2] = {0, 0}, by[2] = {0, 0};   // encoder (per frame), forecaster (per step)
   for (int i = 0; i < 13; ++i) {
     const CrnnLayer &l = m->L[i];
+    const double wb = m->precision == CM_PRECISION_F16 && i >= 1 && i <= 11 ? 2 : 4;   // bytes of a weight; tensors stay fp32
     const double pout = (double)B * m->lh[l.level] * m->lw[l.level];
     const double pin = l.kind == CRNN_DOWN ? pout * 4 : l.kind == CRNN_UP ? pout / 4 : pout;
     double macs, bts;
     if (l.kind == CRNN_CELL) {
       const double cin = l.cin + l.cout, ngate = m->cfg.cell == CM_CELL_GRU ? 3 : 4;
       macs = pout * ngate * l.cout * 9 * cin;
-      bts = 4 * ((m->cfg.cell == CM_CELL_GRU ? 2 : 1) * pout * cin + pout * l.cout * (m->cfg.cell == CM_CELL_GRU ? 5 : 4) + ngate * l.cout * 9 * cin);
+      bts = 4 * ((m->cfg.cell == CM_CELL_GRU ? 2 : 1) * pout * cin + pout * l.cout * (m->cfg.cell == CM_CELL_GRU ? 5 : 4)) +
+            wb * ngate * l.cout * 9 * cin;
     } else {
       const double taps = l.kind == CRNN_UP ? 4 : 9;
       macs = pout * l.cout * taps * l.cin;
-      bts = 4 * (pin * l.cin + pout * l.cout + (l.kind == CRNN_UP ? 16.0 : 9.0) * l.cout * l.cin);
+      bts = 4 * (pin * l.cin + pout * l.cout) + wb * (l.kind == CRNN_UP ? 16.0 : 9.0) * l.cout * l.cin;
     }
     f[i >= 6] += 2 * macs;
     by[i >= 6] += bts;

@@ -159,6 +159,18 @@ void test_handle(int cell) {
   double fl = 0, by = 0;
   EXPECT(cm_convrnn_cost(m, 2, &fl, &by) == 0 && fl > 0 && by > 0);
 
+  // the precision rules: fp32 or f16, before finalize; the f16 plan is inference only and its weights are two bytes
+  double fl16 = 0, by16 = 0;
+  EXPECT(cm_convrnn_set_precision(m, CM_PRECISION_F32R) != 0 && cm_convrnn_set_precision(m, CM_PRECISION_F32X) != 0);
+  EXPECT(cm_convrnn_set_precision(m, 9) != 0 && strstr(cm_last_error(), "unknown precision"));
+  EXPECT(cm_convrnn_set_precision(m, CM_PRECISION_F16) == 0 && m->precision == CM_PRECISION_F16);
+  EXPECT(cm_convrnn_cost(m, 2, &fl16, &by16) == 0 && fl16 == fl && by16 < by);
+  EXPECT(cm_convrnn_train_init(m, 1e-3f, 0.9f, 0.999f, 1e-8f, 0.f) != 0 && strstr(cm_last_error(), "inference only"));
+  double sums16[6];
+  EXPECT(cm_convrnn_loss_sums(m, &one, &one, 0, 1, nullptr, sums16) != 0 && strstr(cm_last_error(), "inference only"));
+  EXPECT(cm_convrnn_debug_launch(m, 1, 0, &one, &one, &one, nullptr, nullptr, &one, &one, 1) != 0);   // not finalized
+  EXPECT(cm_convrnn_set_precision(m, CM_PRECISION_F32) == 0 && m->precision == CM_PRECISION_F32);
+
   // the packers, element by element
   std::vector<float> w0, w1;
   for (int i = 0; i < 13; ++i) {

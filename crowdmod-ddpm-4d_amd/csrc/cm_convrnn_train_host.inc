@@ -110,6 +110,9 @@ int crnn_nsplit(long long rows) { return (int)std::min<long long>(16, std::max<l
 
 int crnn_train_ready(const cm_convrnn *m, int B, bool need_train) {
   if (!m) return fail("null ConvRNN handle");
+  if (m->precision != CM_PRECISION_F32)
+    return fail("the f16 plan of a ConvRNN handle (cm_convrnn_set_precision(CM_PRECISION_F16)) is inference only: train and "
+                "evaluate the loss on a CM_PRECISION_F32 handle");
   if (m->device < 0) return fail("host-only ConvRNN handle (device < 0) cannot train or evaluate a loss");
   if (!m->finalized) return fail("cm_convrnn_finalize has not been called");
   if (need_train && !m->train) return fail("cm_convrnn_train_init has not been called");
@@ -425,6 +428,9 @@ extern "C" {
 
 int cm_convrnn_train_init(cm_convrnn *m, float lr, float beta1, float beta2, float eps, float weight_decay) {
   if (!m) return fail("null ConvRNN handle");
+  if (m->precision != CM_PRECISION_F32)
+    return fail("the f16 plan of a ConvRNN handle (cm_convrnn_set_precision(CM_PRECISION_F16)) is inference only: train and "
+                "evaluate the loss on a CM_PRECISION_F32 handle");
   if (m->device < 0) return fail("cm_convrnn_train_init: host-only ConvRNN handle (device < 0) cannot train");
   if (!m->finalized) return fail("cm_convrnn_train_init: cm_convrnn_finalize has not been called");
   if (m->train) return fail("cm_convrnn_train_init has already been called on this handle");

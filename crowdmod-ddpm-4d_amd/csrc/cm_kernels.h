@@ -595,7 +595,8 @@ hipError_t launch_ditt4_gate_rows(const float *Xin, float *Xout, const float *Yc
 hipError_t launch_ditt_segsum_rows(const float *U, int ldu, long long useg, const float *V, int ldv, long long vseg, float *out,
                                    int ldo, int nseg, long long seg_rows, int N, hipStream_t st);
 
-// ConvRNN forecaster (cm_convrnn.hip): one implicit-GEMM 2-D convolution with fused epilogues, and the frame packer.
+// ConvRNN forecaster (cm_convrnn.hip): one implicit-GEMM 2-D convolution with fused epilogues, on fp32 or (f16 plan) f16
+// operands, and the frame packer.
 enum { CRNN_GEO_S1 = 0, CRNN_GEO_S2 = 1, CRNN_GEO_T4 = 2 };   // 3x3 stride 1 pad 1; 3x3 stride 2 pad 1; transposed 4x4 stride 2 pad 1
 enum { CRNN_EPI_LEAKY = 0, CRNN_EPI_GRU_GATES = 1, CRNN_EPI_GRU_CAND = 2, CRNN_EPI_LSTM = 3, CRNN_EPI_LAST = 4 };
 struct CrnnConvArgs {
@@ -604,6 +605,8 @@ struct CrnnConvArgs {
   long long bs0, bs1;             // elements between two samples of a source
   int C0, C1;                     // multiples of 8
   const float *W;                 // packed [N][K], K = taps * (C0 + C1), k = tap * (C0 + C1) + c; CRNN_GEO_T4: [4 parity classes][N][K]
+  const _Float16 *Wh;             // f16 plan (cm_convrnn_set_precision): the same matrix rounded once to f16; set: the launch forms
+                                  // its products on v_mfma_f32_32x32x16_f16 (crnn_conv_f16_kernel) and W is not read.  Not with LAST.
   int B, Hi, Wi, Ho, Wo, N;
   float *y;                       // LEAKY: [B][Ho][Wo][N]; GRU_GATES: r * h_prev [..][N/2]; GRU_CAND / LSTM: the new h [..][N | N/4]
   float *u;                       // GRU_GATES: writes u [..][N/2]; GRU_CAND: reads it

@@ -191,6 +191,10 @@ SIGNATURES = {
     "cm_convrnn_set_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
     "cm_convrnn_get_param": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
     "cm_convrnn_finalize": (C.c_int, [_P]),
+    # (handle, PRECISION_F32 | PRECISION_F16) before finalize: the f16 forecast plan (inference only)
+    "cm_convrnn_set_precision": (C.c_int, [_P, C.c_int32]),
+    # test hook: (handle, layer 0-11, part, x0, x1, hprev, u, c, y0, y1, B), host arrays in the reference's NCHW
+    "cm_convrnn_debug_launch": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32]),
     "cm_convrnn_forecast": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     "cm_convrnn_forecast_host": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.c_int32]),
     "cm_convrnn_debug_state": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),

@@ -37,7 +37,8 @@ def main(argv=None):
     ap.add_argument('--timesteps', type=int, default=None, help='override MODEL.DDPM.TIMESTEPS, or MODEL.FM.INTEGRATOR_STEPS.EULER for FM-DiT (smoke runs)')
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--precision', choices=('f32', 'f16'), default=None,
-                    help='DDPM-DiT sampling plan (default: MODEL.DDPM.DIT.PRECISION of the config, else f32)')
+                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (default: MODEL.DDPM.DIT.PRECISION / '
+                         'MODEL.CONVRNN.PRECISION of the config, else f32)')
     ap.add_argument('--tables', choices=('host', 'device'), default=None,
                     help='route of the SSIM / ENERGY / MF_* tables (default: METRICS.TABLES of the config, else host)')
     args = ap.parse_args(argv)
@@ -54,9 +55,12 @@ def main(argv=None):
     elif args.timesteps:
         cfg.MODEL.DDPM.TIMESTEPS = int(args.timesteps)
     if args.precision is not None:
-        if args.arch != "DDPM-DiT":
-            raise SystemExit(f"--precision selects the DDPM-DiT sampling plan; {args.arch} does not take it")
-        cfg.MODEL.DDPM.DIT.PRECISION = args.precision
+        if args.arch == "ConvRNN":
+            cfg.MODEL.CONVRNN.PRECISION = args.precision
+        elif args.arch != "DDPM-DiT":
+            raise SystemExit(f"--precision selects the DDPM-DiT sampling plan or the ConvRNN forecast plan; {args.arch} does not take it")
+        else:
+            cfg.MODEL.DDPM.DIT.PRECISION = args.precision
     res = cfgmod.resolve(cfg, args.arch)
     mprops = 4 if args.arch == "ConvRNN" else 3   # generate_metrics.py:60 of the reference; the forecaster takes all four
     # generate_metrics.py:63-68: NSAMPLES chains in chunks of 20 repeats, or BATCH_SIZE * chunk when the flag is given

@@ -60,7 +60,8 @@ def main():
     ap.add_argument('--data-npy', type=str, default=None, help='test sequences [N,C,ROWS,COLS,T] (.npy)')
     ap.add_argument('--device', type=int, default=0)
     ap.add_argument('--precision', choices=('f32', 'f16'), default=None,
-                    help='DDPM-DiT sampling plan (default: MODEL.DDPM.DIT.PRECISION of the config, else f32)')
+                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (default: MODEL.DDPM.DIT.PRECISION / '
+                         'MODEL.CONVRNN.PRECISION of the config, else f32)')
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
@@ -76,9 +77,12 @@ def main():
     else:
         Model = DDPM_model
     if args.precision is not None:
-        if args.arch != "DDPM-DiT":
-            raise SystemExit(f"--precision selects the DDPM-DiT sampling plan; {args.arch} does not take it")
-        cfg.MODEL.DDPM.DIT.PRECISION = args.precision
+        if args.arch == "ConvRNN":
+            cfg.MODEL.CONVRNN.PRECISION = args.precision
+        elif args.arch != "DDPM-DiT":
+            raise SystemExit(f"--precision selects the DDPM-DiT sampling plan or the ConvRNN forecast plan; {args.arch} does not take it")
+        else:
+            cfg.MODEL.DDPM.DIT.PRECISION = args.precision
     model = Model(cfg, args.arch, mprops, output_dir=cfg.DATA_FS.get("OUTPUT_DIR", "output"),
                   from_fixed_past=args.from_fixed_past, device=args.device)
     ckpt = model.checkpoint_path(args.model_sample_to_load) if args.arch.startswith("FM-") or args.arch == "ConvRNN" else \

@@ -563,7 +563,9 @@ int cm_dit4d_train_get_pred(cm_model *m, float *h_out, int64_t numel);
 /* ---- ConvRNN forecaster: replaces Forecaster(...) (models/convRNN/forecaster.py) and
  * ConvRNN_model._generate_convRNN (models/convRNN/convRNN.py:223-231) -----------------------------------
  * The deterministic ConvGRU / ConvLSTM encoder-forecaster baseline of arch "ConvRNN".  It has no timestep and no
- * sampler, so it is a handle of its own.  Inference only.  Exact fp32 on v_mfma_f32_32x32x2_f32 throughout. */
+ * sampler, so it is a handle of its own.  Exact fp32 on v_mfma_f32_32x32x2_f32 throughout by default; an opt-in f16
+ * forecast plan (cm_convrnn_set_precision) forms the products of all but the first and the last conv on
+ * v_mfma_f32_32x32x16_f16. */
 enum { CM_CELL_GRU = 0, CM_CELL_LSTM = 1 };
 typedef struct cm_convrnn_config {
   int32_t in_channels;                    /* mprops_count: 4 (channels 0 and 3 are indexed)       */
@@ -590,6 +592,20 @@ int cm_convrnn_num_params(const cm_convrnn *m, int32_t *count);
 int cm_convrnn_param_info(const cm_convrnn *m, int32_t index, const char **name, int64_t shape[4], int32_t *ndim);
 int cm_convrnn_set_param(cm_convrnn *m, const char *name, const float *h_data, int64_t numel);
 int cm_convrnn_get_param(const cm_convrnn *m, const char *name, float *h_data, int64_t numel);
+/* The forecast plan, chosen before cm_convrnn_finalize (refused after it: create a new handle).  CM_PRECISION_F32 is the
+ * default; a handle that never calls this is unchanged.  CM_PRECISION_F16: every conv launch of a forecast except the first
+ * encoder conv (layer 0: it reads the observation window, data in physical units with exp applied) and the forecaster's last
+ * conv (layer 12: it writes the forecast) forms its products on v_mfma_f32_32x32x16_f16.  Operands are rounded once,
+ * fp32 -> f16, round-to-nearest-even, no clamp: the weights on the host in cm_convrnn_finalize, an activation when a launch
+ * stages it (the GRU candidate's r * h_prev is the fp32 product, then rounded).  Products are exact, accumulation is fp32
+ * with k ascending in a fixed order (64-product chains, then one add into the running sum), and everything else is fp32 and
+ * the default plan's code: the accumulator tile, every epilogue (sigmoid, tanh, LeakyReLU, the GRU / LSTM state updates,
+ * exp), the hidden and cell states, the window, the forecast.  One writer per output element, no atomics, and a result
+ * that does not depend on the batch it ran in or on max_batch, as on the default plan.  The plan is inference only:
+ * cm_convrnn_train_init and the entry points that run the training forward (cm_convrnn_loss, cm_convrnn_loss_sums,
+ * cm_convrnn_train_step, cm_convrnn_train_forward) refuse an f16-plan handle and say so.  CM_PRECISION_F32R and
+ * CM_PRECISION_F32X are conv split forms of the UNet and are refused. */
+int cm_convrnn_set_precision(cm_convrnn *m, int32_t precision);
 /* Packs the weights once and allocates the workspace; fails if a tensor was never set or on a host-only handle. */
 int cm_convrnn_finalize(cm_convrnn *m);
 /* Forecaster.forward(x_obs, target_obs, teacher_forcing) -- forecaster.py:89-176: all future_len steps behind one call,
@@ -604,7 +620,22 @@ int cm_convrnn_forecast_host(cm_convrnn *m, const float *h_past, const float *h_
 /* Test hook: the hidden state the last call left, as [B,C,h,w]; level 0 quarter, 1 half, 2 full resolution; which 0 = h,
  * 1 = c (LSTM only).  The caller has synchronised the stream of that call. */
 int cm_convrnn_debug_state(cm_convrnn *m, int32_t level, int32_t which, float *h_out, int64_t capacity, int64_t shape[4]);
-/* Algorithmic FLOPs and bytes of one forecast at batch B. */
+/* Test hook: ONE launch of layer `layer` (0-11 in state_dict order: encoder.encoder_cell_list.0-5, forecaster_cell_list.0-5;
+ * the last conv writes the forecast itself and is reached through cm_convrnn_forecast) on host-supplied sources, with the
+ * handle's weights under the handle's plan, at batch B in [1, max_batch].  Every array is a host buffer in the reference's
+ * layout [B, C, h, w] at the layer's own resolution; sources are independent of each other and of the handle's states,
+ * which the call leaves alone.  Synchronous.
+ *   a conv layer (0, 2, 4, 7, 9, 11), part 0:  x0 [B, cin, hin, win] -> y0 [B, cout, hout, wout] (LeakyReLU applied)
+ *   a GRU cell (1, 3, 5, 6, 8, 10), part 0, the gates: x0 [B, cin, h, w], x1 = h [B, hid, h, w] (the conv's second
+ *     source), hprev [B, hid, h, w] (the epilogue's) -> y0 = r * hprev, y1 = u
+ *   a GRU cell, part 1, the candidate: x0, x1 = r * h, hprev, u -> y0 = (1 - u) tanh(conv) + u hprev
+ *   an LSTM cell, part 0: x0, x1 = h, c -> y0 = h', y1 = c'
+ * Pointers a launch does not use may be NULL. */
+int cm_convrnn_debug_launch(cm_convrnn *m, int32_t layer, int32_t part, const float *h_x0, const float *h_x1,
+                            const float *h_hprev, const float *h_u, const float *h_c, float *h_y0, float *h_y1, int32_t B);
+/* Algorithmic FLOPs and bytes of one forecast at batch B: 2 FLOPs per multiply-add of the reference's convolutions on
+ * either plan; the bytes of every launch's sources, outputs and weights under the handle's plan (the f16 plan's weights
+ * of layers 1-11 are two bytes each, every tensor stays fp32). */
 int cm_convrnn_cost(const cm_convrnn *m, int32_t B, double *flops, double *bytes);
 
 /* ---- ConvRNN training (convRNN.py:98-171): evaluate_loss (utils/loss.py:15-52), backpropagation through all future_len

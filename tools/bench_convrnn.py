@@ -9,7 +9,13 @@ Each path: `--warmup` calls, then HIP events on the launch stream around `--call
 path's achieved fp32 matrix TFLOP/s and its share of the 157.3 TFLOP/s peak, the native / torch ratio, and the largest
 difference between the two paths' outputs.
 
-    python tools/bench_convrnn.py [--batches 64 1280] [--cells gru lstm] [--calls 20] [--warmup 3]
+    python tools/bench_convrnn.py [--batches 64 1280] [--cells gru lstm] [--calls 20] [--warmup 3] [--precision f32|f16|both]
+
+--precision f16 times the f16 forecast plan (Forecaster.set_precision("f16")) instead of the default fp32 one.  --precision both
+compares the two plans in one process: after the warm-up, `--rounds` rounds that alternate the plans, each timing `--calls`
+calls; one JSON line per (cell, batch) with each plan's median ms per call, its spread (max - min over the rounds), forecasts/s
+and algorithmic TFLOP/s, the speed-up of the medians, whether the f16 plan is faster by more than the two spreads combined, and
+max |f16 - f32| / max |f32| of the two forecasts.  The torch restatement is not run in that mode.
 
 Kernel time per launch: run it on its own under `rocprofv3 --kernel-trace --stats -- python tools/bench_convrnn.py --no-torch ...`."""
 import argparse
@@ -85,6 +91,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-torch", action="store_true", help="time the native path only (profiling runs)")
+    ap.add_argument("--precision", choices=("f32", "f16", "both"), default="f32", help="forecast plan; both: alternated in one process")
+    ap.add_argument("--rounds", type=int, default=5, help="--precision both: rounds the medians and spreads are taken over")
     a = ap.parse_args()
     import torch
     from crowdmod_ddpm_4d_amd import convrnn_spec, native, prng
@@ -110,12 +118,14 @@ def main():
     for cell in a.cells:
         cfg = convrnn_spec.ConvRNNConfig(cell={"gru": "ConvGRUCell", "lstm": "ConvLSTMCell"}[cell])
         params = convrnn_spec.init_params(cfg, 42)
-        tnet = None if a.no_torch else torch_forecaster(params, cfg, dev)
+        tnet = None if a.no_torch or a.precision == "both" else torch_forecaster(params, cfg, dev)
         for B in a.batches:
-            net = Forecaster((cfg.rows, cfg.cols), 4, cfg.enc_hidden, cfg.forc_hidden, cfg.enc_kernels, cfg.forc_kernels, 0,
-                             cfg.cell, max_batch=B)
-            net.load_state_dict(params)
-            h = net.ensure(cfg.rows, cfg.cols, cfg.past_len, cfg.future_len, B)
+            def make(precision):
+                n = Forecaster((cfg.rows, cfg.cols), 4, cfg.enc_hidden, cfg.forc_hidden, cfg.enc_kernels, cfg.forc_kernels, 0,
+                               cfg.cell, max_batch=B).set_precision(precision)
+                n.load_state_dict(params)
+                return n, n.ensure(cfg.rows, cfg.cols, cfg.past_len, cfg.future_len, B)
+            net, h = make("f32" if a.precision == "both" else a.precision)
             shp = (B, 4, cfg.rows, cfg.cols)
             past = prng.normal(7, "bench_convrnn/past", int(np.prod(shp)) * cfg.past_len).reshape(*shp, cfg.past_len)
             past[:, [0, 3]] = np.abs(past[:, [0, 3]])
@@ -126,12 +136,41 @@ def main():
             def native_call():
                 native.check(L.cm_convrnn_forecast(h, d_past.data_ptr(), None, 0, 0, d_out.data_ptr(), B, stream.cuda_stream))
             torch.cuda.synchronize(dev)           # the uploads above ran on torch's default stream
+            if a.precision == "both":
+                net16, h16 = make("f16")
+                d_out16 = torch.empty_like(d_out)
+
+                def f16_call():
+                    native.check(L.cm_convrnn_forecast(h16, d_past.data_ptr(), None, 0, 0, d_out16.data_ptr(), B, stream.cuda_stream))
+                plans = (("f32", native_call, net), ("f16", f16_call, net16))
+                times = {name: [] for name, _, _ in plans}
+                for r in range(a.rounds):
+                    for name, fn, _ in plans:   # the warm-up of timed() runs in every round: the other plan ran in between
+                        times[name].append(timed(fn, a.calls))
+                stream.synchronize()
+                doc = {"cell": cell, "batch": B, "calls": a.calls, "warmup": a.warmup, "rounds": a.rounds}
+                for name, _, n in plans:
+                    flops, nbytes = n.cost(B)
+                    med = float(np.median(times[name]))
+                    doc.update({f"{name}_ms_per_call": med, f"{name}_spread_ms": max(times[name]) - min(times[name]),
+                                f"{name}_forecasts_per_s": B / (med * 1e-3), f"{name}_tflops": flops / (med * 1e-3) / 1e12,
+                                f"{name}_gbytes_per_call": nbytes / 1e9, f"{name}_ms_rounds": times[name]})
+                doc["gflop_per_call"] = flops / 1e9
+                doc["f16_speedup"] = doc["f32_ms_per_call"] / doc["f16_ms_per_call"]
+                doc["f16_faster_by_more_than_both_spreads"] = bool(
+                    doc["f32_ms_per_call"] - doc["f16_ms_per_call"] > doc["f32_spread_ms"] + doc["f16_spread_ms"])
+                doc["max_rel_f16_minus_f32"] = float((d_out16 - d_out).abs().max() / d_out.abs().max())
+                print(json.dumps(doc), flush=True)
+                del net, net16, d_past, d_tgt, d_out, d_out16
+                continue
             ms = timed(native_call, a.calls)
             flops, nbytes = net.cost(B)
             tf = flops / (ms * 1e-3) / 1e12
-            doc = {"cell": cell, "batch": B, "calls": a.calls, "warmup": a.warmup, "native_ms_per_call": ms,
+            doc = {"cell": cell, "batch": B, "precision": a.precision, "calls": a.calls, "warmup": a.warmup, "native_ms_per_call": ms,
                    "native_forecasts_per_s": B / (ms * 1e-3), "gflop_per_call": flops / 1e9, "gbytes_per_call": nbytes / 1e9,
-                   "native_tflops": tf, "frac_fp32_matrix_peak": tf / FP32_MFMA_PEAK_TFLOPS}
+                   "native_tflops": tf}
+            if a.precision == "f32":          # the f16 plan's products do not run on the fp32 instruction
+                doc["frac_fp32_matrix_peak"] = tf / FP32_MFMA_PEAK_TFLOPS
             if tnet is not None:
                 with torch.no_grad(), torch.cuda.stream(stream):
                     tms = timed(lambda: tnet(d_past, d_tgt, False), a.calls)
