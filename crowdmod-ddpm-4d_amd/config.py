@@ -114,7 +114,8 @@ class DiTKeys:
     condition: str
     dropout_rate: float
     train: Optional[AttrDict]
-    precision: str = "f32"   # MODEL.DDPM.DIT.PRECISION: "f32" | "f16", the sampling plan of DiT4D_V4.set_precision (absent: "f32")
+    precision: str = "f32"   # MODEL.DDPM.DIT.PRECISION: "f32" | "f16", the sampling plan of DiT4D_V4.set_precision; MODEL.FM.DIT.PRECISION:
+                             # "f32" | "f16a", that of DiT2D.set_precision (absent: "f32")
 
 
 @dataclass
@@ -202,7 +203,10 @@ def resolve(cfg, arch: str = "DDPM-UNet") -> Resolved:
             # FM_model does not pass CONDITION on (DiT2D keeps its default "Past"): read, not required
             dit = DiTKeys(int(req("PATCH_SIZE")), None, int(req("HIDDEN_SIZE")), int(req("DEPTH")),
                           int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")),
-                          str(back.get("CONDITION", "Past")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"))
+                          str(back.get("CONDITION", "Past")), float(back.get("DROPOUT_RATE", 0.1)), req("TRAIN"),
+                          str(back.get("PRECISION", "f32")))
+            if dit.precision not in ("f32", "f16a"):
+                raise ValueError(f"MODEL.FM.DIT.PRECISION {dit.precision!r}: 'f32' or 'f16a'")
         else:
             dit = DiTKeys(int(req("PATCH_SIZE")), int(req("T_PATCH_SIZE")), int(req("HIDDEN_SIZE")), int(req("DEPTH")),
                           int(req("NUM_HEADS")), float(req("MLP_RATIO")), int(req("TIME_EMB_MULT")),

@@ -18,6 +18,9 @@
 //                     patch) over all T_p slots.
 //   dit_attn_full     the DiT2D variant (models/backbones/DiT2D.py): one self-attention over all S = T_p * N_s tokens of
 //                     a sample, q k^T and P v both on v_mfma_f32_32x32x2_f32 with a streaming softmax.
+//   dit_attn_full_f16 the same attention with both products on v_mfma_f32_32x32x16_f16 (operands rounded to f16, fp32 softmax,
+//                     denominator and accumulation): taken only by an FM-DiT handle on the f16a plan
+//                     (cm_model_set_precision(CM_PRECISION_F16A)), whose four token Linears per block take dit_gemm_f16_kernel.
 // Determinism: every output element is written by one thread with a fixed summation order (k ascending in one fma
 // chain; fixed butterfly reductions), no atomics, and a sample only reads its own rows -- a chain's result does not
 // depend on the batch it runs in, the batch lane, or graph replay.
@@ -471,6 +474,110 @@ __global__ __launch_bounds__(64) void dit_attn_full_kernel(const DitAttnArgs a) 
   }
 }
 
+// dit_attn_full_kernel on f16 operands (the f16a plan of an FM-DiT handle: cm_model_set_precision(CM_PRECISION_F16A)): the same
+// streaming structure -- one wave per (sample, head, 32-query tile), keys in chunks of 32, running max and denominator in fp32, no
+// array bounds S, one writer per output element, fixed order, no atomics, a sample reads only its own rows -- with both products
+// on v_mfma_f32_32x32x16_f16 and fp32 accumulation (operand map: cm_dit_f16.h).
+// Rounding (all fp32 -> f16 round-to-nearest-even, no clamp: a value past 65504 becomes +-inf and surfaces as a non-finite output):
+// q * 0.125 is formed in fp32, then rounded; k and v are rounded when loaded; p = expf(s - m) is fp32, the denominator accumulates
+// the UNROUNDED p, and p is rounded as the second product's operand; the rescale by exp(m_old - m_new) and the final o / den are fp32.
+//   S^T = k q^T   A = k, B = q^T: four K = 16 steps over the 64 head channels; per step a lane supplies the eight channels
+//                 16 s + 8 hf + j of its key row and of its query row (32 contiguous bytes each).  The accumulator map is the fp32
+//                 instruction's: value r of a lane is key (r & 3) + 8 (r >> 2) + 4 hf of the chunk for the query lane & 31, so the
+//                 row max and sum are in-register plus one cross-half shuffle, as in dit_attn_full_kernel.
+//   O^T = v^T P^T two K = 16 steps over the chunk's 32 keys.  P goes from the accumulator registers straight into the B operand:
+//                 registers 8 s .. 8 s + 7 are the fragment of step s, so element j of lane half hf is key
+//                 16 s + 8 (j >> 2) + 4 hf + (j & 3) of the chunk -- NOT the natural 16 s + 8 hf + j.  A contraction is indifferent to
+//                 the order of its k index as long as both operands agree, so the A operand v^T is gathered in that same permuted
+//                 key order: these are the 16 rows (r & 3) + 8 (r >> 2) + 4 hf that dit_attn_full_kernel gathers.
+// Tail keys get the score -inf (weight exactly 0) and a zero v operand; their addresses and those of tail query rows are clamped to
+// row S - 1 of the same sample, and tail query rows are not stored.
+__global__ __launch_bounds__(64) void dit_attn_full_f16_kernel(const DitAttnArgs a) {
+  const int lane = threadIdx.x, c = lane & 31, hf = lane >> 5;
+  const int S = a.Tp * a.Ns, nqt = (S + 31) / 32, E3 = 3 * a.E;
+  const int qt = blockIdx.x % nqt;
+  const long long bh = blockIdx.x / nqt;
+  const int h = (int)(bh % a.heads);
+  const long long b = bh / a.heads;
+  const float *base = a.qkv + b * S * E3 + h * 64;
+  const int q = qt * 32 + c;
+  dit_f16x8 qh[4];   // round(q / 8) at the head channels 16 s + 8 hf + j this lane feeds to step s
+  {
+    const float *qr = base + (long long)min(q, S - 1) * E3 + 8 * hf;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const float4 x = *(const float4 *)(qr + 16 * s), y = *(const float4 *)(qr + 16 * s + 4);
+      const float t[8] = {x.x * 0.125f, x.y * 0.125f, x.z * 0.125f, x.w * 0.125f, y.x * 0.125f, y.y * 0.125f, y.z * 0.125f, y.w * 0.125f};
+      qh[s] = dh_round8(t);
+    }
+  }
+  float m = -INFINITY, den = 0.f;
+  dit_f32x16 o0, o1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
+  // Software pipeline as in dit_attn_full_kernel: a chunk's V rows are requested before its q k^T chain and the next chunk's K row
+  // before its softmax and P v chain.  K is held raw (fp32) while in flight and rounded when it is fed to the matrix unit.
+  float kc[4][8];   // the chunk's K operands, picked like qh
+  auto load_k = [&](int k0) {
+    const float *kr = base + a.E + (long long)min(k0 + c, S - 1) * E3 + 8 * hf;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const float4 x = *(const float4 *)(kr + 16 * s), y = *(const float4 *)(kr + 16 * s + 4);
+      kc[s][0] = x.x; kc[s][1] = x.y; kc[s][2] = x.z; kc[s][3] = x.w; kc[s][4] = y.x; kc[s][5] = y.y; kc[s][6] = y.z; kc[s][7] = y.w;
+    }
+  };
+  load_k(0);
+  const float *vb = base + 2 * a.E + c;
+  for (int k0 = 0; k0 < S; k0 += 32) {
+    float v0[16], v1[16];   // v[key (r & 3) + 8 (r >> 2) + 4 hf][channel c | c + 32]: the permuted key order of the P fragments
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float *vr = vb + (long long)min(k0 + (r & 3) + 8 * (r >> 2) + 4 * hf, S - 1) * E3;
+      v0[r] = vr[0];
+      v1[r] = vr[32];
+    }
+    dit_f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh_round8(kc[i]), qh[i], s, 0, 0, 0);
+    load_k(k0 + 32);   // past the last chunk: row S - 1 again, never used
+    float cmax = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (k0 + (r & 3) + 8 * (r >> 2) + 4 * hf >= S) { s[r] = -INFINITY; v0[r] = 0.f; v1[r] = 0.f; }
+      cmax = fmaxf(cmax, s[r]);
+    }
+    cmax = fmaxf(cmax, __shfl_xor(cmax, 32, 64));
+    const float mn = fmaxf(m, cmax);        // finite from the first chunk on: every chunk holds a key < S
+    const float alpha = expf(m - mn);       // first chunk: exp(-inf) = 0
+    float csum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = expf(s[r] - mn); csum += s[r]; }   // the denominator takes the unrounded weights
+    csum += __shfl_xor(csum, 32, 64);
+    den = den * alpha + csum;
+    m = mn;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      dit_f16x8 p;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) p[j] = (_Float16)s[8 * i + j];
+      o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh_round8(v0 + 8 * i), p, o0, 0, 0, 0);
+      o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(dh_round8(v1 + 8 * i), p, o1, 0, 0, 0);
+    }
+  }
+  if (q >= S) return;
+  // O^T: column = query, row = head channel (r & 3) + 8 (r >> 2) + 4 hf (+ 32 in o1): four consecutive channels per r >> 2
+  float *orow = a.out + (b * S + q) * a.E + h * 64 + 4 * hf;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    *(float4 *)(orow + 8 * g) = make_float4(o0[4 * g] / den, o0[4 * g + 1] / den, o0[4 * g + 2] / den, o0[4 * g + 3] / den);
+    *(float4 *)(orow + 32 + 8 * g) = make_float4(o1[4 * g] / den, o1[4 * g + 1] / den, o1[4 * g + 2] / den, o1[4 * g + 3] / den);
+  }
+}
+
 }  // namespace
 
 hipError_t launch_dit_gemm(const DitGemmArgs &a, hipStream_t st) {
@@ -521,6 +628,15 @@ hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st) {
   const long long nblk = (long long)a.B * a.heads * ((S + 31) / 32);
   if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(dit_attn_full_kernel, dim3((unsigned)nblk), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dit_attn_full_f16(const DitAttnArgs &a, hipStream_t st) {
+  const long long S = (long long)a.Tp * a.Ns;
+  if (S < 1 || a.E != 64 * a.heads) return hipErrorInvalidValue;
+  const long long nblk = (long long)a.B * a.heads * ((S + 31) / 32);
+  if (nblk > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dit_attn_full_f16_kernel, dim3((unsigned)nblk), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

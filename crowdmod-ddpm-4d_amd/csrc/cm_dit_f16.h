@@ -10,6 +10,11 @@
 // sampling plan, by the same rule on the host when the handle is finalized (dit_finalize), and staged as they are.  Products are
 // exact in the matrix unit and the accumulator, the partials and every output are fp32.
 //
+// The f16a plan of an FM-DiT handle (cm_model_set_precision(CM_PRECISION_F16A)) applies the same rule to its four token Linears and,
+// in dit_attn_full_f16_kernel (cm_dit.hip), to both attention products: q * 0.125 is formed in fp32 and then rounded; k and v are
+// rounded when loaded; p = expf(s - m) is fp32, the softmax denominator accumulates the UNROUNDED p, and p is rounded as the
+// operand of p v; the rescale by exp(m_old - m_new) and the final o / den are fp32.
+//
 // LDS image of either operand: [64 tile rows or columns][DH_K = 64 k] halves, k contiguous, row stride DH_S = 72 halves = 144 B =
 // 36 dwords.  Operand read: one 16-byte ds_read_b128 per lane and k step at row * 144 + 32 step + 16 (l >> 5).  That instruction
 // is served in four 16-lane groups ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32), bank = (byte / 4) mod 64; the 16

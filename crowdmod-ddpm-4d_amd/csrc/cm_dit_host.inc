@@ -24,9 +24,11 @@ struct cm_dit_plan {
                                // (DiT2D: depth * 6D + 2D, shift1 scale1 gate1 shift2 scale2 gate2)
   float *tab_h1 = nullptr, *tab_e = nullptr, *tab_cs = nullptr;   // scratch of dit_build_tables
   std::vector<const float *> w;  // device copies of the state_dict tensors, in state_dict order
-  std::vector<const _Float16 *> w16;   // f16 plan (cm_model::precision == CM_PRECISION_F16, DiT4D_V4 only): per tensor of `w`, its copy
-                               // rounded once to f16 (cm_dit_f16.h), same [out][in] order -- the six token-Linear weights of every block;
-                               // null elsewhere.  Empty on the fp32 plan.  Written by dit_finalize, read-only afterwards.
+  std::vector<const _Float16 *> w16;   // f16 plans (cm_model::precision == CM_PRECISION_F16 on DiT4D_V4, CM_PRECISION_F16A on DiT2D): per
+                               // tensor of `w`, its copy rounded once to f16 (cm_dit_f16.h), same [out][in] order -- the six (DiT2D: four)
+                               // token-Linear weights of every block; null elsewhere.  Empty on the fp32 plan.  Written by dit_finalize,
+                               // read-only afterwards.
+  bool attn16() const { return full && !w16.empty(); }   // f16a plan: the full attention takes dit_attn_full_f16_kernel
 };
 
 namespace {
@@ -37,6 +39,8 @@ constexpr int DIT_HEAD = 11;     // tensors before blocks.0 (both variants)
 // f16 plan: the weights of a DiT4D_V4 block (dit_build_params order) that get an f16 copy -- spatial in_proj, spatial out_proj,
 // temporal in_proj, temporal out_proj, mlp.0, mlp.3
 constexpr int DIT_F16_W[6] = {0, 2, 4, 6, 8, 10};
+// f16a plan: those of a DiT2D block (dit2d_build_params order) -- attn.in_proj_weight, attn.out_proj.weight, mlp.0.weight, mlp.3.weight
+constexpr int DIT2D_F16_W[4] = {0, 2, 4, 6};
 
 // state_dict order of DiT2D: spatial_pos_embed, temporal_pos_embed (DiT2D.py:196-201 -- registered after time_embeddings
 // and patch_embed, but a module's own parameters come first), then time_embeddings, time_proj, patch_embed, blocks,
@@ -176,11 +180,14 @@ int dit_finalize(cm_model *m) {
     d.w.push_back(dp);
   }
   if (dit_build_tables(m)) return 1;
-  if (m->precision == CM_PRECISION_F16) {   // the fp32 copies stay: the tables above and cm_model_get_param read them
+  if (m->precision == CM_PRECISION_F16 || m->precision == CM_PRECISION_F16A) {   // the fp32 copies stay: the tables above and cm_model_get_param read them
     d.w16.assign(d.w.size(), nullptr);
     std::vector<_Float16> h16;
+    const int *wsel = d.full ? DIT2D_F16_W : DIT_F16_W;
+    const int nsel = d.full ? 4 : 6;
     for (int i = 0; i < c.depth; ++i)
-      for (const int j : DIT_F16_W) {
+      for (int s = 0; s < nsel; ++s) {
+        const int j = wsel[s];
         const size_t wi = (size_t)(DIT_HEAD + d.per_block() * i + j);
         const std::vector<float> &h = m->params[wi].host;
         h16.resize(h.size());
@@ -208,6 +215,8 @@ int dit_finalize(cm_model *m) {
 // left as that stage wrote it and eps_cl is untouched -- dit_debug_activation).
 // f16 plan (d.w16 filled): the six token Linears of every block take dit_gemm_f16_kernel on the pre-rounded weights; the patch
 // embedding, the final layer, LayerNorm + modulate, both attention kernels, the gates and every tensor stay fp32.
+// f16a plan (a DiT2D handle with d.w16 filled): the four token Linears of every block likewise, and the full attention takes
+// dit_attn_full_f16_kernel (both products on f16 operands, fp32 softmax); everything else as above.
 int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
   const cm_dit_plan &d = *m->dit;
   const cm_dit_config &c = d.cfg;
@@ -246,19 +255,19 @@ int dit_forward(cm_model *m, int B, hipStream_t st, int b0, int nblocks) {
     if (d.full) {
       // self-attention over all tokens of the sample, gated residual on every row (DiT2D.py:104-106)
       a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_BIAS, M, D3, D);
-      a.A = X; a.lda = D; a.W = w[0]; a.bias = w[1]; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
-      CM_HIP(cm::launch_dit_gemm(a, st));
-      CM_HIP(cm::launch_dit_attn_full(at, st));
+      a.A = X; a.lda = D; a.Y = QKV; a.ldy = D3; a.off_shift = mo; a.off_scale = mo + D;
+      CM_HIP(launch(a, 0));
+      CM_HIP(d.attn16() ? cm::launch_dit_attn_full_f16(at, st) : cm::launch_dit_attn_full(at, st));
       a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, D);
-      a.A = AO; a.lda = D; a.W = w[2]; a.bias = w[3]; a.Y = X; a.ldy = D; a.off_gate = mo + 2 * D;
-      CM_HIP(cm::launch_dit_gemm(a, st));
+      a.A = AO; a.lda = D; a.Y = X; a.ldy = D; a.off_gate = mo + 2 * D;
+      CM_HIP(launch(a, 2));
       // MLP (:107-108)
       a = gemm(cm::DIT_PRO_LN, cm::DIT_EPI_GELU, M, mlp, D);
-      a.A = X; a.lda = D; a.W = w[4]; a.bias = w[5]; a.Y = Hm; a.ldy = mlp; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
-      CM_HIP(cm::launch_dit_gemm(a, st));
+      a.A = X; a.lda = D; a.Y = Hm; a.ldy = mlp; a.off_shift = mo + 3 * D; a.off_scale = mo + 4 * D;
+      CM_HIP(launch(a, 4));
       a = gemm(cm::DIT_PRO_NONE, cm::DIT_EPI_GATE, M, D, mlp);
-      a.A = Hm; a.lda = mlp; a.W = w[6]; a.bias = w[7]; a.Y = X; a.ldy = D; a.off_gate = mo + 5 * D;
-      CM_HIP(cm::launch_dit_gemm(a, st));
+      a.A = Hm; a.lda = mlp; a.Y = X; a.ldy = D; a.off_gate = mo + 5 * D;
+      CM_HIP(launch(a, 6));
       continue;
     }
     // spatial self-attention (DiT4D_V4.py:160-169)
@@ -358,6 +367,23 @@ int dit_debug_activation(cm_model *m, const char *name, float *h_out, int64_t ca
   CM_HIP(hipStreamSynchronize(m->stream));
   CM_HIP(hipMemcpy(h_out, d.X, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   if (shape) { shape[0] = B; shape[1] = d.tok; shape[2] = c.hidden_size; shape[3] = 1; shape[4] = 1; }
+  return 0;
+}
+
+// cm_debug_dit_attn: one launch of the full-attention kernel of the handle's plan on the caller's q|k|v, through the handle's own
+// QKV / AO workspace (a later forward overwrites both before it reads them).
+int dit_debug_attn(cm_model *m, const float *h_qkv, float *h_out, int B) {
+  const cm_dit_plan &d = *m->dit;
+  const cm_dit_config &c = d.cfg;
+  if (B < 1 || B > c.max_batch) return fail("cm_debug_dit_attn: B = %d is outside [1, max_batch = %d]", B, c.max_batch);
+  DevGuard g(m->device);
+  const size_t n = (size_t)B * d.tok * c.hidden_size;
+  CM_HIP(hipDeviceSynchronize());
+  CM_HIP(hipMemcpy(d.QKV, h_qkv, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  const cm::DitAttnArgs at{d.QKV, d.AO, B, d.Tp, d.Ns, d.qs, c.hidden_size, c.num_heads};
+  CM_HIP(d.attn16() ? cm::launch_dit_attn_full_f16(at, m->stream) : cm::launch_dit_attn_full(at, m->stream));
+  CM_HIP(hipStreamSynchronize(m->stream));
+  CM_HIP(hipMemcpy(h_out, d.AO, n * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -506,6 +506,8 @@ hipError_t launch_dit_attn_spatial(const DitAttnArgs &a, hipStream_t st);
 hipError_t launch_dit_attn_temporal(const DitAttnArgs &a, hipStream_t st);
 // DiT2D: one self-attention over all T_p * N_s tokens of a sample (any count), on the fp32 matrix instruction
 hipError_t launch_dit_attn_full(const DitAttnArgs &a, hipStream_t st);
+// the same attention with both products on f16 operands (v_mfma_f32_32x32x16_f16), fp32 softmax and accumulation: the f16a plan
+hipError_t launch_dit_attn_full_f16(const DitAttnArgs &a, hipStream_t st);
 
 // DiT2D training step (cm_dit_train.hip; host plan: cm_dit_train_host.inc).
 // Dropout site of a mask value; with (seed, optimizer step, global sample, block, head, row, column) it addresses one Philox word.

@@ -2071,9 +2071,18 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
 int cm_model_set_precision(cm_model *m, int32_t precision) {
   if (!m) return fail("null model handle");
   if (m->finalized) return fail("precision must be chosen before cm_model_finalize");
-  if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16 && precision != CM_PRECISION_F32R && precision != CM_PRECISION_F32X)
+  if (precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16 && precision != CM_PRECISION_F32R && precision != CM_PRECISION_F32X &&
+      precision != CM_PRECISION_F16A)
     return fail("unknown precision %d", precision);
-  if (m->dit && m->dit->full && precision != CM_PRECISION_F32) return refuse_dit(m, "a precision other than CM_PRECISION_F32");
+  if (precision == CM_PRECISION_F16A && !(m->dit && m->dit->full))
+    return fail("CM_PRECISION_F16A (f16 operands, attention included) is the reduced-precision plan of FM-DiT (DiT2D) handles: a %s handle "
+                "takes CM_PRECISION_F16", m->dit ? "DDPM-DiT (DiT4D_V4)" : "UNet");
+  if (m->dit && m->dit->full && precision == CM_PRECISION_F16)
+    return fail("CM_PRECISION_F16 is the plan of UNet and DDPM-DiT handles (fp32 attention): an FM-DiT (DiT2D) handle takes CM_PRECISION_F32 "
+                "or CM_PRECISION_F16A, whose attention products take f16 operands as well");
+  if (m->dit && m->dit->full && precision != CM_PRECISION_F32 && precision != CM_PRECISION_F16A)
+    return fail("CM_PRECISION_F32R and CM_PRECISION_F32X are split forms of the UNet's convs: an FM-DiT (DiT2D) handle takes "
+                "CM_PRECISION_F32 or CM_PRECISION_F16A");
   if (m->dit && (precision == CM_PRECISION_F32R || precision == CM_PRECISION_F32X))
     return fail("CM_PRECISION_F32R and CM_PRECISION_F32X are split forms of the UNet's convs: a DDPM-DiT (DiT4D_V4) handle takes "
                 "CM_PRECISION_F32 or CM_PRECISION_F16");
@@ -2194,6 +2203,15 @@ int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t
   CM_HIP(hipMemcpyAsync(h_loss, m->mse_loss, sizeof(float), hipMemcpyDeviceToHost, st));
   CM_HIP(hipStreamSynchronize(st));
   return 0;
+}
+
+int cm_debug_dit_attn(cm_model *m, const float *h_qkv, float *h_out, int32_t B) {
+  if (!m || !h_qkv || !h_out) return fail("null argument");
+  if (!m->dit || !m->dit->full)
+    return fail("cm_debug_dit_attn: a %s handle has no full-attention launch; this entry point takes FM-DiT (DiT2D) handles only",
+                m->dit ? "DDPM-DiT (DiT4D_V4)" : "UNet");
+  if (!m->finalized) return fail("cm_debug_dit_attn: model not finalized");
+  return dit_debug_attn(m, h_qkv, h_out, B);
 }
 
 int cm_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity, int64_t shape[5]) {

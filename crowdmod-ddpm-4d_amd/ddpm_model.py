@@ -109,7 +109,7 @@ class DDPM_model:
                          grid_cols=r.cols, patch_size=d.patch_size, hidden_size=d.hidden_size, depth=d.depth,
                          num_heads=d.num_heads, mlp_ratio=d.mlp_ratio, dropout_rate=d.dropout_rate,
                          time_multiple=d.time_emb_mult, past_len=r.past_len, future_len=r.future_len,
-                         device=self.device, max_batch=max(1, r.batch_size), seed=self.seed)
+                         device=self.device, max_batch=max(1, r.batch_size), seed=self.seed).set_precision(d.precision)
         return UNet(input_channels=self.mprops_count, output_channels=self.mprops_count,
                     num_res_blocks=r.num_res_blocks, base_channels=r.base_ch,
                     base_channels_multiples=r.base_ch_mult, apply_attention=r.apply_attention,

@@ -286,11 +286,37 @@ class DiT2D(DiT4D_V4):
         self._init_state(self._SPEC, device, max_batch, seed)
 
     def set_precision(self, precision: str):
-        """'f32' only: the reference trains and samples FM-DiT in fp32, and the f16 plan is DiT4D_V4's."""
-        if precision != "f32":
-            raise NotImplementedError(f"precision {precision!r}: FM-DiT (DiT2D) runs in 'f32' only; the f16 sampling plan "
-                                      "is DDPM-DiT's (DiT4D_V4)")
+        """'f32' (default) or 'f16a' ("f16 operands, attention included"): the sampling plan whose four token Linears per
+        block (q|k|v, attention out-projection, fc1, fc2) AND both products of the full self-attention take f16
+        matrix-core operands with fp32 accumulation; the softmax, its denominator, LayerNorm + modulate, gates, patch
+        embedding, final layer, every tensor and the sampler stay fp32 (cm_model_set_precision, CM_PRECISION_F16A).
+        It is not DiT4D_V4's 'f16', whose attention stays fp32: that name, like every other, is refused here.  Inference
+        only: fit_init on an 'f16a' model is refused by the library.  Releases the native handle; returns self."""
+        if precision not in ("f32", "f16a"):
+            raise NotImplementedError(f"precision {precision!r}: FM-DiT (DiT2D) runs in 'f32' or 'f16a'; the 'f16' sampling "
+                                      "plan (fp32 attention) is DDPM-DiT's (DiT4D_V4)")
+        if precision != self.precision:
+            self._release()
+            self.precision = precision
         return self
+
+    def _before_upload(self, h):
+        if self.precision == "f16a":
+            native.check(native.lib().cm_model_set_precision(h, native.PRECISION_F16A))
+
+    def debug_attention(self, qkv: np.ndarray) -> np.ndarray:
+        """Test hook: ONE launch of the full-attention kernel of this model's plan on q|k|v [B, S, 3E] (S = frames *
+        patches of the constructor's geometry, E = hidden_size); returns [B, S, E] (cm_debug_dit_attn)."""
+        g = self.cfg
+        S, E = g.t_p * g.n_s, g.hidden_size
+        qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+        if qkv.ndim != 3 or qkv.shape[1:] != (S, 3 * E):
+            raise ValueError(f"qkv {qkv.shape}: expected [B, {S}, {3 * E}]")
+        B = int(qkv.shape[0])
+        h = self.ensure(g.grid_rows, g.grid_cols, g.past_len, g.future_len, B)
+        out = np.empty((B, S, E), dtype=np.float32)
+        native.check(native.lib().cm_debug_dit_attn(h, qkv.ctypes.data, out.ctypes.data, B))
+        return out
 
     def native_config(self, max_batch: int, device: int) -> native.cm_dit2d_config:
         c, g = native.cm_dit2d_config(), self.cfg

@@ -71,6 +71,7 @@ class cm_sample_opts(C.Structure):
 
 SAMPLER_DDPM, SAMPLER_DDIM, SAMPLER_FM_EULER = 0, 1, 2
 PRECISION_F32, PRECISION_F16, PRECISION_F32R, PRECISION_F32X = 0, 1, 2, 3
+PRECISION_F16A = 4   # FM-DiT (DiT2D) handles only: f16 operands in the token Linears and in both attention products
 CELL_GRU, CELL_LSTM = 0, 1
 GUIDANCE_NONE, GUIDANCE_SPARSITY, GUIDANCE_MASS_PRESERVATION = 0, 1, 2
 TABLES = ("beta", "alpha", "alpha_bar", "sqrt_alpha_bar", "one_by_sqrt_alpha", "sqrt_one_minus_alpha_bar")
@@ -106,6 +107,8 @@ SIGNATURES = {
     "cm_unet_forward_train": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_uint64, C.c_int64, _P, C.c_int32, _P]),
     "cm_mse_loss": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_float), _P]),
     "cm_debug_activation": (C.c_int, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    # test hook: (FM-DiT handle, host qkv [B][S][3E], host out [B][S][E], B): one launch of the plan's full-attention kernel
+    "cm_debug_dit_attn": (C.c_int, [_P, _P, _P, C.c_int32]),
     "cm_schedule_create": (C.c_int, [C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.POINTER(_P)]),
     "cm_schedule_destroy": (C.c_int, [_P]),
     "cm_schedule_table": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),

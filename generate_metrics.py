@@ -36,9 +36,10 @@ def main(argv=None):
     ap.add_argument('--test-windows', type=int, default=None, help='synthetic test windows per batch (default: BATCH_SIZE)')
     ap.add_argument('--timesteps', type=int, default=None, help='override MODEL.DDPM.TIMESTEPS, or MODEL.FM.INTEGRATOR_STEPS.EULER for FM-DiT (smoke runs)')
     ap.add_argument('--device', type=int, default=0)
-    ap.add_argument('--precision', choices=('f32', 'f16'), default=None,
-                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (default: MODEL.DDPM.DIT.PRECISION / '
-                         'MODEL.CONVRNN.PRECISION of the config, else f32)')
+    ap.add_argument('--precision', choices=('f32', 'f16', 'f16a'), default=None,
+                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (f32 | f16), FM-DiT sampling plan (f32 | f16a: f16 '
+                         'operands, attention included); default: MODEL.DDPM.DIT.PRECISION / MODEL.FM.DIT.PRECISION / '
+                         'MODEL.CONVRNN.PRECISION of the config, else f32')
     ap.add_argument('--tables', choices=('host', 'device'), default=None,
                     help='route of the SSIM / ENERGY / MF_* tables (default: METRICS.TABLES of the config, else host)')
     args = ap.parse_args(argv)
@@ -55,7 +56,13 @@ def main(argv=None):
     elif args.timesteps:
         cfg.MODEL.DDPM.TIMESTEPS = int(args.timesteps)
     if args.precision is not None:
-        if args.arch == "ConvRNN":
+        if args.arch == "FM-DiT":
+            if args.precision == "f16":
+                raise SystemExit("--precision f16 is the DDPM-DiT plan (fp32 attention); FM-DiT takes f32 or f16a")
+            cfg.MODEL.FM.DIT.PRECISION = args.precision
+        elif args.precision == "f16a":
+            raise SystemExit(f"--precision f16a is the FM-DiT sampling plan; {args.arch} does not take it")
+        elif args.arch == "ConvRNN":
             cfg.MODEL.CONVRNN.PRECISION = args.precision
         elif args.arch != "DDPM-DiT":
             raise SystemExit(f"--precision selects the DDPM-DiT sampling plan or the ConvRNN forecast plan; {args.arch} does not take it")

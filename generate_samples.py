@@ -59,9 +59,10 @@ def main():
     ap.add_argument('--from-fixed-past', type=bool, default=False)
     ap.add_argument('--data-npy', type=str, default=None, help='test sequences [N,C,ROWS,COLS,T] (.npy)')
     ap.add_argument('--device', type=int, default=0)
-    ap.add_argument('--precision', choices=('f32', 'f16'), default=None,
-                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (default: MODEL.DDPM.DIT.PRECISION / '
-                         'MODEL.CONVRNN.PRECISION of the config, else f32)')
+    ap.add_argument('--precision', choices=('f32', 'f16', 'f16a'), default=None,
+                    help='DDPM-DiT sampling plan or ConvRNN forecast plan (f32 | f16), FM-DiT sampling plan (f32 | f16a: f16 '
+                         'operands, attention included); default: MODEL.DDPM.DIT.PRECISION / MODEL.FM.DIT.PRECISION / '
+                         'MODEL.CONVRNN.PRECISION of the config, else f32')
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
 
@@ -77,7 +78,13 @@ def main():
     else:
         Model = DDPM_model
     if args.precision is not None:
-        if args.arch == "ConvRNN":
+        if args.arch == "FM-DiT":
+            if args.precision == "f16":
+                raise SystemExit("--precision f16 is the DDPM-DiT plan (fp32 attention); FM-DiT takes f32 or f16a")
+            cfg.MODEL.FM.DIT.PRECISION = args.precision
+        elif args.precision == "f16a":
+            raise SystemExit(f"--precision f16a is the FM-DiT sampling plan; {args.arch} does not take it")
+        elif args.arch == "ConvRNN":
             cfg.MODEL.CONVRNN.PRECISION = args.precision
         elif args.arch != "DDPM-DiT":
             raise SystemExit(f"--precision selects the DDPM-DiT sampling plan or the ConvRNN forecast plan; {args.arch} does not take it")

@@ -56,8 +56,8 @@ typedef struct cm_unet_config {
 
 /* Hyper-parameters of reference DiT4D_V4.__init__ (models/backbones/DiT4D_V4.py:235-254) plus the tensor geometry, as
  * DDPM_model builds it for arch "DDPM-DiT" (models/diffusion/ddpm.py:88-104).  A DiT handle is the same opaque cm_model,
- * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 or F16,
- * see there) / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it, and
+ * tagged with its backbone: cm_model_destroy / num_params / param_info / set_param / get_param / set_precision (F32 or F16;
+ * FM-DiT: F32 or F16A, see there) / finalize / cm_unet_forward[_host] (the denoiser forward) / cm_sample_loop[_host] / cm_model_cost work on it, and
  * cm_debug_activation serves "patch_embed" and "blocks.<i>" (see there); every other handle entry point (training,
  * dropout width, the conv and loop debug hooks, profiling, FLOP splits) returns non-zero. */
 typedef struct cm_dit_config {
@@ -156,8 +156,19 @@ int cm_model_get_param(const cm_model *m, const char *name, float *h_data, int64
  * activation operand rounded when staged; patch embedding, final layer, conditioning tables, LayerNorm + modulate, attention,
  * gates, every tensor and the sampler stay fp32.  Inference only: cm_dit4d_train_init refuses such a handle.  Never worse than the
  * reference's own autocast forward against float64 (tests/test_gpu_dit_f16.py; DESIGN.md section 10 "f16 plan").  F32R and F32X
- * are conv split forms and are refused on it; an FM-DiT handle (cm_model_create_dit2d) takes CM_PRECISION_F32 only. */
-enum { CM_PRECISION_F32 = 0, CM_PRECISION_F16 = 1, CM_PRECISION_F32R = 2, CM_PRECISION_F32X = 3 };
+ * are conv split forms and are refused on it.
+ * An FM-DiT handle (cm_model_create_dit2d) takes CM_PRECISION_F32 (default) or CM_PRECISION_F16A ("f16 operands, attention
+ * included") and refuses the other three; DDPM-DiT and UNet handles refuse CM_PRECISION_F16A.  The f16a plan: the four token
+ * Linears of every block (q|k|v, attention out-projection, fc1, fc2) contract f16 operands with fp32 accumulation exactly as above
+ * (weights rounded once at cm_model_finalize, fp32 copies kept), and both products of the full self-attention run on
+ * v_mfma_f32_32x32x16_f16: q * 0.125 is formed in fp32 and then rounded, k and v are rounded when loaded, p = expf(s - m) is
+ * fp32, the softmax denominator accumulates the unrounded p, p is rounded as the operand of p v, and the rescale and o / den are
+ * fp32.  All roundings are round-to-nearest-even without clamp: a value past 65504 becomes +-inf and surfaces as a non-finite
+ * output.  Patch embedding, final layer, conditioning tables, LayerNorm statistics + modulate, gates, every tensor and the sampler
+ * stay fp32.  Inference only: cm_dit_train_init refuses such a handle.  It is a name of its own because the arithmetic differs from
+ * the DDPM-DiT "f16" plan, whose attention stays fp32.  Never worse than the reference's own autocast forward against float64
+ * (tests/test_gpu_dit2d_f16a.py; DESIGN.md section 11 "f16a plan"). */
+enum { CM_PRECISION_F32 = 0, CM_PRECISION_F16 = 1, CM_PRECISION_F32R = 2, CM_PRECISION_F32X = 3, CM_PRECISION_F16A = 4 };
 int cm_model_set_precision(cm_model *m, int32_t precision);
 /* Packs weights into MFMA fragment order and precomputes the time-embedding
  * tables; must be called after the last cm_model_set_param and before any
@@ -195,6 +206,11 @@ int cm_mse_loss(cm_model *m, const float *d_pred, const float *d_target, int64_t
  * is the batch of the last forward (samples of an earlier, larger batch follow it); fails before the first forward. */
 int cm_debug_activation(cm_model *m, const char *name, float *h_out, int64_t capacity,
                         int64_t shape[5]);
+/* Test hook, finalized FM-DiT (DiT2D) handles only (other handles are refused by name): ONE launch of the full-attention kernel of
+ * the handle's plan -- dit_attn_full_kernel on the fp32 plan, dit_attn_full_f16_kernel on the f16a plan -- on host q|k|v
+ * h_qkv [B][S][3E] (S = (past_len + future_len) * patches, E = hidden_size), result to host h_out [B][S][E].  1 <= B <= max_batch.
+ * It goes through the handle's own QKV / AO workspace, which every forward rewrites before reading. */
+int cm_debug_dit_attn(cm_model *m, const float *h_qkv, float *h_out, int32_t B);
 
 /* ---- schedule: replaces ForwardSampler.__init__ (forward.py:10-27) ------ */
 int cm_schedule_create(int32_t timesteps, float scale, float beta_start, float beta_end,
